@@ -5,14 +5,17 @@ A "step" is one pass of the whole hot path (rotator + decimators + per-mode filt
 descramblers) over one batch of synthetic IQ that is already resident in HBM.
 
 Default workload = C1, the configuration BASELINE.json's target is quoted on: 2FSK 1 kbit/s RX chain (gr_demod_2fsk behind the
-gr_demod_base rotator) on 1 Msps IQ, 16384 streams x 262144 samples = 34.4 GB of IQ per step.  The same JSON line carries
-  roofline      the HBM-facing kernel (k_decim_pl: rotator + 1:50 decimator) timed with HIP events on the handle's stream;
-                achieved = SURVEY.md 8(d) algorithmic bytes (C1 8.178 B, C2 8.033 B, C3 8.0625 B per input sample) x samples
-                per launch / average launch duration
+gr_demod_base rotator) on 1 Msps IQ, 16384 streams x 262144 samples = 34.4 GB of IQ per step.  A plain run sets up, warms up, times
+the K steps and prints one JSON line: the headline (value, ms_per_step) and
+  roofline      the HBM-facing kernel (k_decim_pl: rotator + 1:50 decimator) timed with HIP events on the handle's stream during the
+                timed steps; achieved = SURVEY.md 8(d) algorithmic bytes (C1 8.178 B, C2 8.033 B, C3 8.0625 B per input sample) x
+                samples per launch / average launch duration
+With --full the same line also carries what takes runs of its own:
   cpu_baseline  oracle/liborc.so timed on the host cores (a bounded sample of the same workload)
   parity_check  four random streams of one call AT THE BENCH SHAPE compared with the oracle (bits and port 0), untimed
-  c2            the GMSK-10k chain on 25 Msps IQ (BASELINE configs[1]) measured in the same run.
+  c2 .. c5      the other workloads (GMSK-10k on 25 Msps IQ = BASELINE configs[1], ...) measured in the same run, and C1's serial mode.
 Other configs on request: --config c2 | c3 | c4 | c5.
+--dump-outputs DIR writes what the last timed step handed its caller (a fixed, seeded sample of the streams) as DIR/<port>.npy.
 
 Launch: python bench.py --gpus N --steps K --warmup W.  N > 1 re-executes itself under torch.distributed.run (one rank per GPU,
 RCCL); the driver may also launch it that way directly.  C1-C3/C5 shard independent streams over the ranks with no data-path
@@ -118,6 +121,56 @@ def parity_check(dem, iq, mode, rate, offset, torch, nstreams=4, seed=5):
                 bits_per_stream=int(cnt[picks[0], 2]))
 
 
+DUMP_MAX_BYTES = 60 << 20    # --dump-outputs: at most this many bytes of arrays in all
+
+
+def _host_bytes(t):
+    return t.numel() * (8 if t.is_complex() else 4)          # as float32 (complex: two of them)
+
+
+def snapshot_outputs(ports, torch, nstreams=256, seed=2024):
+    """The arrays a caller of the timed path received from its last step, for --dump-outputs.  `ports` = {name: (tensor [batch, ...],
+    valid lengths or None)}, the valid lengths indexing the tensor's last axis.  A fixed, seeded sample of the streams (as many as fit
+    in DUMP_MAX_BYTES, at most `nstreams`; `streams` = their indices), entries past a stream's valid length zeroed (the library leaves
+    them as they were); a port without valid lengths that is small (counts: together at most a quarter of the budget) is taken for
+    every stream, any other is sampled like the rest.  complex -> float32 [..., 2], integers -> float32.  The arrays returned hold at
+    most DUMP_MAX_BYTES; a SystemExit if even one stream does not fit."""
+    batch = next(iter(ports.values()))[0].shape[0]
+    whole, fixed = {}, 0
+    for k, (t, c) in ports.items():
+        if c is None and fixed + _host_bytes(t) <= DUMP_MAX_BYTES // 4:
+            whole[k] = t
+            fixed += _host_bytes(t)
+    sampled = {k: (t, c) for k, (t, c) in ports.items() if k not in whole}
+    per_stream = sum(_host_bytes(t[0]) for t, _ in sampled.values())
+    room = DUMP_MAX_BYTES - fixed - 8 * min(batch, nstreams)   # (8: the float64 index of a sampled stream)
+    n = min(batch, nstreams, room // max(per_stream, 1))
+    if n < 1:
+        raise SystemExit("bench.py: --dump-outputs: one stream's outputs (%d bytes) do not fit in %d bytes" % (per_stream, room))
+    picks = np.sort(np.random.default_rng(seed).choice(batch, size=n, replace=False))
+    idx = torch.as_tensor(picks, device=next(iter(ports.values()))[0].device)
+
+    def host(t):
+        t = torch.view_as_real(t) if t.is_complex() else t
+        return t.to(torch.float32).cpu().numpy()
+    out = {k: host(t) for k, t in whole.items()}
+    for k, (t, c) in sampled.items():
+        x = t.index_select(0, idx)
+        if c is not None:
+            lim = c.index_select(0, idx).to(torch.int64)
+            valid = torch.arange(x.shape[-1], device=x.device) < lim.unsqueeze(-1)
+            x = torch.where(valid, x, torch.zeros((), dtype=x.dtype, device=x.device))
+        out[k] = host(x)
+    out["streams"] = picks.astype(np.float64)
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 class StepMarks:
     """Per-step completion times that order NOTHING: after every queued step one event is recorded on each of the streams the step's
     kernels run on (qrl_*_internal_streams); a step is complete when the last of its events has fired, the differences of consecutive
@@ -155,7 +208,15 @@ class StepMarks:
                     note=self.note)
 
 
-def run_workload(name, args, torch, q, ctx, dev, rank, world, overlap=None, check=False, steps=None):
+def demod_ports(dem):
+    """what one Demod call hands its caller: per port (tensor, valid lengths) -- counts[:, 0..3] = filtered, constellation, bits A, bits B"""
+    o = dem._ports()
+    ports = {k: (o[k], o["counts"][:, i]) for i, k in enumerate(("filtered", "constellation", "bits_a", "bits_b")) if o[k] is not None}
+    ports["counts"] = (o["counts"], None)
+    return ports
+
+
+def run_workload(name, args, torch, q, ctx, dev, rank, world, overlap=None, check=False, steps=None, dump=False):
     label, mode, modem, rate, offset, dbatch, dns, _, abytes = WORKLOADS[name]
     steps = steps or args.steps
     batch = args.batch if (args.batch and name == args.config) else dbatch
@@ -193,6 +254,7 @@ def run_workload(name, args, torch, q, ctx, dev, rank, world, overlap=None, chec
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     counts = dem.counts.cpu().numpy()
+    outputs = snapshot_outputs(demod_ports(dem), torch) if dump else None
     parity = parity_check(dem, iq, mode, rate, offset, torch) if (check and rank == 0) else None
     dem.close()
     del iq
@@ -204,7 +266,7 @@ def run_workload(name, args, torch, q, ctx, dev, rank, world, overlap=None, chec
                 label=label, batch=batch, nsamp=nsamp, rate=rate, seconds=dt, msps=total_samples / dt / 1e6,
                 ms_per_step=dt / steps * 1e3, kernel=kname, kernel_ms=kms / max(launches, 1), launches=launches,
                 achieved_gbps=ach, bits_per_stream=int(counts[:, 2].mean()), bytes_per_launch=bytes_per_launch,
-                bytes_per_sample=abytes, parity=parity, spread=marks.spread())
+                bytes_per_sample=abytes, parity=parity, spread=marks.spread(), outputs=outputs)
 
 
 def timed_loop(fn, sync, args, torch, dev, world, marks=None):
@@ -409,7 +471,7 @@ def parity_check_c4(ch, iq, torch, nstreams=2, seed=6):
                 int16_per_channel=int(ref.shape[1]), dibit_bytes_per_channel=int(dref[0].size))
 
 
-def run_c4(args, torch, q, ctx, dev, rank, world, steps=None, with_form2=True, check=False):
+def run_c4(args, torch, q, ctx, dev, rank, world, steps=None, with_form2=True, check=False, dump=False):
     """C4: multi-carrier MMDVM receiver, 64 x 25 kHz channels from 1.6 Msps wideband IQ (PFB channelizer + per-channel
     24/25 resampler, LPF, FM discriminator -> int16, RSSI tags and the 4FSK symbol tail).  Multi-GPU (PFB form): the CHANNELS
     are sharded -- every rank channelizes its own B / world wideband streams, one RCCL all_to_all_single per step moves each
@@ -462,6 +524,11 @@ def run_c4(args, torch, q, ctx, dev, rank, world, steps=None, with_form2=True, c
     prof.profile(True)
     marks = StepMarks(torch, [x for hnd in handles for x in hnd.internal_streams], enabled=not args.no_marks)
     dt = timed_loop(step, sync, args, torch, dev, world, marks)
+    outputs = None
+    if dump:                                  # (single GPU, no --cluster: main() refuses the other combinations before any setup)
+        outputs = snapshot_outputs({"out": (ch.out, ch.counts), "counts": (ch.counts, None), "rssi": (ch.rssi, ch.rssi_counts),
+                                    "rssi_counts": (ch.rssi_counts, None), "dibits": (ch.dibits, ch.fsk_counts[..., 2]),
+                                    "fsk_constellation": (ch.fsk_const, ch.fsk_counts[..., 1]), "fsk_counts": (ch.fsk_counts, None)}, torch)
     per_kernel = None
     if world == 1 and not args.cluster:
         # every kernel of the call, HIP events on the stream it runs on (the warm-up calls are profiled too: same kernels, same shape)
@@ -536,6 +603,8 @@ def run_c4(args, torch, q, ctx, dev, rank, world, steps=None, with_form2=True, c
                                         % (B * n * C4_BYTES * args.steps / dt / 1e9), name="c4", default_shape=not (args.batch or args.nsamp), ms_per_step=ms_step)
     if parity:
         line["parity_check"] = parity
+    if outputs:
+        line["_outputs"] = outputs
     if world == 1 and with_form2 and not args.cluster:
         # BASELINE configs[3] literally: 64 freq-xlating FIRs (2181 taps, 1:64) -- compute bound (34 MAC per input sample and channel)
         B2, n2 = max(1, B // 8), n // 4
@@ -592,7 +661,7 @@ def parity_check_c5(dem, mod, iq, data, tx_out, torch, nstreams=3, seed=8):
                 bits_per_stream=int(cnt[picks[0], 2]), tx_samples_per_stream=int(tx_out.shape[1]))
 
 
-def run_c5(args, torch, q, ctx, dev, rank, world, steps=None, check=False):
+def run_c5(args, torch, q, ctx, dev, rank, world, steps=None, check=False, dump=False):
     """C5: full duplex -- QPSK-250k modulator and QPSK-250k demodulator handles on their own HIP streams, calls interleaved without
     synchronisation (BASELINE config 5; reference src/radiocontroller.cpp:2043-2078 runs the two top blocks concurrently)."""
     import sig
@@ -639,6 +708,8 @@ def run_c5(args, torch, q, ctx, dev, rank, world, steps=None, check=False):
     # order, so its stream's mark belongs to the call before -- in steady state the intervals are the step period all the same)
     marks = StepMarks(torch, dem.internal_streams, enabled=not args.no_marks)
     dt = timed_loop(both, sync, args, torch, dev, world, marks)
+    # (taken before the RX-alone / TX-alone passes below overwrite the ports)
+    outputs = snapshot_outputs(dict(demod_ports(dem), tx=(tx_out, torch.full((B,), tx_out.shape[1], dtype=torch.int64, device=dev))), torch) if dump else None
     dem.profile(True)
     dt_rx = timed_loop(lambda: dem.process_async(iq), sync, args, torch, dev, world)
     kms, launches, kname = dem.profile_read()
@@ -666,6 +737,8 @@ def run_c5(args, torch, q, ctx, dev, rank, world, steps=None, check=False):
                                      "longest kernels of the trace -- the recursion bound by the latency of its dependent chain, the decoder by the VALU port; the HBM-facing front end k_dec2_fir is in `hbm`")
     if parity:
         line["parity_check"] = parity
+    if outputs:
+        line["_outputs"] = outputs
     return line
 
 
@@ -802,7 +875,11 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--nsamp", type=int, default=0)
     ap.add_argument("--pad", type=int, default=0, help="extra samples of row pitch of the input batch (even)")
-    ap.add_argument("--no-extra", action="store_true", help="only the timed workload: no stand-alone pass, parity check, C2 line, CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: C1's serial-mode pass, the C2 .. C5 lines (C1), C4's form-2 line, "
+                                                        "the parity checks against the oracle, the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="only the timed workload, also with --full (what a run without --full does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<port>.npy (float32 / float64; a fixed, seeded sample of the streams)")
     ap.add_argument("--overlap", action="store_true", help="(the library default since round 3; kept for the tools/ scripts)")
     ap.add_argument("--no-overlap", action="store_true", help="C1 only: QRL_OPT_OVERLAP = 0 (the kernels of a call strictly one after the other)")
     ap.add_argument("--free-tx", action="store_true", help="C5 only: the modulator stream not ordered behind the receiver's front end (it then runs tens of calls ahead)")
@@ -811,9 +888,11 @@ def main():
     ap.add_argument("--cluster", action="store_true", help="c4: drive the channel-sharded path (qrl_host::chan_cluster + RCCL all-to-all) also at N = 1")
     ap.add_argument("--cluster-copy", action="store_true", help="c4 --cluster at N = 1: keep the one-rank ncclAllToAll (a 1 GB device copy per step that moves nothing; by default one rank reads the channelizer's output in place)")
     ap.add_argument("--no-marks", action="store_true", help="no per-step completion events (step_spread_ms = null)")
-    ap.add_argument("--check", action="store_true", help="with --no-extra: still run the parity check against the oracle at the bench shape")
+    ap.add_argument("--check", action="store_true", help="without --full (or with --no-extra): still run the parity check against the oracle at the bench shape")
     ap.add_argument("--legacy-pfb", type=int, default=0, help="c4: QRL_CHAN_OPT_LEGACY_PFB = 1 (the general-M channelizer kernel at the 64-channel shape)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.config == "c4" and (args.cluster or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs covers the single-GPU C4 path only (not --cluster, not --gpus > 1)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args)
@@ -851,18 +930,25 @@ def main():
             torch.distributed.barrier()   # rank 0 may be behind by the CPU baseline: leave together
             torch.distributed.destroy_process_group()
 
-    extra_ok = not args.no_extra
+    extra_ok = args.full and not args.no_extra
+    dump = args.dump_outputs is not None and rank == 0
     ncores = min(os.cpu_count() or 1, 16)
     if args.config in ("c4", "c5"):
         kw = dict(with_form2=extra_ok) if args.config == "c4" else {}
-        line = (run_c4 if args.config == "c4" else run_c5)(args, torch, q, ctx, dev, rank, world, check=extra_ok or args.check, **kw)
+        line = (run_c4 if args.config == "c4" else run_c5)(args, torch, q, ctx, dev, rank, world, check=extra_ok or args.check, dump=dump, **kw)
+        outputs = line.pop("_outputs", None)
+        if outputs:
+            write_outputs(args.dump_outputs, outputs)
         if extra_ok and rank == 0 and world == 1:
             line["cpu_baseline"] = (cpu_baseline_c4 if args.config == "c4" else cpu_baseline_c5)(ncores)
         finish(line)
         if rank == 0 and line.get("parity_check", {}).get("status", "bit-exact") != "bit-exact":
             raise SystemExit("bench.py: parity check against the oracle FAILED at the bench shape: %r" % (line["parity_check"],))
         return
-    main_r = run_workload(args.config, args, torch, q, ctx, dev, rank, world, overlap=False if args.no_overlap else None, check=extra_ok or args.check)
+    main_r = run_workload(args.config, args, torch, q, ctx, dev, rank, world, overlap=False if args.no_overlap else None, check=extra_ok or args.check,
+                          dump=dump)
+    if main_r["outputs"]:
+        write_outputs(args.dump_outputs, main_r["outputs"])
     # C1 runs in the library's default mode (the FLL / discriminator kernels of call k share the GPU with the front end of call
     # k + 1: more whole-chain throughput, but the front-end kernel stretches).  The serial order -- where the front-end kernel has the
     # chip to itself -- is measured in a second short pass for the record.

@@ -56,11 +56,36 @@ def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+MAX_FILE = 1 << 20    # no fixture file above 1 MiB: a larger one keeps the first half of its IQ as iq_f16_head, the rest goes to <name>.iq_tail.npy
+
+
+def save(path, **fields):
+    tail = path[:-4] + ".iq_tail.npy"
+    np.savez_compressed(path, **fields)
+    if os.path.getsize(path) > MAX_FILE:
+        iq = fields.pop("iq_f16")
+        h = iq.size // 4 * 2
+        np.savez_compressed(path, iq_f16_head=iq[:h], **fields)
+        np.save(tail, iq[h:])
+        if max(os.path.getsize(path), os.path.getsize(tail)) > MAX_FILE:
+            raise ValueError("%s: even halved the input is larger than %d bytes per file: shorten the case" % (path, MAX_FILE))
+    elif os.path.exists(tail):      # the fixture fits in one file now: no second half of an earlier version left behind
+        os.remove(tail)
+
+
+def load(path):
+    """the fixture at `path` (tests/golden/<name>.npz) as a dict of arrays, iq_f16 whole again where save() split it"""
+    z = dict(np.load(path))
+    if "iq_f16_head" in z:
+        z["iq_f16"] = np.concatenate([z.pop("iq_f16_head"), np.load(path[:-4] + ".iq_tail.npy")])
+    return z
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--export-iq":   # raw cf32 inputs of the committed fixtures (for tools/gr_golden)
         os.makedirs(sys.argv[2], exist_ok=True)
         for name, *_ in CASES:
-            z = np.load(os.path.join(HERE, name + ".npz"))
+            z = load(os.path.join(HERE, name + ".npz"))
             z["iq_f16"].astype(np.float32).tofile(os.path.join(sys.argv[2], name + ".cf32"))
         return
     only = set(sys.argv[1:])   # optional: names of the fixtures to (re)generate; default = all
@@ -74,7 +99,7 @@ def main():
             y = np.concatenate([y, np.zeros(20000, np.complex64)])   # flush the long RRC filters / Viterbi frames
         y = quantise(y[: y.size & ~1])
         r = run_oracle(kind, kw, y, rate, offset)
-        np.savez_compressed(
+        save(
             os.path.join(HERE, name + ".npz"),
             iq_f16=y.view(np.float32).astype(np.float16), rate=rate, offset=offset,
             bits_a=np.packbits(r["bits_a"]), n_bits_a=r["bits_a"].size,

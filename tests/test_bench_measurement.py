@@ -112,3 +112,76 @@ def test_front_end_flop_roofline_on_the_committed_default_line():
         assert abs(f["frac"] - f["achieved"] / f["peak"]) < 1e-3
     assert 0.35 < f2["frac"] < 0.55 and 0.33 < f3["frac"] < 0.55 and f1["frac"] < 0.2
     assert abs(bench.FRONT_END_FLOP["c2"] - (4 * 1045 / 25 + 6)) < 1e-9
+
+
+def test_dump_outputs_are_a_fixed_sample_cut_at_the_valid_lengths(tmp_path):
+    """--dump-outputs: the same seeded sample of streams on every run, every port cut at its stream's valid length (the rest zero), float32,
+    counts of every stream, and at most bench.DUMP_MAX_BYTES in all"""
+    import torch
+    B = 1000
+    g = torch.Generator().manual_seed(1)
+    ports = dict(filtered=torch.randn((B, 50), dtype=torch.complex64, generator=g), constellation=None,
+                 bits_a=torch.randint(0, 2, (B, 30), dtype=torch.uint8, generator=g), bits_b=torch.randint(0, 2, (B, 30), dtype=torch.uint8, generator=g),
+                 counts=torch.randint(0, 60, (B, 4), dtype=torch.int32, generator=g))
+
+    class Dem:
+        def _ports(self):
+            return ports
+    a = bench.snapshot_outputs(bench.demod_ports(Dem()), torch)
+    b = bench.snapshot_outputs(bench.demod_ports(Dem()), torch)
+    assert sorted(a) == ["bits_a", "bits_b", "counts", "filtered", "streams"] and all(np.array_equal(a[k], b[k]) for k in a)
+    s = a["streams"].astype(np.int64)
+    assert s.size == 256 and np.all(np.diff(s) > 0) and a["counts"].shape == (B, 4) and a["filtered"].shape == (256, 50, 2)
+    c = ports["counts"].numpy()[s]
+    for i in (0, 7, 255):
+        want = torch.view_as_real(ports["filtered"][s[i], :c[i, 0]]).numpy()
+        assert np.array_equal(a["filtered"][i, :c[i, 0]], want) and not a["filtered"][i, c[i, 0]:].any()
+        assert np.array_equal(a["bits_b"][i, :c[i, 3]], ports["bits_b"][s[i], :c[i, 3]].numpy()) and not a["bits_b"][i, c[i, 3]:].any()
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    bench.write_outputs(str(tmp_path / "out"), a)
+    assert np.array_equal(np.load(tmp_path / "out" / "filtered.npy"), a["filtered"])
+    old = bench.DUMP_MAX_BYTES
+    try:
+        bench.DUMP_MAX_BYTES = 100000
+        small = bench.snapshot_outputs(bench.demod_ports(Dem()), torch)
+        assert 1 <= small["streams"].size < 256 and sum(v.nbytes for v in small.values()) <= 100000
+    finally:
+        bench.DUMP_MAX_BYTES = old
+
+
+def test_dump_outputs_budget_covers_ports_without_valid_lengths(monkeypatch):
+    """a port without valid lengths that is larger than a quarter of the budget (C5's modulator output: [16384, 16384] complex64 at the
+    default shape) is sampled with the streams like the others, never written whole: the arrays stay within bench.DUMP_MAX_BYTES"""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 20)
+    B = 1024
+    g = torch.Generator().manual_seed(2)
+    big = torch.randn((B, 1024), dtype=torch.complex64, generator=g)                      # 8 MiB as float32: 8 x the budget
+    counts = torch.randint(0, 64, (B, 4), dtype=torch.int32, generator=g)
+    bits = torch.randint(0, 2, (B, 64), dtype=torch.uint8, generator=g)
+    o = bench.snapshot_outputs({"tx": (big, None), "counts": (counts, None), "bits_a": (bits, counts[:, 2])}, torch)
+    s = o["streams"].astype(np.int64)
+    assert sum(v.nbytes for v in o.values()) <= 1 << 20
+    assert o["counts"].shape == (B, 4) and o["tx"].shape == (s.size, 1024, 2) and 1 <= s.size < B
+    assert np.array_equal(o["tx"], torch.view_as_real(big[torch.as_tensor(s)]).numpy())
+    # C5 hands its modulator output with a full valid length per stream: the same sample
+    o2 = bench.snapshot_outputs({"tx": (big, torch.full((B,), 1024)), "counts": (counts, None), "bits_a": (bits, counts[:, 2])}, torch)
+    assert all(np.array_equal(o[k], o2[k]) for k in o)
+    # one stream larger than the whole budget: refused, not written past it
+    with pytest.raises(SystemExit):
+        bench.snapshot_outputs({"tx": (torch.zeros((4, 1 << 18), dtype=torch.complex64), None)}, torch)
+
+
+def test_dump_outputs_refused_up_front_where_not_covered():
+    """C4's channel-sharded path has no dump: refused while the arguments are parsed (every rank, before any setup), not after the timed steps"""
+    import subprocess
+    for extra in (["--cluster"], ["--gpus", "2"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--dump-outputs", "unused"] + extra,
+                           capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and "--dump-outputs covers the single-GPU C4 path only" in r.stderr
+
+
+def test_command_line_has_full_and_dump_outputs():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

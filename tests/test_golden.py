@@ -4,6 +4,7 @@ GPU: the HIP path reproduces them through the C ABI (bits exact, float ports by 
 import glob
 import hashlib
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +13,8 @@ import orc
 import sig
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import make_golden   # noqa: E402
 FILES = sorted(glob.glob(os.path.join(HERE, "golden", "*.npz")))
 ORACLE = {"2fsk1k": ("2fsk", dict(sps=10, filter_width=2000, fm=False)), "2fsk1kfm": ("2fsk", dict(sps=10, filter_width=2500, fm=True)),
           "gmsk10k": ("gmsk", dict(sps=1, filter_width=20000)), "qpsk250k": ("qpsk", dict(sps=2, filter_width=160000)),
@@ -27,7 +30,7 @@ SINGLE_BRANCH = ("qpsk250k", "4fsk2kfm", "4fsk100k")
 
 
 def _load(path):
-    z = np.load(path)
+    z = make_golden.load(path)
     iq = z["iq_f16"].astype(np.float32).view(np.complex64)
     bits_a = np.unpackbits(z["bits_a"])[: int(z["n_bits_a"])]
     bits_b = np.unpackbits(z["bits_b"])[: int(z["n_bits_b"])]
@@ -104,7 +107,7 @@ def test_oracle_against_real_reference_fixtures():
     cases = {c[0]: c for c in make_golden.CASES}
     for path in files:
         name = os.path.basename(path)[:-4]
-        z, g = np.load(os.path.join(GOLD, name + ".npz")), np.load(path)
+        z, g = make_golden.load(os.path.join(GOLD, name + ".npz")), np.load(path)
         _, mode, rate, offset, (kind, kw) = cases[name]
         x = z["iq_f16"].astype(np.float32).view(np.complex64)
         r = make_golden.run_oracle(kind, kw, x, int(z["rate"]), float(z["offset"]))
@@ -137,3 +140,27 @@ def test_oracle_against_stock_block_fixtures():
         msg = m.compare(name, np.load(path), table[name][1]())
         assert msg is None, msg
 
+
+
+def test_fixture_split_round_trips_and_leaves_no_stale_half(tmp_path, monkeypatch):
+    """make_golden.save keeps every fixture file under MAX_FILE by moving the second half of a large IQ input to <name>.iq_tail.npy;
+    make_golden.load gives back the same arrays either way, and a fixture that fits again removes the tail of its earlier version"""
+    rng = np.random.default_rng(3)
+    fields = dict(iq_f16=rng.standard_normal(20000).astype(np.float16), rate=np.int64(8000000), bits_a=rng.integers(0, 256, 40, dtype=np.uint8))
+    path, tail = str(tmp_path / "x.npz"), tmp_path / "x.iq_tail.npy"
+    monkeypatch.setattr(make_golden, "MAX_FILE", 24000)            # 40 kB of float16 noise: two files of about 20 kB
+    make_golden.save(path, **fields)
+    assert tail.exists() and max(os.path.getsize(path), os.path.getsize(tail)) <= 24000 and "iq_f16" not in np.load(path).files
+    back = make_golden.load(path)
+    assert sorted(back) == sorted(fields) and all(back[k].dtype == fields[k].dtype and np.array_equal(back[k], fields[k]) for k in fields)
+    monkeypatch.setattr(make_golden, "MAX_FILE", 1 << 20)
+    make_golden.save(path, **fields)
+    assert not tail.exists() and np.array_equal(make_golden.load(path)["iq_f16"], fields["iq_f16"])
+    monkeypatch.setattr(make_golden, "MAX_FILE", 8000)             # halving is not enough: refused, not written over the limit
+    with pytest.raises(ValueError):
+        make_golden.save(path, **fields)
+
+
+def test_committed_fixture_files_are_at_most_1_mib():
+    for p in glob.glob(os.path.join(HERE, "golden", "**", "*.np[yz]"), recursive=True):
+        assert os.path.getsize(p) <= make_golden.MAX_FILE, p

@@ -3,6 +3,7 @@ reference's factory arguments, work() ABI, mailbox ownership and error behaviour
 tests/host/test_adaptor.cpp calls work() with scheduler-like ragged item counts."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,8 @@ import torch
 import orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden   # noqa: E402
 EXE = os.path.join(ROOT, "tests", "host", "test_adaptor")
 
 
@@ -33,7 +36,7 @@ def test_adaptor_builds_and_fails_loudly_without_device():
                                                 ("2fsk1k_1M", "2fsk", 10, 2000, 0), ("qpsk250k_1M", "qpsk", 2, 160000, 0),
                                                 ("4fsk2kfm_1M", "4fsk", 5, 3000, 1), ("bpsk2k_1M", "bpsk", 5, 2400, 0)])
 def test_rx_block_matches_golden(tmp_path, name, fam, sps, fw, fm):
-    z = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    z = make_golden.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
     iq = z["iq_f16"].astype(np.float32)
     (tmp_path / "iq.bin").write_bytes(iq.tobytes())
     r = subprocess.run([EXE, "rx", fam, str(sps), str(fw), str(fm), str(int(z["rate"])), str(float(z["offset"])),

@@ -54,7 +54,7 @@ def self_test(cases=("2fsk1k_1M", "qpsk250k_1M"), out=sys.stdout):
         for name, mode, rate, offset, (kind, kw) in make_golden.CASES:
             if name not in cases:
                 continue
-            z = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+            z = make_golden.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
             x = z["iq_f16"].astype(np.float32).view(np.complex64)                      # what make_golden.py --export-iq writes
             x.tofile(os.path.join(d, name + ".cf32"))
             getattr(orc, "demod_" + kind)(x, **kw)["constellation"].astype(np.complex64).tofile(os.path.join(d, name + ".port1"))

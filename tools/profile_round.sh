@@ -43,7 +43,7 @@ for cnt in FETCH_SIZE WRITE_SIZE; do
   f=$(find $O/cal_$cnt -name '*counter_collection.csv' | head -1)
   [ -n "$f" ] && { echo "## calibration $cnt"; python tools/pmc_calibrate.py --summarize "$f"; } >> $O/pmc_summary.txt
 done
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for cfg in c2 c3 c4 c5; do python bench.py --config $cfg --no-extra > $O/bench_$cfg.json 2> $O/bench_$cfg.err; done
 python bench.py --config c1 --no-overlap --no-extra > $O/bench_c1_serial.json 2>/dev/null
 # B sweep at SURVEY 8(d)'s batch sizes (samples per stream and call as in the default shapes)
