@@ -105,6 +105,12 @@ void qrl_demod_destroy(qrl_demod* d);
 int qrl_demod_reset(qrl_demod* d);
 /* replaces: rotator_cc::set_phase_inc (gr_demod_base.cpp:1220-1225); phase-continuous retune */
 int qrl_demod_set_carrier_offset(qrl_demod* d, double carrier_offset_hz);
+/* per-stream rotator_cc::set_phase_inc (gr_demod_base::set_carrier_offset of each radio): hz[b] is stream b's carrier offset, a host array of
+ * `batch` doubles.  Each stream's phase runs on and its increment changes from the next sample, as with the scalar setter; samples already in a
+ * decimator's history keep their old rotation.  Once a handle has per-stream offsets, qrl_demod_set_carrier_offset sets every stream to one
+ * offset and each stream goes on from its own phase; qrl_demod_reset restarts every phase and keeps the offsets.  hz == NULL or a non-finite
+ * value: QRL_ERR_ARG, nothing changes.  Blocks the host like the scalar setter; only the streams whose offset changes get a new table. */
+int qrl_demod_set_carrier_offsets(qrl_demod* d, const double* hz);
 /* capacities (items per stream) a call with n input samples can need */
 /* a37b, QRL_MODEM_DMR only: gr_dmr_dmo_sink (reference src/gr/gr_dmr_dmo_sink.cpp:63-357) on the device, fed from port 3 of
  * gr_demod_dmr (RRC-filtered discriminator output, gr_demod_dmr.cpp:94).  Every following qrl_demod_process call also runs the
@@ -232,6 +238,9 @@ int qrl_mod_set_bb_gain(qrl_mod* m, float value);
 /* replaces: gr_mod_base::set_carrier_offset -> rotator_cc::set_phase_inc (src/gr/gr_mod_base.cpp:799-805); phase-continuous.
  * Only for handles created with the back end (device_samp_rate >= 2e6 or a non-zero initial offset). */
 int qrl_mod_set_carrier_offset(qrl_mod* m, double hz);
+/* per-stream gr_mod_base::set_carrier_offset: hz[b] for stream b (host array of `batch` doubles); same rules as qrl_demod_set_carrier_offsets.
+ * A handle without the gr_mod_base back end returns QRL_ERR_ARG, like the scalar setter. */
+int qrl_mod_set_carrier_offsets(qrl_mod* m, const double* hz);
 size_t qrl_mod_samples_per_byte(const qrl_mod* m);
 typedef struct { int stream; int channel; uint64_t start; uint64_t count; } qrl_zero_run;
 /* QRL_MODEM_DMR (replaces make_gr_mod_dmr(), reference src/gr/gr_mod_dmr.cpp:19-90, instance gr_mod_base.cpp:207, fed by gr_mod_base::setDMRData
@@ -510,6 +519,8 @@ int qrl_amod_reset(qrl_amod* m);
 int qrl_amod_set_bb_gain(qrl_amod* m, float value);
 /* replaces gr_mod_base::set_carrier_offset (src/gr/gr_mod_base.cpp:799-805) for handles created with the back end; phase-continuous like rotator_cc::set_phase_inc */
 int qrl_amod_set_carrier_offset(qrl_amod* m, double carrier_offset_hz);
+/* per-stream form of qrl_amod_set_carrier_offset (see qrl_mod_set_carrier_offsets) */
+int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz);
 /* replaces gr_mod_nbfm::set_ctcss(value) (src/gr/gr_mod_nbfm.cpp:101-135; gr_mod_base::set_ctcss :872-877 forwards to both NBFM instances):
  * tone_hz != 0: _audio_amplify 0.85, the audio filter becomes band_pass_2(1, 8000, 300, 3500, 200, 35, BH) and analog::sig_source_f(8000,
  * GR_COS_WAVE, tone, 0.15) is added to the audio in front of the pre-emphasis; 0: the low-pass again and _audio_amplify 0.98 (sic: the

@@ -97,6 +97,7 @@ def load_library():
     lib.qrl_demod_destroy.argtypes = [vp]
     lib.qrl_demod_reset.argtypes = [vp]
     lib.qrl_demod_set_carrier_offset.argtypes = [vp, C.c_double]
+    lib.qrl_demod_set_carrier_offsets.argtypes = [vp, C.POINTER(C.c_double)]
     lib.qrl_demod_set_option.argtypes = [vp, C.c_int, C.c_int]
     lib.qrl_demod_set_dmo_output.argtypes = [vp, vp, sz, vp]
     lib.qrl_demod_out_caps.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
@@ -127,6 +128,7 @@ def load_library():
     lib.qrl_demod_set_gain.argtypes = [vp, C.c_float]
     lib.qrl_amod_set_filter_width.argtypes = [vp, C.c_int]
     lib.qrl_amod_set_carrier_offset.argtypes = [vp, C.c_double]
+    lib.qrl_amod_set_carrier_offsets.argtypes = [vp, C.POINTER(C.c_double)]
     lib.qrl_amod_set_cw_k.argtypes = [vp, C.c_int]
     lib.qrl_demod_process.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
     lib.qrl_demod_sync.argtypes = [vp]
@@ -163,6 +165,7 @@ def load_library():
     lib.qrl_mod_reset.argtypes = [vp]
     lib.qrl_mod_set_bb_gain.argtypes = [vp, C.c_float]
     lib.qrl_mod_set_carrier_offset.argtypes = [vp, C.c_double]
+    lib.qrl_mod_set_carrier_offsets.argtypes = [vp, C.POINTER(C.c_double)]
     lib.qrl_mod_samples_per_byte.restype = sz
     lib.qrl_mod_samples_per_byte.argtypes = [vp]
     lib.qrl_mod_process.argtypes = [vp, vp, sz, sz, vp, sz]
@@ -226,12 +229,12 @@ def load_library():
 
 EXPORTED_SYMBOLS = [
     "qrl_init", "qrl_shutdown", "qrl_strerror", "qrl_last_error", "qrl_version", "qrl_demod_create",
-    "qrl_demod_destroy", "qrl_demod_reset", "qrl_demod_set_carrier_offset", "qrl_demod_set_option", "qrl_demod_set_dmo_output", "qrl_demod_stream_wait", "qrl_demod_out_caps",
+    "qrl_demod_destroy", "qrl_demod_reset", "qrl_demod_set_carrier_offset", "qrl_demod_set_carrier_offsets", "qrl_demod_set_option", "qrl_demod_set_dmo_output", "qrl_demod_stream_wait", "qrl_demod_out_caps",
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
-    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_sync", "qrl_amod_stream",
+    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
-    "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset",
+    "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
     "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
     "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_sync",
     "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process",
@@ -246,6 +249,14 @@ EXPORTED_SYMBOLS = [
     "qrl_firdes_low_pass_2", "qrl_firdes_complex_band_pass", "qrl_firdes_root_raised_cosine", "qrl_table_mmse",
     "qrl_table_atan", "qrl_table_tanh", "qrl_phase_inc_to_turn",
 ]
+
+
+def _offsets(hz, batch):
+    """A length-`batch` sequence of carrier offsets as a C double array (ValueError before the library is called)."""
+    v = [float(x) for x in hz]
+    if len(v) != batch:
+        raise ValueError("carrier offsets: %d values for batch %d" % (len(v), batch))
+    return (C.c_double * batch)(*v)
 
 
 def _check(rc, what):
@@ -470,6 +481,11 @@ class Demod:
 
     def set_carrier_offset(self, hz):
         _check(self.lib.qrl_demod_set_carrier_offset(self.h, float(hz)), "qrl_demod_set_carrier_offset")
+
+    def set_carrier_offsets(self, hz):
+        """Per-stream carrier offsets: hz[b] for stream b (a sequence or array of length batch); phase-continuous per stream."""
+        arr = _offsets(hz, self.batch)
+        _check(self.lib.qrl_demod_set_carrier_offsets(self.h, arr), "qrl_demod_set_carrier_offsets")
 
     def close(self):
         if self.h:
@@ -860,6 +876,11 @@ class Mod:
     def set_carrier_offset(self, hz):
         _check(self.lib.qrl_mod_set_carrier_offset(self.h, float(hz)), "qrl_mod_set_carrier_offset")
 
+    def set_carrier_offsets(self, hz):
+        """Per-stream carrier offsets of the gr_mod_base back end: hz[b] for stream b (length batch)."""
+        arr = _offsets(hz, self.batch)
+        _check(self.lib.qrl_mod_set_carrier_offsets(self.h, arr), "qrl_mod_set_carrier_offsets")
+
     def add_zero_runs(self, runs):
         """QRL_MODEM_DMR: the "zero_samples" tags of gr_zero_idle_bursts, runs = [(stream, T, count), ...] with T in the block's 24 ksps input
         coordinates (qrl_mod_add_zero_runs)"""
@@ -900,6 +921,11 @@ class AMod:
 
     def set_carrier_offset(self, hz):
         _check(self.lib.qrl_amod_set_carrier_offset(self.h, C.c_double(hz)), "qrl_amod_set_carrier_offset")
+
+    def set_carrier_offsets(self, hz):
+        """Per-stream carrier offsets of the gr_mod_base back end: hz[b] for stream b (length batch)."""
+        arr = _offsets(hz, self.batch)
+        _check(self.lib.qrl_amod_set_carrier_offsets(self.h, arr), "qrl_amod_set_carrier_offsets")
 
     def set_cw_k(self, key_down):
         """gr_mod_base::set_cw_k: amplitude of the CW tone source, 0.98 (key down) / 0.001 (qrl_amod_set_cw_k; QRL_MODEM_CW600USB handles)"""

@@ -81,6 +81,7 @@ struct qrl_amod {
     bool backend = false; int be_interp = 1, be_nt = 0; Dev<float> be_taps;
     Dev<float2> bb, be_ring, rot_lo; size_t bb_stride = 0; uint32_t be_mask = 0;
     uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0, n_bb = 0;
+    RotPs ps;   // per-stream offsets (qrl_amod_set_carrier_offsets); off: the shared NCO above
     int set_rot(double hz)
     {
         rot_inc = phase_inc_to_turn(2 * M_PI * hz / 1000000.0);
@@ -109,7 +110,7 @@ struct qrl_amod {
         }
         return QRL_OK;
     }
-    ~qrl_amod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    ~qrl_amod() { ps.release(); if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int init_state(bool keep_tone_phase = false)
     {
         int r;
@@ -126,7 +127,7 @@ struct qrl_amod {
         if (!keep_tone_phase) tone_k = cw_k = 0;   // qrl_amod_set_filter_width restarts the chain but the reference's sig_source_f keeps running
         if (be_ring.p && (r = be_ring.zero())) return r;
         n_bb = 0; rot_acc = 0; rot_nbase = 0;
-        return QRL_OK;
+        return ps.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -290,9 +291,26 @@ int qrl_amod_set_carrier_offset(qrl_amod* m, double hz)
     if (!m) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
     HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    m->rot_acc += (m->n_bb - m->rot_nbase) * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
+    const uint64_t delta = m->n_bb - m->rot_nbase;
+    m->rot_acc += delta * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
     m->rot_nbase = m->n_bb;
-    return m->set_rot(hz);
+    if (int r = m->set_rot(hz)) return r;
+    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
+    return m->ps.on() ? m->ps.set_all(delta, m->rot_inc, m->rot_lo.p, m->stream) : QRL_OK;
+}
+int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz)
+{
+    if (!m || !hz) return QRL_ERR_ARG;
+    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
+    const int B = m->cfg.batch;
+    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    HIPCHK(hipStreamSynchronize(m->stream));
+    std::vector<uint64_t> ni((size_t)B);
+    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * hz[b] / 1000000.0);
+    const uint64_t delta = m->n_bb - m->rot_nbase;
+    m->rot_acc += delta * m->rot_inc;
+    m->rot_nbase = m->n_bb;
+    return m->ps.set(B, m->rot_acc, m->rot_inc, m->rot_lo.p, delta, ni.data(), m->stream);
 }
 void* qrl_amod_stream(qrl_amod* m) { return m ? m->stream : nullptr; }
 int qrl_amod_sync(qrl_amod* m) { if (!m) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(m->stream)); return QRL_OK; }
@@ -313,7 +331,7 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
         if (!m->backend || !n1) return;
         TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo.p;
+        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo.p; m->ps.fill(rp);
         if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
         else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
         launch_tx_rot(rp, B, s);

@@ -57,6 +57,71 @@ int create_role_stream(hipStream_t* s, int priority, const char* role)
     if (err != hipSuccess) { qrl_set_error(QRL_ERR_HIP, std::string("stream creation: ") + hipGetErrorString(err)); return QRL_ERR_HIP; }
     return QRL_OK;
 }
+
+std::vector<float2> rot_fine_table(uint64_t inc)
+{
+    std::vector<float2> lo(512);
+    for (int r = 0; r < 512; ++r) { float sn, cs; sincos_turn_host((uint64_t)r * inc, sn, cs); lo[r] = make_float2(cs, sn); }
+    return lo;
+}
+int RotPs::set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t delta, const uint64_t* new_inc, hipStream_t s)
+{
+    if (!on()) {   // first per-stream set: every stream starts where the shared NCO is (acc0 = its phase at the new nbase)
+        batch = B;
+        if (hipMalloc(reinterpret_cast<void**>(&acc), (size_t)B * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&inc), (size_t)B * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&lo), (size_t)B * 512 * sizeof(float2)) != hipSuccess) {
+            release();
+            return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipMalloc failed");
+        }
+        launch_rot_ps_fill(acc, inc, lo, B, 1, acc0, inc0, lo0, s);
+        h_inc.assign((size_t)B, inc0);
+    } else {
+        launch_rot_ps_advance(acc, inc, batch, delta, s);
+    }
+    // only the streams whose increment changes: their increments and tables, one copy per run of consecutive streams
+    std::vector<uint32_t> idx;
+    for (int b = 0; b < batch; ++b) if (new_inc[b] != h_inc[(size_t)b]) idx.push_back((uint32_t)b);
+    std::vector<uint64_t> st_inc(idx.size());
+    std::vector<float2> st_lo(idx.size() * 512);
+    for (size_t j = 0; j < idx.size(); ++j) {
+        st_inc[j] = new_inc[idx[j]];
+        const std::vector<float2> t = rot_fine_table(st_inc[j]);
+        std::copy(t.begin(), t.end(), st_lo.begin() + (ptrdiff_t)(j * 512));
+    }
+    for (size_t j0 = 0; j0 < idx.size();) {
+        size_t j1 = j0 + 1;
+        while (j1 < idx.size() && idx[j1] == idx[j1 - 1] + 1) ++j1;
+        const size_t n = j1 - j0;
+        if (hipMemcpyAsync(inc + idx[j0], st_inc.data() + j0, n * sizeof(uint64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(lo + (size_t)idx[j0] * 512, st_lo.data() + j0 * 512, n * 512 * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess)
+            return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: upload failed");
+        j0 = j1;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
+    for (uint32_t b : idx) h_inc[b] = new_inc[b];
+    return QRL_OK;
+}
+int RotPs::set_all(uint64_t delta, uint64_t new_inc, const float2* lo0, hipStream_t s)
+{
+    launch_rot_ps_advance(acc, inc, batch, delta, s);
+    launch_rot_ps_fill(acc, inc, lo, batch, 0, 0, new_inc, lo0, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
+    h_inc.assign((size_t)batch, new_inc);
+    return QRL_OK;
+}
+int RotPs::reset(hipStream_t s)
+{
+    if (!on()) return QRL_OK;
+    if (hipMemsetAsync(acc, 0, (size_t)batch * sizeof(uint64_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: reset failed");
+    return QRL_OK;
+}
+void RotPs::release()
+{
+    for (void* p : {(void*)acc, (void*)inc, (void*)lo}) if (p) (void)hipFree(p);
+    acc = nullptr; inc = nullptr; lo = nullptr; h_inc.clear(); batch = 0;
+}
 }  // namespace qrl
 
 #define HIPCHK(expr)                                                                              \
@@ -243,6 +308,7 @@ struct qrl_demod {
     // rotator (gr_demod_base.cpp:57,1220-1225): exact 2^-64-turn NCO
     uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0;
     DevBuf<float2> rot_lo;
+    RotPs ps;   // per-stream offsets (qrl_demod_set_carrier_offsets); off: the shared NCO above
 
     // rings and state
     DevBuf<float2> hist_a, hist_b; uint32_t hist_len = 0; bool hist_flip = false;
@@ -282,6 +348,7 @@ struct qrl_demod {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
 
     ~qrl_demod() {
+        ps.release();
         for (auto& e : prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         if (ev_ff) (void)hipEventDestroy(ev_ff);
         if (ev_tail) (void)hipEventDestroy(ev_tail);
@@ -383,7 +450,7 @@ int qrl_demod::init_state()
     fec_deferred = false;
     n_in = n1 = n2 = 0;
     rot_acc = 0; rot_nbase = 0; hist_flip = false;
-    return QRL_OK;
+    return ps.reset(stream);   // per-stream phases restart too; the offsets stay
 }
 
 int qrl_demod::build()
@@ -755,7 +822,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         p.hist = hist_old; p.hist_len = hist_len;
         p.out = r1; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
         p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.Jpad;
-        p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p;
+        p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p);
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
         if (fe.launch(p, B, stream, use_pre ? slot : 0)) return fail(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
     }
@@ -767,7 +834,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         DecimParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; }
+               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = r2; p.m0 = n2_0; p.m_count = (uint32_t)(n2_1 - n2_0);
         p.taps = first.taps.p; p.D = first.D; p.Jpad = first.Jpad;
@@ -787,7 +854,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         ResampParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; }
+               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = r2; p.q0 = n2_0; p.q_count = (uint32_t)(n2_1 - n2_0);
         p.taps = rs_taps.p; p.I = interp; p.D = decim; p.Jp = rs_Jp;
@@ -806,7 +873,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         DecimParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; }
+               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = RingC{s_scope.p, scope_mask}; p.m0 = n_scope; p.m_count = (uint32_t)(ns_1 - n_scope);
         p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.Jpad;
@@ -819,7 +886,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         HistParams h{};
         h.in = in; h.in_stride = stride; h.n0 = n_in0; h.n = (uint32_t)n;
         h.hist_old = hist_old; h.hist_new = hist_new; h.hist_len = hist_len;
-        h.rot_enable = 1; h.rot_acc = rot_acc; h.rot_inc = rot_inc; h.rot_nbase = rot_nbase; h.rot_lo = rot_lo.p;
+        h.rot_enable = 1; h.rot_acc = rot_acc; h.rot_inc = rot_inc; h.rot_nbase = rot_nbase; h.rot_lo = rot_lo.p; ps.fill(h);
         if (pre) { HIPCHK(hipEventRecord(ev_fe[slot], stream)); fe_valid[slot] = true; }   // everything of this call that reads the history on the handle's stream has been launched
         if (use_pre) {
             if (fe_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(pre, ev_fe[slot ^ 1], 0));   // hist_new was the history of the call before
@@ -1277,11 +1344,27 @@ int qrl_demod_set_carrier_offset(qrl_demod* d, double hz)
 {
     if (!d) return QRL_ERR_ARG;
     if (int rs = d->sync_all()) return rs;
-    d->rot_acc += (d->n_in - d->rot_nbase) * d->rot_inc;  // phase-continuous
+    const uint64_t delta = d->n_in - d->rot_nbase;
+    d->rot_acc += delta * d->rot_inc;  // phase-continuous
     d->rot_nbase = d->n_in;
     d->cfg.carrier_offset_hz = hz;
     d->rot_inc = phase_inc_to_turn(2 * M_PI * -hz / d->cfg.device_samp_rate);
-    return d->upload_rot_table();
+    if (int r = d->upload_rot_table()) return r;
+    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
+    return d->ps.on() ? d->ps.set_all(delta, d->rot_inc, d->rot_lo.p, d->stream) : QRL_OK;
+}
+int qrl_demod_set_carrier_offsets(qrl_demod* d, const double* hz)
+{
+    if (!d || !hz) return QRL_ERR_ARG;
+    const int B = d->cfg.batch;
+    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    if (int rs = d->sync_all()) return rs;
+    std::vector<uint64_t> ni((size_t)B);
+    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * -hz[b] / d->cfg.device_samp_rate);
+    const uint64_t delta = d->n_in - d->rot_nbase;
+    d->rot_acc += delta * d->rot_inc;
+    d->rot_nbase = d->n_in;
+    return d->ps.set(B, d->rot_acc, d->rot_inc, d->rot_lo.p, delta, ni.data(), d->stream);
 }
 int qrl_demod_stream_wait(qrl_demod* d, void* hip_stream)
 {

@@ -27,6 +27,36 @@ struct RingC { float2* p; uint32_t mask; };   // complex ring, stream stride = m
 struct RingF { float* p; uint32_t mask; };
 struct RingB { uint8_t* p; uint32_t mask; };
 
+// ---- per-stream rotator (qrl_*_set_carrier_offsets) ----
+// A parameter block with rot_acc_s != nullptr carries one NCO per stream: stream b's (acc, inc) are rot_acc_s[b], rot_inc_s[b] and its fine
+// table is rot_lo + 512 b; rot_nbase stays shared.  Kernels take the form as a template flag PS and launchers pick it from the pointer, so a
+// handle that never had per-stream offsets launches the shared-form code (PS = false) unchanged.  ROT_VIEW(T, PS, P, SRC, b) declares
+// `const T& P`: SRC itself for PS = false, a copy of SRC with stream b's rotator in the shared fields for PS = true.
+template <class Pp>
+__device__ __forceinline__ void rot_select(Pp& c, const Pp& p, uint32_t b)
+{
+    c = p; c.rot_acc = p.rot_acc_s[b]; c.rot_inc = p.rot_inc_s[b]; c.rot_lo = p.rot_lo + (size_t)b * 512;
+}
+#define ROT_VIEW(T, PS, P, SRC, B) T P##_ps_; if constexpr (PS) rot_select(P##_ps_, SRC, (uint32_t)(B)); const T& P = (PS) ? P##_ps_ : SRC
+// host side: the per-stream state of one handle (engine.cpp).  Device arrays acc[B], inc[B], lo[B][512]; allocated on the first per-stream set.
+struct RotPs {
+    uint64_t* acc = nullptr; uint64_t* inc = nullptr; float2* lo = nullptr;
+    std::vector<uint64_t> h_inc;   // host copy of inc
+    int batch = 0;
+    bool on() const { return acc != nullptr; }
+    // every stream: acc_b += (n_now - nbase) inc_b (on the device), nbase = n_now (the caller's shared nbase), then inc_b = new_inc[b].  Only streams
+    // whose increment changes get a table upload.  The first call starts every stream at the shared (acc, inc, lo).  Host-synchronous on s.
+    int set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t delta, const uint64_t* new_inc, hipStream_t s);
+    // every stream to one increment (the scalar setter of a per-stream handle): lo0 = that increment's table (device)
+    int set_all(uint64_t delta, uint64_t new_inc, const float2* lo0, hipStream_t s);
+    int reset(hipStream_t s);   // acc_b = 0
+    void release();
+    template <class Pp> void fill(Pp& p) const { if (on()) { p.rot_acc_s = acc; p.rot_inc_s = inc; p.rot_lo = lo; } }
+};
+std::vector<float2> rot_fine_table(uint64_t inc);   // the 512-entry fine table of an increment (sincos_turn_host)
+void launch_rot_ps_advance(uint64_t* acc, const uint64_t* inc, int B, uint64_t delta, hipStream_t s);
+void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set_acc, uint64_t acc0, uint64_t inc0, const float2* lo0, hipStream_t s);
+
 // ---- K1: rotator + decimating FIR (rotator_cc + rational_resampler_ccf(1,D)) ----
 struct DecimParams {
     const float2* in; size_t in_stride;  // caller IQ (or nullptr when in_ring is used)
@@ -54,11 +84,13 @@ struct DecimParams {
     // host side only: when set, the edge scratch is staged on THIS stream (k_pl_edge_stage reads the caller's buffer and the carried history,
     // nothing the call before produces on the launch stream), `pre_event` is recorded behind it and the launch stream waits for that
     hipStream_t pre_stream; hipEvent_t pre_event;
+    const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;   // per-stream rotator (see RotPs below), or nullptr: the shared one above
 };
 struct HistParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;
     const float2* hist_old; float2* hist_new; uint32_t hist_len;
     int rot_enable; uint64_t rot_acc; uint64_t rot_inc; uint64_t rot_nbase; const float2* rot_lo;
+    const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;
 };
 void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s);
 // 1:2 decimator + the channel FIR behind it in one kernel (kernels_frontend.hip k_dec2_fir): d = the decimator's input side (out unused)
@@ -103,6 +135,7 @@ struct ResampParams {
     int I, D, Jp;
     int rot_enable; uint64_t rot_acc; uint64_t rot_inc; uint64_t rot_nbase; const float2* rot_lo;
     float2* port; size_t port_cap; uint32_t* port_counts;   // optional copy of this call's outputs to a caller port (counts[b*4+0])
+    const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;
 };
 void launch_resamp(const ResampParams& p, int batch, hipStream_t s);
 
@@ -298,7 +331,7 @@ void launch_tx_spread(RingB coded, RingB chips, uint64_t c0, uint32_t ncoded, in
 void launch_tx_f2c(RingF in, RingC out, uint64_t n0, uint32_t count, float g, int batch, hipStream_t s);
 void launch_tx_raw_dibits(const uint8_t* bytes, size_t stride, uint32_t nbytes, RingB sym, uint64_t s0, int batch, hipStream_t s);
 struct TxRotParams { const float2* in; size_t in_stride; uint64_t n0; uint32_t count; uint64_t rot_acc, rot_inc, rot_nbase; const float2* rot_lo;
-                     RingC out_ring; float2* out; size_t out_stride; };
+                     RingC out_ring; float2* out; size_t out_stride; const uint64_t* rot_acc_s; const uint64_t* rot_inc_s; };
 void launch_tx_rot(const TxRotParams& p, int batch, hipStream_t s);
 void launch_tx_shape(const TxShapeParams& p, int batch, hipStream_t s);
 void launch_tx_fm(const TxFmParams& p, int batch, hipStream_t s);

@@ -325,10 +325,10 @@ __device__ __forceinline__ void mfma_quarter(const float2* tile, const float* hp
 
 // ---- one-team variant (tiles too large for two LDS buffers, or input from an engine ring): a workgroup
 // of 4 waves walks its tiles; the loads of tile k + 1 fly during the MFMA phase of tile k.
-template <int NA, int NLD, bool FAST, bool ALIAS, int WPE, int NTH>
+template <int NA, int NLD, bool FAST, bool ALIAS, int WPE, int NTH, bool PS = false>
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_decim_mfma(const DecimParams P_)
 {
-    const DecimParams& P = P_;
+    ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int T = 16 * NA;
     const int D = P.D, S = P.S;
@@ -456,7 +456,7 @@ size_t decim_mfma_lds_bytes(int nt, int D) { return mfma_lds(nt, D, decim_mfma_n
 template <int NA, int NLD, bool FAST, int WPE = 2, int NTH = 256>
 static hipError_t launch_k(const DecimParams& q, dim3 grid, size_t lds, hipStream_t s)
 {
-    const auto kern = k_decim_mfma<NA, NLD, FAST, true, WPE, NTH>;
+    const auto kern = q.rot_acc_s ? k_decim_mfma<NA, NLD, FAST, true, WPE, NTH, true> : k_decim_mfma<NA, NLD, FAST, true, WPE, NTH>;
     const hipError_t e = dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, grid, dim3(NTH), lds + (NTH - 256) * 2 * sizeof(float2), s, q);

@@ -218,7 +218,7 @@ constexpr int PM_NHI = 64;   // coarse rotator entries per wave (64 x 512 sample
 // layout of the 16x16x4 instructions (lane (q, n) register r = Z[block n][lag 4 q + r]): A = tap H[D - 1][16 t + 4 q + (n & 3)],
 // B = the rotated last sample of block n in EVERY lane row (row 0 broadcast with two lane-row swaps).  One product added with one
 // rounding: the same link of the pm chain (the three links it drops added 0 x 0).
-template <int J, int NS, int RP, int NW, bool K1 = false>
+template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false>
 __global__ __launch_bounds__(NW * 64)
 void k_decim_pm(const DecimParams P_)
 {
@@ -234,7 +234,15 @@ void k_decim_pm(const DecimParams P_)
     float2 (*t_hi_all)[NHI] = reinterpret_cast<float2 (*)[NHI]>(t_lo + 512);      // coarse rotator table of each wave's segment (NHI x 512 samples)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int k = tid; k < 512; k += NW * 64) t_lo[k] = P.rot_lo[k];
+    if constexpr (!PS) {
+        for (int k = tid; k < 512; k += NW * 64) t_lo[k] = P.rot_lo[k];
+    } else {
+        // per-stream offsets: still ONE fine table per workgroup.  The launcher makes pl_nseg a multiple of NW, so the regular waves of a workgroup
+        // belong to one stream; a workgroup of edge units reads entry 0 only, (1, 0) in every stream's table.
+        const uint32_t u0 = blockIdx.x * (uint32_t)NW, nreg0 = P.pl_nseg * P.pl_batch;
+        const uint32_t b0 = u0 < nreg0 ? u0 / P.pl_nseg : 0u;
+        for (int k = tid; k < 512; k += NW * 64) t_lo[k] = P.rot_lo[(size_t)b0 * 512 + k];
+    }
 
     // unit = (stream, segment); behind the regular units one EDGE unit per stream (outputs pl_edge_ms .. pl_edge_me out of the staged,
     // already rotated scratch: identity phasors)
@@ -244,9 +252,10 @@ void k_decim_pm(const DecimParams P_)
     const bool edge = unit >= nreg;
     const uint32_t nsg = P.pl_nseg ? P.pl_nseg : 1u;
     const uint32_t b = edge ? unit - nreg : unit / nsg, seg = edge ? 0u : unit - b * nsg;
-    const bool active = edge ? (b < B && P.pl_edge_me > P.pl_edge_ms) : true;
     const int D = P.D;
     const uint64_t ms = edge ? P.pl_edge_ms : P.pl_m_begin + (uint64_t)seg * P.pl_S;
+    // (PS: the segment count is rounded up to a multiple of NW, segments past the end are idle)
+    const bool active = edge ? (b < B && P.pl_edge_me > P.pl_edge_ms) : (!PS || ms < P.pl_m_end);
     const uint64_t me = edge ? P.pl_edge_me : (ms + P.pl_S < P.pl_m_end ? ms + P.pl_S : P.pl_m_end);
     // absolute 16-block groups: the first one holds block ms - (J - 1), the oldest block output ms needs
     const int64_t cfs = (int64_t)ms - (J - 1);
@@ -254,8 +263,13 @@ void k_decim_pm(const DecimParams P_)
     const int ngrp = active ? (int)((int64_t)((me - 1) / 16) - G0) + 1 : 0;
     const int64_t i_first_s = (G0 * 16 - 1) * (int64_t)D + 1;        // first sample of block 16 G0 (regular units: >= n0; edge units: the scratch starts here)
     const uint64_t i_first = (uint64_t)i_first_s;
+    uint64_t r_acc = P.rot_acc, r_inc = P.rot_inc;                   // this wave's NCO (PS: two wave-uniform scalar loads)
+    if constexpr (PS) {
+        const uint32_t bs = b < B ? b : 0u;
+        r_acc = P.rot_acc_s[bs]; r_inc = P.rot_inc_s[bs];
+    }
     uint32_t kb0 = edge ? 0u : (uint32_t)((i_first - P.rot_nbase) >> 9);          // 512-sample block of the coarse table's entry 0
-    if (active) t_hi_all[wave][lane] = edge ? make_float2(1.f, 0.f) : sincos_turn(P.rot_acc + ((uint64_t)(kb0 + (uint32_t)lane) << 9) * P.rot_inc);
+    if (active) t_hi_all[wave][lane] = edge ? make_float2(1.f, 0.f) : sincos_turn(r_acc + ((uint64_t)(kb0 + (uint32_t)lane) << 9) * r_inc);
     __syncthreads();
     if (!active) return;
 
@@ -312,7 +326,7 @@ void k_decim_pm(const DecimParams P_)
         if (((kg8 + GB) >> 12) >= (uint32_t)(NHI - 1)) {             // the group would leave the coarse table: re-base it (wave private, no barrier)
             const uint32_t sh = kg8 >> 12;
             kb0 += sh; kg8 -= sh << 12; kb8 -= sh << 12;
-            t_hi_all[wave][lane] = edge ? make_float2(1.f, 0.f) : sincos_turn(P.rot_acc + ((uint64_t)(kb0 + (uint32_t)lane) << 9) * P.rot_inc);
+            t_hi_all[wave][lane] = edge ? make_float2(1.f, 0.f) : sincos_turn(r_acc + ((uint64_t)(kb0 + (uint32_t)lane) << 9) * r_inc);
         }
         {   // everything up to the end of this group must have landed; younger pieces may stay in flight
             uint32_t need = (gbytes + GB + 1023u) >> 10;
@@ -426,9 +440,10 @@ void k_decim_pm(const DecimParams P_)
 // Contract "pm", one THREAD per output with checked fetches: zero in front of the stream, carried (already rotated) history in front of
 // this call's buffer, the caller's buffer with the exact NCO, or an engine ring.  Call edges that do not fit the staged scratch, the
 // outputs behind the last whole block of a call, and the second-stage form (input = an engine ring).
+template <bool PS = false>
 __global__ __launch_bounds__(256) void k_decim_pm_gen(const DecimParams P_, uint64_t m_first, uint32_t count)
 {
-    const DecimParams& P = P_;
+    ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     const uint32_t o = blockIdx.x * 256u + threadIdx.x;
     if (o >= count) return;
     const int b = blockIdx.y;
@@ -546,7 +561,7 @@ __device__ __forceinline__ v2f plx_mul(v2f hpair, v2f x)
     return r;
 }
 
-template <int E, int R, int U>
+template <int E, int R, int U, bool PS = false>
 __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 {
     constexpr int G = 16 / R;              // blocks per group of 16 outputs
@@ -554,13 +569,15 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
     constexpr int WU = (U - 1) / R;        // warm-up blocks in front of a segment
     static_assert(G % PLX_PF == 0 || PLX_PF % G == 0, "prefetch ring and group must nest");
     const DecimParams& P = P_;
-    __shared__ float2 t_lo[512];
+    __shared__ float2 t_lo[PS ? 4 * 512 : 512];   // PS: one fine table per wave (the waves may belong to different streams)
     __shared__ float2 t_one[512];
     __shared__ float2 t_hi_all[4][PLX_NHI];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    t_lo[tid] = P.rot_lo[tid];
-    t_lo[tid + 256] = P.rot_lo[tid + 256];
+    if constexpr (!PS) {
+        t_lo[tid] = P.rot_lo[tid];
+        t_lo[tid + 256] = P.rot_lo[tid + 256];
+    }
     t_one[tid] = make_float2(1.f, 0.f);
     t_one[tid + 256] = make_float2(1.f, 0.f);
 
@@ -581,13 +598,19 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
     const uint64_t c_first = (uint64_t)c_first_s;
     const uint64_t i_first = (uint64_t)((c_first_s - 1) * (int64_t)Dp + 1);   // regular units: >= n0 (interior outputs only)
     const uint32_t kb0 = edge ? 0u : (uint32_t)((i_first - P.rot_nbase) >> 9);
+    uint64_t r_acc = P.rot_acc, r_inc = P.rot_inc;                     // this wave's NCO
+    if constexpr (PS) {
+        const uint32_t bs = b < B ? b : 0u;
+        r_acc = P.rot_acc_s[bs]; r_inc = P.rot_inc_s[bs];
+        for (int k = lane; k < 512; k += 64) t_lo[wave * 512 + k] = P.rot_lo[(size_t)bs * 512 + k];
+    }
     float2* t_hi = t_hi_all[wave];
     if (active) {
 #pragma unroll
         for (int q = 0; q < PLX_NHI / 64; ++q)
-            t_hi[lane + 64 * q] = edge ? make_float2(1.f, 0.f) : sincos_turn(P.rot_acc + ((uint64_t)(kb0 + (uint32_t)(lane + 64 * q)) << 9) * P.rot_inc);
+            t_hi[lane + 64 * q] = edge ? make_float2(1.f, 0.f) : sincos_turn(r_acc + ((uint64_t)(kb0 + (uint32_t)(lane + 64 * q)) << 9) * r_inc);
     }
-    const float2* tl = edge ? t_one : t_lo;
+    const float2* tl = edge ? t_one : t_lo + (PS ? wave * 512 : 0);
     __syncthreads();
     if (!active) return;
 
@@ -673,9 +696,10 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 
 // Edge scratch of one call: for every stream the ROTATED samples i0 .. i0 + len - 1 (absolute indices, i0 may be negative): zeros in
 // front of the stream, the carried (already rotated) history in front of this call's buffer, the buffer's head through the exact NCO
+template <bool PS = false>
 __global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len)
 {
-    const DecimParams& P = P_;
+    ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= len) return;
     const int b = blockIdx.y;
@@ -700,9 +724,10 @@ __global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int
 
 // One wave per output, checked fetches: zero in front of the stream, carried (already rotated) history in front of this
 // call's buffer, the caller's buffer with the exact NCO, or an engine ring.
+template <bool PS = false>
 __global__ __launch_bounds__(256) void k_decim_pl_gen(const DecimParams P_, uint64_t m_first, uint32_t count)
 {
-    const DecimParams& P = P_;
+    ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     const int lane = threadIdx.x & 63;
     const uint32_t o = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (o >= count) return;
@@ -836,18 +861,18 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
         const int64_t i_last = (int64_t)(m_main - 1) * g.Dp;                   // last sample of the last edge block
         if (p.pl_edge && g.R == 1 && i_last - i0 + 1 <= (int64_t)p.pl_edge_cap) {
             const uint32_t len = (uint32_t)(i_last - i0 + 1);
-            hipLaunchKernelGGL(k_pl_edge_stage, dim3((len + 255) / 256, batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, len);
+            hipLaunchKernelGGL(p.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, dim3((len + 255) / 256, batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, len);
             if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
             q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
             edge_unit = true;
         } else {
             const uint32_t cnt = (uint32_t)(m_main - p.m0);
-            hipLaunchKernelGGL(k_decim_pl_gen, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, p.m0, cnt);
+            hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, p.m0, cnt);
         }
     }
     if (m_tail < m_end && m_tail >= m_main) {
         const uint32_t cnt = (uint32_t)(m_end - m_tail);
-        hipLaunchKernelGGL(k_decim_pl_gen, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, m_tail, cnt);
+        hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, m_tail, cnt);
     }
     if (m_main >= m_tail && !edge_unit) return 0;
     const uint64_t total = (m_tail - m_main) * (uint64_t)batch;
@@ -864,7 +889,8 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
     q.pl_S = (uint32_t)S;
     q.pl_nseg = (uint32_t)((m_tail - m_main + S - 1) / S);
     const uint32_t units = q.pl_nseg * (uint32_t)batch + (edge_unit ? (uint32_t)batch : 0u);
-    hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+    if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), dim3((units + 3) / 4), dim3(256), 0, s, q);
     return 0;
 }
 
@@ -929,28 +955,30 @@ std::vector<float> decim_pm_layout(const std::vector<float>& h, int D)
 // Segments: a multiple of 16 outputs each (every segment then starts on a group boundary).  Every segment re-reads `warm` blocks of
 // warm-up, and the call ends when the last wave does: with `cap` waves resident on the chip the cost of a split into nseg segments per
 // stream is  ceil(nseg x batch / cap)  rounds of  S + warm + 16  blocks.  Take the cheapest split; ties go to the finer one.
-static uint32_t pm_pick_segment(uint64_t M, uint32_t batch, uint32_t cap, uint32_t warm)
+// mult > 1 (per-stream offsets): only segment counts that are multiples of mult, each stream's units then fill whole workgroups (idle units counted)
+static uint32_t pm_pick_segment(uint64_t M, uint32_t batch, uint32_t cap, uint32_t warm, uint32_t mult = 1)
 {
     if (M <= 16) return 16;
     uint64_t best_cost = ~0ull; uint32_t best_S = 16;
     uint32_t n_lo = (uint32_t)((M + 4095) / 4096);
     const uint32_t n_hi = (uint32_t)((M + 127) / 128);
-    for (uint32_t nseg = n_lo; nseg <= n_hi; ++nseg) {
+    n_lo = (n_lo + mult - 1) / mult * mult;
+    for (uint32_t nseg = n_lo; nseg <= (n_hi > n_lo ? n_hi : n_lo); nseg += mult) {
         const uint32_t S = (uint32_t)(((M + nseg - 1) / nseg + 15) / 16 * 16);
-        const uint64_t units = ((M + S - 1) / S) * (uint64_t)batch;
+        const uint64_t units = (mult > 1 ? nseg : (M + S - 1) / S) * (uint64_t)batch;
         const uint64_t cost = ((units + cap - 1) / cap) * (uint64_t)(S + warm + 16);
         if (cost <= best_cost) { best_cost = cost; best_S = S; }
     }
     return best_S;
 }
-template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
-static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
+template <int J, int NS, int RP, bool K1, bool PS>
+static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
     // RP = ring pieces per wave (a power of two: one 16-block group -- 128 D bytes -- + what is in flight).
     // 4 waves per workgroup; at D = 50 four workgroups per CU (156 KB of LDS).  8-wave workgroups (two per CU, 144 KB: room for slim
     // recursion kernels of the previous call beside them) were measured: 7.24 ms against 6.57 ms alone, and no gain in the overlapped mode.
     constexpr int NW = QRL_PM_NW;
-    const auto kern = k_decim_pm<J, NS, RP, NW, K1>;
+    const auto kern = k_decim_pm<J, NS, RP, NW, K1, PS>;
     size_t lds = (size_t)NW * RP * 1024 + 512 * sizeof(float2) + NW * PM_NHI * sizeof(float2);
     // experiment (VERDICT r5 #4a): pad the dynamic LDS so that fewer front-end workgroups share a CU and a tail-chain workgroup of the previous call always
     // finds room beside them (QRL_PM_LDS_KB = total KB per workgroup; 45 -> three per CU with 25 KB to spare)
@@ -974,12 +1002,20 @@ static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_
         }
         wg_per_cu = wg_cache[dev]; n_cu = cu_cache[dev];
     }
-    const uint32_t S = pm_pick_segment(M, batch, (uint32_t)(wg_per_cu * n_cu * NW), (uint32_t)(J - 1));
+    // per-stream offsets: a multiple of NW segments per stream (whole workgroups per stream: one fine table each; segments past the end idle)
+    const uint32_t S = pm_pick_segment(M, batch, (uint32_t)(wg_per_cu * n_cu * NW), (uint32_t)(J - 1), PS ? (uint32_t)NW : 1u);
+    uint32_t nseg = M ? (uint32_t)((M + S - 1) / S) : 0u;
+    if (PS) nseg = (nseg + NW - 1) / NW * NW;
     q.pl_S = S;
-    q.pl_nseg = M ? (uint32_t)((M + S - 1) / S) : 0u;
+    q.pl_nseg = nseg;
     const uint32_t units = q.pl_nseg * batch + (edge_unit ? batch : 0u);
     hipLaunchKernelGGL(kern, dim3((units + NW - 1) / NW), dim3(NW * 64), lds, s, q);
     return 0;
+}
+template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
+static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
+{
+    return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false>(q, M, batch, edge_unit, s);
 }
 int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
 {
@@ -991,7 +1027,7 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
     q.pl_hraw = p.pl_taps + (size_t)pm_tiles(J) * NS * 64;
     const uint64_t m_end = p.m0 + p.m_count;
     auto gen = [&](uint64_t first, uint64_t last) {
-        if (last > first) hipLaunchKernelGGL(k_decim_pm_gen, dim3((uint32_t)((last - first + 255) / 256), batch), dim3(256), 0, s, q, first, (uint32_t)(last - first));
+        if (last > first) hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pm_gen<true> : k_decim_pm_gen<false>, dim3((uint32_t)((last - first + 255) / 256), batch), dim3(256), 0, s, q, first, (uint32_t)(last - first));
     };
     // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces: rows 16-byte aligned, even sample counts
     // (what qrl_demod_process demands; the edge scratch is built that way).  Anything else: one thread per output.
@@ -1014,7 +1050,7 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
         const int64_t i_last = (int64_t)(m_main - 1) * D;                  // last sample of the last edge output's newest block
         const int64_t len = ((i_last - i0 + 1) + 1) & ~(int64_t)1;
         if (len <= (int64_t)p.pl_edge_cap) {
-            hipLaunchKernelGGL(k_pl_edge_stage, dim3((uint32_t)((len + 255) / 256), batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, (uint32_t)len);
+            hipLaunchKernelGGL(p.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, dim3((uint32_t)((len + 255) / 256), batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, (uint32_t)len);
             if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
             q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
             edge_unit = true;

@@ -57,10 +57,10 @@ __device__ __forceinline__ float2 decim_fetch(const DecimParams& P, int b, int64
     return P.in_ring.p[(size_t)b * (P.in_ring.mask + 1u) + ((uint32_t)ui & P.in_ring.mask)];
 }
 
-template <int R, int JC>
+template <int R, int JC, bool PS = false>
 __global__ __launch_bounds__(256) void k_decim(const DecimParams P_)
 {
-    const DecimParams& P = P_;
+    ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int TILE = 64 * R;
     const int D = P.D, Jpad = P.Jpad;
@@ -227,7 +227,12 @@ void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
     q.tiles = tiles;
     dim3 grid((tiles + 7) / 8 * 8, batch), block(256);
     const size_t lds = decim_lds_bytes(p.D, p.Jpad, variant);
-    switch (variant) {
+    if (p.rot_acc_s) switch (variant) {
+    case DECIM_R4_J44: hipLaunchKernelGGL((k_decim<4, 44, true>), grid, block, lds, s, q); break;
+    case DECIM_R4_J12: hipLaunchKernelGGL((k_decim<4, 12, true>), grid, block, lds, s, q); break;
+    case DECIM_R2_J10: hipLaunchKernelGGL((k_decim<2, 10, true>), grid, block, lds, s, q); break;
+    default:           hipLaunchKernelGGL((k_decim<1, 14, true>), grid, block, lds, s, q); break;
+    } else switch (variant) {
     case DECIM_R4_J44: hipLaunchKernelGGL((k_decim<4, 44>), grid, block, lds, s, q); break;
     case DECIM_R4_J12: hipLaunchKernelGGL((k_decim<4, 12>), grid, block, lds, s, q); break;
     case DECIM_R2_J10: hipLaunchKernelGGL((k_decim<2, 10>), grid, block, lds, s, q); break;
@@ -236,8 +241,10 @@ void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
 }
 
 // ---- history keeper: hist_new[k] = rotated sample at absolute index n0 + n - H + k ----
-__global__ __launch_bounds__(256) void k_hist(const HistParams P)
+template <bool PS>
+__global__ __launch_bounds__(256) void k_hist(const HistParams P_)
 {
+    ROT_VIEW(HistParams, PS, P, P_, blockIdx.y);
     const int b = blockIdx.y;
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= P.hist_len) return;
@@ -260,7 +267,8 @@ void launch_hist_save(const HistParams& p, int batch, hipStream_t s)
 {
     if (p.hist_len == 0) return;
     dim3 grid((p.hist_len + 255) / 256, batch), block(256);
-    hipLaunchKernelGGL(k_hist, grid, block, 0, s, p);
+    if (p.rot_acc_s) hipLaunchKernelGGL(k_hist<true>, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(k_hist<false>, grid, block, 0, s, p);
 }
 
 // ---- K2: rational resampler I/D.  One fmaf chain per output, j ascending (oracle orc_resamp_ccf).
@@ -288,8 +296,10 @@ __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int
     return P.in_ring.p[(size_t)b * (P.in_ring.mask + 1u) + ((uint32_t)ui & P.in_ring.mask)];
 }
 
-__global__ __launch_bounds__(256) void k_resamp(const ResampParams P, int span)
+template <bool PS>
+__global__ __launch_bounds__(256) void k_resamp(const ResampParams P_, int span)
 {
+    ROT_VIEW(ResampParams, PS, P, P_, blockIdx.y);
     extern __shared__ __align__(16) unsigned char smem[];
     float* taps = reinterpret_cast<float*>(smem);                  // I * Jp
     float2* xs = reinterpret_cast<float2*>(taps + ((P.I * P.Jp + 3) & ~3));  // span
@@ -331,9 +341,10 @@ void launch_resamp(const ResampParams& p, int batch, hipStream_t s)
     int span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2;
     if ((size_t)span * sizeof(float2) > 48 * 1024) { T = 64; span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2; }
     const size_t lds = (size_t)((p.I * p.Jp + 3) & ~3) * sizeof(float) + (size_t)span * sizeof(float2);
-    if (dyn_lds_limit(reinterpret_cast<const void*>(k_resamp), 160 * 1024) != hipSuccess) return;
+    const auto kern = p.rot_acc_s ? k_resamp<true> : k_resamp<false>;
+    if (dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
     dim3 grid((p.q_count + T - 1) / T, batch), block(T);
-    hipLaunchKernelGGL(k_resamp, grid, block, lds, s, p, span);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, p, span);
 }
 
 
@@ -351,10 +362,11 @@ constexpr int D2_NTH = 256, D2_R = 8;
 constexpr int D2_W = 261;                        // positions per image: (40 + 2048) / 8
 constexpr int D2_HALO = 24;                      // second-filter taps, padded to a multiple of 8
 constexpr int D2_TY = D2_R * D2_NTH - D2_HALO;   // outputs a workgroup delivers
+template <bool PS>
 __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
 {
     const Dec2FirParams& P = P_;
-    const DecimParams& Q = P.d;
+    ROT_VIEW(DecimParams, PS, Q, P.d, blockIdx.y);
     __shared__ float2 t_lo[512];
     __shared__ float2 t_hi[16];
     __shared__ v2f img[2 * 8 * D2_W];            // [parity][image][position]; reused as [image][position] of the decimated samples
@@ -537,7 +549,33 @@ std::vector<float> dec2_fir_table(const std::vector<float>& h1, const std::vecto
 void launch_dec2_fir(const Dec2FirParams& p, int batch, hipStream_t s)
 {
     if (p.d.m_count == 0) return;
-    hipLaunchKernelGGL(k_dec2_fir, dim3((p.d.m_count + D2_TY - 1) / D2_TY, batch), dim3(D2_NTH), 0, s, p);
+    if (p.d.rot_acc_s) hipLaunchKernelGGL(k_dec2_fir<true>, dim3((p.d.m_count + D2_TY - 1) / D2_TY, batch), dim3(D2_NTH), 0, s, p);
+    else hipLaunchKernelGGL(k_dec2_fir<false>, dim3((p.d.m_count + D2_TY - 1) / D2_TY, batch), dim3(D2_NTH), 0, s, p);
+}
+
+// ---- per-stream rotator state (RotPs, engine.cpp) ----
+__global__ __launch_bounds__(256) void k_rot_ps_advance(uint64_t* acc, const uint64_t* inc, uint32_t B, uint64_t delta)
+{
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b < B) acc[b] += delta * inc[b];
+}
+void launch_rot_ps_advance(uint64_t* acc, const uint64_t* inc, int B, uint64_t delta, hipStream_t s)
+{
+    if (B > 0 && delta) hipLaunchKernelGGL(k_rot_ps_advance, dim3(((uint32_t)B + 255) / 256), dim3(256), 0, s, acc, inc, (uint32_t)B, delta);
+}
+// every stream: fine table = lo0, inc = inc0, and (set_acc) acc = acc0
+__global__ __launch_bounds__(256) void k_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, uint32_t B, int set_acc, uint64_t acc0, uint64_t inc0,
+                                                     const float2* lo0)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)B * 512) return;
+    const uint32_t b = (uint32_t)(i >> 9), r = (uint32_t)i & 511u;
+    lo[i] = lo0[r];
+    if (r == 0) { inc[b] = inc0; if (set_acc) acc[b] = acc0; }
+}
+void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set_acc, uint64_t acc0, uint64_t inc0, const float2* lo0, hipStream_t s)
+{
+    if (B > 0) hipLaunchKernelGGL(k_rot_ps_fill, dim3((uint32_t)B * 2u), dim3(256), 0, s, acc, inc, lo, (uint32_t)B, set_acc, acc0, inc0, lo0);
 }
 
 }  // namespace qrl

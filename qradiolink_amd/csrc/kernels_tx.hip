@@ -434,8 +434,10 @@ void launch_tx_interp_c(const TxInterpCParams& p, int batch, hipStream_t s)
 
 // ---- gr_mod_base back end (reference src/gr/gr_mod_base.cpp:38,249-258): rotator_cc(2 pi offset / 1e6) at 1 Msps, then
 // rational_resampler_ccf(fs/1e6, 1, low_pass(I, fs, 480k, 20k, BH)) (k_tx_interp_c).  Exact 2^-64-turn NCO as on RX.
-__global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P)
+template <bool PS>
+__global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P_)
 {
+    ROT_VIEW(TxRotParams, PS, P, P_, blockIdx.y);
     const int b = blockIdx.y;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= P.count) return;
@@ -450,7 +452,8 @@ __global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P)
 void launch_tx_rot(const TxRotParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    hipLaunchKernelGGL(k_tx_rot, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    if (p.rot_acc_s) hipLaunchKernelGGL(k_tx_rot<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_tx_rot<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 }  // namespace qrl

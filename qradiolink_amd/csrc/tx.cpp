@@ -4,6 +4,7 @@
 #include "engine.hpp"
 #include "firdes.hpp"
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -51,6 +52,7 @@ struct qrl_mod {
     float2* bb = nullptr; size_t bb_stride = 0;            // modulator output, linear, one call's worth
     float2* be_ring = nullptr; uint32_t be_mask = 0;       // rotated 1 Msps signal (interpolator history)
     float2* rot_lo = nullptr; uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0, n_bb = 0;
+    RotPs ps;   // per-stream offsets (qrl_mod_set_carrier_offsets); off: the shared NCO above
     int set_rot(double hz) {
         rot_inc = phase_inc_to_turn(2 * M_PI * hz / 1000000.0);
         std::vector<float2> lo(512);
@@ -58,6 +60,7 @@ struct qrl_mod {
         return hipMemcpy(rot_lo, lo.data(), 512 * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
     }
     ~qrl_mod() {
+        ps.release();
         if (taps) (void)hipFree(taps);
         for (void* p : {(void*)zero_dev, (void*)shape_taps, (void*)shaped, (void*)fmv, (void*)phase, (void*)m17_filt, (void*)m17_flt, (void*)ds_chips, (void*)ds_shaped, (void*)ds_c52, (void*)ds_c20, (void*)ds_if_taps}) if (p) (void)hipFree(p);
         if (st) (void)hipFree(st);
@@ -85,7 +88,7 @@ struct qrl_mod {
         if (be_ring && hipMemset(be_ring, 0, (size_t)cfg.batch * (be_mask + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
         nsym = 0; n_bb = 0; rot_acc = 0; rot_nbase = 0;
         zero_runs.clear();
-        return QRL_OK;
+        return ps.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -318,9 +321,26 @@ int qrl_mod_set_carrier_offset(qrl_mod* m, double hz)
     if (!m) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
     HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    m->rot_acc += (m->n_bb - m->rot_nbase) * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
+    const uint64_t delta = m->n_bb - m->rot_nbase;
+    m->rot_acc += delta * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
     m->rot_nbase = m->n_bb;
-    return m->set_rot(hz);
+    if (int r = m->set_rot(hz)) return r;
+    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
+    return m->ps.on() ? m->ps.set_all(delta, m->rot_inc, m->rot_lo, m->stream) : QRL_OK;
+}
+int qrl_mod_set_carrier_offsets(qrl_mod* m, const double* hz)
+{
+    if (!m || !hz) return QRL_ERR_ARG;
+    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
+    const int B = m->cfg.batch;
+    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    HIPCHK(hipStreamSynchronize(m->stream));
+    std::vector<uint64_t> ni((size_t)B);
+    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * hz[b] / 1000000.0);
+    const uint64_t delta = m->n_bb - m->rot_nbase;
+    m->rot_acc += delta * m->rot_inc;
+    m->rot_nbase = m->n_bb;
+    return m->ps.set(B, m->rot_acc, m->rot_inc, m->rot_lo, delta, ni.data(), m->stream);
 }
 int qrl_mod_set_bb_gain(qrl_mod* m, float g) { if (!m) return QRL_ERR_ARG; m->bb_gain = g; return QRL_OK; }
 int qrl_mod_add_zero_runs(qrl_mod* m, const qrl_zero_run* runs, size_t n)
@@ -371,7 +391,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
         TxRotParams rp{}; rp.in = m->bb; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo;
+        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo; m->ps.fill(rp);
         if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring, m->be_mask};
         else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
         launch_tx_rot(rp, B, m->stream);

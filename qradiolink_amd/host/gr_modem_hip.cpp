@@ -77,7 +77,7 @@ static constexpr size_t kDmoCap = 16;
 
 gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_chunk)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_chunk(max_chunk & ~(size_t)1),
-      d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams)
+      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams)
 {
     d_boxf[0].resize(streams); d_boxf[1].resize(streams); d_boxs.resize(streams);
     for (int k = 0; k < 2; ++k) { d_fbits[k].assign(streams, 0); d_fact[k].assign(streams, 0); }
@@ -137,6 +137,7 @@ void gr_demod_base_hip::open()
     c.batch = d_n; c.max_chunk = d_chunk; c.enable_side_outputs = 1;
     c.time_domain_samp_rate = d_scope_rate; c.time_domain_filter_width = d_scope_fw;
     chk(qrl_demod_create(d_rt.ctx(), &c, &d_h), "qrl_demod_create");
+    if (d_per_stream) chk(qrl_demod_set_carrier_offsets(d_h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
     chk(qrl_demod_out_caps(d_h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
     chk(qrl_demod_audio_cap(d_h, d_chunk, &d_acap), "qrl_demod_audio_cap");
     if (d_acap) chk(qrl_demod_set_squelch(d_h, (double)d_squelch), "qrl_demod_set_squelch");
@@ -244,7 +245,18 @@ void gr_demod_base_hip::set_carrier_offset(double hz)   // gr_demod_base.cpp:122
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_offset = hz;
+    d_offsets.assign((size_t)d_n, hz);
     if (d_h) chk(qrl_demod_set_carrier_offset(d_h, hz), "qrl_demod_set_carrier_offset");
+}
+void gr_demod_base_hip::set_carrier_offset(double hz, int stream)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (stream < 0 || stream >= d_n) throw std::out_of_range("gr_demod_base_hip::set_carrier_offset: stream out of range");
+    std::vector<double> v = d_offsets;
+    v[(size_t)stream] = hz;
+    if (d_h) chk(qrl_demod_set_carrier_offsets(d_h, v.data()), "qrl_demod_set_carrier_offsets");
+    d_offsets.swap(v);
+    d_per_stream = true;
 }
 void gr_demod_base_hip::set_samp_rate(int device_samp_rate)   // gr_demod_base.cpp:1303-1362: the resampler is rebuilt
 {
@@ -560,7 +572,7 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRData(int stream
 
 // ================================================================================================ gr_mod_base_hip
 gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_bytes)
-    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_queue(streams), d_aqueue(streams), d_sent(streams, 0)
+    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0)
 {
     d_cw_n = std::min<size_t>(1024, d_max);   // a facade built for fewer than 1024 items per call must still key CW
 }
@@ -572,6 +584,16 @@ gr_mod_base_hip::~gr_mod_base_hip()
     if (d_audio) (void)hipFree(d_audio);
     if (d_iq) (void)hipFree(d_iq);
 }
+static bool tx_mode_has_back_end(int mode)   // qrl_mod_create builds the gr_mod_base back end (rotator + interpolator) for every family but these (tx.cpp)
+{
+    return !(mode == QRL_MODEM_M17 || mode == QRL_MODEM_BPSK8);
+}
+bool gr_mod_base_hip::any_offset() const
+{
+    if (d_offset != 0.0) return true;
+    for (double f : d_offsets) if (f != 0.0) return true;
+    return false;
+}
 static bool analog_tx_mode(int mode)
 {
     return mode == QRL_MODEM_NBFM2500 || mode == QRL_MODEM_NBFM5000 || mode == QRL_MODEM_AM5000 || mode == QRL_MODEM_USB2500 || mode == QRL_MODEM_LSB2500 ||
@@ -580,15 +602,19 @@ static bool analog_tx_mode(int mode)
 void gr_mod_base_hip::open()
 {
     // create first, swap in on success: a mode / offset the engine rejects leaves the running modulator intact
-    const bool backend = d_rate >= 2000000 || d_offset != 0.0;
+    const bool backend = d_rate >= 2000000 || any_offset();
+    // the engine builds the back end at 1 Msps only for a non-zero configured offset: any stream's will do, open() sets each stream's below
+    double cfg_offset = d_offset;
+    if (d_per_stream && cfg_offset == 0.0) for (double f : d_offsets) if (f != 0.0) { cfg_offset = f; break; }
     qrl_mod* nh = nullptr; qrl_amod* nah = nullptr; uint8_t* nbytes = nullptr; float* naudio = nullptr; float* niq = nullptr;
     size_t spblock = 0, bpb = 1;
     try {
         if (analog_tx_mode(d_mode)) {
             qrl_amod_config c{};
             c.modem_type = d_mode; c.batch = d_n; c.max_samples = d_max; c.bb_gain = d_gain;
-            c.device_samp_rate = d_rate; c.carrier_offset_hz = d_offset;
+            c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
             chk(qrl_amod_create(d_rt.ctx(), &c, &nah), "qrl_amod_create");
+            if (d_per_stream && backend) chk(qrl_amod_set_carrier_offsets(nah, d_offsets.data()), "qrl_amod_set_carrier_offsets");
             // the reference's instances keep what their setters did across mode changes
             if (d_ctcss_touched && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(nah, d_ctcss), "qrl_amod_set_ctcss");
             if (d_width.count(d_mode)) chk(qrl_amod_set_filter_width(nah, d_width[d_mode]), "qrl_amod_set_filter_width");
@@ -598,8 +624,9 @@ void gr_mod_base_hip::open()
         } else {
             qrl_mod_config c{};
             c.modem_type = d_mode; c.use_mode_defaults = 1; c.batch = d_n; c.max_bytes = d_max; c.bb_gain = d_gain;
-            c.device_samp_rate = d_rate; c.carrier_offset_hz = d_offset;
+            c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
             chk(qrl_mod_create(d_rt.ctx(), &c, &nh), "qrl_mod_create");
+            if (d_per_stream && backend && tx_mode_has_back_end(d_mode)) chk(qrl_mod_set_carrier_offsets(nh, d_offsets.data()), "qrl_mod_set_carrier_offsets");
             hchk(hipMalloc(reinterpret_cast<void**>(&nbytes), (size_t)d_n * d_max), "hipMalloc");
             spblock = qrl_mod_samples_per_block(nh, &bpb);     // M17: 2500 samples per 3 bytes; every other mode: samples per byte, 1
             hchk(hipMalloc(reinterpret_cast<void**>(&niq), (size_t)d_n * (d_max / bpb + 1) * spblock * sizeof(gr_complex)), "hipMalloc");
@@ -699,10 +726,6 @@ void gr_mod_base_hip::set_bb_gain(float v)
     if (d_h) chk(qrl_mod_set_bb_gain(d_h, v), "qrl_mod_set_bb_gain");
     if (d_ah) chk(qrl_amod_set_bb_gain(d_ah, v), "qrl_amod_set_bb_gain");
 }
-static bool tx_mode_has_back_end(int mode)   // qrl_mod_create builds the gr_mod_base back end (rotator + interpolator) for every family but these (tx.cpp)
-{
-    return !(mode == QRL_MODEM_M17 || mode == QRL_MODEM_BPSK8);
-}
 void gr_mod_base_hip::set_carrier_offset(double hz)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
@@ -714,16 +737,47 @@ void gr_mod_base_hip::set_carrier_offset(double hz)
         if (d_mode >= 0 && !tx_mode_has_back_end(d_mode))
             throw std::invalid_argument("gr_mod_base_hip::set_carrier_offset: this mode's modulator has no rotator (M17 / DSSS back end not built); offset unchanged");
         const double old = d_offset;
+        const std::vector<double> old_v = d_offsets;
         d_offset = hz;
+        d_offsets.assign((size_t)d_n, hz);
         if (d_mode >= 0) {
             try { open(); }
-            catch (...) { d_offset = old; throw; }
+            catch (...) { d_offset = old; d_offsets = old_v; throw; }
         }
         return;
     }
     if (d_h) chk(qrl_mod_set_carrier_offset(d_h, hz), "qrl_mod_set_carrier_offset");
     if (d_ah) chk(qrl_amod_set_carrier_offset(d_ah, hz), "qrl_amod_set_carrier_offset");
     d_offset = hz;
+    d_offsets.assign((size_t)d_n, hz);
+}
+void gr_mod_base_hip::set_carrier_offset(double hz, int stream)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (stream < 0 || stream >= d_n) throw std::out_of_range("gr_mod_base_hip::set_carrier_offset: stream out of range");
+    std::vector<double> v = d_offsets;
+    v[(size_t)stream] = hz;
+    if (!d_backend) {
+        // the rule of the one-argument setter, for any stream: the first non-zero offset re-opens a back-end-less handle with a back end
+        bool any = false;
+        for (double f : v) any = any || f != 0.0;
+        if (!any) { d_offsets.swap(v); return; }
+        if (d_mode >= 0 && !tx_mode_has_back_end(d_mode))
+            throw std::invalid_argument("gr_mod_base_hip::set_carrier_offset: this mode's modulator has no rotator (M17 / DSSS back end not built); offset unchanged");
+        const std::vector<double> old_v = d_offsets;
+        const bool old_ps = d_per_stream;
+        d_offsets.swap(v);
+        d_per_stream = true;
+        if (d_mode >= 0) {
+            try { open(); }
+            catch (...) { d_offsets = old_v; d_per_stream = old_ps; throw; }
+        }
+        return;
+    }
+    if (d_h) chk(qrl_mod_set_carrier_offsets(d_h, v.data()), "qrl_mod_set_carrier_offsets");
+    if (d_ah) chk(qrl_amod_set_carrier_offsets(d_ah, v.data()), "qrl_amod_set_carrier_offsets");
+    d_offsets.swap(v);
+    d_per_stream = true;
 }
 void gr_mod_base_hip::set_samp_rate(int device_samp_rate)
 {

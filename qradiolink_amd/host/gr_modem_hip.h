@@ -45,7 +45,8 @@ public:
     gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate = 1000000, double carrier_offset_hz = 0.0, size_t max_chunk = 1 << 18);
     virtual ~gr_demod_base_hip();
     void set_mode(int mode);                                   // gr_modem_types value; flushes the mailboxes like the reference's graph swap
-    void set_carrier_offset(double hz);
+    void set_carrier_offset(double hz);                        // every stream
+    void set_carrier_offset(double hz, int stream);            // one radio (gr_modem::setCarrierOffset of radio `stream`); kept across set_mode / set_samp_rate
     void set_samp_rate(int device_samp_rate);
     void start() {}
     void stop() { flush(); }
@@ -114,6 +115,7 @@ private:
     void harvest(int which);
     qrl_runtime& d_rt;
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_chunk;
+    std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
     qrl_demod* d_h = nullptr;
     qrl_rssi* d_rssi = nullptr; qrl_fft* d_fft = nullptr; bool d_rssi_on = false, d_fft_on = false; float d_rssi_cal = 0.0f; unsigned d_fftsize = 32768;
     float d_ctcss = 0.0f; bool d_const_on = true, d_demod_on = true;
@@ -154,8 +156,11 @@ public:
     // samples at the zero-idle block's 24 ksps input).  The source's tx_time tags belong to the SDR sink and are not produced.  QRL_MODEM_DMR mode only.
     int setDMRData(const std::vector<std::vector<uint8_t>>& frames, int stream = 0);
     void set_bb_gain(float value);
-    void set_carrier_offset(double hz);
+    void set_carrier_offset(double hz);                        // every stream
+    void set_carrier_offset(double hz, int stream);            // one radio (gr_modem::setTxCarrierOffset of radio `stream`); kept across set_mode / set_samp_rate
     double carrier_offset() const { return d_offset; }
+    double carrier_offset(int stream) const { return d_offsets.at((size_t)stream); }
+    bool has_back_end() const { return d_backend; }           // the open handle has the gr_mod_base back end (rotator + interpolator)
     void set_samp_rate(int device_samp_rate);                  // gr_mod_base::set_samp_rate (src/gr/gr_mod_base.cpp:211-262): the output interpolator is rebuilt (the modulator restarts)
     void flush_sources();                                      // gr_mod_base::flush_sources (:959-965): what is queued in the byte and audio sources is dropped
     int mode() const { return d_mode; }
@@ -185,6 +190,8 @@ private:
     void open();
     qrl_runtime& d_rt;
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_max; float d_gain = 1.0f;
+    std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
+    bool any_offset() const;
     qrl_mod* d_h = nullptr; uint8_t* d_bytes = nullptr; float* d_iq = nullptr;
     qrl_amod* d_ah = nullptr; float* d_audio = nullptr; float d_ctcss = 0.0f; bool d_ctcss_touched = false; std::map<int, int> d_width;
     bool d_cw_key = false; size_t d_cw_n = 1024;   // clamped to max_bytes by the constructor and by open()
