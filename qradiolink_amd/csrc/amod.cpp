@@ -7,10 +7,8 @@
 // Kernels: k_am_load, k_fir_fff, k_am_iir, k_an_resamp (host-side counts), k_tx_fm, k_fir_ccf, k_scale_c, k_tx_interp_c.
 // Arithmetic = oracle/orc_chains.c orc_mod_nbfm, bit for bit, independent of how the audio is cut into calls (multiples of 4 samples:
 // the 25:4 resampler then produces whole groups of 25).
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -19,24 +17,8 @@
 #include <vector>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
-template <class T> struct Dev {
-    T* p = nullptr; size_t n = 0;
-    ~Dev() { if (p) (void)hipFree(p); }
-    int alloc(size_t count) { if (p) { (void)hipFree(p); p = nullptr; } n = count; return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
-    int upload(const std::vector<T>& v) { if (int r = alloc(v.size())) return r; return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
-    int zero() { return hipMemset(p, 0, n * sizeof(T)) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
-};
-uint32_t pow2_at_least(size_t v) { uint32_t c = 1024; while (c < v) c <<= 1; return c; }
 // gr::fxpt's 1024-row interpolated sine table {slope, intercept} (oracle orc_fxpt_sine_table)
 std::vector<float> fxpt_sine_table()
 {
@@ -66,29 +48,21 @@ struct qrl_amod {
     hipStream_t stream = nullptr; bool own_stream = false;
     int sps = 20, fw = 5000; bool ssb = false, lsb = false, am = false;
     bool cw = false; double cw_ampl = 0.001;   // QRL_MODEM_CW600USB: the SSB chain fed by sig_source_f(8000, GR_SIN_WAVE, 600, 0.001, 1) (gr_mod_base.cpp:144,180,679-683)
-    Dev<float> am_gain; Dev<float2> t_chan, m1, m2; int n_chan = 0; uint32_t mm = 0; uint64_t n1m = 0;   // AM: agc gain per stream, 1 Msps rings, channel filter
-    Dev<float2> t_side, c1, c2, c3; int n_side = 0; Dev<float> atan_tab; uint64_t ns = 0; size_t last = 0;   // SSB
+    DevBuf<float> am_gain; DevBuf<float2> t_chan, m1, m2; int n_chan = 0; uint32_t mm = 0; uint64_t n1m = 0;   // AM: agc gain per stream, 1 Msps rings, channel filter
+    DevBuf<float2> t_side, c1, c2, c3; int n_side = 0; DevBuf<float> atan_tab; uint64_t ns = 0; size_t last = 0;   // SSB
     float bb_gain = 1.0f, fm_k = 0.f;
-    Dev<float> t_audio, t_if, t_filt, t_interp; int n_audio = 0, n_if = 0, n_filt = 0, n_interp = 0;
+    DevBuf<float> t_audio, t_if, t_filt, t_interp; int n_audio = 0, n_if = 0, n_filt = 0, n_interp = 0;
     // gr_mod_nbfm::set_ctcss (src/gr/gr_mod_nbfm.cpp:101-135): band-pass audio filter, _audio_amplify 0.85 / 0.98, tone source + add_ff
-    Dev<float> t_audio_bp, tone_tab; int n_audio_bp = 0; float k_audio = 0.99f; float tone_hz = 0.0f; uint32_t tone_inc = 0; uint64_t tone_k = 0, cw_k = 0;   // sample counters of the CTCSS tone and of the CW key's tone source (sig_source_f free-runs: a filter change does not reset them)
-    Dev<float> a0, a1, a2, r50; uint32_t m8 = 0, m50 = 0;       // rings: audio in, filtered, pre-emphasised (8 ksps); 50 ksps
-    Dev<float2> fmv, flt;                                        // 50 ksps complex: modulator out, channel filter out
-    Dev<AmIirState> iir; Dev<float> phase;
+    DevBuf<float> t_audio_bp, tone_tab; int n_audio_bp = 0; float k_audio = 0.99f; float tone_hz = 0.0f; uint32_t tone_inc = 0; uint64_t tone_k = 0, cw_k = 0;   // sample counters of the CTCSS tone and of the CW key's tone source (sig_source_f free-runs: a filter change does not reset them)
+    DevBuf<float> a0, a1, a2, r50; uint32_t m8 = 0, m50 = 0;       // rings: audio in, filtered, pre-emphasised (8 ksps); 50 ksps
+    DevBuf<float2> fmv, flt;                                        // 50 ksps complex: modulator out, channel filter out
+    DevBuf<AmIirState> iir; DevBuf<float> phase;
     double pb[2] = {0, 0}, pa[2] = {0, 0};
     uint64_t n8 = 0, n50 = 0;
     // gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258), as behind the digital modulators (tx.cpp): rotator at 1 Msps, then the interpolator to the device rate
-    bool backend = false; int be_interp = 1, be_nt = 0; Dev<float> be_taps;
-    Dev<float2> bb, be_ring, rot_lo; size_t bb_stride = 0; uint32_t be_mask = 0;
-    uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0, n_bb = 0;
-    RotPs ps;   // per-stream offsets (qrl_amod_set_carrier_offsets); off: the shared NCO above
-    int set_rot(double hz)
-    {
-        rot_inc = phase_inc_to_turn(2 * M_PI * hz / 1000000.0);
-        std::vector<float2> lo(512);
-        for (int r = 0; r < 512; ++r) { float sn, cs; sincos_turn_host((uint64_t)r * rot_inc, sn, cs); lo[r] = make_float2(cs, sn); }
-        return hipMemcpy(rot_lo.p, lo.data(), 512 * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
+    bool backend = false; int be_interp = 1, be_nt = 0; DevBuf<float> be_taps;
+    DevBuf<float2> bb, be_ring; size_t bb_stride = 0; uint32_t be_mask = 0;
+    Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
     size_t cap_1msps(size_t n) const { return am ? n * (size_t)sps : ssb ? (n + 1024) * (size_t)sps : n * 25 / 4 * (size_t)sps; }
     int init_back_end()
     {
@@ -100,17 +74,17 @@ struct qrl_amod {
         if (!backend) return QRL_OK;
         int r;
         bb_stride = cap_1msps(cfg.max_samples);
-        if ((r = bb.alloc((size_t)cfg.batch * bb_stride)) || (r = rot_lo.alloc(512)) || (r = set_rot(cfg.carrier_offset_hz))) return r;
+        if ((r = bb.alloc((size_t)cfg.batch * bb_stride)) || (r = rot.init(phase_inc_to_turn(2 * M_PI * cfg.carrier_offset_hz / 1000000.0)))) return r;
         if (be_interp > 1) {
             const std::vector<float> lp = low_pass(be_interp, rate, 480000, 20000, WIN_BLACKMAN_HARRIS);   // gr_mod_base.cpp:215-258
             be_nt = (int)lp.size();
             if ((r = be_taps.upload(lp))) return r;
-            be_mask = pow2_at_least(bb_stride + (size_t)be_nt / be_interp + 64) - 1;
+            be_mask = pow2_at_least(bb_stride + (size_t)be_nt / be_interp + 64, 1024) - 1;
             if ((r = be_ring.alloc((size_t)cfg.batch * (be_mask + 1)))) return r;
         }
         return QRL_OK;
     }
-    ~qrl_amod() { ps.release(); if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    ~qrl_amod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int init_state(bool keep_tone_phase = false)
     {
         int r;
@@ -126,8 +100,8 @@ struct qrl_amod {
         n8 = n50 = ns = 0; last = 0;
         if (!keep_tone_phase) tone_k = cw_k = 0;   // qrl_amod_set_filter_width restarts the chain but the reference's sig_source_f keeps running
         if (be_ring.p && (r = be_ring.zero())) return r;
-        n_bb = 0; rot_acc = 0; rot_nbase = 0;
-        return ps.reset(stream);   // per-stream phases restart too; the offsets stay
+        n_bb = 0;
+        return rot.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -164,8 +138,8 @@ int qrl_amod_create(qrl_ctx* ctx, const qrl_amod_config* cfg, qrl_amod** outp)
         for (size_t i = 0; i < tc.size(); ++i) tc2[i] = make_float2(tc[i].real(), tc[i].imag());
         int r;
         if ((r = m->t_audio.upload(ta)) || (r = m->t_interp.upload(tr)) || (r = m->t_chan.upload(tc2))) return r;
-        m->m8 = pow2_at_least(cfg->max_samples + 1024) - 1;
-        m->mm = pow2_at_least((size_t)cfg->max_samples * m->sps + (size_t)m->n_chan + 1024) - 1;
+        m->m8 = pow2_at_least(cfg->max_samples + 1024, 1024) - 1;
+        m->mm = pow2_at_least((size_t)cfg->max_samples * m->sps + (size_t)m->n_chan + 1024, 1024) - 1;
         const size_t r8 = (size_t)B * (m->m8 + 1), r1m = (size_t)B * (m->mm + 1);
         if ((r = m->a0.alloc(r8)) || (r = m->a1.alloc(r8)) || (r = m->a2.alloc(r8)) || (r = m->c1.alloc(r8)) || (r = m->c2.alloc(1)) || (r = m->c3.alloc(1)) ||
             (r = m->m1.alloc(r1m)) || (r = m->m2.alloc(r1m)) || (r = m->am_gain.alloc(B))) return r;
@@ -186,7 +160,7 @@ int qrl_amod_create(qrl_ctx* ctx, const qrl_amod_config* cfg, qrl_amod** outp)
         int r;
         if ((r = m->t_audio.upload(ta)) || (r = m->t_side.upload(ts2)) || (r = m->t_interp.upload(tr)) || (r = m->atan_tab.upload(atan_table()))) return r;
         if (m->cw) { if ((r = m->tone_tab.upload(fxpt_sine_table()))) return r; m->tone_inc = fxpt_phase_inc(8000.0, 600.0); }
-        m->m8 = pow2_at_least(cfg->max_samples + 2048) - 1;        // the stretcher holds back up to 1025 items
+        m->m8 = pow2_at_least(cfg->max_samples + 2048, 1024) - 1;        // the stretcher holds back up to 1025 items
         const size_t r8 = (size_t)B * (m->m8 + 1);
         if ((r = m->a0.alloc(r8)) || (r = m->a1.alloc(r8)) || (r = m->c1.alloc(r8)) || (r = m->c2.alloc(r8)) || (r = m->c3.alloc(r8))) return r;
         // (members of the FM chain stay empty)
@@ -211,8 +185,8 @@ int qrl_amod_create(qrl_ctx* ctx, const qrl_amod_config* cfg, qrl_amod** outp)
     m->fm_k = (float)(4 * M_PI * fw / 50000.0f);                                                          // frequency_modulator_fc, :41
     preemph_taps(8000, 50e-6, m->pa, m->pb);                                                              // :39
     const size_t max50 = cfg->max_samples * 25 / 4 + 32;
-    m->m8 = pow2_at_least(cfg->max_samples + 1024) - 1;
-    m->m50 = pow2_at_least(max50 + 2048) - 1;
+    m->m8 = pow2_at_least(cfg->max_samples + 1024, 1024) - 1;
+    m->m50 = pow2_at_least(max50 + 2048, 1024) - 1;
     const size_t r8 = (size_t)B * (m->m8 + 1), r5 = (size_t)B * (m->m50 + 1);
     if ((r = m->a0.alloc(r8)) || (r = m->a1.alloc(r8)) || (r = m->a2.alloc(r8)) || (r = m->r50.alloc(r5)) || (r = m->fmv.alloc(r5)) ||
         (r = m->flt.alloc(r5)) || (r = m->iir.alloc(B)) || (r = m->phase.alloc(B))) return r;
@@ -291,26 +265,16 @@ int qrl_amod_set_carrier_offset(qrl_amod* m, double hz)
     if (!m) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
     HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    const uint64_t delta = m->n_bb - m->rot_nbase;
-    m->rot_acc += delta * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
-    m->rot_nbase = m->n_bb;
-    if (int r = m->set_rot(hz)) return r;
-    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
-    return m->ps.on() ? m->ps.set_all(delta, m->rot_inc, m->rot_lo.p, m->stream) : QRL_OK;
+    return m->rot.retune(m->n_bb, phase_inc_to_turn(2 * M_PI * hz / 1000000.0), m->stream);   // phase-continuous, like rotator_cc::set_phase_inc
 }
 int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz)
 {
     if (!m || !hz) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
-    const int B = m->cfg.batch;
-    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    std::vector<uint64_t> ni;
+    if (int r = carrier_incs(hz, m->cfg.batch, 1.0, 1000000.0, ni)) return r;
     HIPCHK(hipStreamSynchronize(m->stream));
-    std::vector<uint64_t> ni((size_t)B);
-    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * hz[b] / 1000000.0);
-    const uint64_t delta = m->n_bb - m->rot_nbase;
-    m->rot_acc += delta * m->rot_inc;
-    m->rot_nbase = m->n_bb;
-    return m->ps.set(B, m->rot_acc, m->rot_inc, m->rot_lo.p, delta, ni.data(), m->stream);
+    return m->rot.retune_streams(m->n_bb, ni, m->stream);
 }
 void* qrl_amod_stream(qrl_amod* m) { return m ? m->stream : nullptr; }
 int qrl_amod_sync(qrl_amod* m) { if (!m) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(m->stream)); return QRL_OK; }
@@ -331,7 +295,7 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
         if (!m->backend || !n1) return;
         TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo.p; m->ps.fill(rp);
+        m->rot.fill(rp);
         if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
         else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
         launch_tx_rot(rp, B, s);

@@ -2,10 +2,8 @@
 // PFB channelizer -> per channel {rational_resampler_ccf(24,25), fft_filter_ccf, quadrature_demod_cf, level, float_to_short}.
 // A handle owns `batch` wideband inputs and produces the channels [channel_first, channel_first + channel_count):
 // a multi-GPU job gives every rank the same wideband samples (or its own inputs) and a different channel range.
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -15,41 +13,16 @@
 #include <vector>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-namespace {
-template <class T> struct Buf {
-    T* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) {
-        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return QRL_ERR_NOMEM;
-        return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
-    int upload(const std::vector<T>& v) {
-        int r = alloc(v.size());
-        if (r) return r;
-        return v.empty() || hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
-};
-uint32_t pow2ge(size_t v) { uint32_t c = 64; while (c < v) c <<= 1; return c; }
-}  // namespace
 
 struct qrl_chan {
     qrl_ctx* ctx = nullptr;
     qrl_chan_config cfg{};
     hipStream_t stream = nullptr; bool own_stream = false;
     int M = 10, J = 0, nt = 0, rs_Jp = 0, filt_nt = 0;
-    Buf<float> taps, rs_taps, filt_taps, atan_tab; Buf<float2> twiddle;
-    Buf<float> ct_a, ct_b, ct_e;   // step-major tap tables of the fused per-channel kernel
-    Buf<float2> hist_a, hist_b; uint32_t hist_len = 0; bool flip = false;
-    Buf<float2> r1, r2, r3; Buf<float> r4; uint32_t m1 = 0, m2 = 0;
+    DevBuf<float> taps, rs_taps, filt_taps, atan_tab; DevBuf<float2> twiddle;
+    DevBuf<float> ct_a, ct_b, ct_e;   // step-major tap tables of the fused per-channel kernel
+    DevBuf<float2> hist_a, hist_b; uint32_t hist_len = 0; bool flip = false;
+    DevBuf<float2> r1, r2, r3; DevBuf<float> r4; uint32_t m1 = 0, m2 = 0;
     uint64_t n_in = 0, n1 = 0, n2 = 0;
     float gain = 0, level = 1.0f, rssi_cal = 0.0f;
     bool tail_only = false;   // form 3: only the per-channel chain; its input = 25 ksps channel streams (qrl_chan_process_channels)
@@ -71,11 +44,11 @@ struct qrl_chan {
     int opt_legacy_pfb = 0, opt_legacy_tail = 0;   // qrl_chan_set_option
     bool profiling = false; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;   // qrl_chan_profile: the HBM-facing kernel(s) of each call
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_tail, prof_ss;                      // ... the fused per-channel kernel and the symbol synchroniser (qrl_chan_profile_read_kernels)
-    bool xlat = false; int xl_D = 10, xl_nt = 0, xl_S = 0; Buf<float> xl_taps; Buf<float2> xl_rot_lo; std::vector<uint64_t> xl_inc;   // form 1
+    bool xlat = false; int xl_D = 10, xl_nt = 0, xl_S = 0; DevBuf<float> xl_taps; DevBuf<float2> xl_rot_lo; std::vector<uint64_t> xl_inc;   // form 1
     bool single = false; int rs_I = 24, rs_D = 25;   // single: gr_demod_mmdvm (one carrier at 250 ksps, 12/125 resampler, no channelizer)
     float* rssi_out = nullptr; size_t rssi_cap = 0; uint32_t* rssi_counts = nullptr;
     // optional 4FSK symbol tail behind every channel (gr_demod_dmr.cpp:62-105 on the 24 ksps channel signal)
-    Buf<float> r5, r6, symf_taps, mmse; Buf<SymSyncState> ss; Buf<uint8_t> soft_dummy; int symf_nt = 0; float ss_alpha = 0, ss_beta = 0;
+    DevBuf<float> r5, r6, symf_taps, mmse; DevBuf<SymSyncState> ss; DevBuf<uint8_t> soft_dummy; int symf_nt = 0; float ss_alpha = 0, ss_beta = 0;
     uint8_t* fsk_bits = nullptr; size_t fsk_bits_cap = 0; float* fsk_const = nullptr; size_t fsk_const_cap = 0; uint32_t* fsk_counts = nullptr;
     int init_ss() {
         std::vector<SymSyncState> s((size_t)cfg.batch * cfg.channel_count);
@@ -95,18 +68,12 @@ struct qrl_chan {
                   if (tail) (void)hipStreamDestroy(tail);
                   if (ev_user) (void)hipEventDestroy(ev_user); if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int reset_state() {
-        const size_t S = (size_t)cfg.batch * cfg.channel_count;
-        if (hipMemset(hist_a.p, 0, (size_t)cfg.batch * hist_len * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(hist_b.p, 0, (size_t)cfg.batch * hist_len * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(r1.p, 0, S * (m1 + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(r2.p, 0, S * (m2 + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(r3.p, 0, S * (m2 + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(r4.p, 0, S * (m2 + 1) * sizeof(float)) != hipSuccess) return QRL_ERR_HIP;
+        if (hist_a.zero() || hist_b.zero() || r1.zero() || r2.zero() || r3.zero() || r4.zero()) return QRL_ERR_HIP;
         n_in = n1 = n2 = 0; flip = false;
         mid_valid[0] = mid_valid[1] = mid_valid[2] = false;
         if (!ss.p) call_no = 0;
         if (ss.p) {
-            if (hipMemset(r5.p, 0, S * (m2 + 1) * sizeof(float)) != hipSuccess || hipMemset(r6.p, 0, S * (m6 + 1) * sizeof(float)) != hipSuccess) return QRL_ERR_HIP;
+            if (r5.zero() || r6.zero()) return QRL_ERR_HIP;
             tail_valid[0] = tail_valid[1] = false; call_no = 0;
             return init_ss();
         }
@@ -191,7 +158,8 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
             const int ct = c.num_channels <= 7 ? (i > 3 ? 3 - i : i) : (i <= c.num_channels / 2 ? i : i - c.num_channels);
             const float carrier_offset = (float)(-sep);
             h->xl_inc[cl] = phase_inc_to_turn(2 * M_PI * carrier_offset * ct / (float)fs);
-            for (int k = 0; k < 512; ++k) { float sn, cs; sincos_turn_host((uint64_t)k * h->xl_inc[cl], sn, cs); lo[(size_t)cl * 512 + k] = make_float2(cs, sn); }
+            const std::vector<float2> t = rot_fine_table(h->xl_inc[cl]);
+            std::copy(t.begin(), t.end(), lo.begin() + (ptrdiff_t)cl * 512);
         }
         if ((r = h->xl_rot_lo.upload(lo))) return r;
         h->rs_I = 1; h->rs_D = h->xl_D;
@@ -217,7 +185,8 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
             const int ct = i <= c.num_channels / 2 ? i : i - c.num_channels;
             const float carrier_offset = -25000.0f;
             h->xl_inc[cl] = phase_inc_to_turn(2 * M_PI * carrier_offset * ct / (float)fs);
-            for (int k = 0; k < 512; ++k) { float sn, cs; sincos_turn_host((uint64_t)k * h->xl_inc[cl], sn, cs); lo[(size_t)cl * 512 + k] = make_float2(cs, sn); }
+            const std::vector<float2> t = rot_fine_table(h->xl_inc[cl]);
+            std::copy(t.begin(), t.end(), lo.begin() + (ptrdiff_t)cl * 512);
         }
         if ((r = h->xl_rot_lo.upload(lo))) return r;
     }
@@ -238,8 +207,8 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
     // (PFB form on a handle-owned stream: TWO calls, the channelizer of call k + 1 writes while the per-channel kernel of call k still reads)
     const bool can_overlap = h->own_stream && !h->single && !h->xlat && !h->xlat2 && !h->tail_only && ct_ok;
     if (const char* e = std::getenv("QRL_CHAN_RING_CALLS")) { const int v = std::atoi(e); if (v == 2 || v == 3) h->ring_calls = v; }
-    h->m1 = (h->single || h->xlat) ? 63 : pow2ge((can_overlap ? h->ring_calls : 1) * max1 + h->rs_Jp + 64 + chan_tail_lookback()) - 1;   // the single-carrier chain reads the caller's IQ directly
-    h->m2 = pow2ge(max2 + h->filt_nt + 64 + 300) - 1;   // + one rssi_tag_block window
+    h->m1 = (h->single || h->xlat) ? 63 : pow2_at_least((can_overlap ? h->ring_calls : 1) * max1 + h->rs_Jp + 64 + chan_tail_lookback(), 64) - 1;   // the single-carrier chain reads the caller's IQ directly
+    h->m2 = pow2_at_least(max2 + h->filt_nt + 64 + 300, 64) - 1;   // + one rssi_tag_block window
     if ((r = h->hist_a.alloc((size_t)c.batch * h->hist_len)) || (r = h->hist_b.alloc((size_t)c.batch * h->hist_len)) ||
         (r = h->r1.alloc(S * (h->m1 + 1))) || (r = h->r2.alloc(S * (h->m2 + 1))) || (r = h->r3.alloc(S * (h->m2 + 1))) ||
         (r = h->r4.alloc(S * (h->m2 + 1))))
@@ -305,7 +274,7 @@ int qrl_chan_set_4fsk_output(qrl_chan* h, uint8_t* bits, size_t bits_cap, float*
         const std::vector<float> rrc = root_raised_cosine(1, 24000, 4800, 0.2, 25 * 5);      // gr_demod_dmr.cpp:62-66
         h->symf_nt = (int)rrc.size();
         const size_t max2 = (h->cfg.max_chunk / (h->xlat2 ? h->xl_D : h->M) + 2) * h->rs_I / h->rs_D + 2;
-        h->m6 = pow2ge(2 * max2 + h->symf_nt + 64 + 300) - 1;   // two calls: the symbol sync of call k runs beside the kernels of call k + 1
+        h->m6 = pow2_at_least(2 * max2 + h->symf_nt + 64 + 300, 64) - 1;   // two calls: the symbol sync of call k runs beside the kernels of call k + 1
         if (chan_tail_supported(h->rs_I, h->rs_D, h->rs_Jp, h->filt_nt, h->symf_nt) && (r = h->ct_e.upload(chan_tail_tables(2, rrc.data())))) return r;
         if ((r = h->symf_taps.upload(rrc)) || (r = h->mmse.upload(mmse_table())) || (r = h->r5.alloc(S * (h->m2 + 1))) ||
             (r = h->r6.alloc(S * (h->m6 + 1))) || (r = h->ss.alloc(S)) || (r = h->soft_dummy.alloc(64)))

@@ -1,30 +1,17 @@
 // deframe.cpp — host side of the device deframer (gr_deframer_bb, reference src/gr/gr_deframer_bb.cpp:24-185).
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
-#include <hip/hip_runtime.h>
+#include "host_common.hpp"
 #include <memory>
 #include <new>
 #include <string>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct qrl_deframer {
     qrl_ctx* ctx = nullptr;
     int type = 1, batch = 1;
     hipStream_t stream = nullptr; bool own_stream = false;
-    DeframeState* st = nullptr;
-    ~qrl_deframer() {
-        if (st) (void)hipFree(st);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    DevBuf<DeframeState> st;
+    ~qrl_deframer() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 
 extern "C" {
@@ -40,8 +27,7 @@ int qrl_deframer_create(qrl_ctx* ctx, int deframer_type, int batch, void* hip_st
     HIPCHK(hipSetDevice(ctx->device));
     if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
     else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->st), (size_t)batch * sizeof(DeframeState)));
-    HIPCHK(hipMemset(h->st, 0, (size_t)batch * sizeof(DeframeState)));
+    if (int r = h->st.alloc(batch)) return r;
     *out = h.release();
     return QRL_OK;
 }
@@ -49,7 +35,7 @@ void qrl_deframer_destroy(qrl_deframer* h) { if (h) { (void)hipStreamSynchronize
 int qrl_deframer_reset(qrl_deframer* h)
 {
     if (!h) return QRL_ERR_ARG;
-    HIPCHK(hipMemsetAsync(h->st, 0, (size_t)h->batch * sizeof(DeframeState), h->stream));
+    HIPCHK(hipMemsetAsync(h->st.p, 0, (size_t)h->batch * sizeof(DeframeState), h->stream));
     return QRL_OK;
 }
 int qrl_deframer_process(qrl_deframer* h, const uint8_t* bits, size_t stride, size_t n, const uint32_t* counts, size_t count_stride,
@@ -61,7 +47,7 @@ int qrl_deframer_process(qrl_deframer* h, const uint8_t* bits, size_t stride, si
     DeframeParams p{};
     p.bits = bits; p.stride = stride; p.n = (uint32_t)n; p.counts = counts; p.count_stride = count_stride;
     p.type = h->type; p.buf_len = h->type == 1 ? 64u : h->type == 2 ? 32u : 384u;
-    p.st = h->st; p.out = out; p.out_cap = out_cap; p.out_counts = out_counts;
+    p.st = h->st.p; p.out = out; p.out_cap = out_cap; p.out_counts = out_counts;
     launch_deframe(p, h->batch, h->stream);
     HIPCHK(hipGetLastError());
     return QRL_OK;
@@ -79,12 +65,8 @@ int qrl_deframer_sync(qrl_deframer* h)
 struct qrl_framesync {
     qrl_ctx* ctx = nullptr; int batch = 1, cls = 2; uint32_t bit_buf_len = 64, frame_length = 7;
     hipStream_t stream = nullptr; bool own_stream = false;
-    FrameSyncState* st = nullptr; uint8_t* bitbuf = nullptr; size_t bitbuf_stride = 0; uint32_t* activity = nullptr;
-    ~qrl_framesync() {
-        if (st) (void)hipFree(st);
-        if (bitbuf) (void)hipFree(bitbuf);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    DevBuf<FrameSyncState> st; DevBuf<uint8_t> bitbuf; size_t bitbuf_stride = 0; uint32_t* activity = nullptr;
+    ~qrl_framesync() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 // mode table of gr_modem::toggleRxMode (src/gr_modem.cpp:203-322) and the sync-word classes of gr_modem::findSync (:1183-1282)
 static int framesync_geometry(int modem_type, uint32_t& bits, uint32_t& len)
@@ -116,9 +98,8 @@ int qrl_framesync_create(qrl_ctx* ctx, int modem_type, int batch, void* hip_stre
     if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
     else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
     h->bitbuf_stride = (h->bit_buf_len + 15u) & ~15u;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->st), (size_t)batch * sizeof(FrameSyncState)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->bitbuf), (size_t)batch * h->bitbuf_stride));
-    HIPCHK(hipMemset(h->st, 0, (size_t)batch * sizeof(FrameSyncState)));
+    int r;
+    if ((r = h->st.alloc(batch)) || (r = h->bitbuf.alloc((size_t)batch * h->bitbuf_stride))) return r;
     *out = h.release();
     return QRL_OK;
 }
@@ -126,7 +107,7 @@ void qrl_framesync_destroy(qrl_framesync* h) { if (h) { (void)hipStreamSynchroni
 int qrl_framesync_reset(qrl_framesync* h)
 {
     if (!h) return QRL_ERR_ARG;
-    HIPCHK(hipMemsetAsync(h->st, 0, (size_t)h->batch * sizeof(FrameSyncState), h->stream));
+    HIPCHK(hipMemsetAsync(h->st.p, 0, (size_t)h->batch * sizeof(FrameSyncState), h->stream));
     return QRL_OK;
 }
 int qrl_framesync_frame_bytes(const qrl_framesync* h) { return h ? (int)h->frame_length : 0; }
@@ -139,7 +120,7 @@ int qrl_framesync_process(qrl_framesync* h, const uint8_t* bits, size_t stride, 
     FrameSyncParams p{};
     p.bits = bits; p.stride = stride; p.n = (uint32_t)n; p.counts = counts; p.count_stride = count_stride;
     p.cls = h->cls; p.bit_buf_len = h->bit_buf_len; p.frame_length = h->frame_length;
-    p.st = h->st; p.bitbuf = h->bitbuf; p.bitbuf_stride = h->bitbuf_stride;
+    p.st = h->st.p; p.bitbuf = h->bitbuf.p; p.bitbuf_stride = h->bitbuf_stride;
     p.out = out; p.out_cap = out_cap; p.out_counts = out_counts; p.activity = h->activity;
     launch_framesync(p, h->batch, h->stream);
     HIPCHK(hipGetLastError());

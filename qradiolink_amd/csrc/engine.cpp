@@ -2,10 +2,8 @@
 // as a GNU Radio flowgraph (gr_demod_base.cpp:299-828 connects rotator -> resampler -> gr_demod_X),
 // owns all device state, and exposes it through the C ABI of include/qrl_hip.h.
 // There is NO CPU fallback: without a usable HIP device qrl_init() fails.
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -22,8 +20,7 @@
 using namespace qrl;
 
 static thread_local std::string g_last_error;
-static int fail(int code, const std::string& msg) { g_last_error = msg; return code; }
-int qrl_set_error(int code, const std::string& msg) { return fail(code, msg); }   // shared with tx.cpp
+int qrl_set_error(int code, const std::string& msg) { g_last_error = msg; return code; }
 
 namespace qrl {
 static thread_local bool t_launch_error = false;
@@ -64,24 +61,34 @@ std::vector<float2> rot_fine_table(uint64_t inc)
     for (int r = 0; r < 512; ++r) { float sn, cs; sincos_turn_host((uint64_t)r * inc, sn, cs); lo[r] = make_float2(cs, sn); }
     return lo;
 }
-int RotPs::set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t delta, const uint64_t* new_inc, hipStream_t s)
+int Rotator::retune(uint64_t n_now, uint64_t new_inc, hipStream_t s)
 {
-    if (!on()) {   // first per-stream set: every stream starts where the shared NCO is (acc0 = its phase at the new nbase)
-        batch = B;
-        if (hipMalloc(reinterpret_cast<void**>(&acc), (size_t)B * sizeof(uint64_t)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&inc), (size_t)B * sizeof(uint64_t)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&lo), (size_t)B * 512 * sizeof(float2)) != hipSuccess) {
-            release();
-            return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipMalloc failed");
-        }
-        launch_rot_ps_fill(acc, inc, lo, B, 1, acc0, inc0, lo0, s);
-        h_inc.assign((size_t)B, inc0);
+    const uint64_t delta = advance(n_now);
+    inc = new_inc;
+    if (hipMemcpy(lo.p, rot_fine_table(inc).data(), 512 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+    if (!per_stream()) return QRL_OK;
+    const int B = (int)h_inc.size();
+    launch_rot_ps_advance(acc_s.p, inc_s.p, B, delta, s);
+    launch_rot_ps_fill(acc_s.p, inc_s.p, lo_s.p, B, 0, 0, inc, lo.p, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
+    h_inc.assign((size_t)B, inc);
+    return QRL_OK;
+}
+int Rotator::retune_streams(uint64_t n_now, const std::vector<uint64_t>& new_inc, hipStream_t s)
+{
+    const uint64_t delta = advance(n_now);
+    const int B = (int)new_inc.size();
+    if (!per_stream()) {   // first per-stream set: every stream starts where the shared NCO is (acc = its phase at the new nbase)
+        int r;
+        if ((r = acc_s.grow((size_t)B)) || (r = inc_s.grow((size_t)B)) || (r = lo_s.grow((size_t)B * 512))) return r;
+        launch_rot_ps_fill(acc_s.p, inc_s.p, lo_s.p, B, 1, acc, inc, lo.p, s);
+        h_inc.assign((size_t)B, inc);
     } else {
-        launch_rot_ps_advance(acc, inc, batch, delta, s);
+        launch_rot_ps_advance(acc_s.p, inc_s.p, B, delta, s);
     }
     // only the streams whose increment changes: their increments and tables, one copy per run of consecutive streams
     std::vector<uint32_t> idx;
-    for (int b = 0; b < batch; ++b) if (new_inc[b] != h_inc[(size_t)b]) idx.push_back((uint32_t)b);
+    for (int b = 0; b < B; ++b) if (new_inc[(size_t)b] != h_inc[(size_t)b]) idx.push_back((uint32_t)b);
     std::vector<uint64_t> st_inc(idx.size());
     std::vector<float2> st_lo(idx.size() * 512);
     for (size_t j = 0; j < idx.size(); ++j) {
@@ -93,8 +100,8 @@ int RotPs::set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t 
         size_t j1 = j0 + 1;
         while (j1 < idx.size() && idx[j1] == idx[j1 - 1] + 1) ++j1;
         const size_t n = j1 - j0;
-        if (hipMemcpyAsync(inc + idx[j0], st_inc.data() + j0, n * sizeof(uint64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(lo + (size_t)idx[j0] * 512, st_lo.data() + j0 * 512, n * 512 * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess)
+        if (hipMemcpyAsync(inc_s.p + idx[j0], st_inc.data() + j0, n * sizeof(uint64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(lo_s.p + (size_t)idx[j0] * 512, st_lo.data() + j0 * 512, n * 512 * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess)
             return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: upload failed");
         j0 = j1;
     }
@@ -102,36 +109,22 @@ int RotPs::set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t 
     for (uint32_t b : idx) h_inc[b] = new_inc[b];
     return QRL_OK;
 }
-int RotPs::set_all(uint64_t delta, uint64_t new_inc, const float2* lo0, hipStream_t s)
+int Rotator::reset(hipStream_t s)
 {
-    launch_rot_ps_advance(acc, inc, batch, delta, s);
-    launch_rot_ps_fill(acc, inc, lo, batch, 0, 0, new_inc, lo0, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
-    h_inc.assign((size_t)batch, new_inc);
-    return QRL_OK;
-}
-int RotPs::reset(hipStream_t s)
-{
-    if (!on()) return QRL_OK;
-    if (hipMemsetAsync(acc, 0, (size_t)batch * sizeof(uint64_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    acc = 0; nbase = 0;
+    if (!per_stream()) return QRL_OK;
+    if (hipMemsetAsync(acc_s.p, 0, h_inc.size() * sizeof(uint64_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: reset failed");
     return QRL_OK;
 }
-void RotPs::release()
+int carrier_incs(const double* hz, int B, double sign, double rate, std::vector<uint64_t>& inc)
 {
-    for (void* p : {(void*)acc, (void*)inc, (void*)lo}) if (p) (void)hipFree(p);
-    acc = nullptr; inc = nullptr; lo = nullptr; h_inc.clear(); batch = 0;
+    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    inc.resize((size_t)B);
+    for (int b = 0; b < B; ++b) inc[(size_t)b] = phase_inc_to_turn(2 * M_PI * (sign * hz[b]) / rate);
+    return QRL_OK;
 }
 }  // namespace qrl
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-struct qrl_ctx { int device; };
 
 #ifndef QRL_FEC_GATE_US
 #define QRL_FEC_GATE_US 30u   // grouped order: head start of the recursion kernel over the decoder (profiles/r04_c5_rx_timeline.log: without it the decoder takes every wave slot first)
@@ -141,26 +134,6 @@ struct qrl_ctx { int device; };
 #endif
 namespace {
 
-template <class T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t count) {
-        if (p) { (void)hipFree(p); p = nullptr; }   // re-designed filters (qrl_demod_set_filter_width) replace their tables
-        n = count;
-        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return QRL_ERR_NOMEM;
-        if (hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return QRL_ERR_HIP;
-        return QRL_OK;
-    }
-    int upload(const std::vector<T>& v) {
-        int r = alloc(v.size());
-        if (r) return r;
-        if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        return QRL_OK;
-    }
-    int zero() { return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
-};
-
-uint32_t pow2_at_least(size_t v) { uint32_t c = 64; while (c < v) c <<= 1; return c; }
 uint64_t decim_count(uint64_t n, int I, int D) { return n ? ((n - 1) * (uint64_t)I + (uint64_t)I - 1) / (uint64_t)D + 1 : 0; }
 
 // polyphase layout for k_decim: taps[p*Jpad + j] = h[p + j*D]
@@ -306,9 +279,7 @@ struct qrl_demod {
     float ss_alpha = 0, ss_beta = 0, ss_maxp = 0, ss_minp = 0;
 
     // rotator (gr_demod_base.cpp:57,1220-1225): exact 2^-64-turn NCO
-    uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0;
-    DevBuf<float2> rot_lo;
-    RotPs ps;   // per-stream offsets (qrl_demod_set_carrier_offsets); off: the shared NCO above
+    Rotator rot;
 
     // rings and state
     DevBuf<float2> hist_a, hist_b; uint32_t hist_len = 0; bool hist_flip = false;
@@ -348,7 +319,6 @@ struct qrl_demod {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
 
     ~qrl_demod() {
-        ps.release();
         for (auto& e : prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
         if (ev_ff) (void)hipEventDestroy(ev_ff);
         if (ev_tail) (void)hipEventDestroy(ev_tail);
@@ -364,12 +334,6 @@ struct qrl_demod {
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 
-    int upload_rot_table() {
-        std::vector<float2> lo(512);
-        for (int r = 0; r < 512; ++r) { float s, c; sincos_turn_host((uint64_t)r * rot_inc, s, c); lo[r] = make_float2(c, s); }
-        if (!rot_lo.p) return rot_lo.upload(lo);
-        return hipMemcpy(rot_lo.p, lo.data(), 512 * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
     int flush_fec(bool behind_front_end) {
         if (!fec_deferred) return QRL_OK;
         fec_deferred = false;
@@ -449,8 +413,8 @@ int qrl_demod::init_state()
     fe_valid[0] = fe_valid[1] = false; pre_pending = false;
     fec_deferred = false;
     n_in = n1 = n2 = 0;
-    rot_acc = 0; rot_nbase = 0; hist_flip = false;
-    return ps.reset(stream);   // per-stream phases restart too; the offsets stay
+    hist_flip = false;
+    return rot.reset(stream);   // per-stream phases restart too; the offsets stay
 }
 
 int qrl_demod::build()
@@ -461,46 +425,46 @@ int qrl_demod::build()
         if (sps == 10)     { target = 20000; sps_eff = sps;     decim = 50; interp = 1; }
         else if (sps >= 5) { target = 40000; sps_eff = sps * 2; decim = 25; interp = 1; }
         else if (sps == 1) { target = 80000; sps_eff = 4;       decim = 25; interp = 2; }
-        else return fail(QRL_ERR_ARG, "2fsk: unsupported sps");
+        else return qrl_set_error(QRL_ERR_ARG, "2fsk: unsupported sps");
     } else if (fam == F_GMSK) {
         if (sps == 10)     { target = 20000; sps_eff = sps;     decim = 50; interp = 1; }
         else if (sps == 5) { target = 40000; sps_eff = sps * 2; decim = 25; interp = 1; }
         else if (sps == 1) { target = 80000; sps_eff = 4;       decim = 25; interp = 2; }
-        else return fail(QRL_ERR_ARG, "gmsk: unsupported sps");
+        else return qrl_set_error(QRL_ERR_ARG, "gmsk: unsupported sps");
     } else if (fam == F_DMR) {
         // gr_demod_dmr.cpp:36-58, gr_demod_m17.cpp:38-58: 3/125 resampler to 24 ksps, 5 samples per symbol
         target = 24000; sps_eff = 5; decim = 125; interp = 3; branches = 1;
     } else if (fam == F_4FSK) {
         // gr_demod_4fsk.cpp:45-82 (FM branch only; the non-FM discriminator bank of 4FSK2K is not built)
         fsk4_disc = !cfg.fm;   // ModemType4FSK2K: four band-pass magnitudes -> gr_4fsk_discriminator -> symbol_sync_cc (:110-127,165-181)
-        if (fsk4_disc && sps == 2) return fail(QRL_ERR_ARG, "4fsk: the sps = 2 geometry exists as FM variant only (gr_demod_4fsk.cpp:78-85 sets no rs/bw)");
+        if (fsk4_disc && sps == 2) return qrl_set_error(QRL_ERR_ARG, "4fsk: the sps = 2 geometry exists as FM variant only (gr_demod_4fsk.cpp:78-85 sets no rs/bw)");
         if (sps == 1)       { target = 80000;  sps_eff = 8;  decim = 25;  interp = 2; }
         else if (sps == 5)  { target = 20000;  sps_eff = 10; decim = 50;  interp = 1; }
         else if (sps == 10) { target = 10000;  sps_eff = 10; decim = 100; interp = 1; }
         else if (sps == 2)  { target = 500000; sps_eff = 5;  decim = 2;   interp = 1; }
-        else return fail(QRL_ERR_ARG, "4fsk: unsupported sps");
+        else return qrl_set_error(QRL_ERR_ARG, "4fsk: unsupported sps");
         branches = 1;
     } else if (fam == F_DSSS) {
         // gr_demod_dsss.cpp:37-59: 1:50 to 20 ksps (this stage), then 13/50 to 5 200 samples/s (dsss_stages); sps = samples per chip
-        if (sps != 25) return fail(QRL_ERR_ARG, "dsss: sps must be 25 (make_gr_demod_dsss(25, ...), gr_demod_base.cpp:218)");
+        if (sps != 25) return qrl_set_error(QRL_ERR_ARG, "dsss: sps must be 25 (make_gr_demod_dsss(25, ...), gr_demod_base.cpp:218)");
         target = 20000; sps_eff = 10; decim = 50; interp = 1;
     } else if (fam == F_ANALOG) {
         // gr_demod_nbfm.cpp:39,50 / gr_demod_am.cpp:36,44: 1:50 to 20 ksps; gr_demod_wbfm.cpp:37,49: 1:5 to 200 ksps (sps is unused there)
         // gr_demod_ssb.cpp:35,41-43: 1:sps (125) to 8 ksps
         target = an_kind == 2 ? 200000 : an_kind == 3 ? 8000 : 20000; decim = an_kind == 2 ? 5 : an_kind == 3 ? 125 : 50; interp = 1; sps_eff = 10; branches = 1;
-        if (an_kind == 3 && sps != 125) return fail(QRL_ERR_ARG, "ssb: sps must be 125 (make_gr_demod_ssb(125, ...), gr_demod_base.cpp:226-227)");
+        if (an_kind == 3 && sps != 125) return qrl_set_error(QRL_ERR_ARG, "ssb: sps must be 125 (make_gr_demod_ssb(125, ...), gr_demod_base.cpp:226-227)");
     } else if (fam == F_BPSK) {
         // gr_demod_bpsk.cpp:40-52: 1:50 to 20 ksps, sps samples per symbol
-        if (sps != 10 && sps != 5) return fail(QRL_ERR_ARG, "bpsk: sps must be 10 (BPSK1K) or 5 (BPSK2K)");
+        if (sps != 10 && sps != 5) return qrl_set_error(QRL_ERR_ARG, "bpsk: sps must be 10 (BPSK1K) or 5 (BPSK2K)");
         target = 20000; sps_eff = sps; decim = 50; interp = 1;
     } else {
         // gr_demod_qpsk.cpp:39-60: sps <= 4 (QPSK250K / video: 1:2, no FLL), 4 < sps < 125 (QPSK20K: 1:25 to 40 ksps),
         // sps >= 125 (QPSK2K: 1:100 to 10 ksps); the last two run fll_band_edge_cc in front of the shaping filter (:130-138)
-        if (sps < 2) return fail(QRL_ERR_ARG, "qpsk: sps must be >= 2");
+        if (sps < 2) return qrl_set_error(QRL_ERR_ARG, "qpsk: sps must be >= 2");
         if (sps > 4 && sps < 125) { target = 40000; sps_eff = sps * 4 / 25; decim = 25; }
         else if (sps >= 125)      { target = 10000; sps_eff = sps / 25;     decim = 100; }
         else                      { target = 500000; sps_eff = sps;         decim = 2; }
-        if (sps_eff < 2 || sps_eff > 10) return fail(QRL_ERR_ARG, "qpsk: unsupported samples per symbol");
+        if (sps_eff < 2 || sps_eff > 10) return qrl_set_error(QRL_ERR_ARG, "qpsk: unsupported samples per symbol");
         interp = 1; branches = 1; qpsk_fll = sps > 4;
     }
     fm = cfg.fm != 0;
@@ -511,11 +475,10 @@ int qrl_demod::build()
     fe_decim = 1;
     if (cfg.device_samp_rate >= 2000000) {
         fe_decim = cfg.device_samp_rate / 1000000;
-        if ((r = fe.plan(low_pass(1, cfg.device_samp_rate, 480000, 100000, WIN_BLACKMAN_HARRIS), fe_decim))) return fail(r, "front-end plan");
-        if ((r = fe.alloc_edge(cfg.batch))) return fail(r, "front-end edge scratch");
+        if ((r = fe.plan(low_pass(1, cfg.device_samp_rate, 480000, 100000, WIN_BLACKMAN_HARRIS), fe_decim))) return qrl_set_error(r, "front-end plan");
+        if ((r = fe.alloc_edge(cfg.batch))) return qrl_set_error(r, "front-end edge scratch");
     }
-    rot_inc = phase_inc_to_turn(2 * M_PI * -cfg.carrier_offset_hz / cfg.device_samp_rate);
-    if ((r = upload_rot_table())) return r;
+    if ((r = rot.init(phase_inc_to_turn(2 * M_PI * -cfg.carrier_offset_hz / cfg.device_samp_rate)))) return r;
 
     // --- per-mode first resampler (gr_demod_2fsk.cpp:82-88, gr_demod_gmsk.cpp:80-83)
     const std::vector<float> rtaps = fam == F_DMR && m17
@@ -525,7 +488,7 @@ int qrl_demod::build()
         : fam == F_QPSK
         ? low_pass_2(interp, (double)interp * samp_rate, target / 2, target / 10, 60, WIN_BLACKMAN_HARRIS)   // gr_demod_qpsk.cpp:92-96
         : low_pass(interp, (double)interp * samp_rate, target / 2, target / 2, WIN_BLACKMAN_HARRIS);
-    if (interp == 1) { if ((r = first.plan(rtaps, decim))) return fail(r, "resampler plan"); if (!fe.used && (r = first.alloc_edge(cfg.batch))) return fail(r, "resampler edge scratch"); }
+    if (interp == 1) { if ((r = first.plan(rtaps, decim))) return qrl_set_error(r, "resampler plan"); if (!fe.used && (r = first.alloc_edge(cfg.batch))) return qrl_set_error(r, "resampler edge scratch"); }
     else {
         rs_Jp = ((int)rtaps.size() + interp - 1) / interp;
         if ((r = rs_taps.upload(resamp_layout(rtaps, interp, rs_Jp)))) return r;
@@ -542,16 +505,16 @@ int qrl_demod::build()
     // --- the scope tap's 1:10 decimator on the 1 Msps signal (planned here so that the history below covers it; its ring is allocated on first use)
     {
         const int sr = cfg.time_domain_samp_rate;
-        if (sr < 0 || sr > 500000 || cfg.time_domain_filter_width < 0 || cfg.time_domain_filter_width > 500000) return fail(QRL_ERR_ARG, "time_domain_samp_rate / filter_width out of range");
+        if (sr < 0 || sr > 500000 || cfg.time_domain_filter_width < 0 || cfg.time_domain_filter_width > 500000) return qrl_set_error(QRL_ERR_ARG, "time_domain_samp_rate / filter_width out of range");
         scope_D = sr > 0 ? 1000000 / sr : 10;
-        if (sr > 0 && sr / 2 - sr / 8 <= 0) return fail(QRL_ERR_ARG, "time_domain_samp_rate too small");
+        if (sr > 0 && sr / 2 - sr / 8 <= 0) return qrl_set_error(QRL_ERR_ARG, "time_domain_samp_rate too small");
         const std::vector<float> h = cfg.time_domain_filter_width > 0 ? low_pass(1, 1000000, cfg.time_domain_filter_width, cfg.time_domain_filter_width, WIN_HAMMING)   // gr_demod_base.cpp:1292-1301
                                    : sr > 0 ? low_pass(1, 1000000, sr / 2 - sr / 8, sr / 4, WIN_HAMMING)                                                                  // :1249-1290
                                             : low_pass(1, 1000000, 50000, 25000, WIN_HAMMING);                                                                            // :62-63
-        if (h.size() > 4096) return fail(QRL_ERR_ARG, "time-domain filter too long (> 4096 taps)");
-        if ((r = scope.plan(h, scope_D))) return fail(r, "scope plan");
+        if (h.size() > 4096) return qrl_set_error(QRL_ERR_ARG, "time-domain filter too long (> 4096 taps)");
+        if ((r = scope.plan(h, scope_D))) return qrl_set_error(r, "scope plan");
     }
-    if (!fe.used && (r = scope.alloc_edge(cfg.batch))) return fail(r, "scope edge scratch");
+    if (!fe.used && (r = scope.alloc_edge(cfg.batch))) return qrl_set_error(r, "scope edge scratch");
     // --- history of the caller's IQ kept by whichever stage reads it
     if (fe.used) hist_len = fe.lookback();
     else if (interp == 1) hist_len = std::max(first_look, scope.lookback());
@@ -564,7 +527,7 @@ int qrl_demod::build()
     const size_t max2 = in2 * interp / decim + 2;                    // target-rate items per call
     if (fe.used) {
         const size_t look = std::max<size_t>(interp == 1 ? first_look : (size_t)(rs_Jp + decim + 2), scope.lookback());
-        s1_mask = pow2_at_least(max1 + look + 64) - 1;
+        s1_mask = pow2_at_least(max1 + look + 64, 64) - 1;
         if ((r = s1.alloc((size_t)B * (s1_mask + 1)))) return r;
     }
     // default: only the 2FSK family, whose FLL + discriminator kernels are a third of a call (measured, C1: 15.2 -> 12.9 ms per
@@ -580,12 +543,12 @@ int qrl_demod::build()
         grouped = grouped_capable && 2 * ((B + 63) / 64) >= cus;   // (below that the recursion's workgroups leave CUs free: the front end of the next call belongs beside it -- C3)
     }
     overlap = overlap_capable;   // round 3: ON by default for the 2FSK family (same-box A/B on C1: 8.79 against 9.49 ms per step); qrl_demod_set_option(QRL_OPT_OVERLAP, 0) gives the serial order
-    s2_mask = pow2_at_least((overlap_capable || loops_family() ? 2 : 1) * max2 + (fam == F_DMR ? 2048 : fam == F_ANALOG ? 4096 : 1024)) - 1;   // DMR: the DMO slicer looks back 1440 samples   // history needs: <= 501 taps downstream; overlapped mode: two calls
+    s2_mask = pow2_at_least((overlap_capable || loops_family() ? 2 : 1) * max2 + (fam == F_DMR ? 2048 : fam == F_ANALOG ? 4096 : 1024), 64) - 1;   // DMR: the DMO slicer looks back 1440 samples   // history needs: <= 501 taps downstream; overlapped mode: two calls
     const size_t ring2 = (size_t)B * (s2_mask + 1);
     if ((r = s2.alloc(ring2)) || (r = s2f.alloc(ring2)) || (r = s2d.alloc(ring2)) || (r = s3.alloc(ring2))) return r;
     if ((fam == F_2FSK || fam == F_BPSK || (fam == F_QPSK && qpsk_fll)) && (r = s2l.alloc(ring2))) return r;
     const size_t maxsym = max2 / (size_t)(sps_eff > 1 ? sps_eff - 1 : 1) + 8;
-    soft_mask = pow2_at_least((loops_family() ? 2 : 1) * (fam == F_QPSK || fam == F_4FSK ? 2 : 1) * maxsym + 512) - 1;   // loops families: two calls (decoder of call k beside the recursion of call k + 1)
+    soft_mask = pow2_at_least((loops_family() ? 2 : 1) * (fam == F_QPSK || fam == F_4FSK ? 2 : 1) * maxsym + 512, 64) - 1;   // loops families: two calls (decoder of call k beside the recursion of call k + 1)
     if ((r = soft.alloc((size_t)B * (soft_mask + 1)))) return r;
 
     // --- decimated-rate filters
@@ -626,7 +589,7 @@ int qrl_demod::build()
             // sin(-x) = -sin(x)) -- and run the shared real-tap chains once (oracle orc_fir_ccc_conj_pair)
             for (size_t k = 0; k < up2.size(); ++k) {
                 const float ur = up2[k].real(), ui = -up2[k].imag(), lr = lo2[k].real(), li = lo2[k].imag();
-                if (std::memcmp(&ur, &lr, sizeof ur) || std::memcmp(&ui, &li, sizeof ui)) return fail(QRL_ERR_ARG, "2FSK discriminator filters are not a conjugate pair");
+                if (std::memcmp(&ur, &lr, sizeof ur) || std::memcmp(&ui, &li, sizeof ui)) return qrl_set_error(QRL_ERR_ARG, "2FSK discriminator filters are not a conjugate pair");
             }
             if ((r = disc_up.upload(to_f2(up2))) || (r = disc_lo.upload(to_f2(lo2)))) return r;
             const std::vector<float> sf = low_pass(1.0, target, target / sps_eff, target / sps_eff, WIN_HAMMING);
@@ -755,8 +718,8 @@ int qrl_demod::build()
         }
         an_nr = (int)rt.size(); an_nf = (int)ft.size();
         if ((an_nr && (r = an_rtaps.upload(rt))) || (an_nf && (r = an_ftaps.upload(ft))) || (r = an_env.upload(squelch_envelope(an_ramp)))) return r;
-        an_m1 = pow2_at_least(max2 + 2048) - 1;                                  // the audio resampler looks <= 419 gated items back, the stretcher <= 1025
-        an_m2 = an_kind == 3 ? an_m1 : pow2_at_least(max2 * an_I / an_D + 512) - 1;
+        an_m1 = pow2_at_least(max2 + 2048, 64) - 1;                              // the audio resampler looks <= 419 gated items back, the stretcher <= 1025
+        an_m2 = an_kind == 3 ? an_m1 : pow2_at_least(max2 * an_I / an_D + 512, 64) - 1;
         if (an_kind == 3) { if ((r = an_c1.alloc((size_t)B * (an_m1 + 1)))) return r; }
         else if ((r = an_f1.alloc((size_t)B * (an_m1 + 1)))) return r;
         if ((r = an_f2.alloc((size_t)B * (an_m2 + 1))) || ((an_kind == 0 || an_kind == 1) && (r = an_f3.alloc((size_t)B * (an_m2 + 1)))) || (r = an_st.alloc(B))) return r;
@@ -771,8 +734,8 @@ int qrl_demod::build()
         control_loop_gains((float)(M_PI / 200), ds_a1, ds_b1);                                          // _costas_freq, :64
         control_loop_gains((float)(2 * M_PI / 100), ds_a2, ds_b2);                                      // _costas_loop, :63
         const size_t max5 = max2 * 13 / 50 + 2;
-        ds_mask = pow2_at_least(max5 + 2048) - 1;                                                       // the matched filter looks 2 x 325 + 600 items back
-        ds_sym_mask = pow2_at_least(max5 / 325 + 64) - 1;
+        ds_mask = pow2_at_least(max5 + 2048, 64) - 1;                                                   // the matched filter looks 2 x 325 + 600 items back
+        ds_sym_mask = pow2_at_least(max5 / 325 + 64, 64) - 1;
         const size_t r5 = (size_t)B * (ds_mask + 1);
         if ((r = ds_ra.alloc(r5)) || (r = ds_rb.alloc(r5)) || (r = ds_rc.alloc(r5)) || (r = ds_rd.alloc(r5)) ||
             (r = ds_sym.alloc((size_t)B * (ds_sym_mask + 1))) || (r = ds_st.alloc(B)) || (r = ds_tail.alloc(B))) return r;
@@ -782,8 +745,8 @@ int qrl_demod::build()
 
 int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod_out* out)
 {
-    if (n > cfg.max_chunk) return fail(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
-    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return fail(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
+    if (n > cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
+    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return qrl_set_error(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
     const int B = cfg.batch;
     uint32_t* counts = (out && out->counts) ? out->counts : counts_scratch.p;
     hipStream_t cs = overlap ? tail : stream;   // stream of stage C (decimated-rate feed-forward kernels)
@@ -822,9 +785,9 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         p.hist = hist_old; p.hist_len = hist_len;
         p.out = r1; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
         p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.Jpad;
-        p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p);
+        p.rot_enable = 1; rot.fill(p);
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
-        if (fe.launch(p, B, stream, use_pre ? slot : 0)) return fail(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
+        if (fe.launch(p, B, stream, use_pre ? slot : 0)) return qrl_set_error(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
     }
     if (profiling && fe.used) { HIPCHK(hipEventRecord(ev1, stream)); prof_events.emplace_back(ev0, ev1); }
     // ---- stage B: per-mode resampler
@@ -834,7 +797,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         DecimParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
+               p.rot_enable = 1; rot.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = r2; p.m0 = n2_0; p.m_count = (uint32_t)(n2_1 - n2_0);
         p.taps = first.taps.p; p.D = first.D; p.Jpad = first.Jpad;
@@ -848,13 +811,13 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
             launch_dec2_fir(f, B, stream);
         } else {
             if (use_pre && !fe.used) { p.pre_stream = pre; p.pre_event = ev_pre; }   // (device rate 1 Msps: this stage is the one that reads the caller's IQ)
-            if (first.launch(p, B, stream, use_pre && !fe.used ? slot : 0)) return fail(QRL_ERR_HIP, "first-stage launch: hipFuncSetAttribute failed");
+            if (first.launch(p, B, stream, use_pre && !fe.used ? slot : 0)) return qrl_set_error(QRL_ERR_HIP, "first-stage launch: hipFuncSetAttribute failed");
         }
     } else {
         ResampParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
+               p.rot_enable = 1; rot.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = r2; p.q0 = n2_0; p.q_count = (uint32_t)(n2_1 - n2_0);
         p.taps = rs_taps.p; p.I = interp; p.D = decim; p.Jp = rs_Jp;
@@ -873,11 +836,11 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         DecimParams p{};
         if (fe.used) { p.in = nullptr; p.in_ring = r1; }
         else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; p.rot_acc = rot_acc; p.rot_inc = rot_inc; p.rot_nbase = rot_nbase; p.rot_lo = rot_lo.p; ps.fill(p); }
+               p.rot_enable = 1; rot.fill(p); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
         p.out = RingC{s_scope.p, scope_mask}; p.m0 = n_scope; p.m_count = (uint32_t)(ns_1 - n_scope);
         p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.Jpad;
-        if (scope.launch(p, B, stream)) return fail(QRL_ERR_HIP, "scope launch: hipFuncSetAttribute failed");
+        if (scope.launch(p, B, stream)) return qrl_set_error(QRL_ERR_HIP, "scope launch: hipFuncSetAttribute failed");
         launch_ring_store(RingC{s_scope.p, scope_mask}, n_scope, (uint32_t)(ns_1 - n_scope), scope_out, scope_cap, scope_counts, B, stream);
         n_scope = ns_1;
     }
@@ -886,7 +849,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         HistParams h{};
         h.in = in; h.in_stride = stride; h.n0 = n_in0; h.n = (uint32_t)n;
         h.hist_old = hist_old; h.hist_new = hist_new; h.hist_len = hist_len;
-        h.rot_enable = 1; h.rot_acc = rot_acc; h.rot_inc = rot_inc; h.rot_nbase = rot_nbase; h.rot_lo = rot_lo.p; ps.fill(h);
+        h.rot_enable = 1; rot.fill(h);
         if (pre) { HIPCHK(hipEventRecord(ev_fe[slot], stream)); fe_valid[slot] = true; }   // everything of this call that reads the history on the handle's stream has been launched
         if (use_pre) {
             if (fe_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(pre, ev_fe[slot ^ 1], 0));   // hist_new was the history of the call before
@@ -1208,13 +1171,13 @@ int qrl_init(int device, qrl_ctx** ctx)
 {
     if (!ctx) return QRL_ERR_ARG;
     int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(QRL_ERR_NO_DEVICE, "hipGetDeviceCount: no device");
-    if (device < 0 || device >= count) return fail(QRL_ERR_NO_DEVICE, "device index out of range");
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return qrl_set_error(QRL_ERR_NO_DEVICE, "hipGetDeviceCount: no device");
+    if (device < 0 || device >= count) return qrl_set_error(QRL_ERR_NO_DEVICE, "device index out of range");
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && std::strncmp(prop.gcnArchName, "gfx94", 5) != 0)
-        return fail(QRL_ERR_NO_DEVICE, std::string("unsupported architecture ") + prop.gcnArchName);
+        return qrl_set_error(QRL_ERR_NO_DEVICE, std::string("unsupported architecture ") + prop.gcnArchName);
     *ctx = new (std::nothrow) qrl_ctx{device};
     return *ctx ? QRL_OK : QRL_ERR_NOMEM;
 }
@@ -1223,7 +1186,7 @@ void qrl_shutdown(qrl_ctx* ctx) { delete ctx; }
 int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp)
 {
     if (!ctx || !cfg || !outp) return QRL_ERR_ARG;
-    if (cfg->batch < 1 || cfg->max_chunk < 1) return fail(QRL_ERR_ARG, "batch and max_chunk must be >= 1");
+    if (cfg->batch < 1 || cfg->max_chunk < 1) return qrl_set_error(QRL_ERR_ARG, "batch and max_chunk must be >= 1");
     std::unique_ptr<qrl_demod> d(new (std::nothrow) qrl_demod);
     if (!d) return QRL_ERR_NOMEM;
     d->ctx = ctx;
@@ -1259,7 +1222,7 @@ int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp
         case QRL_MODEM_AM5000:    c.sps = 125; c.filter_width = 5000;  c.fm = 0; break;
         case QRL_MODEM_USB2500: case QRL_MODEM_LSB2500: c.sps = 125; c.filter_width = 2700; c.fm = 0; break;   // make_gr_demod_ssb(125, ., 1700, 2700, sb) :226-227   // make_gr_demod_am(125, ., 1700, 5000) :215   // make_gr_demod_dsss(25, ., 1700, 150) gr_demod_base.cpp:218
         case QRL_MODEM_M17:       c.sps = 125; c.filter_width = 9000;  c.fm = 0; break;   // make_gr_demod_m17() gr_demod_base.cpp:252, defaults gr_demod_m17.h:41-42
-        default: return fail(QRL_ERR_ARG, "modem_type not supported by this build");
+        default: return qrl_set_error(QRL_ERR_ARG, "modem_type not supported by this build");
         }
     }
     switch (c.modem_type) {
@@ -1287,11 +1250,11 @@ int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp
         d->fam = qrl_demod::F_ANALOG; d->an_kind = 2; break;
     case QRL_MODEM_USB2500: case QRL_MODEM_LSB2500:
         d->fam = qrl_demod::F_ANALOG; d->an_kind = 3; d->an_lsb = c.modem_type == QRL_MODEM_LSB2500; break;
-    default: return fail(QRL_ERR_ARG, "modem_type not supported by this build");
+    default: return qrl_set_error(QRL_ERR_ARG, "modem_type not supported by this build");
     }
-    if (c.samp_rate != 1000000) return fail(QRL_ERR_ARG, "internal samp_rate must be 1000000 (gr_demod_base.cpp:21)");
+    if (c.samp_rate != 1000000) return qrl_set_error(QRL_ERR_ARG, "internal samp_rate must be 1000000 (gr_demod_base.cpp:21)");
     if (c.device_samp_rate != 1000000 && (c.device_samp_rate < 2000000 || c.device_samp_rate % 1000000))
-        return fail(QRL_ERR_ARG, "device_samp_rate must be 1e6 or a multiple of 1e6 >= 2e6");
+        return qrl_set_error(QRL_ERR_ARG, "device_samp_rate must be 1e6 or a multiple of 1e6 >= 2e6");
     HIPCHK(hipSetDevice(ctx->device));
     // Streams.  The tail stream has the highest priority and its kernels are small enough to take over the slot of ONE
     // retiring front-end workgroup.  (Reserving CUs for it with a CU mask was measured: it costs the front end ~18 %.)
@@ -1344,27 +1307,16 @@ int qrl_demod_set_carrier_offset(qrl_demod* d, double hz)
 {
     if (!d) return QRL_ERR_ARG;
     if (int rs = d->sync_all()) return rs;
-    const uint64_t delta = d->n_in - d->rot_nbase;
-    d->rot_acc += delta * d->rot_inc;  // phase-continuous
-    d->rot_nbase = d->n_in;
     d->cfg.carrier_offset_hz = hz;
-    d->rot_inc = phase_inc_to_turn(2 * M_PI * -hz / d->cfg.device_samp_rate);
-    if (int r = d->upload_rot_table()) return r;
-    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
-    return d->ps.on() ? d->ps.set_all(delta, d->rot_inc, d->rot_lo.p, d->stream) : QRL_OK;
+    return d->rot.retune(d->n_in, phase_inc_to_turn(2 * M_PI * -hz / d->cfg.device_samp_rate), d->stream);   // phase-continuous
 }
 int qrl_demod_set_carrier_offsets(qrl_demod* d, const double* hz)
 {
     if (!d || !hz) return QRL_ERR_ARG;
-    const int B = d->cfg.batch;
-    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    std::vector<uint64_t> ni;
+    if (int r = carrier_incs(hz, d->cfg.batch, -1.0, d->cfg.device_samp_rate, ni)) return r;
     if (int rs = d->sync_all()) return rs;
-    std::vector<uint64_t> ni((size_t)B);
-    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * -hz[b] / d->cfg.device_samp_rate);
-    const uint64_t delta = d->n_in - d->rot_nbase;
-    d->rot_acc += delta * d->rot_inc;
-    d->rot_nbase = d->n_in;
-    return d->ps.set(B, d->rot_acc, d->rot_inc, d->rot_lo.p, delta, ni.data(), d->stream);
+    return d->rot.retune_streams(d->n_in, ni, d->stream);
 }
 int qrl_demod_stream_wait(qrl_demod* d, void* hip_stream)
 {
@@ -1422,7 +1374,7 @@ int qrl_demod_set_option(qrl_demod* d, int option, int value)
         if (int rs = d->sync_all()) return rs;
         if (value != 0 && d->pre) {   // the second edge scratch of the stage that reads the caller's IQ (the helper stages a call ahead)
             DecimStage& st = d->fe.used ? d->fe : d->first;
-            if (st.edge_len && !st.edge_b.p && st.edge_b.alloc((size_t)d->cfg.batch * st.edge_len)) return qrl_set_error(QRL_ERR_HIP, "edge scratch");
+            if (st.edge_len && !st.edge_b.p) if (int r = st.edge_b.alloc((size_t)d->cfg.batch * st.edge_len)) return qrl_set_error(r, "edge scratch");
         }
         d->input_resident = value != 0;
         return QRL_OK;
@@ -1477,7 +1429,7 @@ int qrl_demod_set_time_domain_output(qrl_demod* d, float* samples, size_t cap, u
     if (samples && !d->s_scope.p) {   // first use: the ring of the 100 ksps scope signal (one call + the stages' block granularity)
         if (int rs = d->sync_all()) return rs;
         const size_t max1 = d->fe.used ? d->cfg.max_chunk / d->fe_decim + 2 : d->cfg.max_chunk;
-        d->scope_mask = pow2_at_least(max1 / (size_t)d->scope_D + 256) - 1;
+        d->scope_mask = pow2_at_least(max1 / (size_t)d->scope_D + 256, 64) - 1;
         if (int r = d->s_scope.alloc((size_t)d->cfg.batch * (d->scope_mask + 1))) return qrl_set_error(r, "scope ring");
         // the tap starts with the samples of the next call: outputs are indexed from the stream's 1 Msps position
         d->n_scope = decim_count(d->fe.used ? d->n1 : d->n_in, 1, d->scope_D);

@@ -38,21 +38,7 @@ __device__ __forceinline__ void rot_select(Pp& c, const Pp& p, uint32_t b)
     c = p; c.rot_acc = p.rot_acc_s[b]; c.rot_inc = p.rot_inc_s[b]; c.rot_lo = p.rot_lo + (size_t)b * 512;
 }
 #define ROT_VIEW(T, PS, P, SRC, B) T P##_ps_; if constexpr (PS) rot_select(P##_ps_, SRC, (uint32_t)(B)); const T& P = (PS) ? P##_ps_ : SRC
-// host side: the per-stream state of one handle (engine.cpp).  Device arrays acc[B], inc[B], lo[B][512]; allocated on the first per-stream set.
-struct RotPs {
-    uint64_t* acc = nullptr; uint64_t* inc = nullptr; float2* lo = nullptr;
-    std::vector<uint64_t> h_inc;   // host copy of inc
-    int batch = 0;
-    bool on() const { return acc != nullptr; }
-    // every stream: acc_b += (n_now - nbase) inc_b (on the device), nbase = n_now (the caller's shared nbase), then inc_b = new_inc[b].  Only streams
-    // whose increment changes get a table upload.  The first call starts every stream at the shared (acc, inc, lo).  Host-synchronous on s.
-    int set(int B, uint64_t acc0, uint64_t inc0, const float2* lo0, uint64_t delta, const uint64_t* new_inc, hipStream_t s);
-    // every stream to one increment (the scalar setter of a per-stream handle): lo0 = that increment's table (device)
-    int set_all(uint64_t delta, uint64_t new_inc, const float2* lo0, hipStream_t s);
-    int reset(hipStream_t s);   // acc_b = 0
-    void release();
-    template <class Pp> void fill(Pp& p) const { if (on()) { p.rot_acc_s = acc; p.rot_inc_s = inc; p.rot_lo = lo; } }
-};
+// host side: struct Rotator (host_common.hpp) owns the arrays
 std::vector<float2> rot_fine_table(uint64_t inc);   // the 512-entry fine table of an increment (sincos_turn_host)
 void launch_rot_ps_advance(uint64_t* acc, const uint64_t* inc, int B, uint64_t delta, hipStream_t s);
 void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set_acc, uint64_t acc0, uint64_t inc0, const float2* lo0, hipStream_t s);
@@ -84,7 +70,7 @@ struct DecimParams {
     // host side only: when set, the edge scratch is staged on THIS stream (k_pl_edge_stage reads the caller's buffer and the carried history,
     // nothing the call before produces on the launch stream), `pre_event` is recorded behind it and the launch stream waits for that
     hipStream_t pre_stream; hipEvent_t pre_event;
-    const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;   // per-stream rotator (see RotPs below), or nullptr: the shared one above
+    const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;   // per-stream rotator (see rot_select below), or nullptr: the shared one above
 };
 struct HistParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;

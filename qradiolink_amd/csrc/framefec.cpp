@@ -1,20 +1,10 @@
 // framefec.cpp — C ABI of the frame FEC kernels (kernels_framefec.hip): stateless batch calls on a caller-chosen HIP stream.
 //   qrl_bptc19696_decode / _encode   CBPTC19696::decode / encode    reference src/MMDVM/BPTC19696.cpp:47-87
 //   qrl_m17_decode_frames            M17FrameDecoder::decodeFrame   reference src/M17/M17/M17FrameDecoder.cpp:44-215
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
-#include <hip/hip_runtime.h>
+#include "host_common.hpp"
 #include <string>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" {
 

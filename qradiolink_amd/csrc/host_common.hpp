@@ -1,0 +1,80 @@
+// host_common.hpp — what every host translation unit of libqrl_hip.so shares: the context, error reporting, the owning device
+// buffer and the carrier NCO of a handle.  Host only: no .hip file includes it.
+#pragma once
+#include "../../include/qrl_hip.h"
+#include "engine.hpp"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+struct qrl_ctx { int device; };
+
+int qrl_set_error(int code, const std::string& msg);   // engine.cpp: records the text of qrl_last_error (per thread), returns code
+
+#define HIPCHK(expr)                                                                          \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+namespace qrl {
+
+inline uint32_t pow2_at_least(size_t v, uint32_t floor) { uint32_t c = floor; while (c < v) c <<= 1; return c; }
+
+// Owning device buffer of n items (at least one is allocated).  alloc() replaces what it held and zeroes the new buffer.
+template <class T> struct DevBuf {
+    T* p = nullptr; size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    size_t bytes() const { return std::max<size_t>(n, 1) * sizeof(T); }
+    // alloc() without the zeroing: one hipFree and one hipMalloc -- for a buffer that grows inside a process() call, or one its first kernel fills whole
+    int grow(size_t count) {
+        if (p) { (void)hipFree(p); p = nullptr; }
+        n = count;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), bytes());
+        if (e == hipSuccess) return QRL_OK;
+        const std::string what = "hipMalloc(" + std::to_string(bytes()) + " bytes): ";
+        p = nullptr; n = 0;
+        return qrl_set_error(QRL_ERR_NOMEM, what + hipGetErrorString(e));
+    }
+    int alloc(size_t count) { if (int r = grow(count)) return r; return zero(); }
+    // v followed by `pad` zero items (a kernel that reads its table unguarded)
+    int upload(const std::vector<T>& v, size_t pad = 0) {
+        if (int r = alloc(v.size() + pad)) return r;
+        if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+        return QRL_OK;
+    }
+    int zero() { return hipMemset(p, 0, bytes()) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
+};
+
+// ---- the carrier NCO of a handle (qrl_demod, qrl_mod, qrl_amod): exact 2^-64-turn accumulator, phase continuous across retunes ----
+// Shared form: one (acc, inc) for every stream, phase of sample n = acc + (n - nbase) inc, and the 512-entry fine table of inc.
+// Per-stream form (from the first retune_streams on): device arrays acc_s[B], inc_s[B], lo_s[B][512]; nbase stays shared.
+// The caller turns Hz into increments (its sign and rate), says which sample counter is "now" and drains its streams before a retune.
+struct Rotator {
+    uint64_t inc = 0, acc = 0, nbase = 0;
+    DevBuf<float2> lo;                                     // allocated once by init(), rewritten in place
+    DevBuf<uint64_t> acc_s, inc_s; DevBuf<float2> lo_s;
+    std::vector<uint64_t> h_inc;                           // host copy of inc_s
+    bool per_stream() const { return lo_s.p != nullptr; }   // (the last of the three to be allocated)
+    int init(uint64_t inc0) { inc = inc0; return lo.upload(rot_fine_table(inc)); }
+    // every stream to new_inc.  Per-stream form: each goes on from its own phase.  Host-synchronous on s.
+    int retune(uint64_t n_now, uint64_t new_inc, hipStream_t s);
+    // stream b to new_inc[b]; only streams whose increment changes get a table upload.  The first call starts every stream at the shared
+    // phase.  Host-synchronous on s.
+    int retune_streams(uint64_t n_now, const std::vector<uint64_t>& new_inc, hipStream_t s);
+    int reset(hipStream_t s);   // every phase and nbase to 0; the offsets stay
+    template <class Pp> void fill(Pp& p) const {
+        p.rot_acc = acc; p.rot_inc = inc; p.rot_nbase = nbase; p.rot_lo = lo.p;
+        if (per_stream()) { p.rot_acc_s = acc_s.p; p.rot_inc_s = inc_s.p; p.rot_lo = lo_s.p; }
+    }
+private:
+    uint64_t advance(uint64_t n_now) { const uint64_t delta = n_now - nbase; acc += delta * inc; nbase = n_now; return delta; }
+};
+// the increments of B carrier offsets: sign * hz[b] cycles per `rate` samples.  QRL_ERR_ARG unless every offset is finite.
+int carrier_incs(const double* hz, int B, double sign, double rate, std::vector<uint64_t>& inc);
+
+}  // namespace qrl

@@ -4,10 +4,8 @@
 //   qrl_fft_*   reference src/gr/rx_fft.cpp:44-213 (make_rx_fft_c(fftsize, wintype), work, set_enabled, get_fft_data, set_fft_size,
 //               set_window_type), instance make_rx_fft_c(32768, WIN_BLACKMAN_HARRIS) src/gr/gr_demod_base.cpp:166,185
 // The transform is hipFFT (batched C2C forward, one plan per FFT size); window, power spectrum and half swap are kernels.
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <hipfft/hipfft.h>
 #include <cmath>
 #include <memory>
@@ -16,14 +14,7 @@
 #include <vector>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
 
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define FFTCHK(expr)                                                                          \
     do {                                                                                      \
         hipfftResult r_ = (expr);                                                             \
@@ -33,12 +24,8 @@ struct qrl_ctx { int device; };
 struct qrl_rssi {
     qrl_ctx* ctx = nullptr; int batch = 1; float level = 0.f;
     hipStream_t stream = nullptr; bool own_stream = false;
-    RssiState* st = nullptr; float* ring = nullptr;
-    ~qrl_rssi() {
-        if (st) (void)hipFree(st);
-        if (ring) (void)hipFree(ring);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    DevBuf<RssiState> st; DevBuf<float> ring;
+    ~qrl_rssi() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 
 struct qrl_fft {
@@ -46,15 +33,11 @@ struct qrl_fft {
     unsigned fftsize = 0; int wintype = -1;
     hipStream_t stream = nullptr; bool own_stream = false;
     hipfftHandle plan = 0; bool have_plan = false;
-    float* win = nullptr; float2* buf = nullptr; float2* spec = nullptr; float* points = nullptr;
+    DevBuf<float> win, points; DevBuf<float2> buf, spec;
     unsigned counter = 0; int push = 0; bool data_ready = false, enabled = false;
-    void release() {
-        if (have_plan) { (void)hipfftDestroy(plan); have_plan = false; }
-        for (void* p : {(void*)win, (void*)buf, (void*)spec, (void*)points}) if (p) (void)hipFree(p);
-        win = nullptr; buf = nullptr; spec = nullptr; points = nullptr;
-    }
+    void drop_plan() { if (have_plan) { (void)hipfftDestroy(plan); have_plan = false; } }
     ~qrl_fft() {
-        release();
+        drop_plan();
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -104,13 +87,10 @@ static int fft_configure(qrl_fft* h, unsigned fftsize, int wintype)
     HIPCHK(hipSetDevice(h->ctx->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (fftsize != h->fftsize) {
-        h->release();
+        h->drop_plan();
         const size_t nb = (size_t)h->batch * fftsize;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->win), (size_t)fftsize * sizeof(float)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->buf), nb * sizeof(float2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->spec), nb * sizeof(float2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->points), nb * sizeof(float)));
-        HIPCHK(hipMemset(h->buf, 0, nb * sizeof(float2)));
+        int r;
+        if ((r = h->win.alloc(fftsize)) || (r = h->buf.alloc(nb)) || (r = h->spec.alloc(nb)) || (r = h->points.alloc(nb))) return r;
         int n[1] = {(int)fftsize};
         FFTCHK(hipfftPlanMany(&h->plan, 1, n, nullptr, 1, (int)fftsize, nullptr, 1, (int)fftsize, HIPFFT_C2C, h->batch));
         h->have_plan = true;
@@ -120,7 +100,7 @@ static int fft_configure(qrl_fft* h, unsigned fftsize, int wintype)
     }
     if (wintype != h->wintype) {
         const std::vector<float> w = fft_window(wintype, fftsize, 6.76);
-        HIPCHK(hipMemcpy(h->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
         h->wintype = wintype;
     }
     return QRL_OK;
@@ -138,10 +118,8 @@ int qrl_rssi_create(qrl_ctx* ctx, int batch, float level, void* hip_stream, qrl_
     HIPCHK(hipSetDevice(ctx->device));
     if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
     else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->st), (size_t)batch * sizeof(RssiState)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->ring), (size_t)batch * RSSI_RING * sizeof(float)));
-    HIPCHK(hipMemset(h->st, 0, (size_t)batch * sizeof(RssiState)));
-    HIPCHK(hipMemset(h->ring, 0, (size_t)batch * RSSI_RING * sizeof(float)));
+    int r;
+    if ((r = h->st.alloc(batch)) || (r = h->ring.alloc((size_t)batch * RSSI_RING))) return r;
     *out = h.release();
     return QRL_OK;
 }
@@ -149,8 +127,8 @@ void qrl_rssi_destroy(qrl_rssi* h) { if (h) { (void)hipStreamSynchronize(h->stre
 int qrl_rssi_reset(qrl_rssi* h)
 {
     if (!h) return QRL_ERR_ARG;
-    HIPCHK(hipMemsetAsync(h->st, 0, (size_t)h->batch * sizeof(RssiState), h->stream));
-    HIPCHK(hipMemsetAsync(h->ring, 0, (size_t)h->batch * RSSI_RING * sizeof(float), h->stream));
+    HIPCHK(hipMemsetAsync(h->st.p, 0, (size_t)h->batch * sizeof(RssiState), h->stream));
+    HIPCHK(hipMemsetAsync(h->ring.p, 0, (size_t)h->batch * RSSI_RING * sizeof(float), h->stream));
     return QRL_OK;
 }
 int qrl_rssi_set_level(qrl_rssi* h, float level) { if (!h) return QRL_ERR_ARG; h->level = level; return QRL_OK; }
@@ -164,7 +142,7 @@ int qrl_rssi_process(qrl_rssi* h, const float* filtered, size_t stride, size_t n
     RssiBlockParams p{};
     p.in = reinterpret_cast<const float2*>(filtered); p.in_stride = stride; p.n = (uint32_t)n;
     p.counts = counts; p.count_stride = count_stride;
-    p.st = h->st; p.ring = h->ring; p.batch = h->batch;
+    p.st = h->st.p; p.ring = h->ring.p; p.batch = h->batch;
     p.level = h->level;
     p.n_log2_10 = 1.0f / log2f(10.0f);                         // nlog10_ff: n / log2f(10), n = 1
     p.out = out; p.out_cap = out ? out_cap : (size_t)0xFFFFFFFFu; p.last = last; p.out_counts = out_counts;
@@ -215,13 +193,13 @@ int qrl_fft_process(qrl_fft* h, const float* iq, size_t stride, size_t n)
     while (i < n) {
         if (h->counter >= N) {
             h->counter = 0;
-            FFTCHK(hipfftExecC2C(h->plan, reinterpret_cast<hipfftComplex*>(h->buf), reinterpret_cast<hipfftComplex*>(h->spec), HIPFFT_FORWARD));
-            launch_fft_power(h->spec, h->points, N, h->batch, h->stream);
+            FFTCHK(hipfftExecC2C(h->plan, reinterpret_cast<hipfftComplex*>(h->buf.p), reinterpret_cast<hipfftComplex*>(h->spec.p), HIPFFT_FORWARD));
+            launch_fft_power(h->spec.p, h->points.p, N, h->batch, h->stream);
             h->data_ready = true;
             h->push++;
         }
         const size_t chunk = std::min(n - i, (size_t)(N - h->counter));
-        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win, h->counter, h->buf, N, h->batch, h->stream);
+        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win.p, h->counter, h->buf.p, N, h->batch, h->stream);
         h->counter += (unsigned)chunk;
         i += chunk;
     }
@@ -236,7 +214,7 @@ int qrl_fft_get_fft_data(qrl_fft* h, float* fft_points, size_t out_stride, unsig
     if (!h->data_ready) { *fft_size = 0; return QRL_OK; }
     if (out_stride < h->fftsize) return qrl_set_error(QRL_ERR_ARG, "out_stride < fft size");
     HIPCHK(hipSetDevice(h->ctx->device));
-    launch_fft_shift(h->points, fft_points, out_stride, h->fftsize, h->batch, h->stream);
+    launch_fft_shift(h->points.p, fft_points, out_stride, h->fftsize, h->batch, h->stream);
     HIPCHK(hipGetLastError());
     *fft_size = h->fftsize;
     h->data_ready = false;

@@ -1,9 +1,7 @@
 // synth.cpp — host side of the multi-carrier MMDVM transmitter (reference src/gr/gr_mod_mmdvm_multi2.cpp:30-128):
 // per channel int16 -> FM modulator -> LPF -> x0.8 -> 25/24 resampler, then pfb_synthesizer_ccf(10) -> x(1/N) -> bb gain.
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <memory>
 #include <new>
@@ -11,47 +9,18 @@
 #include <vector>
 
 using namespace qrl;
-extern int qrl_set_error(int code, const std::string& msg);
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-namespace {
-template <class T> struct Buf {
-    T* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) {
-        if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return QRL_ERR_NOMEM;
-        return hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
-    int upload(const std::vector<T>& v) {
-        int r = alloc(v.size());
-        if (r) return r;
-        return v.empty() || hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
-};
-uint32_t pow2ge(size_t v) { uint32_t c = 64; while (c < v) c <<= 1; return c; }
-}  // namespace
 
 struct qrl_synth {
     qrl_ctx* ctx = nullptr; qrl_synth_config cfg{};
     hipStream_t stream = nullptr; bool own_stream = false;
     int N = 3, J = 0, filt_nt = 0, rs_Jp = 0; float bb_gain = 1.0f; bool single = false; int rs_I = 25, rs_D = 24;
-    Buf<float> filt_taps, rs_taps, syn_taps, rA, phase; Buf<float2> twiddle, rB, rC, rD;
+    DevBuf<float> filt_taps, rs_taps, syn_taps, rA, phase; DevBuf<float2> twiddle, rB, rC, rD;
     uint32_t m1 = 0, m25 = 0; uint64_t n1 = 0, n25 = 0;
     int port_chan[16];
-    std::vector<ZeroRun> zero_runs; Buf<ZeroRun> zero_dev; size_t zero_dev_cap = 0;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
+    std::vector<ZeroRun> zero_runs; DevBuf<ZeroRun> zero_dev;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
     ~qrl_synth() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int reset_state() {
-        const size_t S = (size_t)cfg.batch * N;
-        if (hipMemset(rA.p, 0, S * (m1 + 1) * sizeof(float)) != hipSuccess || hipMemset(rB.p, 0, S * (m1 + 1) * sizeof(float2)) != hipSuccess ||
-            hipMemset(rC.p, 0, S * (m1 + 1) * sizeof(float2)) != hipSuccess || hipMemset(rD.p, 0, S * (m25 + 1) * sizeof(float2)) != hipSuccess ||
-            hipMemset(phase.p, 0, S * sizeof(float)) != hipSuccess)
-            return QRL_ERR_HIP;
+        if (rA.zero() || rB.zero() || rC.zero() || rD.zero() || phase.zero()) return QRL_ERR_HIP;
         n1 = n25 = 0;
         zero_runs.clear();
         return QRL_OK;
@@ -61,11 +30,8 @@ struct qrl_synth {
         std::vector<ZeroRun> live;
         for (const ZeroRun& z : zero_runs) if (z.start < hi && z.start + z.count > lo) live.push_back(z);
         if (!live.empty()) {
-            if (live.size() > zero_dev_cap) {
-                zero_dev_cap = live.size() + 16;
-                if (zero_dev.p) { (void)hipFree(zero_dev.p); zero_dev.p = nullptr; }
-                int rr = zero_dev.alloc(zero_dev_cap);
-                if (rr) return rr;
+            if (live.size() > zero_dev.n) {
+                if (int rr = zero_dev.alloc(live.size() + 16)) return rr;
             }
             if (hipMemcpyAsync(zero_dev.p, live.data(), live.size() * sizeof(ZeroRun), hipMemcpyHostToDevice, stream) != hipSuccess) return QRL_ERR_HIP;
             if (hipStreamSynchronize(stream) != hipSuccess) return QRL_ERR_HIP;   // `live` is a stack vector: the copy must be through
@@ -118,8 +84,8 @@ int qrl_synth_create(qrl_ctx* ctx, const qrl_synth_config* cfg, qrl_synth** outp
     for (int c = 0, m = 1; c < h->N; ++c) h->port_chan[c <= 3 ? c : 10 - m++] = c;
     const size_t S = (size_t)cfg->batch * h->N;
     const size_t max25 = cfg->max_samples * h->rs_I / h->rs_D + 2;
-    h->m1 = pow2ge(cfg->max_samples + h->filt_nt + h->rs_Jp + 64) - 1;
-    h->m25 = pow2ge(max25 + h->J + 64) - 1;
+    h->m1 = pow2_at_least(cfg->max_samples + h->filt_nt + h->rs_Jp + 64, 64) - 1;
+    h->m25 = pow2_at_least(max25 + h->J + 64, 64) - 1;
     if ((r = h->rA.alloc(S * (h->m1 + 1))) || (r = h->rB.alloc(S * (h->m1 + 1))) || (r = h->rC.alloc(S * (h->m1 + 1))) ||
         (r = h->rD.alloc(S * (h->m25 + 1))) || (r = h->phase.alloc(S)))
         return qrl_set_error(r, "synthesizer buffers");

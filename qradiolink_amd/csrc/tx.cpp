@@ -1,9 +1,7 @@
 // tx.cpp — host side of the TX half of libqrl_hip.so: the "modulator" top_block of the reference
 // (src/gr/gr_mod_base.cpp:25,175; src/gr/gr_mod_qpsk.cpp:56-89) as a two-kernel pipeline per call.
-#include "../../include/qrl_hip.h"
-#include "engine.hpp"
+#include "host_common.hpp"
 #include "firdes.hpp"
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -13,15 +11,6 @@
 
 using namespace qrl;
 
-extern int qrl_set_error(int code, const std::string& msg);   // engine.cpp
-struct qrl_ctx { int device; };
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct qrl_mod {
     qrl_ctx* ctx = nullptr;
     qrl_mod_config cfg{};
@@ -30,65 +19,45 @@ struct qrl_mod {
     enum { F_QPSK, F_FSK } fam = F_QPSK;   // F_QPSK: symbols -> RRC interpolator (QPSK, BPSK); F_FSK: shape -> FM -> interpolator
     bool bpsk = false, fsk4 = false; float shape_scale = 0.0f;
     // gr_mod_m17: raw dibits -> RRC x5 -> FM -> channel filter -> gains -> 125 / 3 (2500 samples per 3 bytes)
-    bool m17 = false; float* m17_filt = nullptr; int m17_nf = 0; float2* m17_flt = nullptr;
+    bool m17 = false; DevBuf<float> m17_filt; int m17_nf = 0; DevBuf<float2> m17_flt;
     // gr_mod_dmr (src/gr/gr_mod_dmr.cpp:26-90): the m17 path with the DMR pulse and deviation; gr_zero_idle_bursts(62) in the place of the channel
     // filter = the stream 2 x 720 - 1 items late (the block's history, gr_zero_idle_bursts.cpp:34-37,76) + the tagged runs zeroed `delay` items early
-    bool dmr = false; std::vector<ZeroRun> zero_runs; ZeroRun* zero_dev = nullptr; size_t zero_dev_cap = 0;
+    bool dmr = false; std::vector<ZeroRun> zero_runs; DevBuf<ZeroRun> zero_dev;
     static constexpr uint32_t kDmrHist = 2 * 720 - 1, kDmrTagDelay = 62;
     // gr_mod_dsss: coded bits -> Barker-13 chips -> RRC x25 (5200 sps) -> gains -> 50 / 13 (20 ksps) -> 1:50; 1 000 000 samples per byte
-    bool dsss = false; uint8_t* ds_chips = nullptr; uint32_t ds_chip_mask = 0; float* ds_shaped = nullptr; float2 *ds_c52 = nullptr, *ds_c20 = nullptr;
-    uint32_t ds_m52 = 0, ds_m20 = 0; float* ds_if_taps = nullptr; int ds_if_Jp = 0;
+    bool dsss = false; DevBuf<uint8_t> ds_chips; uint32_t ds_chip_mask = 0; DevBuf<float> ds_shaped; DevBuf<float2> ds_c52, ds_c20;
+    uint32_t ds_m52 = 0, ds_m20 = 0; DevBuf<float> ds_if_taps; int ds_if_Jp = 0;
     int sps = 4;
     float bb_gain = 1.0f;
-    float* taps = nullptr; int nt = 0;
+    DevBuf<float> taps; int nt = 0;
     // FSK family (2FSK / GMSK): shaping taps (nt_shape = 0: repeat), FM constant, amplitude, second interpolator
-    float* shape_taps = nullptr; int nt_shape = 0; float fm_k = 0, amplif = 0; int interp2 = 1;
-    float* shaped = nullptr; float2* fmv = nullptr; uint32_t r1_mask = 0; float* phase = nullptr;
-    TxState* st = nullptr;
-    uint8_t* sym = nullptr; uint32_t sym_mask = 0;
+    DevBuf<float> shape_taps; int nt_shape = 0; float fm_k = 0, amplif = 0; int interp2 = 1;
+    DevBuf<float> shaped; DevBuf<float2> fmv; uint32_t r1_mask = 0; DevBuf<float> phase;
+    DevBuf<TxState> st;
+    DevBuf<uint8_t> sym; uint32_t sym_mask = 0;
     uint64_t nsym = 0;   // symbols (= input bits) so far
     // gr_mod_base back end (gr_mod_base.cpp:38,215-258): rotator at 1 Msps, then interpolation to the device rate
-    bool backend = false; int be_interp = 1; float* be_taps = nullptr; int be_nt = 0;
-    float2* bb = nullptr; size_t bb_stride = 0;            // modulator output, linear, one call's worth
-    float2* be_ring = nullptr; uint32_t be_mask = 0;       // rotated 1 Msps signal (interpolator history)
-    float2* rot_lo = nullptr; uint64_t rot_inc = 0, rot_acc = 0, rot_nbase = 0, n_bb = 0;
-    RotPs ps;   // per-stream offsets (qrl_mod_set_carrier_offsets); off: the shared NCO above
-    int set_rot(double hz) {
-        rot_inc = phase_inc_to_turn(2 * M_PI * hz / 1000000.0);
-        std::vector<float2> lo(512);
-        for (int r = 0; r < 512; ++r) { float s, c; sincos_turn_host((uint64_t)r * rot_inc, s, c); lo[r] = make_float2(c, s); }
-        return hipMemcpy(rot_lo, lo.data(), 512 * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
-    }
-    ~qrl_mod() {
-        ps.release();
-        if (taps) (void)hipFree(taps);
-        for (void* p : {(void*)zero_dev, (void*)shape_taps, (void*)shaped, (void*)fmv, (void*)phase, (void*)m17_filt, (void*)m17_flt, (void*)ds_chips, (void*)ds_shaped, (void*)ds_c52, (void*)ds_c20, (void*)ds_if_taps}) if (p) (void)hipFree(p);
-        if (st) (void)hipFree(st);
-        for (void* p : {(void*)be_taps, (void*)bb, (void*)be_ring, (void*)rot_lo}) if (p) (void)hipFree(p);
-        if (sym) (void)hipFree(sym);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    bool backend = false; int be_interp = 1; DevBuf<float> be_taps; int be_nt = 0;
+    DevBuf<float2> bb; size_t bb_stride = 0;           // modulator output, linear, one call's worth
+    DevBuf<float2> be_ring; uint32_t be_mask = 0;       // rotated 1 Msps signal (interpolator history)
+    Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
+    ~qrl_mod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int init_state() {
         std::vector<TxState> s(cfg.batch);
         for (auto& x : s) { x.sr = 0x7F; x.enc = 0; x.prev = 0; x.pad = 0; }   // scrambler seed 0x7F (gr_mod_qpsk.cpp:62)
-        if (hipMemcpy(st, s.data(), s.size() * sizeof(TxState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        if (hipMemset(sym, 0, (size_t)cfg.batch * (sym_mask + 1)) != hipSuccess) return QRL_ERR_HIP;
+        if (hipMemcpy(st.p, s.data(), s.size() * sizeof(TxState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+        int r;
+        if ((r = sym.zero())) return r;
         if (fam == F_FSK) {
-            if (hipMemset(shaped, 0, (size_t)cfg.batch * (r1_mask + 1) * sizeof(float)) != hipSuccess) return QRL_ERR_HIP;
-            if (hipMemset(fmv, 0, (size_t)cfg.batch * (r1_mask + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-            if (hipMemset(phase, 0, (size_t)cfg.batch * sizeof(float)) != hipSuccess) return QRL_ERR_HIP;
-            if (m17_flt && hipMemset(m17_flt, 0, (size_t)cfg.batch * (r1_mask + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
+            if ((r = shaped.zero()) || (r = fmv.zero()) || (r = phase.zero()) || (m17_flt.p && (r = m17_flt.zero()))) return r;
         }
         if (dsss) {
-            if (hipMemset(ds_chips, 0, (size_t)cfg.batch * (ds_chip_mask + 1)) != hipSuccess) return QRL_ERR_HIP;
-            if (hipMemset(ds_shaped, 0, (size_t)cfg.batch * (ds_m52 + 1) * sizeof(float)) != hipSuccess) return QRL_ERR_HIP;
-            if (hipMemset(ds_c52, 0, (size_t)cfg.batch * (ds_m52 + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-            if (hipMemset(ds_c20, 0, (size_t)cfg.batch * (ds_m20 + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
+            if ((r = ds_chips.zero()) || (r = ds_shaped.zero()) || (r = ds_c52.zero()) || (r = ds_c20.zero())) return r;
         }
-        if (be_ring && hipMemset(be_ring, 0, (size_t)cfg.batch * (be_mask + 1) * sizeof(float2)) != hipSuccess) return QRL_ERR_HIP;
-        nsym = 0; n_bb = 0; rot_acc = 0; rot_nbase = 0;
+        if (be_ring.p && (r = be_ring.zero())) return r;
+        nsym = 0; n_bb = 0;
         zero_runs.clear();
-        return ps.reset(stream);   // per-stream phases restart too; the offsets stay
+        return rot.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -179,13 +148,7 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
         else HIPCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
         m->own_stream = true;
     }
-    auto upload = [](const std::vector<float>& v, float** dst) -> int {   // followed by 64 zeros: k_tx_interp_sym reads its I x J = 64 taps unguarded
-        const size_t bytes = (v.size() + 64) * sizeof(float);
-        if (hipMalloc(reinterpret_cast<void**>(dst), bytes) != hipSuccess) return QRL_ERR_NOMEM;
-        if (hipMemset(*dst, 0, bytes) != hipSuccess) return QRL_ERR_HIP;
-        if (!v.empty() && hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        return QRL_OK;
-    };
+    constexpr size_t kTapPad = 64;   // zeros behind every tap table: k_tx_interp_sym reads its I x J = 64 taps unguarded
     size_t ring_items = c.max_bytes * 8 + 256;   // symbol ring: one item per input bit (QPSK) or per coded bit (FSK: x2)
     if (m->dsss) {   // gr_mod_dsss.cpp:60-76
         const int fw = c.filter_width;
@@ -198,18 +161,14 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
         std::vector<float> lay((size_t)50 * m->ds_if_Jp, 0.0f);
         for (size_t k = 0; k < ti.size(); ++k) lay[(k % 50) * m->ds_if_Jp + k / 50] = ti[k];
         int r0;
-        if ((r0 = upload(rrc, &m->shape_taps)) || (r0 = upload(tr, &m->taps)) || (r0 = upload(lay, &m->ds_if_taps))) return r0;
+        if ((r0 = m->shape_taps.upload(rrc, kTapPad)) || (r0 = m->taps.upload(tr, kTapPad)) || (r0 = m->ds_if_taps.upload(lay, kTapPad))) return r0;
         m->shape_scale = 0.65f;                                                                             // _amplify
         ring_items = c.max_bytes * 16 + 256;                                                                // coded bits
-        uint32_t cc = 1024, c52 = 1024, c20 = 1024;
-        while (cc < c.max_bytes * 208 + 256) cc <<= 1;
-        while (c52 < c.max_bytes * 5200 + 1024) c52 <<= 1;
-        while (c20 < c.max_bytes * 20000 + 1024) c20 <<= 1;
+        const uint32_t cc = pow2_at_least(c.max_bytes * 208 + 256, 1024), c52 = pow2_at_least(c.max_bytes * 5200 + 1024, 1024);
+        const uint32_t c20 = pow2_at_least(c.max_bytes * 20000 + 1024, 1024);
         m->ds_chip_mask = cc - 1; m->ds_m52 = c52 - 1; m->ds_m20 = c20 - 1;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->ds_chips), (size_t)c.batch * cc));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->ds_shaped), (size_t)c.batch * c52 * sizeof(float)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->ds_c52), (size_t)c.batch * c52 * sizeof(float2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->ds_c20), (size_t)c.batch * c20 * sizeof(float2)));
+        if ((r0 = m->ds_chips.alloc((size_t)c.batch * cc)) || (r0 = m->ds_shaped.alloc((size_t)c.batch * c52)) ||
+            (r0 = m->ds_c52.alloc((size_t)c.batch * c52)) || (r0 = m->ds_c20.alloc((size_t)c.batch * c20))) return r0;
     } else if (!fsk) {
         const std::vector<float> rrc = bpsk ? root_raised_cosine(m->sps, m->sps, 1, 0.35, 11 * m->sps)   // gr_mod_bpsk.cpp:52-54
                                             : root_raised_cosine(m->sps, m->sps, 1, 0.35,             // gr_mod_qpsk.cpp:46-51
@@ -217,7 +176,7 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
         m->nt = (int)rrc.size();
         if (m->nt > 16384) return qrl_set_error(QRL_ERR_ARG, "modulator: pulse-shaping filter too long");
         if (bpsk) ring_items = c.max_bytes * 16 + 256;
-        int r0 = upload(rrc, &m->taps);
+        int r0 = m->taps.upload(rrc, kTapPad);
         if (r0) return r0;
     } else {
         m->fam = qrl_mod::F_FSK;
@@ -252,29 +211,26 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
         m->sps = sps;
         m->nt_shape = (int)shape.size();
         if (m->nt_shape > 1536) return qrl_set_error(QRL_ERR_ARG, "modulator: shaping filter too long");
-        int r0 = upload(shape, &m->shape_taps);
+        int r0 = m->shape_taps.upload(shape, kTapPad);
         if (r0) return r0;
         const std::vector<float> lp = m->dmr ? low_pass_2(125, (double)c.samp_rate * 3, c.filter_width, 2000, 60, WIN_BLACKMAN_HARRIS)   // gr_mod_dmr.cpp:65-68
                                     : m->m17 ? low_pass(125, (double)c.samp_rate * 3, 12000, 12000, WIN_BLACKMAN_HARRIS)   // _resampler (125, 3), gr_mod_m17.cpp:64-66
                                              : low_pass(m->interp2, c.samp_rate, c.filter_width, c.filter_width, WIN_HAMMING);
         m->nt = (int)lp.size();
         if (m->nt > (m->dmr ? 8192 : 2048)) return qrl_set_error(QRL_ERR_ARG, "modulator: interpolator filter too long");   // (gr_mod_dmr: 4091 taps; k_tx_interp_c reads taps beyond 2048 through the caches)
-        if ((r0 = upload(lp, &m->taps))) return r0;
+        if ((r0 = m->taps.upload(lp, kTapPad))) return r0;
         ring_items = c.max_bytes * 16 + 256;
-        uint32_t cap1 = 1024;
-        while (cap1 < c.max_bytes * 16 * (size_t)sps + (size_t)m->nt + 256 + (m->dmr ? qrl_mod::kDmrHist + 64 : 0)) cap1 <<= 1;
+        const uint32_t cap1 = pow2_at_least(c.max_bytes * 16 * (size_t)sps + (size_t)m->nt + 256 + (m->dmr ? qrl_mod::kDmrHist + 64 : 0), 1024);
         m->r1_mask = cap1 - 1;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->shaped), (size_t)c.batch * cap1 * sizeof(float)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->fmv), (size_t)c.batch * cap1 * sizeof(float2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->phase), (size_t)c.batch * sizeof(float)));
+        if ((r0 = m->shaped.alloc((size_t)c.batch * cap1)) || (r0 = m->fmv.alloc((size_t)c.batch * cap1)) || (r0 = m->phase.alloc(c.batch))) return r0;
         if (m->m17) {
             // _filter, gr_mod_m17.cpp:69-70.  gr_mod_dmr: one tap 1.0 at lag 2 x 720 - 1 -- the delay of gr_zero_idle_bursts' history read
             // through the same FIR kernel (fmaf(1, x, +0) = x; the zero taps leave the chain untouched)
             std::vector<float> ft = low_pass(1, 24000, c.filter_width, c.filter_width, WIN_BLACKMAN_HARRIS);
             if (m->dmr) { ft.assign(qrl_mod::kDmrHist + 1, 0.0f); ft.back() = 1.0f; }
             m->m17_nf = (int)ft.size();
-            if ((r0 = upload(ft, &m->m17_filt))) return r0;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->m17_flt), (size_t)c.batch * cap1 * sizeof(float2)));
+            if ((r0 = m->m17_filt.upload(ft, kTapPad))) return r0;
+            if ((r0 = m->m17_flt.alloc((size_t)c.batch * cap1))) return r0;
         }
     }
     if (c.device_samp_rate != 0 && c.device_samp_rate != 1000000 &&
@@ -285,27 +241,19 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
     if (m->backend) {
         const size_t spb1 = fsk4 ? (size_t)8 * m->sps * m->interp2 : fsk ? (size_t)16 * m->sps * m->interp2 : (size_t)(bpsk ? 16 : 8) * m->sps;
         m->bb_stride = c.max_bytes * spb1;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->bb), (size_t)c.batch * m->bb_stride * sizeof(float2)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->rot_lo), 512 * sizeof(float2)));
-        int r0 = m->set_rot(c.carrier_offset_hz);
-        if (r0) return r0;
+        int r0;
+        if ((r0 = m->bb.alloc((size_t)c.batch * m->bb_stride)) || (r0 = m->rot.init(phase_inc_to_turn(2 * M_PI * c.carrier_offset_hz / 1000000.0)))) return r0;
         if (m->be_interp > 1) {
             const std::vector<float> lp = low_pass(m->be_interp, c.device_samp_rate, 480000, 20000, WIN_BLACKMAN_HARRIS);
             m->be_nt = (int)lp.size();
-            if ((r0 = upload(lp, &m->be_taps))) return r0;
-            uint32_t capb = 1024;
-            while (capb < m->bb_stride + (size_t)m->be_nt / m->be_interp + 64) capb <<= 1;
-            m->be_mask = capb - 1;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->be_ring), (size_t)c.batch * capb * sizeof(float2)));
+            if ((r0 = m->be_taps.upload(lp, kTapPad))) return r0;
+            m->be_mask = pow2_at_least(m->bb_stride + (size_t)m->be_nt / m->be_interp + 64, 1024) - 1;
+            if ((r0 = m->be_ring.alloc((size_t)c.batch * (m->be_mask + 1)))) return r0;
         }
     }
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->st), (size_t)c.batch * sizeof(TxState)));
-    uint32_t cap = 1024;
-    while (cap < ring_items) cap <<= 1;
-    m->sym_mask = cap - 1;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->sym), (size_t)c.batch * cap));
-    int r = m->init_state();
-    if (r) return r;
+    m->sym_mask = pow2_at_least(ring_items, 1024) - 1;
+    int r;
+    if ((r = m->st.alloc(c.batch)) || (r = m->sym.alloc((size_t)c.batch * (m->sym_mask + 1))) || (r = m->init_state())) return r;
     *outp = m.release();
     return QRL_OK;
 }
@@ -321,26 +269,16 @@ int qrl_mod_set_carrier_offset(qrl_mod* m, double hz)
     if (!m) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
     HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    const uint64_t delta = m->n_bb - m->rot_nbase;
-    m->rot_acc += delta * m->rot_inc;   // phase-continuous, like rotator_cc::set_phase_inc
-    m->rot_nbase = m->n_bb;
-    if (int r = m->set_rot(hz)) return r;
-    // a handle with per-stream offsets stays on that path: every stream goes on from its own phase
-    return m->ps.on() ? m->ps.set_all(delta, m->rot_inc, m->rot_lo, m->stream) : QRL_OK;
+    return m->rot.retune(m->n_bb, phase_inc_to_turn(2 * M_PI * hz / 1000000.0), m->stream);   // phase-continuous, like rotator_cc::set_phase_inc
 }
 int qrl_mod_set_carrier_offsets(qrl_mod* m, const double* hz)
 {
     if (!m || !hz) return QRL_ERR_ARG;
     if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
-    const int B = m->cfg.batch;
-    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
+    std::vector<uint64_t> ni;
+    if (int r = carrier_incs(hz, m->cfg.batch, 1.0, 1000000.0, ni)) return r;
     HIPCHK(hipStreamSynchronize(m->stream));
-    std::vector<uint64_t> ni((size_t)B);
-    for (int b = 0; b < B; ++b) ni[(size_t)b] = phase_inc_to_turn(2 * M_PI * hz[b] / 1000000.0);
-    const uint64_t delta = m->n_bb - m->rot_nbase;
-    m->rot_acc += delta * m->rot_inc;
-    m->rot_nbase = m->n_bb;
-    return m->ps.set(B, m->rot_acc, m->rot_inc, m->rot_lo, delta, ni.data(), m->stream);
+    return m->rot.retune_streams(m->n_bb, ni, m->stream);
 }
 int qrl_mod_set_bb_gain(qrl_mod* m, float g) { if (!m) return QRL_ERR_ARG; m->bb_gain = g; return QRL_OK; }
 int qrl_mod_add_zero_runs(qrl_mod* m, const qrl_zero_run* runs, size_t n)
@@ -387,17 +325,17 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     HIPCHK(hipSetDevice(m->ctx->device));
     const int B = m->cfg.batch;
     const uint32_t nbits = (uint32_t)nbytes * 8;
-    float2* mod_out = m->backend ? m->bb : reinterpret_cast<float2*>(iq);
+    float2* mod_out = m->backend ? m->bb.p : reinterpret_cast<float2*>(iq);
     const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
-        TxRotParams rp{}; rp.in = m->bb; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        rp.rot_acc = m->rot_acc; rp.rot_inc = m->rot_inc; rp.rot_nbase = m->rot_nbase; rp.rot_lo = m->rot_lo; m->ps.fill(rp);
-        if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring, m->be_mask};
+        TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
+        m->rot.fill(rp);
+        if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
         else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
         launch_tx_rot(rp, B, m->stream);
         if (m->be_interp > 1) {
             TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = m->n_bb * (uint64_t)m->be_interp; bp.count = n1 * (uint32_t)m->be_interp;
-            bp.taps = m->be_taps; bp.nt = m->be_nt; bp.interp = m->be_interp;
+            bp.taps = m->be_taps.p; bp.nt = m->be_nt; bp.interp = m->be_interp;
             bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride;
             launch_tx_interp_c(bp, B, m->stream);
         }
@@ -406,17 +344,17 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     if (m->m17) {
         if (nbytes % 3) return qrl_set_error(QRL_ERR_ARG, "modulator: m17 takes multiples of 3 bytes per call (2500 samples per 3 bytes)");
         const uint32_t nsy = (uint32_t)nbytes * 4, c24 = nsy * 5, cout = c24 / 3 * 125;
-        RingB sym{m->sym, m->sym_mask};
+        RingB sym{m->sym.p, m->sym_mask};
         launch_tx_raw_dibits(bytes, stride, (uint32_t)nbytes, sym, m->nsym, B, m->stream);
         const uint64_t n24 = m->nsym * 5;
-        TxShapeParams sp{}; sp.sym = sym; sp.out = RingF{m->shaped, m->r1_mask}; sp.n0 = n24; sp.count = c24; sp.sps = 5;
-        sp.taps = m->shape_taps; sp.nt = m->nt_shape; sp.levels = 4; sp.scale = m->shape_scale;
+        TxShapeParams sp{}; sp.sym = sym; sp.out = RingF{m->shaped.p, m->r1_mask}; sp.n0 = n24; sp.count = c24; sp.sps = 5;
+        sp.taps = m->shape_taps.p; sp.nt = m->nt_shape; sp.levels = 4; sp.scale = m->shape_scale;
         launch_tx_shape(sp, B, m->stream);                                              // _chunks_to_symbols, _first_resampler, _scale_pulses
-        TxFmParams fp{}; fp.in = sp.out; fp.out = RingC{m->fmv, m->r1_mask}; fp.n0 = n24; fp.count = c24; fp.k = m->fm_k; fp.amp = 1.0f;
-        fp.phase = m->phase;
+        TxFmParams fp{}; fp.in = sp.out; fp.out = RingC{m->fmv.p, m->r1_mask}; fp.n0 = n24; fp.count = c24; fp.k = m->fm_k; fp.amp = 1.0f;
+        fp.phase = m->phase.p;
         launch_tx_fm(fp, B, m->stream);                                                 // _fm_modulator
-        RingC flt{m->m17_flt, m->r1_mask};
-        FirCcfParams cf{}; cf.in = fp.out; cf.out = flt; cf.q0 = n24; cf.count = c24; cf.taps = m->m17_filt; cf.nt = m->m17_nf;
+        RingC flt{m->m17_flt.p, m->r1_mask};
+        FirCcfParams cf{}; cf.in = fp.out; cf.out = flt; cf.q0 = n24; cf.count = c24; cf.taps = m->m17_filt.p; cf.nt = m->m17_nf;
         launch_fir_ccf(cf, B, m->stream);                                               // _filter (gr_mod_dmr: the history delay of _zero_idle)
         if (m->dmr && !m->zero_runs.empty()) {                                          // _zero_idle: the tagged runs of this call's items
             const uint64_t lo = n24, hi = n24 + c24;
@@ -426,22 +364,19 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
                 if (z.start + z.count > hi) keep.push_back(z);
             }
             if (!live.empty()) {
-                if (live.size() > m->zero_dev_cap) {
+                if (live.size() > m->zero_dev.n) {
                     HIPCHK(hipStreamSynchronize(m->stream));
-                    if (m->zero_dev) (void)hipFree(m->zero_dev);
-                    m->zero_dev = nullptr; m->zero_dev_cap = 0;
-                    HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->zero_dev), live.size() * 2 * sizeof(ZeroRun)));
-                    m->zero_dev_cap = live.size() * 2;
+                    if (int rz = m->zero_dev.grow(live.size() * 2)) return rz;
                 }
-                HIPCHK(hipMemcpyAsync(m->zero_dev, live.data(), live.size() * sizeof(ZeroRun), hipMemcpyHostToDevice, m->stream));
+                HIPCHK(hipMemcpyAsync(m->zero_dev.p, live.data(), live.size() * sizeof(ZeroRun), hipMemcpyHostToDevice, m->stream));
                 HIPCHK(hipStreamSynchronize(m->stream));                                // (`live` is pageable host memory: the copy has left it)
-                launch_zero_runs(flt, m->zero_dev, (uint32_t)live.size(), lo, hi, m->stream);
+                launch_zero_runs(flt, m->zero_dev.p, (uint32_t)live.size(), lo, hi, m->stream);
             }
             m->zero_runs.swap(keep);
         }
         launch_scale_c(flt, n24, c24, 0.9f, B, m->stream);                              // _amplify
         launch_scale_c(flt, n24, c24, m->bb_gain, B, m->stream);                        // _bb_gain
-        TxInterpCParams ip{}; ip.in = flt; ip.n0 = n24 / 3 * 125; ip.count = cout; ip.taps = m->taps; ip.nt = m->nt; ip.interp = 125; ip.decim = 3;
+        TxInterpCParams ip{}; ip.in = flt; ip.n0 = n24 / 3 * 125; ip.count = cout; ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = 125; ip.decim = 3;
         ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride;
         launch_tx_interp_c(ip, B, m->stream);                                           // _resampler (125, 3)
         HIPCHK(hipGetLastError());
@@ -453,23 +388,23 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     p.bytes = bytes; p.stride = stride; p.nbytes = (uint32_t)nbytes;
     p.L = ((nbits + 63) / 64 + 31) / 32 * 32;
     lfsr_powers(p.L, p.tl_pow);
-    p.st = m->st; p.sym = RingB{m->sym, m->sym_mask}; p.s0 = m->nsym;
+    p.st = m->st.p; p.sym = RingB{m->sym.p, m->sym_mask}; p.s0 = m->nsym;
     p.mode = m->fsk4 ? 2 : (m->fam == qrl_mod::F_FSK || m->bpsk || m->dsss) ? 1 : 0;
     launch_tx_qpsk_bits(p, B, m->stream);
     if (m->dsss) {
         const uint32_t ncoded = 2 * nbits, nchips = ncoded * 13u, c52 = nchips * 25u, c20 = c52 / 13u * 50u;
         const uint64_t chip0 = m->nsym * 13ull, n52 = chip0 * 25ull, n20 = n52 / 13ull * 50ull;
-        RingB chips{m->ds_chips, m->ds_chip_mask};
+        RingB chips{m->ds_chips.p, m->ds_chip_mask};
         launch_tx_spread(p.sym, chips, m->nsym, ncoded, B, m->stream);                   // _dsss_encoder
-        TxShapeParams sp{}; sp.sym = chips; sp.out = RingF{m->ds_shaped, m->ds_m52}; sp.n0 = n52; sp.count = c52; sp.sps = 25;
-        sp.taps = m->shape_taps; sp.nt = m->nt_shape; sp.levels = 2; sp.scale = m->shape_scale;
+        TxShapeParams sp{}; sp.sym = chips; sp.out = RingF{m->ds_shaped.p, m->ds_m52}; sp.n0 = n52; sp.count = c52; sp.sps = 25;
+        sp.taps = m->shape_taps.p; sp.nt = m->nt_shape; sp.levels = 2; sp.scale = m->shape_scale;
         launch_tx_shape(sp, B, m->stream);                                               // _chunks_to_symbols, _resampler, _amplify
-        RingC r52{m->ds_c52, m->ds_m52}, r20{m->ds_c20, m->ds_m20};
+        RingC r52{m->ds_c52.p, m->ds_m52}, r20{m->ds_c20.p, m->ds_m20};
         launch_tx_f2c(sp.out, r52, n52, c52, m->bb_gain, B, m->stream);                  // _bb_gain
         ResampParams rp{}; rp.in = nullptr; rp.in_ring = r52; rp.n0 = n52; rp.n = c52; rp.out = r20; rp.q0 = n20; rp.q_count = c20;
-        rp.taps = m->ds_if_taps; rp.I = 50; rp.D = 13; rp.Jp = m->ds_if_Jp;
+        rp.taps = m->ds_if_taps.p; rp.I = 50; rp.D = 13; rp.Jp = m->ds_if_Jp;
         launch_resamp(rp, B, m->stream);                                                 // _resampler_if (50, 13)
-        TxInterpCParams ip{}; ip.in = r20; ip.n0 = n20 * 50ull; ip.count = c20 * 50u; ip.taps = m->taps; ip.nt = m->nt; ip.interp = 50;
+        TxInterpCParams ip{}; ip.in = r20; ip.n0 = n20 * 50ull; ip.count = c20 * 50u; ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = 50;
         ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride;
         launch_tx_interp_c(ip, B, m->stream);                                            // _resampler_rf (50, 1)
         HIPCHK(hipGetLastError());
@@ -482,14 +417,14 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
         const uint32_t ncoded = m->fsk4 ? nbits : 2 * nbits;   // ring items per call: 4-level symbols, or coded bits
         const uint64_t n1_0 = m->nsym * (uint64_t)m->sps;
         const uint32_t c1 = ncoded * (uint32_t)m->sps;
-        TxShapeParams sp{}; sp.sym = p.sym; sp.out = RingF{m->shaped, m->r1_mask}; sp.n0 = n1_0; sp.count = c1; sp.sps = m->sps;
-        sp.taps = m->shape_taps; sp.nt = m->nt_shape; sp.levels = m->fsk4 ? 4 : 2; sp.scale = m->shape_scale;
+        TxShapeParams sp{}; sp.sym = p.sym; sp.out = RingF{m->shaped.p, m->r1_mask}; sp.n0 = n1_0; sp.count = c1; sp.sps = m->sps;
+        sp.taps = m->shape_taps.p; sp.nt = m->nt_shape; sp.levels = m->fsk4 ? 4 : 2; sp.scale = m->shape_scale;
         launch_tx_shape(sp, B, m->stream);
-        TxFmParams fp{}; fp.in = sp.out; fp.out = RingC{m->fmv, m->r1_mask}; fp.n0 = n1_0; fp.count = c1; fp.k = m->fm_k; fp.amp = m->amplif;
-        fp.phase = m->phase;
+        TxFmParams fp{}; fp.in = sp.out; fp.out = RingC{m->fmv.p, m->r1_mask}; fp.n0 = n1_0; fp.count = c1; fp.k = m->fm_k; fp.amp = m->amplif;
+        fp.phase = m->phase.p;
         launch_tx_fm(fp, B, m->stream);
         TxInterpCParams ip{}; ip.in = fp.out; ip.n0 = n1_0 * (uint64_t)m->interp2; ip.count = c1 * (uint32_t)m->interp2;
-        ip.taps = m->taps; ip.nt = m->nt; ip.interp = m->interp2; ip.out = mod_out; ip.out_stride = mod_stride;
+        ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = m->interp2; ip.out = mod_out; ip.out_stride = mod_stride;
         launch_tx_interp_c(ip, B, m->stream);
         if (m->backend) back_end(ip.count);
         HIPCHK(hipGetLastError());
@@ -500,7 +435,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     TxInterpParams q{};
     const uint32_t nitems = m->bpsk ? 2 * nbits : nbits;   // BPSK: one symbol per coded bit (gr_mod_bpsk.cpp:60-61)
     q.sym = p.sym; q.n0 = m->nsym * (uint64_t)m->sps; q.count = nitems * (uint32_t)m->sps;
-    q.taps = m->taps; q.nt = m->nt; q.interp = m->sps;
+    q.taps = m->taps.p; q.nt = m->nt; q.interp = m->sps;
     // chunks_to_symbols_bc table of gr_mod_qpsk.cpp:44-54
     q.table[0] = make_float2(-0.707f, -0.707f); q.table[1] = make_float2(-0.707f, 0.707f);
     q.table[2] = make_float2(0.707f, 0.707f);   q.table[3] = make_float2(0.707f, -0.707f);
