@@ -93,8 +93,7 @@ struct qrl_amod {
         if (c1.p && ((r = c1.zero()) || (r = c2.zero()) || (r = c3.zero()))) return r;
         if (am) {
             if ((r = m1.zero()) || (r = m2.zero())) return r;
-            std::vector<float> one((size_t)cfg.batch, 1.0f);                      // agc2_ff(..., gain = 1)
-            if (hipMemcpy(am_gain.p, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+            if ((r = am_gain.fill(cfg.batch, 1.0f))) return r;                    // agc2_ff(..., gain = 1)
             n1m = 0;
         }
         n8 = n50 = ns = 0; last = 0;

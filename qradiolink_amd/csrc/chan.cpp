@@ -51,9 +51,8 @@ struct qrl_chan {
     DevBuf<float> r5, r6, symf_taps, mmse; DevBuf<SymSyncState> ss; DevBuf<uint8_t> soft_dummy; int symf_nt = 0; float ss_alpha = 0, ss_beta = 0;
     uint8_t* fsk_bits = nullptr; size_t fsk_bits_cap = 0; float* fsk_const = nullptr; size_t fsk_const_cap = 0; uint32_t* fsk_counts = nullptr;
     int init_ss() {
-        std::vector<SymSyncState> s((size_t)cfg.batch * cfg.channel_count);
-        for (auto& x : s) { std::memset(&x, 0, sizeof x); x.avg = x.inst = 5.0f; }
-        return hipMemcpy(ss.p, s.data(), s.size() * sizeof(SymSyncState), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
+        SymSyncState x; std::memset(&x, 0, sizeof x); x.avg = x.inst = 5.0f;
+        return ss.fill((size_t)cfg.batch * cfg.channel_count, x);
     }
     size_t zeroed = 0;
     ~qrl_chan() { for (auto* v : {&prof_events, &prof_tail, &prof_ss}) for (auto& e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

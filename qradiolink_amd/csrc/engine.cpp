@@ -2,129 +2,11 @@
 // as a GNU Radio flowgraph (gr_demod_base.cpp:299-828 connects rotator -> resampler -> gr_demod_X),
 // owns all device state, and exposes it through the C ABI of include/qrl_hip.h.
 // There is NO CPU fallback: without a usable HIP device qrl_init() fails.
-#include "host_common.hpp"
-#include "firdes.hpp"
-#include <algorithm>
+#include "demod.hpp"
 #include <cmath>
-#include <complex>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <memory>
 #include <new>
-#include <string>
-#include <mutex>
-#include <set>
-#include <vector>
-
-using namespace qrl;
-
-static thread_local std::string g_last_error;
-int qrl_set_error(int code, const std::string& msg) { g_last_error = msg; return code; }
-
-namespace qrl {
-static thread_local bool t_launch_error = false;
-hipError_t dyn_lds_limit(const void* kernel, int bytes)
-{
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) { t_launch_error = true; qrl_set_error(QRL_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e)); return e; }
-    std::lock_guard<std::mutex> g(mu);
-    if (done.count({kernel, dev})) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done.insert({kernel, dev});
-    else { t_launch_error = true; qrl_set_error(QRL_ERR_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e)); }
-    return e;
-}
-bool take_launch_error() { const bool r = t_launch_error; t_launch_error = false; return r; }
-int create_role_stream(hipStream_t* s, int priority, const char* role)
-{
-    const char* e = role ? std::getenv((std::string("QRL_CU_") + role).c_str()) : nullptr;
-    int first = 0, count = 0;
-    hipError_t err;
-    if (e && std::sscanf(e, "%d:%d", &first, &count) == 2 && first >= 0 && count > 0 && first + count <= 32) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // 256 CUs
-        for (int b = 8 * first; b < 8 * (first + count); ++b) mask[b >> 5] |= 1u << (b & 31);
-        err = hipExtStreamCreateWithCUMask(s, 8, mask);
-    } else {
-        err = hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority);
-    }
-    if (err != hipSuccess) { qrl_set_error(QRL_ERR_HIP, std::string("stream creation: ") + hipGetErrorString(err)); return QRL_ERR_HIP; }
-    return QRL_OK;
-}
-
-std::vector<float2> rot_fine_table(uint64_t inc)
-{
-    std::vector<float2> lo(512);
-    for (int r = 0; r < 512; ++r) { float sn, cs; sincos_turn_host((uint64_t)r * inc, sn, cs); lo[r] = make_float2(cs, sn); }
-    return lo;
-}
-int Rotator::retune(uint64_t n_now, uint64_t new_inc, hipStream_t s)
-{
-    const uint64_t delta = advance(n_now);
-    inc = new_inc;
-    if (hipMemcpy(lo.p, rot_fine_table(inc).data(), 512 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-    if (!per_stream()) return QRL_OK;
-    const int B = (int)h_inc.size();
-    launch_rot_ps_advance(acc_s.p, inc_s.p, B, delta, s);
-    launch_rot_ps_fill(acc_s.p, inc_s.p, lo_s.p, B, 0, 0, inc, lo.p, s);
-    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
-    h_inc.assign((size_t)B, inc);
-    return QRL_OK;
-}
-int Rotator::retune_streams(uint64_t n_now, const std::vector<uint64_t>& new_inc, hipStream_t s)
-{
-    const uint64_t delta = advance(n_now);
-    const int B = (int)new_inc.size();
-    if (!per_stream()) {   // first per-stream set: every stream starts where the shared NCO is (acc = its phase at the new nbase)
-        int r;
-        if ((r = acc_s.grow((size_t)B)) || (r = inc_s.grow((size_t)B)) || (r = lo_s.grow((size_t)B * 512))) return r;
-        launch_rot_ps_fill(acc_s.p, inc_s.p, lo_s.p, B, 1, acc, inc, lo.p, s);
-        h_inc.assign((size_t)B, inc);
-    } else {
-        launch_rot_ps_advance(acc_s.p, inc_s.p, B, delta, s);
-    }
-    // only the streams whose increment changes: their increments and tables, one copy per run of consecutive streams
-    std::vector<uint32_t> idx;
-    for (int b = 0; b < B; ++b) if (new_inc[(size_t)b] != h_inc[(size_t)b]) idx.push_back((uint32_t)b);
-    std::vector<uint64_t> st_inc(idx.size());
-    std::vector<float2> st_lo(idx.size() * 512);
-    for (size_t j = 0; j < idx.size(); ++j) {
-        st_inc[j] = new_inc[idx[j]];
-        const std::vector<float2> t = rot_fine_table(st_inc[j]);
-        std::copy(t.begin(), t.end(), st_lo.begin() + (ptrdiff_t)(j * 512));
-    }
-    for (size_t j0 = 0; j0 < idx.size();) {
-        size_t j1 = j0 + 1;
-        while (j1 < idx.size() && idx[j1] == idx[j1 - 1] + 1) ++j1;
-        const size_t n = j1 - j0;
-        if (hipMemcpyAsync(inc_s.p + idx[j0], st_inc.data() + j0, n * sizeof(uint64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(lo_s.p + (size_t)idx[j0] * 512, st_lo.data() + j0 * 512, n * 512 * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess)
-            return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: upload failed");
-        j0 = j1;
-    }
-    if (hipStreamSynchronize(s) != hipSuccess) return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: hipStreamSynchronize failed");
-    for (uint32_t b : idx) h_inc[b] = new_inc[b];
-    return QRL_OK;
-}
-int Rotator::reset(hipStream_t s)
-{
-    acc = 0; nbase = 0;
-    if (!per_stream()) return QRL_OK;
-    if (hipMemsetAsync(acc_s.p, 0, h_inc.size() * sizeof(uint64_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return qrl_set_error(QRL_ERR_HIP, "per-stream rotator: reset failed");
-    return QRL_OK;
-}
-int carrier_incs(const double* hz, int B, double sign, double rate, std::vector<uint64_t>& inc)
-{
-    for (int b = 0; b < B; ++b) if (!std::isfinite(hz[b])) return qrl_set_error(QRL_ERR_ARG, "carrier offsets must be finite");
-    inc.resize((size_t)B);
-    for (int b = 0; b < B; ++b) inc[(size_t)b] = phase_inc_to_turn(2 * M_PI * (sign * hz[b]) / rate);
-    return QRL_OK;
-}
-}  // namespace qrl
 
 #ifndef QRL_FEC_GATE_US
 #define QRL_FEC_GATE_US 30u   // grouped order: head start of the recursion kernel over the decoder (profiles/r04_c5_rx_timeline.log: without it the decoder takes every wave slot first)
@@ -132,233 +14,20 @@ int carrier_incs(const double* hz, int B, double sign, double rate, std::vector<
 #ifndef QRL_DEV_SKIP
 #define QRL_DEV_SKIP 0   // developer builds only (tools/engine_variants.sh): bit 0 no FLL, 1 no fused 2FSK feed-forward kernel, 2 no symbol sync, 3 no decoder launch -- WRONG results, timing experiments on who stretches the front end
 #endif
-namespace {
 
-uint64_t decim_count(uint64_t n, int I, int D) { return n ? ((n - 1) * (uint64_t)I + (uint64_t)I - 1) / (uint64_t)D + 1 : 0; }
-
-// polyphase layout for k_decim: taps[p*Jpad + j] = h[p + j*D]
-std::vector<float> decim_layout(const std::vector<float>& h, int D, int Jpad)
+int qrl_demod::flush_fec(bool behind_front_end)
 {
-    std::vector<float> t((size_t)D * Jpad, 0.0f);
-    for (size_t k = 0; k < h.size(); ++k) t[(k % D) * Jpad + k / D] = h[k];
-    return t;
+    if (!fec_deferred) return QRL_OK;
+    fec_deferred = false;
+    HIPCHK(hipStreamWaitEvent(fecs, ev_q[fec_pending_slot], 0));
+    if (behind_front_end) {   // starts with the recursion of the next call, not beside its front end -- and a moment AFTER it (k_fec_gate)
+        HIPCHK(hipStreamWaitEvent(fecs, ev_ff, 0));
+        launch_fec_gate(QRL_FEC_GATE_US, fecs);
+    }
+    launch_fec(fec_pending, cfg.batch, fecs);
+    HIPCHK(hipEventRecord(ev_fec[fec_pending_slot], fecs));
+    return QRL_OK;
 }
-std::vector<float> resamp_layout(const std::vector<float>& h, int I, int Jp)
-{
-    std::vector<float> t((size_t)I * Jp, 0.0f);
-    for (size_t k = 0; k < h.size(); ++k) t[(k % I) * Jp + k / I] = h[k];
-    return t;
-}
-std::vector<float2> to_f2(const std::vector<std::complex<float>>& v)
-{
-    std::vector<float2> r(v.size());
-    for (size_t i = 0; i < v.size(); ++i) r[i] = make_float2(v[i].real(), v[i].imag());
-    return r;
-}
-
-struct DecimStage {
-    bool used = false, mfma = false, pl = false, pm = false;
-    int D = 1, Jpad = 0, variant = DECIM_R4_J12, nt = 0, S = 0;
-    DevBuf<float> taps;
-    DevBuf<float2> edge, edge_b; uint32_t edge_len = 0;   // phase-lane kernels: per-stream scratch for the call's edge outputs (two: staged a call ahead)
-    int alloc_edge(int B, bool two = false) {
-        if (!pl && !pm) return QRL_OK;
-        edge_len = (uint32_t)(pm ? decim_pm_edge_len(nt, D) : decim_pl_edge_len(nt, D));
-        if (!edge_len) return QRL_OK;
-        if (int r = edge.alloc((size_t)B * edge_len)) return r;
-        return two ? edge_b.alloc((size_t)B * edge_len) : QRL_OK;
-    }
-    int plan(const std::vector<float>& h, int D_) {
-        used = true; D = D_; nt = (int)h.size();
-        if (decim_uses_pm(nt, D)) {   // phase-major matrix-pipe kernel (the 1:50 first stages)
-            pm = true;
-            return taps.upload(decim_pm_layout(h, D));
-        }
-        if (decim_uses_pl(nt, D)) {   // register-resident phase-lane kernel (the 100:1 front end)
-            pl = true;
-            return taps.upload(decim_pl_layout(h, D));
-        }
-        if (decim_uses_mfma(nt, D)) {
-            // zero-padded tap vector the MFMA A operands are read from: hp[k + (4S - nt + 1)] = h[k]
-            mfma = true;
-            S = decim_mfma_steps(nt, D);
-            std::vector<float> g((size_t)decim_mfma_hpn(nt, D), 0.0f);
-            for (int k = 0; k < nt; ++k) g[(size_t)k + (size_t)(4 * S - nt + 1)] = h[k];
-            return taps.upload(g);
-        }
-        const int J = (nt + D - 1) / D;
-        const size_t kLds2 = 80 * 1024;  // two workgroups per CU
-        auto pad = [&](int v) { const int jc = decim_jc(v); return (J + jc - 1) / jc * jc; };
-        variant = -1;
-        if (J <= 10 && decim_lds_bytes(D, pad(DECIM_R2_J10), DECIM_R2_J10) <= kLds2) variant = DECIM_R2_J10;
-        else if (J > 36 && J <= 44 && decim_lds_bytes(D, 44, DECIM_R4_J44) <= kLds2) variant = DECIM_R4_J44;
-        else if (decim_lds_bytes(D, pad(DECIM_R4_J12), DECIM_R4_J12) <= kLds2) variant = DECIM_R4_J12;
-        else variant = DECIM_R1_J14;
-        Jpad = pad(variant);
-        if (decim_lds_bytes(D, Jpad, variant) > 160 * 1024) return QRL_ERR_ARG;
-        return taps.upload(decim_layout(h, D, Jpad));
-    }
-    uint32_t lookback() const { return pm ? decim_pm_lookback(nt, D) : pl ? (uint32_t)(((nt + D - 1) / D + 1) * D) : mfma ? (uint32_t)(nt + D) : (uint32_t)(Jpad * D); }
-    int launch(DecimParams& p, int B, hipStream_t s, int parity = 0) const {
-        p.nt = nt;
-        float2* e = parity && edge_b.p ? edge_b.p : edge.p;
-        if (pm) { p.pl_taps = taps.p; p.pl_edge = e; p.pl_edge_stride = edge_len; p.pl_edge_cap = edge_len; return launch_decim_pm(p, B, s); }
-        if (pl) { p.pl_taps = taps.p; p.pl_edge = e; p.pl_edge_stride = edge_len; p.pl_edge_cap = edge_len; return launch_decim_pl(p, B, s); }
-        if (mfma) { p.gtab = taps.p; p.S = S; return launch_decim_mfma(p, B, s); }
-        launch_decim(p, B, variant, s);
-        return 0;
-    }
-};
-
-}  // namespace
-
-struct qrl_demod {
-    qrl_ctx* ctx = nullptr;
-    qrl_demod_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // the serial tail (symbol sync + Viterbi: a handful of waves) runs on its own stream so that it overlaps the
-    // HBM-facing kernels of the NEXT call instead of idling 250 CUs
-    hipStream_t tail = nullptr;
-    // QPSK / BPSK / 4FSK-discriminator families: the recursive chain (k_qpsk_*: latency bound, 64 streams per workgroup) runs on
-    // `tail`, the Viterbi decoder on `fecs`: call k's decoder, call k + 1's recursion and call k + 2's front end run side by side.
-    // The rings between them hold two calls; ev_q / ev_fec guard their reuse two calls later.
-    hipStream_t fecs = nullptr;
-    hipEvent_t ev_q[2] = {nullptr, nullptr}, ev_fec[2] = {nullptr, nullptr}; bool q_valid[2] = {false, false};
-    // GROUPED ORDER (gr_demod_qpsk chain whose recursion kernel has a workgroup for at least every second CU): k_qpsk_pipe4 is a serial
-    // walk, one workgroup of 6 waves and 137 KB of LDS per 64 streams.  Left to the three streams, the front end of call k + 1 (tens of
-    // thousands of small workgroups) and the decoder of call k - 1 (a wave per two trellises, for its whole run) take every LDS byte
-    // and wave slot the moment they free up, and the recursion of call k is only placed once both have drained: (front end || decoder)
-    // 2.6 ms, then the recursion alone 1.9 ms (profiles/r04_c5_rx_timeline.log).  Grouped: the front end of call k + 1 waits for the
-    // recursion of call k, and the decoder of call k - 1 is LAUNCHED with the recursion of call k (behind the same front-end event),
-    // which leaves front end alone -> recursion || decoder.  The deferred launch is flushed by everything that waits for results
-    // (qrl_demod_sync, qrl_demod_stream_wait, reset, destroy), so a caller never sees the difference.
-    bool grouped = false, grouped_capable = false, fec_deferred = false; FecParams fec_pending{}; int fec_pending_slot = 0;
-    DevBuf<uint64_t> qp_snap;   // [2][B] symbols produced up to the end of call k (slot k & 1): what that call's decoder may read
-    hipEvent_t ev_ff = nullptr, ev_tail = nullptr;
-    // HELPER STREAM of the front end (round 6): k_hist (the rotated tail of this call's IQ, kept for the next call) and k_pl_edge_stage (the
-    // next call's edge scratch: that history + the head of the next buffer) read the caller's buffers only, yet they sat between two front-end
-    // launches on the handle's stream -- 0.2 - 0.29 ms of C1's 8 ms step (profiles/r06_c1_helper_stream.log).  On `pre` they run BESIDE the
-    // front end: edge(k) behind hist(k - 1); hist(k) behind the front end of call k - 1 (the last reader of the history buffer it overwrites);
-    // the front end of call k waits for ev_pre.  The history and the edge scratch are double buffers.
-    // Only with QRL_OPT_INPUT_RESIDENT: the helpers then read a call's IQ WITHOUT waiting for what the caller queued on the handle's stream before the call.
-    hipStream_t pre = nullptr; hipEvent_t ev_pre = nullptr, ev_fe[2] = {nullptr, nullptr}; bool fe_valid[2] = {false, false}; bool pre_pending = false;
-    bool input_resident = false;
-    hipEvent_t ev_user[4] = {nullptr, nullptr, nullptr, nullptr};   // qrl_demod_stream_wait
-    bool tail_pending = false;
-    // overlapped mode (2FSK / GMSK / 4FSK families): everything behind the first decimated ring runs on the tail stream while
-    // the front end of the NEXT call already runs on the main stream; ring s2 holds two calls, ev_tail2 guards its reuse
-    bool qpsk_fll = false, fsk4_disc = false;
-    bool m17 = false;   // F_DMR family, gr_demod_m17 variant: channel filter behind the resampler (port 0), mod-M&M TED, no level control
-    DevBuf<float2> s2g, disc4_taps; DevBuf<float> sym4_taps; int disc4_nt = 0, sym4_nt = 0;   // 4FSK non-FM branch
-    bool fll_slim = false;   // QRL_OPT_FLL_SLIM: single-wave FLL workgroups (3 KB of LDS) that fit beside four front-end workgroups
-    bool d2f_capable = false, d2f = false; DevBuf<float> d2f_taps;   // 1:2 decimator + shaping filter in one kernel (k_dec2_fir)
-    bool overlap = false, overlap_capable = false; hipEvent_t ev_tail2[2] = {nullptr, nullptr}; bool tail2_valid[2] = {false, false}; uint64_t call_no = 0;
-    enum Family { F_2FSK, F_GMSK, F_QPSK, F_DMR, F_4FSK, F_BPSK, F_DSSS, F_ANALOG } fam = F_2FSK;
-    int branches = 2;
-
-    // derived chain parameters (gr_demod_2fsk.cpp:39-63, gr_demod_gmsk.cpp:39-63)
-    int fe_decim = 1, interp = 1, decim = 1, target = 0, sps_eff = 0;
-    bool fm = false;
-
-    // stage objects
-    DecimStage fe;      // gr_demod_base resampler (device rate >= 2 Msps)
-    DecimStage first;   // per-mode _resampler when interp == 1
-    // time-domain scope tap (gr_demod_base.cpp:62-63, 1115-1147, 988-1018): _demod_valve -> rational_resampler_ccf(1, 10, low_pass(1, 1e6,
-    // 50000, 25000, HAMMING)) -> gr_sample_sink; off until qrl_demod_set_time_domain_output gives it a buffer
-    DecimStage scope; DevBuf<float2> s_scope; uint32_t scope_mask = 0; uint64_t n_scope = 0; int scope_D = 10;
-    float2* scope_out = nullptr; size_t scope_cap = 0; uint32_t* scope_counts = nullptr;
-    DevBuf<float> rs_taps; int rs_Jp = 0;  // per-mode _resampler when interp > 1
-    DevBuf<float> filt_taps; int filt_nt = 0;
-    DevBuf<float> symf_taps; int symf_nt = 0;
-    DevBuf<float2> disc_up, disc_lo; int disc_nt = 0;
-    DevBuf<float> ff_tf, ff_ts; DevBuf<float2> ff_up, ff_lo;   // zero-padded copies for the fused 2FSK kernel (k_2fsk_ff)
-    DevBuf<float2> fll_lo, fll_up; float fll_alpha = 0, fll_beta = 0, fll_maxf = 0;
-    DevBuf<float> atan_tab, mmse_tab;
-    float demod_gain = 0;
-    float ss_alpha = 0, ss_beta = 0, ss_maxp = 0, ss_minp = 0;
-
-    // rotator (gr_demod_base.cpp:57,1220-1225): exact 2^-64-turn NCO
-    Rotator rot;
-
-    // rings and state
-    DevBuf<float2> hist_a, hist_b; uint32_t hist_len = 0; bool hist_flip = false;
-    DevBuf<float2> s1, s2, s2l, s2f; DevBuf<float> s2d, s3; DevBuf<uint8_t> soft;
-    uint32_t s1_mask = 0, s2_mask = 0, soft_mask = 0;
-    DevBuf<FllState> fll_st; DevBuf<SymSyncState> ss_st; DevBuf<FecState> fec_st;
-    // a37b: gr_dmr_dmo_sink behind port 3 of gr_demod_dmr (qrl_demod_set_dmo_output)
-    DevBuf<DmoState> dmo_st; DevBuf<uint32_t> dmo_golay; uint8_t* dmo_out = nullptr; uint32_t dmo_cap = 0; uint32_t* dmo_counts = nullptr;
-    // QPSK (gr_demod_qpsk.cpp:97-126)
-    DevBuf<QpskState> qp_st; DevBuf<float> tanh_tab;
-    float c1_alpha = 0, c1_beta = 0, c2_alpha = 0, c2_beta = 0; float2 qp_rot{};
-    DevBuf<uint32_t> counts_scratch;
-    // DSSS mode (gr_demod_dsss.cpp:30-111): behind the 1:50 stage (ring s2, 20 ksps) a 13/50 resampler to 5 200 samples/s, Costas,
-    // channel filter, agc2, Barker-13 matched filter (16 symbols/s), clock recovery + Costas (kernels_dsss.hip)
-    DevBuf<float> ds_rs, ds_filt, ds_mf; int ds_Jp = 0, ds_nf = 0;
-    DevBuf<float2> ds_ra, ds_rb, ds_rc, ds_rd, ds_sym; uint32_t ds_mask = 0, ds_sym_mask = 0;
-    DevBuf<DsssState> ds_st; DevBuf<DsssTailState> ds_tail;
-    float ds_a1 = 0, ds_b1 = 0, ds_a2 = 0, ds_b2 = 0;
-    uint64_t n5 = 0, nsy = 0;   // items so far at 5 200 samples/s, matched-filter outputs so far
-    int dsss_stages(uint64_t n2_0, uint64_t n2_1, const qrl_demod_out* out, uint32_t* counts, bool side);
-    // analogue voice receivers (gr_demod_nbfm / gr_demod_am / gr_demod_wbfm): kernels_analog.hip
-    int an_kind = 0; bool an_lsb = false;                        // 0 NBFM, 1 AM, 2 WBFM, 3 SSB (an_lsb: lower sideband)
-    DevBuf<float2> an_c1;                                        // SSB: clipped complex items behind the gate
-    DevBuf<float2> an_filt_c; int an_nfc = 0;                    // AM channel filter (complex taps)
-    DevBuf<float> an_env, an_rtaps, an_ftaps; int an_ramp = 0, an_nr = 0, an_nf = 0, an_I = 2, an_D = 5;
-    DevBuf<float> an_f1, an_f2, an_f3; uint32_t an_m1 = 0, an_m2 = 0;
-    DevBuf<AnState> an_st;
-    // gr_demod_nbfm::set_ctcss: ctcss_squelch_ff between audio resampler and audio filter, band-pass audio filter while it is on
-    float ctcss_tone = 0.0f; DevBuf<CtcssState> an_cs; DevBuf<float> an_f4, an_ftaps_ct; DevBuf<double> an_env_ct; int an_nf_ct = 0;
-    float ct_wr[3] = {0, 0, 0}, ct_wi[3] = {0, 0, 0};
-    double an_threshold = 1e-14, an_ff[2] = {0, 0}, an_fb1 = 0, an_de_ff[2] = {0, 0}, an_de_fb1 = 0;
-    float an_gain = 1.f, an_attack = 0.1f, an_decay = 0.1f;
-    int analog_stages(uint64_t n2_0, uint64_t n2_1, const qrl_demod_out* out, uint32_t* counts, bool side);
-    float an_if_gain = 0.9f;
-    uint64_t n_in = 0, n1 = 0, n2 = 0;  // items so far: device rate, 1 Msps, target rate
-    bool profiling = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-
-    ~qrl_demod() {
-        for (auto& e : prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        if (ev_ff) (void)hipEventDestroy(ev_ff);
-        if (ev_tail) (void)hipEventDestroy(ev_tail);
-        for (auto e : ev_user) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_tail2) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_q) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_fec) if (e) (void)hipEventDestroy(e);
-        if (ev_pre) (void)hipEventDestroy(ev_pre);
-        for (auto e : ev_fe) if (e) (void)hipEventDestroy(e);
-        if (pre) (void)hipStreamDestroy(pre);
-        if (fecs) (void)hipStreamDestroy(fecs);
-        if (tail) (void)hipStreamDestroy(tail);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
-
-    int flush_fec(bool behind_front_end) {
-        if (!fec_deferred) return QRL_OK;
-        fec_deferred = false;
-        HIPCHK(hipStreamWaitEvent(fecs, ev_q[fec_pending_slot], 0));
-        if (behind_front_end) {   // starts with the recursion of the next call, not beside its front end -- and a moment AFTER it (k_fec_gate)
-            HIPCHK(hipStreamWaitEvent(fecs, ev_ff, 0));
-            launch_fec_gate(QRL_FEC_GATE_US, fecs);
-        }
-        launch_fec(fec_pending, cfg.batch, fecs);
-        HIPCHK(hipEventRecord(ev_fec[fec_pending_slot], fecs));
-        return QRL_OK;
-    }
-    int sync_all() {
-        if (int r = flush_fec(false)) return r;
-        HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipStreamSynchronize(tail));
-        HIPCHK(hipStreamSynchronize(fecs));
-        if (pre) HIPCHK(hipStreamSynchronize(pre));
-        return QRL_OK;
-    }
-    bool loops_family() const { return fam == F_QPSK || fam == F_BPSK || fsk4_disc; }
-    int init_state();
-    int build();
-    int process(const float* iq, size_t stride, size_t n, const qrl_demod_out* out);
-};
 
 int qrl_demod::init_state()
 {
@@ -369,46 +38,16 @@ int qrl_demod::init_state()
     n_scope = 0;
     if ((r = soft.zero())) return r;
     if (fll_st.p && (r = fll_st.zero())) return r;
-    if (fam == F_QPSK || fam == F_BPSK || fsk4_disc) {
-        std::vector<QpskState> qs(cfg.batch);
-        for (auto& q : qs) { std::memset(&q, 0, sizeof q); q.gain = 1.0f; q.avg = q.inst = (float)sps_eff;
-                             if (fam == F_BPSK) q.mu = 0.5f; }   // clock_recovery_mm_cc(mu = 0.5), gr_demod_bpsk.cpp:58-60
-        if (hipMemcpy(qp_st.p, qs.data(), qs.size() * sizeof(QpskState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+    if (loops_family()) {
+        QpskState q; std::memset(&q, 0, sizeof q); q.gain = 1.0f; q.avg = q.inst = (float)sps_eff; q.mu = fam == F_BPSK ? 0.5f : 0.0f;   // BPSK: clock_recovery_mm_cc(mu = 0.5), gr_demod_bpsk.cpp:58-60
+        if ((r = qp_st.fill(cfg.batch, q))) return r;
     }
-    if (dmo_st.p) {
-        std::vector<DmoState> ds(cfg.batch);
-        for (auto& x : ds) { std::memset(&x, 0, sizeof x); x.endPtr = 9999; }
-        if (hipMemcpy(dmo_st.p, ds.data(), ds.size() * sizeof(DmoState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-    }
-    std::vector<SymSyncState> ss(cfg.batch);
-    for (auto& s : ss) { std::memset(&s, 0, sizeof s); s.avg = s.inst = (float)sps_eff; }
-    if (hipMemcpy(ss_st.p, ss.data(), ss.size() * sizeof(SymSyncState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-    std::vector<FecState> fs((size_t)cfg.batch * 2);
-    for (auto& f : fs) { f.consumed = 0; f.start_state = 0; f.last_bits = 0xFE; }  // descrambler seed 0x7F, newest bit first
-    if (hipMemcpy(fec_st.p, fs.data(), fs.size() * sizeof(FecState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+    if (dmo_st.p && (r = init_dmo_state())) return r;
+    SymSyncState ss; std::memset(&ss, 0, sizeof ss); ss.avg = ss.inst = (float)sps_eff;
+    FecState fs; std::memset(&fs, 0, sizeof fs); fs.last_bits = 0xFE;   // descrambler seed 0x7F, newest bit first
+    if ((r = ss_st.fill(cfg.batch, ss)) || (r = fec_st.fill((size_t)cfg.batch * 2, fs))) return r;
     if (qp_snap.p && (r = qp_snap.zero())) return r;
-    if (fam == F_DSSS) {
-        for (auto* b : {&ds_ra, &ds_rb, &ds_rc, &ds_rd, &ds_sym}) if ((r = b->zero())) return r;
-        std::vector<DsssState> ds(cfg.batch);
-        for (auto& x : ds) { x.phase = 0.f; x.freq = 0.f; x.gain = 10.0f; x.pad = 0.f; }   // agc2_cc(0.1, 0.1, 1, 10), gr_demod_dsss.cpp:61
-        if (hipMemcpy(ds_st.p, ds.data(), ds.size() * sizeof(DsssState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        std::vector<DsssTailState> dt(cfg.batch);
-        for (auto& x : dt) { std::memset(&x, 0, sizeof x); x.mu = 0.5f; x.omega = 1.0f; }   // clock_recovery_mm_cc(1, ., 0.5, ., .), :69-70
-        if (hipMemcpy(ds_tail.p, dt.data(), dt.size() * sizeof(DsssTailState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        n5 = nsy = 0;
-    }
-    if (fam == F_ANALOG) {
-        for (auto* b : {&an_f1, &an_f2, &an_f3, &an_f4}) if (b->p && (r = b->zero())) return r;
-        if (an_cs.p) {   // squelch_base: muted, envelope 0 (ramp 160); the Goertzel filters empty
-            std::vector<CtcssState> cs(cfg.batch);
-            for (auto& x : cs) { std::memset(&x, 0, sizeof x); x.mute = 1; x.env = 0.0; }
-            if (hipMemcpy(an_cs.p, cs.data(), cs.size() * sizeof(CtcssState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-        }
-        if (an_c1.p && (r = an_c1.zero())) return r;
-        std::vector<AnState> as(cfg.batch);
-        for (auto& x : as) { std::memset(&x, 0, sizeof x); x.env = an_ramp ? 0.0f : 1.0f; x.gain = 1.0f; }   // agc2_ff(0.1, 0.1, 1, 1), gr_demod_am.cpp:48
-        if (hipMemcpy(an_st.p, as.data(), as.size() * sizeof(AnState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-    }
+    if ((fam == F_DSSS && (r = ds.init_state(*this))) || (fam == F_ANALOG && (r = an.init_state(*this)))) return r;
     q_valid[0] = q_valid[1] = false; tail2_valid[0] = tail2_valid[1] = false; tail_pending = false; call_no = 0;
     fe_valid[0] = fe_valid[1] = false; pre_pending = false;
     fec_deferred = false;
@@ -445,14 +84,14 @@ int qrl_demod::build()
         else return qrl_set_error(QRL_ERR_ARG, "4fsk: unsupported sps");
         branches = 1;
     } else if (fam == F_DSSS) {
-        // gr_demod_dsss.cpp:37-59: 1:50 to 20 ksps (this stage), then 13/50 to 5 200 samples/s (dsss_stages); sps = samples per chip
+        // gr_demod_dsss.cpp:37-59: 1:50 to 20 ksps (this stage), then 13/50 to 5 200 samples/s (ds.stages); sps = samples per chip
         if (sps != 25) return qrl_set_error(QRL_ERR_ARG, "dsss: sps must be 25 (make_gr_demod_dsss(25, ...), gr_demod_base.cpp:218)");
         target = 20000; sps_eff = 10; decim = 50; interp = 1;
     } else if (fam == F_ANALOG) {
         // gr_demod_nbfm.cpp:39,50 / gr_demod_am.cpp:36,44: 1:50 to 20 ksps; gr_demod_wbfm.cpp:37,49: 1:5 to 200 ksps (sps is unused there)
         // gr_demod_ssb.cpp:35,41-43: 1:sps (125) to 8 ksps
-        target = an_kind == 2 ? 200000 : an_kind == 3 ? 8000 : 20000; decim = an_kind == 2 ? 5 : an_kind == 3 ? 125 : 50; interp = 1; sps_eff = 10; branches = 1;
-        if (an_kind == 3 && sps != 125) return qrl_set_error(QRL_ERR_ARG, "ssb: sps must be 125 (make_gr_demod_ssb(125, ...), gr_demod_base.cpp:226-227)");
+        target = an.kind == 2 ? 200000 : an.kind == 3 ? 8000 : 20000; decim = an.kind == 2 ? 5 : an.kind == 3 ? 125 : 50; interp = 1; sps_eff = 10; branches = 1;
+        if (an.kind == 3 && sps != 125) return qrl_set_error(QRL_ERR_ARG, "ssb: sps must be 125 (make_gr_demod_ssb(125, ...), gr_demod_base.cpp:226-227)");
     } else if (fam == F_BPSK) {
         // gr_demod_bpsk.cpp:40-52: 1:50 to 20 ksps, sps samples per symbol
         if (sps != 10 && sps != 5) return qrl_set_error(QRL_ERR_ARG, "bpsk: sps must be 10 (BPSK1K) or 5 (BPSK2K)");
@@ -469,7 +108,6 @@ int qrl_demod::build()
     }
     fm = cfg.fm != 0;
     const int B = cfg.batch;
-    const size_t maxn = cfg.max_chunk;
 
     // --- front end (gr_demod_base.cpp:1317-1340)
     fe_decim = 1;
@@ -522,12 +160,10 @@ int qrl_demod::build()
     if ((r = hist_a.alloc((size_t)B * hist_len)) || (r = hist_b.alloc((size_t)B * hist_len))) return r;
 
     // --- rings
-    const size_t max1 = fe.used ? maxn / fe_decim + 2 : 0;           // 1 Msps items per call
-    const size_t in2 = fe.used ? max1 : maxn;                        // items entering the mode resampler per call
-    const size_t max2 = in2 * interp / decim + 2;                    // target-rate items per call
+    const CallCounts mx = call_counts(cfg.max_chunk);   // per call: 1 Msps items (behind the front end, else the caller's), target-rate items, symbols
     if (fe.used) {
         const size_t look = std::max<size_t>(interp == 1 ? first_look : (size_t)(rs_Jp + decim + 2), scope.lookback());
-        s1_mask = pow2_at_least(max1 + look + 64, 64) - 1;
+        s1_mask = pow2_at_least(mx.n1 + look + 64, 64) - 1;
         if ((r = s1.alloc((size_t)B * (s1_mask + 1)))) return r;
     }
     // default: only the 2FSK family, whose FLL + discriminator kernels are a third of a call (measured, C1: 15.2 -> 12.9 ms per
@@ -543,12 +179,11 @@ int qrl_demod::build()
         grouped = grouped_capable && 2 * ((B + 63) / 64) >= cus;   // (below that the recursion's workgroups leave CUs free: the front end of the next call belongs beside it -- C3)
     }
     overlap = overlap_capable;   // round 3: ON by default for the 2FSK family (same-box A/B on C1: 8.79 against 9.49 ms per step); qrl_demod_set_option(QRL_OPT_OVERLAP, 0) gives the serial order
-    s2_mask = pow2_at_least((overlap_capable || loops_family() ? 2 : 1) * max2 + (fam == F_DMR ? 2048 : fam == F_ANALOG ? 4096 : 1024), 64) - 1;   // DMR: the DMO slicer looks back 1440 samples   // history needs: <= 501 taps downstream; overlapped mode: two calls
+    s2_mask = pow2_at_least((overlap_capable || loops_family() ? 2 : 1) * mx.n2 + (fam == F_DMR ? 2048 : fam == F_ANALOG ? 4096 : 1024), 64) - 1;   // DMR: the DMO slicer looks back 1440 samples   // history needs: <= 501 taps downstream; overlapped mode: two calls
     const size_t ring2 = (size_t)B * (s2_mask + 1);
     if ((r = s2.alloc(ring2)) || (r = s2f.alloc(ring2)) || (r = s2d.alloc(ring2)) || (r = s3.alloc(ring2))) return r;
     if ((fam == F_2FSK || fam == F_BPSK || (fam == F_QPSK && qpsk_fll)) && (r = s2l.alloc(ring2))) return r;
-    const size_t maxsym = max2 / (size_t)(sps_eff > 1 ? sps_eff - 1 : 1) + 8;
-    soft_mask = pow2_at_least((loops_family() ? 2 : 1) * (fam == F_QPSK || fam == F_4FSK ? 2 : 1) * maxsym + 512, 64) - 1;   // loops families: two calls (decoder of call k beside the recursion of call k + 1)
+    soft_mask = pow2_at_least((loops_family() ? 2 : 1) * (fam == F_QPSK || fam == F_4FSK ? 2 : 1) * mx.nsym + 512, 64) - 1;   // loops families: two calls (decoder of call k beside the recursion of call k + 1)
     if ((r = soft.alloc((size_t)B * (soft_mask + 1)))) return r;
 
     // --- decimated-rate filters
@@ -560,8 +195,8 @@ int qrl_demod::build()
             : fam == F_4FSK
             ? low_pass(1, target, fw, fw / 2, WIN_BLACKMAN_HARRIS)             // _filter, gr_demod_4fsk.cpp:108-109
             : fam == F_ANALOG
-            ? (an_kind == 2 ? low_pass_2(1, target, fw, 600, 90, WIN_BLACKMAN_HARRIS)      // gr_demod_wbfm.cpp:52-53
-                            : low_pass_2(1, target, fw, 3500, 60, WIN_BLACKMAN_HARRIS))    // gr_demod_nbfm.cpp:53-54 (AM: an_filt_c)
+            ? (an.kind == 2 ? low_pass_2(1, target, fw, 600, 90, WIN_BLACKMAN_HARRIS)      // gr_demod_wbfm.cpp:52-53
+                            : low_pass_2(1, target, fw, 3500, 60, WIN_BLACKMAN_HARRIS))    // gr_demod_nbfm.cpp:53-54 (AM: an.filt_c)
             : low_pass(1, target, fw, fw, WIN_BLACKMAN_HARRIS);
         filt_nt = (int)f.size();
         if ((r = filt_taps.upload(f))) return r;
@@ -684,62 +319,7 @@ int qrl_demod::build()
     }
     if ((r = ss_st.alloc(B)) || (r = fec_st.alloc((size_t)B * 2)) || (r = counts_scratch.alloc((size_t)B * 4))) return r;
     if (loops_family() && (r = qp_snap.alloc((size_t)B * 2))) return r;
-    if (fam == F_ANALOG) {
-        std::vector<float> rt, ft;
-        double a[2], b[2];
-        if (an_kind == 0) {          // gr_demod_nbfm.cpp:43-64
-            an_ramp = 320; an_I = 2; an_D = 5;
-            rt = low_pass_2(2, 2 * target, 3600, 250, 60, WIN_BLACKMAN_HARRIS);
-            ft = low_pass_2(1, 8000, 3500, 200, 35, WIN_BLACKMAN_HARRIS);
-            an_gain = (float)(target / (4 * M_PI * fw));
-            deemph_taps(target, 50e-6, a, b);
-            an_de_ff[0] = b[0]; an_de_ff[1] = b[1]; an_de_fb1 = -a[1];            // iir_filter_ffd(btaps, ataps, oldstyle = false)
-        } else if (an_kind == 1) {   // gr_demod_am.cpp:40-61
-            an_ramp = 0; an_I = 2; an_D = 5;
-            rt = low_pass(2, 2 * target, 3600, 600, WIN_BLACKMAN_HARRIS);
-            ft = low_pass(1, 8000, 3600, 300, WIN_BLACKMAN_HARRIS);
-            const auto fc = complex_band_pass_2(1, target, -fw, fw, 200, 90, WIN_BLACKMAN_HARRIS);
-            an_nfc = (int)fc.size();
-            if ((r = an_filt_c.upload(to_f2(fc)))) return r;
-            an_ff[0] = 1; an_ff[1] = -1; an_fb1 = 0.9999;                          // iir_filter_ffd({1, -1}, {0, 0.9999}), old style
-        } else if (an_kind == 3) {   // gr_demod_ssb.cpp:41-58
-            an_ramp = 0; an_I = 0; an_D = 1;                                       // I = 0: the stretcher's chunked output count
-            ft = band_pass_2(1, target, 200, fw, 200, 90, WIN_BLACKMAN_HARRIS);
-            const auto fc = an_lsb ? complex_band_pass_2(1, target, -fw, -200, 200, 90, WIN_BLACKMAN_HARRIS)
-                                   : complex_band_pass_2(1, target, 200, fw, 200, 90, WIN_BLACKMAN_HARRIS);
-            an_nfc = (int)fc.size();
-            if ((r = an_filt_c.upload(to_f2(fc)))) return r;
-        } else {                     // gr_demod_wbfm.cpp:41-57
-            an_ramp = 0; an_I = 1; an_D = 25;
-            rt = low_pass(1, target, 4000, 2000, WIN_BLACKMAN_HARRIS);
-            an_gain = (float)(target / (2 * M_PI * fw));
-            deemph_taps(8000, 50e-6, a, b);
-            an_ff[0] = b[0]; an_ff[1] = b[1]; an_fb1 = -a[1];
-        }
-        an_nr = (int)rt.size(); an_nf = (int)ft.size();
-        if ((an_nr && (r = an_rtaps.upload(rt))) || (an_nf && (r = an_ftaps.upload(ft))) || (r = an_env.upload(squelch_envelope(an_ramp)))) return r;
-        an_m1 = pow2_at_least(max2 + 2048, 64) - 1;                              // the audio resampler looks <= 419 gated items back, the stretcher <= 1025
-        an_m2 = an_kind == 3 ? an_m1 : pow2_at_least(max2 * an_I / an_D + 512, 64) - 1;
-        if (an_kind == 3) { if ((r = an_c1.alloc((size_t)B * (an_m1 + 1)))) return r; }
-        else if ((r = an_f1.alloc((size_t)B * (an_m1 + 1)))) return r;
-        if ((r = an_f2.alloc((size_t)B * (an_m2 + 1))) || ((an_kind == 0 || an_kind == 1) && (r = an_f3.alloc((size_t)B * (an_m2 + 1)))) || (r = an_st.alloc(B))) return r;
-    }
-    if (fam == F_DSSS) {
-        const std::vector<float> ti = low_pass(1, target, 2600, 2600, WIN_BLACKMAN_HARRIS);              // _resampler_if (13, 50), gr_demod_dsss.cpp:57-59
-        ds_Jp = ((int)ti.size() + 12) / 13;
-        const std::vector<float> tf = low_pass(1, 5200, fw, 1200, WIN_BLACKMAN_HARRIS);                 // _filter, :62-63
-        ds_nf = (int)tf.size();
-        if ((r = ds_rs.upload(resamp_layout(ti, 13, ds_Jp))) || (r = ds_filt.upload(tf)) || (r = ds_mf.upload(dsss_matched_filter(sps)))) return r;
-        if (!tanh_tab.p && (r = tanh_tab.upload(tanh_table()))) return r;
-        control_loop_gains((float)(M_PI / 200), ds_a1, ds_b1);                                          // _costas_freq, :64
-        control_loop_gains((float)(2 * M_PI / 100), ds_a2, ds_b2);                                      // _costas_loop, :63
-        const size_t max5 = max2 * 13 / 50 + 2;
-        ds_mask = pow2_at_least(max5 + 2048, 64) - 1;                                                   // the matched filter looks 2 x 325 + 600 items back
-        ds_sym_mask = pow2_at_least(max5 / 325 + 64, 64) - 1;
-        const size_t r5 = (size_t)B * (ds_mask + 1);
-        if ((r = ds_ra.alloc(r5)) || (r = ds_rb.alloc(r5)) || (r = ds_rc.alloc(r5)) || (r = ds_rd.alloc(r5)) ||
-            (r = ds_sym.alloc((size_t)B * (ds_sym_mask + 1))) || (r = ds_st.alloc(B)) || (r = ds_tail.alloc(B))) return r;
-    }
+    if ((fam == F_ANALOG && (r = an.build(*this, mx.n2))) || (fam == F_DSSS && (r = ds.build(*this, mx.n2)))) return r;
     return init_state();
 }
 
@@ -764,11 +344,12 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     const bool use_pre = pre && input_resident;
     const float2* in = reinterpret_cast<const float2*>(iq);
     const float2* hist_old = hist_flip ? hist_b.p : hist_a.p;
+    const PortC fport = filtered_port(out), cport = constellation_port(out);
     float2* hist_new = hist_flip ? hist_a.p : hist_b.p;
 
     const uint64_t n_in0 = n_in, n_in1 = n_in + n;
     uint64_t n1_0 = n1, n1_1 = n1;
-    RingC r1{s1.p, s1_mask}, r2{s2.p, s2_mask}, r2l{s2l.p, s2_mask}, r2f{s2f.p, s2_mask};
+    RingC r2{s2.p, s2_mask}, r2l{s2l.p, s2_mask}, r2f{s2f.p, s2_mask};
     RingF r2d{s2d.p, s2_mask}, r3{s3.p, s2_mask};
 
     // the HBM-facing kernel is the first launch that reads the caller's IQ
@@ -783,7 +364,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         DecimParams p{};
         p.in = in; p.in_stride = stride; p.n0 = n_in0; p.n = (uint32_t)n;
         p.hist = hist_old; p.hist_len = hist_len;
-        p.out = r1; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
+        p.out = RingC{s1.p, s1_mask}; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
         p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.Jpad;
         p.rot_enable = 1; rot.fill(p);
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
@@ -795,19 +376,13 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     const uint64_t n2_0 = n2, n2_1 = decim_count(src1, interp, decim);
     if (interp == 1) {
         DecimParams p{};
-        if (fe.used) { p.in = nullptr; p.in_ring = r1; }
-        else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; rot.fill(p); }
-        p.n0 = src0; p.n = (uint32_t)(src1 - src0);
+        input_source(p, in, stride, hist_old, src0, src1);
         p.out = r2; p.m0 = n2_0; p.m_count = (uint32_t)(n2_1 - n2_0);
         p.taps = first.taps.p; p.D = first.D; p.Jpad = first.Jpad;
         if (d2f) {   // + _shaping_filter -> port 0 and the filtered ring, in the same kernel
-            const bool sd = cfg.enable_side_outputs && out;
             Dec2FirParams f{};
             f.d = p; f.taps = d2f_taps.p; f.out = RingC{s2f.p, s2_mask};
-            f.port = sd && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-            f.port_cap = sd ? out->filtered_cap : 0;
-            f.counts = counts;
+            f.port = fport.p; f.port_cap = fport.cap; f.counts = counts;
             launch_dec2_fir(f, B, stream);
         } else {
             if (use_pre && !fe.used) { p.pre_stream = pre; p.pre_event = ev_pre; }   // (device rate 1 Msps: this stage is the one that reads the caller's IQ)
@@ -815,17 +390,11 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         }
     } else {
         ResampParams p{};
-        if (fe.used) { p.in = nullptr; p.in_ring = r1; }
-        else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; rot.fill(p); }
-        p.n0 = src0; p.n = (uint32_t)(src1 - src0);
+        input_source(p, in, stride, hist_old, src0, src1);
         p.out = r2; p.q0 = n2_0; p.q_count = (uint32_t)(n2_1 - n2_0);
         p.taps = rs_taps.p; p.I = interp; p.D = decim; p.Jp = rs_Jp;
         if (fam == F_DMR && !m17) {   // port 0 of gr_demod_dmr is the resampler output (gr_demod_dmr.cpp:89)
-            const bool sd = cfg.enable_side_outputs && out;
-            p.port = sd && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-            p.port_cap = sd ? out->filtered_cap : 0;
-            p.port_counts = counts;
+            p.port = fport.p; p.port_cap = fport.cap; p.port_counts = counts;
         }
         launch_resamp(p, B, stream);
     }
@@ -834,10 +403,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     if (scope_out) {
         const uint64_t ns_1 = decim_count(src1, 1, scope_D);
         DecimParams p{};
-        if (fe.used) { p.in = nullptr; p.in_ring = r1; }
-        else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len;
-               p.rot_enable = 1; rot.fill(p); }
-        p.n0 = src0; p.n = (uint32_t)(src1 - src0);
+        input_source(p, in, stride, hist_old, src0, src1);
         p.out = RingC{s_scope.p, scope_mask}; p.m0 = n_scope; p.m_count = (uint32_t)(ns_1 - n_scope);
         p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.Jpad;
         if (scope.launch(p, B, stream)) return qrl_set_error(QRL_ERR_HIP, "scope launch: hipFuncSetAttribute failed");
@@ -866,9 +432,8 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     }
     // ---- stage C: decimated-rate feed-forward (+ FLL for 2FSK)
     const uint32_t c2 = (uint32_t)(n2_1 - n2_0);
-    const bool side = cfg.enable_side_outputs && out;
     if (fam == F_DSSS || fam == F_ANALOG) {
-        if (int rr = fam == F_DSSS ? dsss_stages(n2_0, n2_1, out, counts, side) : analog_stages(n2_0, n2_1, out, counts, side)) return rr;
+        if (int rr = fam == F_DSSS ? ds.stages(*this, n2_0, n2_1, out, counts) : an.stages(*this, n2_0, n2_1, out, counts)) return rr;
         HIPCHK(hipGetLastError());
         if (take_launch_error()) return QRL_ERR_HIP;
         n_in = n_in1; n1 = n1_1; n2 = n2_1; ++call_no;
@@ -891,9 +456,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         if (m17) {   // gr_demod_m17.cpp:60-61,89-90: channel filter behind the resampler, its output is port 0
             FirCcfParams f{};
             f.in = r2; f.out = r2f; f.q0 = n2_0; f.count = c2; f.taps = filt_taps.p; f.nt = filt_nt;
-            f.port = side && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-            f.port_cap = side ? out->filtered_cap : 0;
-            f.counts = counts;
+            f.port = fport.p; f.port_cap = fport.cap; f.counts = counts;
             launch_fir_ccf(f, B, cs);
             dem_in = r2f;
         }
@@ -909,18 +472,14 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         f.in = filt_in; f.out = r3; f.q0 = n2_0; f.count = c2;
         f.tf = ff_tf.p; f.nf = fsk2_ff_padded(filt_nt); f.up = ff_up.p; f.lo = ff_lo.p; f.nb = fsk2_ff_padded(disc_nt);
         f.ts = ff_ts.p; f.ns = fsk2_ff_padded(symf_nt);
-        f.port = side && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-        f.port_cap = side ? out->filtered_cap : 0;
-        f.counts = counts;
+        f.port = fport.p; f.port_cap = fport.cap; f.counts = counts;
         if (!(QRL_DEV_SKIP & 2)) launch_2fsk_ff(f, B, cs);
         if (!overlap) { HIPCHK(hipEventRecord(ev_ff, stream)); HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0)); }
     } else {
         if (!d2f) {
             FirCcfParams f{};
             f.in = filt_in; f.out = r2f; f.q0 = n2_0; f.count = c2; f.taps = filt_taps.p; f.nt = filt_nt;
-            f.port = side && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-            f.port_cap = side ? out->filtered_cap : 0;
-            f.counts = counts;
+            f.port = fport.p; f.port_cap = fport.cap; f.counts = counts;
             launch_fir_ccf(f, B, cs);
         }
         if (fam == F_QPSK || fam == F_BPSK) {
@@ -963,9 +522,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
             q.cr_gain_omega = gain_omega * gain_omega; q.cr_gain_mu = 0.05f;
             q.cr_omega_mid = (float)sps_eff; q.cr_omega_lim = 0.001f * (float)sps_eff;
         }
-        q.port = side && out->constellation ? reinterpret_cast<float2*>(out->constellation) : nullptr;
-        q.port_cap = side ? out->constellation_cap : 0;
-        q.counts = counts;
+        q.port = cport.p; q.port_cap = cport.cap; q.counts = counts;
         q.oo_snap = qp_snap.p + (size_t)slot * B;
         // recursion on `tail` behind this call's feed-forward kernels, decoder on `fecs` behind the recursion
         HIPCHK(hipEventRecord(ev_ff, stream));
@@ -999,9 +556,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         s.slim = overlap ? 1 : 0;
         s.slicer = fam == F_DMR || fam == F_4FSK ? 1 : 0; s.tail = fam == F_DMR ? 1 : fam == F_4FSK ? 2 : 0;
         s.bits = out ? out->bits_a : nullptr; s.bits_cap = out ? out->bits_cap : 0;
-        s.port = side && out->constellation ? reinterpret_cast<float2*>(out->constellation) : nullptr;
-        s.port_cap = side ? out->constellation_cap : 0;
-        s.counts = counts;
+        s.port = cport.p; s.port_cap = cport.cap; s.counts = counts;
         if (!(QRL_DEV_SKIP & 4)) launch_symsync_ff(s, B, tail);
         if (fam == F_DMR && !m17 && dmo_out) {   // gr_dmr_dmo_sink on port 3 (= ring r3) of this call
             DmoParams dp{}; dp.in = r3; dp.q0 = n2_0; dp.count = (uint32_t)(n2_1 - n2_0); dp.st = dmo_st.p; dp.golay = dmo_golay.p;
@@ -1026,146 +581,46 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     return QRL_OK;
 }
 
-// everything of gr_demod_dsss behind the 1:50 stage (gr_demod_dsss.cpp:57-111); all on the handle's main stream
-int qrl_demod::dsss_stages(uint64_t n2_0, uint64_t n2_1, const qrl_demod_out* out, uint32_t* counts, bool side)
-{
-    const int B = cfg.batch;
-    RingC r2{s2.p, s2_mask}, ra{ds_ra.p, ds_mask}, rb{ds_rb.p, ds_mask}, rc{ds_rc.p, ds_mask}, rd{ds_rd.p, ds_mask}, rs{ds_sym.p, ds_sym_mask};
-    const uint64_t n5_0 = n5, n5_1 = decim_count(n2_1, 13, 50);
-    const uint32_t c5 = (uint32_t)(n5_1 - n5_0);
-    {   // _resampler_if: rational_resampler_ccf(13, 50)
-        ResampParams p{};
-        p.in = nullptr; p.in_ring = r2; p.n0 = n2_0; p.n = (uint32_t)(n2_1 - n2_0);
-        p.out = ra; p.q0 = n5_0; p.q_count = c5;
-        p.taps = ds_rs.p; p.I = 13; p.D = 50; p.Jp = ds_Jp;
-        launch_resamp(p, B, stream);
-    }
-    {   // _costas_freq
-        DsssLoopParams p{}; p.in = ra; p.out = rb; p.q0 = n5_0; p.count = c5; p.st = ds_st.p; p.tanh_tab = tanh_tab.p; p.alpha = ds_a1; p.beta = ds_b1;
-        launch_dsss_loop(p, 0, B, stream);
-    }
-    {   // _filter -> port 0
-        FirCcfParams f{};
-        f.in = rb; f.out = rc; f.q0 = n5_0; f.count = c5; f.taps = ds_filt.p; f.nt = ds_nf;
-        f.port = side && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-        f.port_cap = side ? out->filtered_cap : 0;
-        f.counts = counts;
-        launch_fir_ccf(f, B, stream);
-    }
-    {   // _agc
-        DsssLoopParams p{}; p.in = rc; p.out = rd; p.q0 = n5_0; p.count = c5; p.st = ds_st.p; p.tanh_tab = tanh_tab.p;
-        launch_dsss_loop(p, 1, B, stream);
-    }
-    // _dsss_decoder: output I needs x[325 (I - 1) + 599]
-    const uint64_t nsy_1 = n5_1 >= 275 ? (n5_1 - 275) / 325 + 1 : 0;
-    {
-        DsssMfParams p{}; p.in = rd; p.out = rs; p.i0 = nsy; p.count = (uint32_t)(nsy_1 - nsy); p.taps = ds_mf.p;
-        launch_dsss_mf(p, B, stream);
-    }
-    {   // _clock_recovery -> _costas_loop (port 1) -> soft symbols
-        DsssTailParams p{};
-        p.in = rs; p.avail = nsy_1; p.soft = RingB{soft.p, soft_mask}; p.st = ds_tail.p; p.mmse = mmse_tab.p;
-        const float gain_omega = 0.005f;
-        p.gain_omega = gain_omega * gain_omega; p.gain_mu = 0.05f; p.omega_mid = 1.0f; p.omega_lim = 0.005f * 1.0f;
-        p.alpha = ds_a2; p.beta = ds_b2;
-        p.port = side && out->constellation ? reinterpret_cast<float2*>(out->constellation) : nullptr;
-        p.port_cap = side ? out->constellation_cap : 0;
-        p.counts = counts;
-        launch_dsss_tail(p, B, stream);
-    }
-    FecParams f{};
-    f.soft = RingB{soft.p, soft_mask};
-    f.avail = &ds_tail.p[0].oo; f.avail_stride = sizeof(DsssTailState); f.avail_mul = 1;
-    f.st = fec_st.p;
-    f.bits_a = out ? out->bits_a : nullptr; f.bits_b = out ? out->bits_b : nullptr; f.bits_cap = out ? out->bits_cap : 0;
-    f.counts = counts; f.branches = 2;
-    launch_fec(f, B, stream);
-    n5 = n5_1; nsy = nsy_1;
-    return QRL_OK;
-}
-
-// everything of gr_demod_nbfm / gr_demod_am / gr_demod_wbfm behind the first resampler; all on the handle's main stream
-int qrl_demod::analog_stages(uint64_t n2_0, uint64_t n2_1, const qrl_demod_out* out, uint32_t* counts, bool side)
-{
-    const int B = cfg.batch;
-    RingC r2{s2.p, s2_mask}, r2f{s2f.p, s2_mask};
-    const uint32_t c2 = (uint32_t)(n2_1 - n2_0);
-    float2* fport = side && out->filtered ? reinterpret_cast<float2*>(out->filtered) : nullptr;
-    const size_t fcap = side ? out->filtered_cap : 0;
-    if (an_kind == 3) launch_scale_c(r2, n2_0, c2, an_if_gain, B, stream);   // _if_gain, gr_demod_ssb.cpp:45 (0.9 until gr_demod_ssb::set_gain)
-    if (an_kind == 1 || an_kind == 3) {   // _filter -> port 0
-        FirCccParams f{}; f.in = r2; f.out = r2f; f.q0 = n2_0; f.count = c2; f.taps = an_filt_c.p; f.nt = an_nfc;
-        f.port = fport; f.port_cap = fcap; f.counts = counts;
-        launch_an_fir_ccc(f, B, stream);
-    } else {
-        FirCcfParams f{}; f.in = r2; f.out = r2f; f.q0 = n2_0; f.count = c2; f.taps = filt_taps.p; f.nt = filt_nt;
-        f.port = fport; f.port_cap = fcap; f.counts = counts;
-        launch_fir_ccf(f, B, stream);
-    }
-    RingF f1{an_f1.p, an_m1}, f2{an_f2.p, an_m2}, f3{an_f3.p, an_m2};
-    {   // _squelch and the recursions directly behind it
-        AnGateParams g{}; g.in = r2f; g.out = f1; g.q0 = n2_0; g.count = c2; g.st = an_st.p; g.atan_tab = atan_tab.p;
-        g.env = an_env.p; g.ramp = an_ramp; g.alpha = 0.01; g.one_minus_alpha = 1.0 - 0.01; g.threshold = an_threshold;
-        g.gain = an_gain; g.attack = an_attack; g.decay = an_decay; g.ff0 = an_ff[0]; g.ff1 = an_ff[1]; g.fb1 = an_fb1;
-        g.outc = RingC{an_c1.p, an_m1}; g.ref = 0.25f; g.clip = 0.95f;             // agc2_cc(0.1, 0.1, 0.25, 1), clipper_cc(0.95): gr_demod_ssb.cpp:52,58
-        launch_an_gate(g, an_kind, B, stream);
-    }
-    float* aport = out ? out->audio : nullptr;
-    const size_t acap = out ? out->audio_cap : 0;
-    if (an_kind == 3) {   // _stretcher, _complex_to_real, _level_control, _audio_filter -> port 1 (whole chunks of 1024 gated items)
-        const uint32_t max_chunked = c2 + 1024;
-        AnStretchParams sp{}; sp.in = RingC{an_c1.p, an_m1}; sp.out = f2; sp.st = an_st.p; sp.level = 1.333f;
-        launch_an_stretch(sp, max_chunked, B, stream);
-        AnFirParams p{}; p.in = f2; p.out = RingF{nullptr, 0}; p.st = an_st.p; p.taps = an_ftaps.p; p.nt = an_nf; p.I = 0; p.D = 1;
-        p.port = aport; p.port_cap = acap; p.counts = counts;
-        launch_an_fir(p, max_chunked, B, stream);
-        return QRL_OK;
-    }
-    const uint32_t max_out = (uint32_t)((uint64_t)c2 * an_I / an_D + 2);
-    {   // _audio_resampler (WBFM: -> port 1)
-        AnResampParams p{}; p.in = f1; p.out = f2; p.st = an_st.p; p.taps = an_rtaps.p; p.nt = an_nr; p.I = an_I; p.D = an_D;
-        if (an_kind == 2) { p.port = aport; p.port_cap = acap; p.counts = counts; }
-        launch_an_resamp(p, max_out, B, stream);
-    }
-    const bool ctcss = an_kind == 0 && ctcss_tone != 0.0f;
-    if (ctcss) {   // _ctcss (gating): audio resampler -> ring f4, item count g2 (gr_demod_nbfm.cpp:110-119)
-        CtcssParams p{}; p.in = f2; p.out = RingF{an_f4.p, an_m2}; p.st = an_st.p; p.cs = an_cs.p; p.I = an_I; p.D = an_D;
-        for (int k = 0; k < 3; ++k) { p.wr[k] = ct_wr[k]; p.wi[k] = ct_wi[k]; }
-        p.level = 0.01; p.len = 8000; p.ramp = 160; p.env = an_env_ct.p;
-        launch_an_ctcss(p, B, stream);
-    }
-    if (an_kind != 2) {   // _audio_filter (AM: -> port 1)
-        AnFirParams p{}; p.in = f2; p.out = f3; p.st = an_st.p; p.taps = an_ftaps.p; p.nt = an_nf; p.I = an_I; p.D = an_D;
-        if (ctcss) { p.in = RingF{an_f4.p, an_m2}; p.taps = an_ftaps_ct.p; p.nt = an_nf_ct; p.cs = an_cs.p; }   // band_pass_2(1, 8000, 300, 3500, 200, 35, BH), :112-113
-        if (an_kind == 1) { p.port = aport; p.port_cap = acap; p.counts = counts; }
-        launch_an_fir(p, max_out, B, stream);
-    }
-    if (an_kind == 0) {   // _de_emph_filter, _level_control -> port 1
-        AnDeemphParams p{}; p.in = f3; p.st = an_st.p; p.I = an_I; p.D = an_D; p.cs = ctcss ? an_cs.p : nullptr;
-        p.ff0 = an_de_ff[0]; p.ff1 = an_de_ff[1]; p.fb1 = an_de_fb1; p.port = aport; p.port_cap = acap; p.counts = counts;
-        launch_an_deemph(p, B, stream);
-    }
-    return QRL_OK;
-}
+// One row per receiver mode: the family that runs it and, for use_mode_defaults, the literals the reference constructs it with
+// (gr_demod_base.cpp:203-210: samp_rate 1 000 000, carrier_freq 1700).  kind (analogue receivers): 0 NBFM, 1 AM, 2 WBFM, 3 SSB.
+namespace {
+struct Mode { int modem_type; qrl_demod::Family fam; int kind; bool m17, lsb; int sps, filter_width, fm; };
+const Mode kModes[] = {
+    {QRL_MODEM_2FSK2KFM,  qrl_demod::F_2FSK,   0, false, false, 5,   4000,   1},
+    {QRL_MODEM_2FSK1KFM,  qrl_demod::F_2FSK,   0, false, false, 10,  2500,   1},
+    {QRL_MODEM_2FSK2K,    qrl_demod::F_2FSK,   0, false, false, 5,   4000,   0},
+    {QRL_MODEM_2FSK1K,    qrl_demod::F_2FSK,   0, false, false, 10,  2000,   0},
+    {QRL_MODEM_2FSK10KFM, qrl_demod::F_2FSK,   0, false, false, 1,   25000,  1},
+    {QRL_MODEM_GMSK2K,    qrl_demod::F_GMSK,   0, false, false, 5,   4000,   0},
+    {QRL_MODEM_GMSK1K,    qrl_demod::F_GMSK,   0, false, false, 10,  2000,   0},
+    {QRL_MODEM_GMSK10K,   qrl_demod::F_GMSK,   0, false, false, 1,   20000,  0},
+    {QRL_MODEM_QPSK250K,  qrl_demod::F_QPSK,   0, false, false, 2,   160000, 0},   // gr_demod_base.cpp:223
+    {QRL_MODEM_QPSKVIDEO, qrl_demod::F_QPSK,   0, false, false, 2,   160000, 0},   // :224
+    {QRL_MODEM_QPSK2K,    qrl_demod::F_QPSK,   0, false, false, 125, 1300,   0},   // :221
+    {QRL_MODEM_QPSK20K,   qrl_demod::F_QPSK,   0, false, false, 25,  6500,   0},   // :222
+    {QRL_MODEM_4FSK2K,    qrl_demod::F_4FSK,   0, false, false, 5,   4000,   0},   // gr_demod_base.cpp:211
+    {QRL_MODEM_4FSK2KFM,  qrl_demod::F_4FSK,   0, false, false, 5,   3000,   1},   // gr_demod_base.cpp:212
+    {QRL_MODEM_4FSK1KFM,  qrl_demod::F_4FSK,   0, false, false, 10,  2000,   1},   // :213
+    {QRL_MODEM_4FSK10KFM, qrl_demod::F_4FSK,   0, false, false, 1,   20000,  1},   // :214
+    {QRL_MODEM_4FSK100K,  qrl_demod::F_4FSK,   0, false, false, 2,   125000, 1},   // :225
+    {QRL_MODEM_BPSK1K,    qrl_demod::F_BPSK,   0, false, false, 10,  1300,   0},   // :216
+    {QRL_MODEM_BPSK2K,    qrl_demod::F_BPSK,   0, false, false, 5,   2400,   0},   // :217
+    {QRL_MODEM_DMR,       qrl_demod::F_DMR,    0, false, false, 5,   5000,   0},   // make_gr_demod_dmr(5, 1000000) gr_demod_base.cpp:253
+    {QRL_MODEM_M17,       qrl_demod::F_DMR,    0, true,  false, 125, 9000,   0},   // make_gr_demod_m17() gr_demod_base.cpp:252, defaults gr_demod_m17.h:41-42
+    {QRL_MODEM_BPSK8,     qrl_demod::F_DSSS,   0, false, false, 25,  150,    0},   // make_gr_demod_dsss(25, ., 1700, 150) gr_demod_base.cpp:218
+    {QRL_MODEM_NBFM2500,  qrl_demod::F_ANALOG, 0, false, false, 125, 2500,   0},   // make_gr_demod_nbfm(125, ., 1700, 2500) gr_demod_base.cpp:219
+    {QRL_MODEM_NBFM5000,  qrl_demod::F_ANALOG, 0, false, false, 125, 5000,   0},   // :220
+    {QRL_MODEM_AM5000,    qrl_demod::F_ANALOG, 1, false, false, 125, 5000,   0},   // make_gr_demod_am(125, ., 1700, 5000) :215
+    {QRL_MODEM_WBFM,      qrl_demod::F_ANALOG, 2, false, false, 125, 75000,  0},   // make_gr_demod_wbfm(125, ., 1700, 75000) :228
+    {QRL_MODEM_USB2500,   qrl_demod::F_ANALOG, 3, false, false, 125, 2700,   0},   // make_gr_demod_ssb(125, ., 1700, 2700, sb) :226-227
+    {QRL_MODEM_LSB2500,   qrl_demod::F_ANALOG, 3, false, true,  125, 2700,   0},   // :227
+};
+}  // namespace
 
 // =============================================================================== C ABI
 extern "C" {
 
 const char* qrl_version(void) { return "qrl_hip 0.1 (gfx950)"; }
-const char* qrl_last_error(void) { return g_last_error.c_str(); }
-const char* qrl_strerror(int s)
-{
-    switch (s) {
-    case QRL_OK: return "ok";
-    case QRL_ERR_ARG: return "invalid argument or unsupported mode";
-    case QRL_ERR_NO_DEVICE: return "no usable HIP device (this library has no CPU fallback)";
-    case QRL_ERR_HIP: return "HIP runtime error";
-    case QRL_ERR_NOMEM: return "out of device memory";
-    case QRL_ERR_TOO_BIG: return "chunk larger than max_chunk";
-    case QRL_ERR_STATE: return "invalid handle state";
-    }
-    return "unknown";
-}
 
 int qrl_init(int device, qrl_ctx** ctx)
 {
@@ -1192,66 +647,11 @@ int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp
     d->ctx = ctx;
     d->cfg = *cfg;
     qrl_demod_config& c = d->cfg;
-    if (c.use_mode_defaults) {  // literals of gr_demod_base.cpp:203-210
-        c.samp_rate = 1000000; c.carrier_freq = 1700;
-        switch (c.modem_type) {
-        case QRL_MODEM_2FSK2KFM:  c.sps = 5;  c.filter_width = 4000;  c.fm = 1; break;
-        case QRL_MODEM_2FSK1KFM:  c.sps = 10; c.filter_width = 2500;  c.fm = 1; break;
-        case QRL_MODEM_2FSK2K:    c.sps = 5;  c.filter_width = 4000;  c.fm = 0; break;
-        case QRL_MODEM_2FSK1K:    c.sps = 10; c.filter_width = 2000;  c.fm = 0; break;
-        case QRL_MODEM_2FSK10KFM: c.sps = 1;  c.filter_width = 25000; c.fm = 1; break;
-        case QRL_MODEM_GMSK2K:    c.sps = 5;  c.filter_width = 4000;  c.fm = 0; break;
-        case QRL_MODEM_GMSK1K:    c.sps = 10; c.filter_width = 2000;  c.fm = 0; break;
-        case QRL_MODEM_GMSK10K:   c.sps = 1;  c.filter_width = 20000; c.fm = 0; break;
-        case QRL_MODEM_QPSK250K:  c.sps = 2;  c.filter_width = 160000; c.fm = 0; break;   // gr_demod_base.cpp:223
-        case QRL_MODEM_QPSKVIDEO: c.sps = 2;  c.filter_width = 160000; c.fm = 0; break;   // :224
-        case QRL_MODEM_QPSK2K:    c.sps = 125; c.filter_width = 1300;  c.fm = 0; break;   // :221
-        case QRL_MODEM_QPSK20K:   c.sps = 25;  c.filter_width = 6500;  c.fm = 0; break;   // :222
-        case QRL_MODEM_4FSK2K:    c.sps = 5;  c.filter_width = 4000;   c.fm = 0; break;   // gr_demod_base.cpp:211
-        case QRL_MODEM_4FSK2KFM:  c.sps = 5;  c.filter_width = 3000;   c.fm = 1; break;   // gr_demod_base.cpp:212
-        case QRL_MODEM_4FSK1KFM:  c.sps = 10; c.filter_width = 2000;   c.fm = 1; break;   // :213
-        case QRL_MODEM_4FSK10KFM: c.sps = 1;  c.filter_width = 20000;  c.fm = 1; break;   // :214
-        case QRL_MODEM_4FSK100K:  c.sps = 2;  c.filter_width = 125000; c.fm = 1; break;   // :225
-        case QRL_MODEM_BPSK1K:    c.sps = 10; c.filter_width = 1300;   c.fm = 0; break;   // :216
-        case QRL_MODEM_BPSK2K:    c.sps = 5;  c.filter_width = 2400;   c.fm = 0; break;   // :217
-        case QRL_MODEM_DMR:       c.sps = 5;  c.filter_width = 5000;   c.fm = 0; break;   // make_gr_demod_dmr(5, 1000000) gr_demod_base.cpp:253
-        case QRL_MODEM_BPSK8:     c.sps = 25;  c.filter_width = 150;   c.fm = 0; break;
-        case QRL_MODEM_NBFM2500:  c.sps = 125; c.filter_width = 2500;  c.fm = 0; break;   // make_gr_demod_nbfm(125, ., 1700, 2500) gr_demod_base.cpp:219
-        case QRL_MODEM_NBFM5000:  c.sps = 125; c.filter_width = 5000;  c.fm = 0; break;   // :220
-        case QRL_MODEM_WBFM:      c.sps = 125; c.filter_width = 75000; c.fm = 0; break;   // make_gr_demod_wbfm(125, ., 1700, 75000) :228
-        case QRL_MODEM_AM5000:    c.sps = 125; c.filter_width = 5000;  c.fm = 0; break;
-        case QRL_MODEM_USB2500: case QRL_MODEM_LSB2500: c.sps = 125; c.filter_width = 2700; c.fm = 0; break;   // make_gr_demod_ssb(125, ., 1700, 2700, sb) :226-227   // make_gr_demod_am(125, ., 1700, 5000) :215   // make_gr_demod_dsss(25, ., 1700, 150) gr_demod_base.cpp:218
-        case QRL_MODEM_M17:       c.sps = 125; c.filter_width = 9000;  c.fm = 0; break;   // make_gr_demod_m17() gr_demod_base.cpp:252, defaults gr_demod_m17.h:41-42
-        default: return qrl_set_error(QRL_ERR_ARG, "modem_type not supported by this build");
-        }
-    }
-    switch (c.modem_type) {
-    case QRL_MODEM_2FSK2KFM: case QRL_MODEM_2FSK1KFM: case QRL_MODEM_2FSK2K: case QRL_MODEM_2FSK1K: case QRL_MODEM_2FSK10KFM:
-        d->fam = qrl_demod::F_2FSK; break;
-    case QRL_MODEM_GMSK2K: case QRL_MODEM_GMSK1K: case QRL_MODEM_GMSK10K:
-        d->fam = qrl_demod::F_GMSK; break;
-    case QRL_MODEM_QPSK250K: case QRL_MODEM_QPSKVIDEO: case QRL_MODEM_QPSK2K: case QRL_MODEM_QPSK20K:
-        d->fam = qrl_demod::F_QPSK; break;
-    case QRL_MODEM_DMR:
-        d->fam = qrl_demod::F_DMR; break;
-    case QRL_MODEM_M17:
-        d->fam = qrl_demod::F_DMR; d->m17 = true; break;
-    case QRL_MODEM_4FSK2K: case QRL_MODEM_4FSK2KFM: case QRL_MODEM_4FSK1KFM: case QRL_MODEM_4FSK10KFM: case QRL_MODEM_4FSK100K:
-        d->fam = qrl_demod::F_4FSK; break;
-    case QRL_MODEM_BPSK1K: case QRL_MODEM_BPSK2K:
-        d->fam = qrl_demod::F_BPSK; break;
-    case QRL_MODEM_BPSK8:
-        d->fam = qrl_demod::F_DSSS; break;
-    case QRL_MODEM_NBFM2500: case QRL_MODEM_NBFM5000:
-        d->fam = qrl_demod::F_ANALOG; d->an_kind = 0; break;
-    case QRL_MODEM_AM5000:
-        d->fam = qrl_demod::F_ANALOG; d->an_kind = 1; break;
-    case QRL_MODEM_WBFM:
-        d->fam = qrl_demod::F_ANALOG; d->an_kind = 2; break;
-    case QRL_MODEM_USB2500: case QRL_MODEM_LSB2500:
-        d->fam = qrl_demod::F_ANALOG; d->an_kind = 3; d->an_lsb = c.modem_type == QRL_MODEM_LSB2500; break;
-    default: return qrl_set_error(QRL_ERR_ARG, "modem_type not supported by this build");
-    }
+    const Mode* mode = nullptr;
+    for (const Mode& m : kModes) if (m.modem_type == c.modem_type) mode = &m;
+    if (!mode) return qrl_set_error(QRL_ERR_ARG, "modem_type not supported by this build");
+    if (c.use_mode_defaults) { c.samp_rate = 1000000; c.carrier_freq = 1700; c.sps = mode->sps; c.filter_width = mode->filter_width; c.fm = mode->fm; }
+    d->fam = mode->fam; d->m17 = mode->m17; d->an.kind = mode->kind; d->an.lsb = mode->lsb;
     if (c.samp_rate != 1000000) return qrl_set_error(QRL_ERR_ARG, "internal samp_rate must be 1000000 (gr_demod_base.cpp:21)");
     if (c.device_samp_rate != 1000000 && (c.device_samp_rate < 2000000 || c.device_samp_rate % 1000000))
         return qrl_set_error(QRL_ERR_ARG, "device_samp_rate must be 1e6 or a multiple of 1e6 >= 2e6");
@@ -1344,9 +744,7 @@ int qrl_demod_set_dmo_output(qrl_demod* d, uint8_t* frames, size_t cap_frames, u
     if (!d->dmo_st.p) {
         if (int rs = d->sync_all()) return rs;
         if ((r = d->dmo_st.alloc(d->cfg.batch)) || (r = d->dmo_golay.upload(golay1987_table()))) return r;
-        std::vector<DmoState> ds(d->cfg.batch);
-        for (auto& x : ds) { std::memset(&x, 0, sizeof x); x.endPtr = 9999; }
-        if (hipMemcpy(d->dmo_st.p, ds.data(), ds.size() * sizeof(DmoState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
+        if ((r = d->init_dmo_state())) return r;
     }
     d->dmo_out = frames; d->dmo_cap = (uint32_t)cap_frames; d->dmo_counts = counts;
     return QRL_OK;
@@ -1391,34 +789,17 @@ int qrl_demod_set_option(qrl_demod* d, int option, int value)
 int qrl_demod_out_caps(const qrl_demod* d, size_t n, size_t* fcap, size_t* ccap, size_t* bcap)
 {
     if (!d) return QRL_ERR_ARG;
-    const size_t n1 = d->fe.used ? n / d->fe_decim + 2 : n;
-    const size_t n2 = n1 * d->interp / d->decim + 2;
-    const size_t ns = n2 / (size_t)(d->sps_eff > 1 ? d->sps_eff - 1 : 1) + 8;
-    if (fcap) *fcap = n2;
+    const CallCounts cc = d->call_counts(n);
+    const size_t ns = cc.nsym;
+    if (fcap) *fcap = cc.n2;
     if (ccap) *ccap = ns;
     if (bcap) *bcap = d->fam == qrl_demod::F_DMR ? 2 * ns + 8 : d->fam == qrl_demod::F_QPSK || d->fam == qrl_demod::F_4FSK ? (ns / 80 + 2) * 80 : (ns / 2 / 80 + 2) * 80;
-    return QRL_OK;
-}
-int qrl_demod_audio_cap(const qrl_demod* d, size_t n, size_t* audio_cap)
-{
-    if (!d || !audio_cap) return QRL_ERR_ARG;
-    if (d->fam != qrl_demod::F_ANALOG) { *audio_cap = 0; return QRL_OK; }
-    const size_t n1 = d->fe.used ? n / d->fe_decim + 2 : n;
-    const size_t n2 = n1 * d->interp / d->decim + 2;
-    *audio_cap = d->an_kind == 3 ? n2 + 1024 + 4 : n2 * d->an_I / d->an_D + 4;
-    return QRL_OK;
-}
-int qrl_demod_set_squelch(qrl_demod* d, double db)
-{
-    if (!d || d->fam != qrl_demod::F_ANALOG) return QRL_ERR_ARG;
-    d->an_threshold = std::pow(10.0, db / 10);   // pwr_squelch_cc::set_threshold
     return QRL_OK;
 }
 int qrl_demod_time_domain_cap(const qrl_demod* d, size_t n, size_t* cap)
 {
     if (!d || !cap) return QRL_ERR_ARG;
-    const size_t n1 = d->fe.used ? n / d->fe_decim + 2 : n;
-    *cap = n1 / (size_t)d->scope_D + 2;
+    *cap = d->call_counts(n).n1 / (size_t)d->scope_D + 2;
     return QRL_OK;
 }
 int qrl_demod_set_time_domain_output(qrl_demod* d, float* samples, size_t cap, uint32_t* counts)
@@ -1428,99 +809,13 @@ int qrl_demod_set_time_domain_output(qrl_demod* d, float* samples, size_t cap, u
     HIPCHK(hipSetDevice(d->ctx->device));
     if (samples && !d->s_scope.p) {   // first use: the ring of the 100 ksps scope signal (one call + the stages' block granularity)
         if (int rs = d->sync_all()) return rs;
-        const size_t max1 = d->fe.used ? d->cfg.max_chunk / d->fe_decim + 2 : d->cfg.max_chunk;
-        d->scope_mask = pow2_at_least(max1 / (size_t)d->scope_D + 256, 64) - 1;
+        d->scope_mask = pow2_at_least(d->call_counts(d->cfg.max_chunk).n1 / (size_t)d->scope_D + 256, 64) - 1;
         if (int r = d->s_scope.alloc((size_t)d->cfg.batch * (d->scope_mask + 1))) return qrl_set_error(r, "scope ring");
         // the tap starts with the samples of the next call: outputs are indexed from the stream's 1 Msps position
         d->n_scope = decim_count(d->fe.used ? d->n1 : d->n_in, 1, d->scope_D);
     }
     if (samples && !d->scope_out) d->n_scope = decim_count(d->fe.used ? d->n1 : d->n_in, 1, d->scope_D);   // (re-)enabled: skip what was not tapped
     d->scope_out = reinterpret_cast<float2*>(samples); d->scope_cap = cap; d->scope_counts = counts;
-    return QRL_OK;
-}
-int qrl_demod_set_ctcss(qrl_demod* d, float tone_hz)
-{
-    if (!d || d->fam != qrl_demod::F_ANALOG || d->an_kind != 0) return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_ctcss: NBFM receivers only (gr_demod_nbfm::set_ctcss)");
-    if (tone_hz < 0.0f || tone_hz > 1000.0f) return QRL_ERR_ARG;
-    HIPCHK(hipSetDevice(d->ctx->device));
-    const bool was_on = d->ctcss_tone != 0.0f, on = tone_hz != 0.0f;
-    if (int rs = d->sync_all()) return rs;
-    if (on && !d->an_cs.p) {   // first use: state, the gated ring, the band-pass audio filter, the envelope of ramp 160 (double: float item x double envelope)
-        int r;
-        const std::vector<float> ft = band_pass_2(1, 8000, 300, 3500, 200, 35, WIN_BLACKMAN_HARRIS);       // gr_demod_nbfm.cpp:112-113
-        d->an_nf_ct = (int)ft.size();
-        std::vector<double> env(161);
-        for (int k = 0; k <= 160; ++k) env[k] = 0.5 - std::cos(M_PI * (double)k / 160.0) / 2.0;
-        if ((r = d->an_ftaps_ct.upload(ft)) || (r = d->an_env_ct.upload(env)) || (r = d->an_cs.alloc(d->cfg.batch)) ||
-            (r = d->an_f4.alloc((size_t)d->cfg.batch * (d->an_m2 + 1)))) return qrl_set_error(r, "ctcss buffers");
-    }
-    if (on) {   // ctcss_squelch_ff::set_frequency -> update_fft_params: the tone and its neighbours in the CTCSS table (2 % at the ends / off the table)
-        static const float tones[38] = {67.0f, 71.9f, 74.4f, 77.0f, 79.7f, 82.5f, 85.4f, 88.5f, 91.5f, 94.8f, 97.4f, 100.0f, 103.5f, 107.2f, 110.9f, 114.8f,
-                                        118.8f, 123.0f, 127.3f, 131.8f, 136.5f, 141.3f, 146.2f, 151.4f, 156.7f, 162.2f, 167.9f, 173.8f, 179.9f, 186.2f, 192.8f,
-                                        203.5f, 210.7f, 218.1f, 225.7f, 233.6f, 241.8f, 250.3f};
-        int i = -1;
-        for (int k = 0; k < 38; ++k) if (tones[k] == tone_hz) i = k;
-        const float f[3] = {(i == -1 || i == 0) ? (float)((double)tone_hz * 0.98) : tones[i - 1], tone_hz, (i == -1 || i == 37) ? (float)((double)tone_hz * 1.02) : tones[i + 1]};   // double literals, then narrowed (ctcss_squelch_ff_impl.cc compute_freqs)
-        for (int k = 0; k < 3; ++k) {
-            const float w = (float)(2.0 * M_PI * f[k] / 8000);
-            d->ct_wr[k] = (float)(2.0 * (double)cosf(w));
-            d->ct_wi[k] = sinf(w);
-        }
-    }
-    d->ctcss_tone = tone_hz;
-    // switching the block in or out re-wires the audio path (the reference disconnects / connects under lock()): the chain restarts
-    // from a fresh state, like qrl_demod_reset; a new tone while it is on re-initialises the Goertzel filters only (set_frequency)
-    if (was_on != on) return d->init_state();
-    if (on) {
-        std::vector<CtcssState> cs(d->cfg.batch);
-        if (hipMemcpy(cs.data(), d->an_cs.p, cs.size() * sizeof(CtcssState), hipMemcpyDeviceToHost) != hipSuccess) return QRL_ERR_HIP;
-        for (auto& x : cs) { for (int k = 0; k < 3; ++k) x.d1[k] = x.d2[k] = 0.0f; x.processed = 0; }
-        if (hipMemcpy(d->an_cs.p, cs.data(), cs.size() * sizeof(CtcssState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
-    }
-    return QRL_OK;
-}
-int qrl_demod_set_filter_width(qrl_demod* d, int width)
-{
-    if (!d || d->fam != qrl_demod::F_ANALOG)
-        return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_filter_width: analogue receivers only (gr_demod_base::set_filter_width forwards to WBFM, AM, NBFM, USB, LSB)");
-    // firdes' sanity checks: 0 < cutoff <= fs / 2; the SSB band starts at 200 Hz
-    if (width <= 0 || 2 * width > d->target || (d->an_kind == 3 && width <= 200)) return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_filter_width: width out of range");
-    HIPCHK(hipSetDevice(d->ctx->device));
-    if (int rs = d->sync_all()) return rs;
-    const double fs = d->target, w = width;
-    int r = QRL_OK;
-    // the setters do not repeat the constructors' designs (transition widths, design functions, the SSB audio filter's gain of 2)
-    if (d->an_kind == 0 || d->an_kind == 2) {   // gr_demod_nbfm.cpp:82-90, gr_demod_wbfm.cpp:76-84
-        const std::vector<float> f = low_pass(1, fs, w, 1200, WIN_BLACKMAN_HARRIS);
-        d->filt_nt = (int)f.size();
-        r = d->filt_taps.upload(f);
-        d->an_gain = (float)(d->target / ((d->an_kind == 0 ? 4 : 2) * M_PI * width));
-    } else if (d->an_kind == 1) {               // gr_demod_am.cpp:84-91
-        const auto fc = complex_band_pass(1, fs, -w, w, 1200, WIN_BLACKMAN_HARRIS);
-        d->an_nfc = (int)fc.size();
-        r = d->an_filt_c.upload(to_f2(fc));
-    } else {                                    // gr_demod_ssb.cpp:89-101
-        const auto fc = d->an_lsb ? complex_band_pass_2(1, fs, -w, -200, 200, 90, WIN_BLACKMAN_HARRIS) : complex_band_pass_2(1, fs, 200, w, 200, 90, WIN_BLACKMAN_HARRIS);
-        const std::vector<float> ft = band_pass_2(2, fs, 200, w, 200, 90, WIN_BLACKMAN_HARRIS);
-        d->an_nfc = (int)fc.size(); d->an_nf = (int)ft.size();
-        if (!(r = d->an_filt_c.upload(to_f2(fc)))) r = d->an_ftaps.upload(ft);
-    }
-    if (r) return qrl_set_error(r, "qrl_demod_set_filter_width: filter tables");
-    d->cfg.filter_width = width;
-    // The reference swaps the taps of a running graph under lock() / unlock(), at a sample position its scheduler decides; here the chain restarts
-    // from a fresh state (like qrl_demod_reset; squelch, CTCSS and AGC settings are kept) -- what the tests compare is the chain built with the setter's designs.
-    return d->init_state();
-}
-int qrl_demod_set_gain(qrl_demod* d, float value)
-{
-    if (!d || d->fam != qrl_demod::F_ANALOG || d->an_kind != 3) return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_gain: SSB receivers only (gr_demod_base::set_gain)");
-    d->an_if_gain = value;   // multiply_const_cc::set_k: from the next call on, nothing restarts
-    return QRL_OK;
-}
-int qrl_demod_set_agc(qrl_demod* d, float attack, float decay)
-{
-    if (!d || d->fam != qrl_demod::F_ANALOG || (d->an_kind != 1 && d->an_kind != 3)) return QRL_ERR_ARG;
-    d->an_attack = attack; d->an_decay = decay;
     return QRL_OK;
 }
 int qrl_demod_process(qrl_demod* d, const float* iq, size_t stride, size_t n, const qrl_demod_out* out)

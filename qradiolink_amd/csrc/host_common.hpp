@@ -5,12 +5,13 @@
 #include "engine.hpp"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
 struct qrl_ctx { int device; };
 
-int qrl_set_error(int code, const std::string& msg);   // engine.cpp: records the text of qrl_last_error (per thread), returns code
+int qrl_set_error(int code, const std::string& msg);   // host_common.cpp: records the text of qrl_last_error (per thread), returns code
 
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
@@ -48,6 +49,12 @@ template <class T> struct DevBuf {
         return QRL_OK;
     }
     int zero() { return hipMemset(p, 0, bytes()) == hipSuccess ? QRL_OK : QRL_ERR_HIP; }
+    // `count` byte-copies of proto (padding included) into the buffer alloc() made: the initial state of `count` identical streams
+    int fill(size_t count, const T& proto) {
+        std::vector<unsigned char> h(count * sizeof(T));
+        for (size_t i = 0; i < count; ++i) std::memcpy(h.data() + i * sizeof(T), &proto, sizeof(T));
+        return hipMemcpy(p, h.data(), h.size(), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
+    }
 };
 
 // ---- the carrier NCO of a handle (qrl_demod, qrl_mod, qrl_amod): exact 2^-64-turn accumulator, phase continuous across retunes ----

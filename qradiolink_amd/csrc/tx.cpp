@@ -43,11 +43,9 @@ struct qrl_mod {
     Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
     ~qrl_mod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int init_state() {
-        std::vector<TxState> s(cfg.batch);
-        for (auto& x : s) { x.sr = 0x7F; x.enc = 0; x.prev = 0; x.pad = 0; }   // scrambler seed 0x7F (gr_mod_qpsk.cpp:62)
-        if (hipMemcpy(st.p, s.data(), s.size() * sizeof(TxState), hipMemcpyHostToDevice) != hipSuccess) return QRL_ERR_HIP;
         int r;
-        if ((r = sym.zero())) return r;
+        const TxState x{0x7F, 0, 0, 0};   // scrambler seed 0x7F (gr_mod_qpsk.cpp:62)
+        if ((r = st.fill(cfg.batch, x)) || (r = sym.zero())) return r;
         if (fam == F_FSK) {
             if ((r = shaped.zero()) || (r = fmv.zero()) || (r = phase.zero()) || (m17_flt.p && (r = m17_flt.zero()))) return r;
         }
