@@ -227,17 +227,21 @@ void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
     q.tiles = tiles;
     dim3 grid((tiles + 7) / 8 * 8, batch), block(256);
     const size_t lds = decim_lds_bytes(p.D, p.Jpad, variant);
+    void (*kern)(const DecimParams);
     if (p.rot_acc_s) switch (variant) {
-    case DECIM_R4_J44: hipLaunchKernelGGL((k_decim<4, 44, true>), grid, block, lds, s, q); break;
-    case DECIM_R4_J12: hipLaunchKernelGGL((k_decim<4, 12, true>), grid, block, lds, s, q); break;
-    case DECIM_R2_J10: hipLaunchKernelGGL((k_decim<2, 10, true>), grid, block, lds, s, q); break;
-    default:           hipLaunchKernelGGL((k_decim<1, 14, true>), grid, block, lds, s, q); break;
+    case DECIM_R4_J44: kern = k_decim<4, 44, true>; break;
+    case DECIM_R4_J12: kern = k_decim<4, 12, true>; break;
+    case DECIM_R2_J10: kern = k_decim<2, 10, true>; break;
+    default:           kern = k_decim<1, 14, true>; break;
     } else switch (variant) {
-    case DECIM_R4_J44: hipLaunchKernelGGL((k_decim<4, 44>), grid, block, lds, s, q); break;
-    case DECIM_R4_J12: hipLaunchKernelGGL((k_decim<4, 12>), grid, block, lds, s, q); break;
-    case DECIM_R2_J10: hipLaunchKernelGGL((k_decim<2, 10>), grid, block, lds, s, q); break;
-    default:           hipLaunchKernelGGL((k_decim<1, 14>), grid, block, lds, s, q); break;
+    case DECIM_R4_J44: kern = k_decim<4, 44>; break;
+    case DECIM_R4_J12: kern = k_decim<4, 12>; break;
+    case DECIM_R2_J10: kern = k_decim<2, 10>; break;
+    default:           kern = k_decim<1, 14>; break;
     }
+    // DecimStage::plan admits tiles of up to 160 KiB (the front ends at 115:1 and above); past 64 KiB a kernel needs the attribute
+    if (lds > 64 * 1024 && dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, q);
 }
 
 // ---- history keeper: hist_new[k] = rotated sample at absolute index n0 + n - H + k ----

@@ -75,7 +75,7 @@ PARITY_LIST = [
     ("qpsk250k", 26, 1000000, 1 << 20),     # C3 chain at the internal rate: agc2, 2x Costas, symbol_sync_cc, diff_phasor
     ("qpsk250k", 26, 10000000, 1 << 23),    # C3 behind the 10:1 front end
     ("gmsk10k", 22, 64000000, 1 << 24),     # front end 64:1, 2677 taps: 8-block tile, 22 loads per thread (NLD = 36 variant)
-    ("gmsk10k", 22, 100000000, 1 << 24),    # front end 100:1, 4181 taps: only the 4-block MFMA tile fits the LDS
+    ("gmsk10k", 22, 100000000, 1 << 24),    # front end 100:1, 4181 taps: k_decim_pm with 25 phase slabs (rounds 1-2: the 4-block MFMA tile)
     ("qpsk250k", 26, 100000000, 1 << 24),   # BASELINE config C3 literally: QPSK-250k behind the 100:1 front end
     ("qpsk2k", 7, 1000000, 1 << 21),        # gr_demod_qpsk sps >= 125: 1:100 (3621 taps), FLL(32 taps), 5 samples per symbol
     ("qpsk20k", 1, 2000000, 1 << 22),       # gr_demod_qpsk 4 < sps < 125: 1:25, FLL, 4 samples per symbol

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+import front_end_rates as fer
 import orc
 import sig
 
@@ -252,6 +253,54 @@ def test_rules_leave_the_other_front_ends_on_m16():
     for fs, d in ((8e6, 8), (16e6, 16), (32e6, 32), (40e6, 40), (64e6, 64)):
         nt = orc.low_pass(1, fs, 480e3, 100e3, BH).size
         assert not orc.lib.orc_decim_uses_pl(nt, d) and not orc.lib.orc_decim_uses_pm(nt, d) and orc.lib.orc_decim_uses_m16(nt, d)
+
+
+def _front_end_contract(D):
+    """the oracle's rules in orc_decim_auto's order, as the kernel name of front_end_rates"""
+    nt = orc.frontend_taps(D * 1000000).size
+    u = orc.lib
+    return fer.PM if u.orc_decim_uses_pm(nt, D) else fer.PL if u.orc_decim_uses_pl(nt, D) else fer.M16 if u.orc_decim_uses_m16(nt, D) else fer.GENERIC
+
+
+def test_front_end_partition_is_pinned_for_every_accepted_rate():
+    """Which contract defines which device rate, 2 .. 183 Msps, against the table written out in front_end_rates.py (docs/KERNELS.md 17):
+    a change of a selection rule shows here before the GPU test's kernel-name check does.  Also what the table's comments claim: 42 taps
+    per phase for every D, the pm kernel's slab counts, and the generic tile's LDS bound that ends the range at 183."""
+    wrong = [(D, _front_end_contract(D), fer.front_end_class(D)) for D in range(fer.FIRST_D, fer.LAST_D + 1)
+             if _front_end_contract(D) != fer.front_end_class(D)]
+    assert not wrong, wrong
+    for D in range(fer.FIRST_D, fer.LAST_D + 1):
+        h = orc.frontend_taps(D * 1000000)
+        assert np.array_equal(h, orc.low_pass(1, D * 1e6, 480e3, 100e3, BH))
+        assert (h.size + D - 1) // D == 42, (D, h.size)
+        if fer.front_end_class(D) == fer.PM:
+            assert (D + 3) // 4 in fer.PM_NS
+    assert sorted({(D + 3) // 4 for D in range(fer.FIRST_D, fer.LAST_D + 1) if fer.front_end_class(D) == fer.PM}) == list(fer.PM_NS)
+    assert fer.generic_lds_bytes(fer.LAST_D) <= 160 * 1024 < fer.generic_lds_bytes(fer.LAST_D + 1)
+    assert _front_end_contract(fer.LAST_D + 1) == fer.GENERIC and _front_end_contract(200) == fer.GENERIC   # no other kernel takes what the generic one refuses
+
+
+def test_every_front_end_rate_matches_float64_definition():
+    """orc_decim_auto with the front-end filter of every D = 2 .. 183 (whatever contract the rules pick for it) against the float64
+    definition of the decimating FIR: 1e-5 of the output RMS, the project's bound for a summation order.  40 D + ntaps noise samples,
+    one fixed seed per D.  And auto IS the contract the partition names, bit for bit."""
+    by_class = {fer.GENERIC: orc.decim_fir_ccf, fer.M16: orc.decim_fir_ccf_m16, fer.PM: orc.decim_fir_ccf_pm, fer.PL: orc.decim_fir_ccf_pl}
+    worst, over, other = (0.0, 0), [], []
+    for D in range(fer.FIRST_D, fer.LAST_D + 1):
+        rng = np.random.default_rng(5000 + D)
+        h = orc.frontend_taps(D * 1000000)
+        n = 40 * D + h.size
+        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
+        y = orc.decim_auto(x, h, D)
+        e = _definition_error(y, x, h, D)
+        worst = max(worst, (e, D))
+        if not e < 1e-5:
+            over.append((D, e))
+        if not np.array_equal(y.view(np.uint32), by_class[fer.front_end_class(D)](x, h, D).view(np.uint32)):
+            other.append(D)
+    print("worst definition error %.3g of RMS at D = %d" % worst)
+    assert not over, over
+    assert not other, other
 
 
 def test_cpu_baseline_simd_decimator_matches_definition():
