@@ -185,6 +185,21 @@ int qrl_demod_set_gain(qrl_demod* d, float value);
  * Viterbi decoder of a call run on internal streams up to two calls behind the front end, so a caller that reuses one qrl_demod_out
  * for back-to-back calls must put qrl_demod_sync() or qrl_demod_stream_wait() between them (or alternate two buffer sets). */
 int qrl_demod_process(qrl_demod* d, const float* iq, size_t stride, size_t n, const qrl_demod_out* out);
+/* like qrl_demod_process, but iq is interleaved int16 I, Q (sc16, 4 bytes per sample: what UHD / SoapySDR / LimeSuite / HackRF put on the
+ * wire): stream b at iq + 2*b*stride int16s.  Replaces the driver's own sc16 -> fc32 conversion: the front end reads the raw pairs (half
+ * the HBM bytes, half the upload) and converts in registers, x = (float)v * scale per component (one exact int -> float conversion, one
+ * rounded f32 multiply, in front of the rotator) -- bit for bit what qrl_demod_process computes when fed (float)v * scale.
+ * scale: qrl_demod_set_sc16_scale, default 1.0f / 32768; the setter takes effect from the next call and refuses a non-finite or zero
+ * value with QRL_ERR_ARG.  The format belongs to the CALL, not the handle: the carried state is cf32, so cf32 and sc16 calls may
+ * alternate on one handle and give the result of the concatenated stream; options, per-stream carrier offsets, profiling (the same
+ * kernel names) and the scope tap work as with cf32.
+ * iq must be 16-byte aligned and stride a multiple of 4 samples, else QRL_ERR_ARG; any n <= max_chunk (the LDS-DMA kernel streams calls
+ * with n % 4 == 0, other n take the per-output kernels).
+ * Handles with device_samp_rate >= 2000000 only (every modem type, every rate qrl_demod_create accepts): there the device-rate front
+ * end and the history keeper are all that read the caller's buffer.  A 1 Msps handle returns QRL_ERR_ARG (qrl_last_error says so),
+ * changes nothing and stays usable; widening the per-mode first stages (k_resamp, k_dec2_fir, the analogue loaders) is a later change. */
+int qrl_demod_process_sc16(qrl_demod* d, const int16_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
+int qrl_demod_set_sc16_scale(qrl_demod* d, float scale);
 int qrl_demod_sync(qrl_demod* d);
 void* qrl_demod_stream(qrl_demod* d); /* hipStream_t */
 /* Profiling aid: the HIP streams a call's stages are launched on -- out[0] the handle's stream (front end), out[1] the stream of the
@@ -207,6 +222,9 @@ int qrl_demod_profile_read(qrl_demod* d, double* kernel_ms, uint64_t* launches, 
  * runs one pass, copies bits back.  bits_x_host: [batch][bits_cap]; counts_host: [batch][4]. */
 int qrl_demod_process_host(qrl_demod* d, const float* iq_host, size_t stride, size_t n,
                            uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host);
+/* the same for int16 I, Q host samples (iq_host[b*2*stride + 2*i], 4 bytes per sample staged and uploaded): qrl_demod_process_sc16 */
+int qrl_demod_process_sc16_host(qrl_demod* d, const int16_t* iq_host, size_t stride, size_t n,
+                                uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host);
 
 /* ---- TX: the "modulator" top_block (reference src/gr/gr_mod_base.cpp:25) ----------------------------------
  * One handle = make_gr_mod_qpsk(sps, samp_rate, carrier_freq, filter_width) (src/gr/gr_mod_qpsk.cpp:19-30;

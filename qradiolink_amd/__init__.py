@@ -131,6 +131,8 @@ def load_library():
     lib.qrl_amod_set_carrier_offsets.argtypes = [vp, C.POINTER(C.c_double)]
     lib.qrl_amod_set_cw_k.argtypes = [vp, C.c_int]
     lib.qrl_demod_process.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
+    lib.qrl_demod_process_sc16.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
+    lib.qrl_demod_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_demod_sync.argtypes = [vp]
     lib.qrl_rssi_create.argtypes = [vp, C.c_int, C.c_float, vp, C.POINTER(vp)]
     lib.qrl_rssi_destroy.argtypes = [vp]
@@ -160,6 +162,7 @@ def load_library():
     lib.qrl_demod_profile.argtypes = [vp, C.c_int]
     lib.qrl_demod_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
     lib.qrl_demod_process_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
+    lib.qrl_demod_process_sc16_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
     lib.qrl_mod_create.argtypes = [vp, C.POINTER(_ModConfig), C.POINTER(vp)]
     lib.qrl_mod_destroy.argtypes = [vp]
     lib.qrl_mod_reset.argtypes = [vp]
@@ -233,7 +236,7 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_sync", "qrl_amod_stream",
-    "qrl_demod_process", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
+    "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
     "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
     "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_sync",
@@ -403,6 +406,24 @@ class Demod:
         self.process_async(iq)
         self.sync()
         return self._ports()
+
+    def process_sc16_async(self, iq):
+        """Queue one pass over 16-bit integer IQ: iq is an int16 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_sc16).
+        Handles with device_samp_rate >= 2 Msps; the row pitch must be a multiple of 4 samples and the base 16-byte aligned."""
+        assert iq.is_cuda and iq.dtype == self.torch.int16 and iq.dim() == 2 and iq.shape[0] == self.batch
+        assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
+        self.torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_demod_process_sc16(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2, C.byref(self._out)),
+               "qrl_demod_process_sc16")
+
+    def process_sc16(self, iq):
+        self.process_sc16_async(iq)
+        self.sync()
+        return self._ports()
+
+    def set_sc16_scale(self, scale):
+        """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_demod_set_sc16_scale)"""
+        _check(self.lib.qrl_demod_set_sc16_scale(self.h, C.c_float(scale)), "qrl_demod_set_sc16_scale")
 
     def set_squelch(self, db):
         _check(self.lib.qrl_demod_set_squelch(self.h, C.c_double(db)), "qrl_demod_set_squelch")

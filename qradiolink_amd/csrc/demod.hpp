@@ -234,7 +234,10 @@ struct qrl_demod {
     bool loops_family() const { return fam == F_QPSK || fam == F_BPSK || fsk4_disc; }
     int init_state();
     int build();
-    int process(const float* iq, size_t stride, size_t n, const qrl_demod_out* out);
+    // fmt: IN_CF32 (iq = interleaved floats) | IN_SC16 (iq = interleaved int16 pairs, stride in samples of 4 bytes; front-end handles only).
+    // The format belongs to the CALL: history, edge scratch and rings are rotated cf32 whatever the calls before were fed.
+    int process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt = IN_CF32);
+    float sc16_scale = 1.0f / 32768.0f;   // qrl_demod_set_sc16_scale
     int init_dmo_state() { DmoState x; std::memset(&x, 0, sizeof x); x.endPtr = 9999; return dmo_st.fill(cfg.batch, x); }
     CallCounts call_counts(size_t n) const {
         const size_t c1 = fe.used ? n / fe_decim + 2 : n, c2 = c1 * interp / decim + 2;

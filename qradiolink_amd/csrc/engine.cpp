@@ -323,10 +323,14 @@ int qrl_demod::build()
     return init_state();
 }
 
-int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod_out* out)
+int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt)
 {
+    if (fmt == IN_SC16 && !fe.used)
+        return qrl_set_error(QRL_ERR_ARG, "qrl_demod_process_sc16: int16 input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps");
     if (n > cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
-    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return qrl_set_error(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
+    if (fmt == IN_SC16) {
+        if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, "sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+    } else if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return qrl_set_error(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
     const int B = cfg.batch;
     uint32_t* counts = (out && out->counts) ? out->counts : counts_scratch.p;
     hipStream_t cs = overlap ? tail : stream;   // stream of stage C (decimated-rate feed-forward kernels)
@@ -342,7 +346,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
     if (grouped && q_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(stream, ev_q[slot ^ 1], 0));   // grouped order: this front end behind the recursion of the call before
     if (pre_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_pre, 0)); pre_pending = false; }   // k_hist of the call before (helper stream)
     const bool use_pre = pre && input_resident;
-    const float2* in = reinterpret_cast<const float2*>(iq);
+    const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16: int16 pairs behind it; only the front end and k_hist read it, both told so)
     const float2* hist_old = hist_flip ? hist_b.p : hist_a.p;
     const PortC fport = filtered_port(out), cport = constellation_port(out);
     float2* hist_new = hist_flip ? hist_a.p : hist_b.p;
@@ -367,6 +371,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         p.out = RingC{s1.p, s1_mask}; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
         p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.Jpad;
         p.rot_enable = 1; rot.fill(p);
+        p.in_fmt = fmt; p.in_scale = sc16_scale;
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
         if (fe.launch(p, B, stream, use_pre ? slot : 0)) return qrl_set_error(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
     }
@@ -416,6 +421,7 @@ int qrl_demod::process(const float* iq, size_t stride, size_t n, const qrl_demod
         h.in = in; h.in_stride = stride; h.n0 = n_in0; h.n = (uint32_t)n;
         h.hist_old = hist_old; h.hist_new = hist_new; h.hist_len = hist_len;
         h.rot_enable = 1; rot.fill(h);
+        h.in_fmt = fmt; h.in_scale = sc16_scale;
         if (pre) { HIPCHK(hipEventRecord(ev_fe[slot], stream)); fe_valid[slot] = true; }   // everything of this call that reads the history on the handle's stream has been launched
         if (use_pre) {
             if (fe_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(pre, ev_fe[slot ^ 1], 0));   // hist_new was the history of the call before
@@ -825,6 +831,20 @@ int qrl_demod_process(qrl_demod* d, const float* iq, size_t stride, size_t n, co
     (void)take_launch_error();   // a mark left on this thread by an earlier call that returned before reading it must not fail this one
     return d->process(iq, stride, n, out);
 }
+int qrl_demod_process_sc16(qrl_demod* d, const int16_t* iq, size_t stride, size_t n, const qrl_demod_out* out)
+{
+    if (!d || (!iq && n)) return QRL_ERR_ARG;
+    HIPCHK(hipSetDevice(d->ctx->device));
+    (void)take_launch_error();
+    return d->process(iq, stride, n, out, IN_SC16);
+}
+int qrl_demod_set_sc16_scale(qrl_demod* d, float scale)
+{
+    if (!d) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_sc16_scale: scale must be finite and non-zero");
+    d->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
+    return QRL_OK;
+}
 int qrl_demod_sync(qrl_demod* d)
 {
     if (!d) return QRL_ERR_ARG;
@@ -884,6 +904,29 @@ int qrl_demod_process_host(qrl_demod* d, const float* iq_host, size_t stride, si
     qrl_demod_out o{};
     o.bits_a = ba.p; o.bits_b = bb.p; o.bits_cap = bits_cap; o.counts = cnt.p;
     if ((r = d->process(reinterpret_cast<const float*>(iq.p), st, n, &o))) return r;
+    if (int rs = d->sync_all()) return rs;
+    if (bits_a_host) HIPCHK(hipMemcpy(bits_a_host, ba.p, B * bits_cap, hipMemcpyDeviceToHost));
+    if (bits_b_host) HIPCHK(hipMemcpy(bits_b_host, bb.p, B * bits_cap, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts_host, cnt.p, B * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return QRL_OK;
+}
+
+int qrl_demod_process_sc16_host(qrl_demod* d, const int16_t* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
+                                uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
+{
+    if (!d || !iq_host || !counts_host) return QRL_ERR_ARG;
+    HIPCHK(hipSetDevice(d->ctx->device));
+    (void)take_launch_error();
+    if (!d->fe.used) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
+    const size_t B = (size_t)d->cfg.batch;
+    const size_t st = (n + 3) & ~(size_t)3;
+    DevBuf<uint32_t> iq, cnt; DevBuf<uint8_t> ba, bb;
+    int r;
+    if ((r = iq.alloc(B * st)) || (r = ba.alloc(B * bits_cap)) || (r = bb.alloc(B * bits_cap)) || (r = cnt.alloc(B * 4))) return r;
+    HIPCHK(hipMemcpy2D(iq.p, st * 4, iq_host, stride * 4, n * 4, B, hipMemcpyHostToDevice));
+    qrl_demod_out o{};
+    o.bits_a = ba.p; o.bits_b = bb.p; o.bits_cap = bits_cap; o.counts = cnt.p;
+    if ((r = d->process(iq.p, st, n, &o, IN_SC16))) return r;
     if (int rs = d->sync_all()) return rs;
     if (bits_a_host) HIPCHK(hipMemcpy(bits_a_host, ba.p, B * bits_cap, hipMemcpyDeviceToHost));
     if (bits_b_host) HIPCHK(hipMemcpy(bits_b_host, bb.p, B * bits_cap, hipMemcpyDeviceToHost));

@@ -43,9 +43,34 @@ std::vector<float2> rot_fine_table(uint64_t inc);   // the 512-entry fine table 
 void launch_rot_ps_advance(uint64_t* acc, const uint64_t* inc, int B, uint64_t delta, hipStream_t s);
 void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set_acc, uint64_t acc0, uint64_t inc0, const float2* lo0, hipStream_t s);
 
+// ---- format of the caller's IQ (qrl_demod_process / qrl_demod_process_sc16) ----
+// IN_SC16: `in` points at interleaved int16 I, Q pairs (4 bytes per sample, in_stride still in samples) and a sample is
+// x = (float)v * in_scale per component: one exact int -> float conversion, one rounded multiply, in front of the rotator.  Only the kernels
+// that read the caller's buffer know the format (the front-end stage and k_hist); history, edge scratch and rings stay rotated cf32.
+enum { IN_CF32 = 0, IN_SC16 = 1 };
+__device__ __forceinline__ float2 sc16_to_f2(uint32_t w, float scale)
+{
+    return make_float2((float)(int16_t)(w & 0xffffu) * scale, (float)((int32_t)w >> 16) * scale);
+}
+// sample r of stream b of the caller's buffer of a parameter block (DecimParams, HistParams), converted.  in_load: the format read from
+// the block (the checked per-sample paths); in_load_as<SC>: the format a compile-time flag (kernels that have an instantiation per format,
+// so that their cf32 code stays what it was)
+template <class Pp>
+__device__ __forceinline__ float2 in_load(const Pp& P, size_t b, size_t r)
+{
+    if (P.in_fmt == IN_SC16) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[b * P.in_stride + r], P.in_scale);
+    return P.in[b * P.in_stride + r];
+}
+template <bool SC, class Pp>
+__device__ __forceinline__ float2 in_load_as(const Pp& P, size_t b, size_t r)
+{
+    if constexpr (SC) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[b * P.in_stride + r], P.in_scale);
+    else return P.in[b * P.in_stride + r];
+}
+
 // ---- K1: rotator + decimating FIR (rotator_cc + rational_resampler_ccf(1,D)) ----
 struct DecimParams {
-    const float2* in; size_t in_stride;  // caller IQ (or nullptr when in_ring is used)
+    const float2* in; size_t in_stride;  // caller IQ (or nullptr when in_ring is used); in_fmt below says what it points at
     RingC in_ring;                       // alternative input: an engine ring (second-stage decimators)
     uint64_t n0; uint32_t n;             // absolute index of in[0], samples in this call
     const float2* hist; uint32_t hist_len;  // last hist_len (rotated) samples before n0, per stream
@@ -71,12 +96,14 @@ struct DecimParams {
     // nothing the call before produces on the launch stream), `pre_event` is recorded behind it and the launch stream waits for that
     hipStream_t pre_stream; hipEvent_t pre_event;
     const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;   // per-stream rotator (see rot_select below), or nullptr: the shared one above
+    int in_fmt; float in_scale;                             // IN_CF32 (0, what a zeroed block means) | IN_SC16 and its scale
 };
 struct HistParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;
     const float2* hist_old; float2* hist_new; uint32_t hist_len;
     int rot_enable; uint64_t rot_acc; uint64_t rot_inc; uint64_t rot_nbase; const float2* rot_lo;
     const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;
+    int in_fmt; float in_scale;
 };
 void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s);
 // 1:2 decimator + the channel FIR behind it in one kernel (kernels_frontend.hip k_dec2_fir): d = the decimator's input side (out unused)

@@ -53,7 +53,7 @@ __device__ __forceinline__ float2 mf_fetch(const DecimParams& P, int b, int64_t 
     if (ui >= P.n0 + P.n) return make_float2(0.f, 0.f);
     if (P.in) {
         if (ui >= P.n0) {
-            float2 x = P.in[(size_t)b * P.in_stride + (size_t)(ui - P.n0)];
+            float2 x = in_load(P, (size_t)b, (size_t)(ui - P.n0));
             if (P.rot_enable) x = mf_rot_rel(x, (uint32_t)(ui - P.rot_nbase - ((uint64_t)kb0 << 9)), t_hi, t_lo);
             return x;
         }
@@ -465,8 +465,9 @@ static hipError_t launch_k(const DecimParams& q, dim3 grid, size_t lds, hipStrea
 template <int NA, int NLD>
 static hipError_t launch_one(const DecimParams& q, dim3 grid, size_t lds, hipStream_t s)
 {
-    // FAST: the tile comes from the caller's buffer through register-prefetched 16-byte loads
-    if (q.in && q.n >= 2 && q.n < (1u << 28)) return launch_k<NA, NLD, true>(q, grid, lds, s);
+    // FAST: the tile comes from the caller's buffer through register-prefetched 16-byte loads (cf32 only; int16 input is converted
+    // sample by sample in mf_fetch)
+    if (q.in && q.in_fmt == IN_CF32 && q.n >= 2 && q.n < (1u << 28)) return launch_k<NA, NLD, true>(q, grid, lds, s);
     return launch_k<NA, 1, false>(q, grid, lds, s);
 }
 
@@ -493,7 +494,7 @@ int launch_decim_mfma(const DecimParams& p, int batch, hipStream_t s)
     const size_t lds = mfma_lds(p.nt, p.D, NA, tpw);
     const long long pairs = (mfma_jtot(p.nt, p.D, NA) + 2) / 2;
     const int nld = (int)((pairs + 255) / 256);
-    const bool fast = q.in && q.n >= 2 && q.n < (1u << 28);
+    const bool fast = q.in && q.in_fmt == IN_CF32 && q.n >= 2 && q.n < (1u << 28);
     // More than 16 loads per thread (front ends beyond ~40:1): a 36-load variant would need 144 prefetch registers, more than
     // the accumulator half of the register file holds, and hipcc then spills registers whose asm-issued loads are still in
     // flight.  Those tiles run with 512 threads (<= 16 loads per thread); anything larger takes the slow per-sample staging.

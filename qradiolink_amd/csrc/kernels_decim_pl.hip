@@ -181,6 +181,10 @@ __device__ __forceinline__ float2 pm_lds(uint32_t addr)   // ds_read_b64 from a 
     const v2f v = *(pm_lds_f2)(uintptr_t)addr;
     return make_float2(v.x, v.y);
 }
+__device__ __forceinline__ uint32_t pm_lds32(uint32_t addr)   // ds_read_b32 from a raw LDS byte address
+{
+    return *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)addr;
+}
 __device__ __forceinline__ uint32_t pm_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
 template <int N> __device__ __forceinline__ void pm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ void pm_wait_vm_dyn(uint32_t allowed)   // wave uniform; at most `allowed` DMA pieces may still be in flight
@@ -218,7 +222,12 @@ constexpr int PM_NHI = 64;   // coarse rotator entries per wave (64 x 512 sample
 // layout of the 16x16x4 instructions (lane (q, n) register r = Z[block n][lag 4 q + r]): A = tap H[D - 1][16 t + 4 q + (n & 3)],
 // B = the rotated last sample of block n in EVERY lane row (row 0 broadcast with two lane-row swaps).  One product added with one
 // rounding: the same link of the pm chain (the three links it drops added 0 x 0).
-template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false>
+// SC (the caller's buffer holds int16 pairs, DecimParams::in_fmt == IN_SC16): the regular units' byte stream has 4-byte samples -- the
+// ring holds the raw pairs, a group is 16 D 4 bytes, the lane reads 4 bytes (ds_read_b32) and converts in registers in front of the
+// rotator.  The edge units of the same launch still read the rotated cf32 scratch, so the sample size is a per-wave (wave-uniform) shift
+// `ssh`; with SC = false it is the constant 3 and the code is what it was.  NCO indices count SAMPLES whatever the format: kb8 / kg8 are
+// 8 x index (byte offsets into the float2 tables), the data offsets (gbytes, lane_byte, GB) are bytes of the wave's stream.
+template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false, bool SC = false>
 __global__ __launch_bounds__(NW * 64)
 void k_decim_pm(const DecimParams P_)
 {
@@ -283,12 +292,16 @@ void k_decim_pm(const DecimParams P_)
 #pragma unroll
     for (int t = 0; t < NT; ++t) a1[t] = K1 ? __shfl(a[t][NS - 1], 4 * q + (nn & 3), 64) : 0.f;   // held by lane (row 0, column 4 q + (n & 3)) of the K = 4 layout
     // the wave's byte stream: row = the stream's buffer (or its edge scratch), first byte of block 16 G0 at row + off0
-    const unsigned char* rowp = reinterpret_cast<const unsigned char*>(edge ? P.pl_edge + (size_t)b * P.pl_edge_stride : P.in + (size_t)b * P.in_stride);
-    const uint64_t off0 = edge ? 0ull : (uint64_t)(i_first - P.n0) * 8ull;
-    const uint64_t row_bytes = edge ? (uint64_t)P.pl_edge_stride * 8ull : (uint64_t)P.n * 8ull;   // multiples of 16 (even sample counts)
+    const uint32_t ssh = (SC && !edge) ? 2u : 3u;                    // log2 of the sample size of this wave's stream
+    const bool raw16 = SC && !edge;
+    const unsigned char* rowp = edge ? reinterpret_cast<const unsigned char*>(P.pl_edge + (size_t)b * P.pl_edge_stride)
+                                     : reinterpret_cast<const unsigned char*>(P.in) + (((size_t)b * P.in_stride) << ssh);   // (in_stride counts samples)
+    const uint64_t off0 = edge ? 0ull : (uint64_t)(i_first - P.n0) << ssh;
+    const uint64_t row_bytes = edge ? (uint64_t)P.pl_edge_stride * 8ull : (uint64_t)P.n << ssh;   // multiples of 16 (cf32: even sample counts, sc16: multiples of 4)
     const uint32_t o0 = (uint32_t)(off0 & 127u);                     // offset of the first block inside piece 0
     const uint64_t a_off = off0 - o0;                                // piece 0 starts here (128-byte aligned relative to the row)
-    const uint32_t GB = 16u * (uint32_t)D * 8u;                      // bytes per group
+    const uint32_t GB = (16u * (uint32_t)D) << ssh;                  // bytes per group
+    const uint32_t GK = 16u * (uint32_t)D * 8u;                      // 8 x samples per group (NCO table offsets)
     const uint32_t npieces = (o0 + (uint32_t)ngrp * GB + 1023u) >> 10;
     const uint32_t q_safe = (uint32_t)((row_bytes - a_off) >> 10);   // pieces [0, q_safe) lie inside the row; later ones are clamped to its last 16 bytes (never consumed)
     const uint32_t rbase = pm_lds_addr(ring_all) + (uint32_t)wave * (RP * 1024u);   // multiple of the ring size
@@ -308,7 +321,8 @@ void k_decim_pm(const DecimParams P_)
     };
     const uint32_t k0 = edge ? 0u : (uint32_t)(i_first - P.rot_nbase) - (kb0 << 9);   // < 512
     const uint32_t tl_mask = edge ? 0u : 4095u;
-    const uint32_t lane_byte = ((uint32_t)nn * (uint32_t)D + (uint32_t)q) * 8u;      // this lane's sample of step 0 inside a group
+    const uint32_t lane_smp = (uint32_t)nn * (uint32_t)D + (uint32_t)q;             // this lane's sample of step 0 inside a group
+    const uint32_t lane_byte = lane_smp << ssh;
     const bool last_valid = 4 * (NS - 1) + q < D;                    // step NS - 1 reaches past the block for the upper lane rows
     float2* orow = P.out.p + ((size_t)b * (P.out_row_mul_m1 + 1u) + P.out_row_add) * (P.out.mask + 1u);
     float Cpr = 0.f, Cpi = 0.f;                                      // carries of the previous group, per lane row
@@ -320,10 +334,10 @@ void k_decim_pm(const DecimParams P_)
 #endif
     issue_upto(npieces < RP ? npieces : RP);                         // (piece 0 is the first piece of group 0)
     uint32_t gbytes = o0;                                            // byte offset of the current group in the wave's stream
-    uint32_t kb8 = (k0 * 8u) + lane_byte;                            // 8 x NCO index (relative to the coarse table) of this lane's step-0 sample
+    uint32_t kb8 = (k0 * 8u) + lane_smp * 8u;                            // 8 x NCO index (relative to the coarse table) of this lane's step-0 sample
     uint32_t kg8 = k0 * 8u;                                          // the same for the group's first sample (wave uniform)
     for (int g = 0; g < ngrp; ++g) {
-        if (((kg8 + GB) >> 12) >= (uint32_t)(NHI - 1)) {             // the group would leave the coarse table: re-base it (wave private, no barrier)
+        if (((kg8 + GK) >> 12) >= (uint32_t)(NHI - 1)) {             // the group would leave the coarse table: re-base it (wave private, no barrier)
             const uint32_t sh = kg8 >> 12;
             kb0 += sh; kg8 -= sh << 12; kb8 -= sh << 12;
             t_hi_all[wave][lane] = edge ? make_float2(1.f, 0.f) : sincos_turn(r_acc + ((uint64_t)(kb0 + (uint32_t)lane) << 9) * r_inc);
@@ -337,8 +351,16 @@ void k_decim_pm(const DecimParams P_)
         float2 x[NS];
         {
             const uint32_t xb = gbytes + lane_byte;
+            if (raw16) {                                             // (constant false without SC)
+                uint32_t w[NS];
 #pragma unroll
-            for (int s = 0; s < NS; ++s) x[s] = pm_lds(rbase | ((xb + 32u * (uint32_t)s) & (RP * 1024u - 1u)));
+                for (int s = 0; s < NS; ++s) w[s] = pm_lds32(rbase | ((xb + 16u * (uint32_t)s) & (RP * 1024u - 1u)));
+#pragma unroll
+                for (int s = 0; s < NS; ++s) x[s] = sc16_to_f2(w[s], P.in_scale);
+            } else {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) x[s] = pm_lds(rbase | ((xb + 32u * (uint32_t)s) & (RP * 1024u - 1u)));
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the group is in registers: its ring slots are free
         PM_STAMP(1);
@@ -428,7 +450,7 @@ void k_decim_pm(const DecimParams P_)
             reinterpret_cast<float*>(orow + ((uint32_t)m & P.out.mask))[q] = y;
 #endif
         gbytes += GB;
-        kb8 += GB; kg8 += GB;
+        kb8 += GK; kg8 += GK;
         PM_STAMP(4);
     }
 #ifdef QRL_PM_PROF
@@ -473,7 +495,7 @@ __global__ __launch_bounds__(256) void k_decim_pm_gen(const DecimParams P_, uint
                         if (ui >= P.n0) {
                             const uint64_t rel = ui - P.n0;
                             if (rel < P.n) {
-                                x = inb[rel];
+                                x = in_load(P, (size_t)b, (size_t)rel);
                                 if (P.rot_enable) {
                                     const uint64_t kk = kk0 + rel;
                                     if ((kk >> 9) != hi_blk) { hi_blk = kk >> 9; hi = sincos_turn(P.rot_acc + (hi_blk << 9) * P.rot_inc); }
@@ -561,7 +583,9 @@ __device__ __forceinline__ v2f plx_mul(v2f hpair, v2f x)
     return r;
 }
 
-template <int E, int R, int U, bool PS = false>
+// SC: int16 input -- the regular units load the raw 4-byte pairs (the prefetch registers hold the words) and convert when a block is
+// taken out of the prefetch ring; edge units read the rotated cf32 scratch as before (wave-uniform choice).
+template <int E, int R, int U, bool PS = false, bool SC = false>
 __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 {
     constexpr int G = 16 / R;              // blocks per group of 16 outputs
@@ -625,7 +649,16 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
     }
     const int lo = lane < NL ? lane : NL - 1;                         // idle lanes re-read the last samples against zero taps
     const int nblk = WU + (int)((me - ms + R - 1) / R);
-    const float2* ub = (edge ? P.pl_edge + (size_t)b * P.pl_edge_stride : P.in + (size_t)b * P.in_stride + (size_t)(i_first - P.n0)) + (size_t)(E * lo);   // lane's first sample of block 0
+    // raw16 waves never read through `ub` (it gets a valid dummy); the SC kernel's edge waves need the float2 prefetch ring, so the regular
+    // waves keep their raw words in the same registers (.x, moves only) rather than in a second array
+    const bool raw16 = SC && !edge;
+    const float2* ub = (edge ? P.pl_edge + (size_t)b * P.pl_edge_stride : raw16 ? P.pl_edge : P.in + (size_t)b * P.in_stride + (size_t)(i_first - P.n0)) + (size_t)(E * lo);   // lane's first sample of block 0
+    const uint32_t* ub16 = reinterpret_cast<const uint32_t*>(P.in) + (raw16 ? (size_t)b * P.in_stride + (size_t)(i_first - P.n0) + (size_t)(E * lo) : (size_t)0);   // (raw16 only)
+    auto fetch = [&](size_t idx) -> v2f {                              // what the prefetch ring holds: the sample, or the raw word in .x
+        if (raw16) return v2f{__uint_as_float(ub16[idx]), 0.f};
+        const float2 v = ub[idx];
+        return v2f{v.x, v.y};
+    };
     const uint32_t k0 = (edge ? 0u : (uint32_t)(i_first - P.rot_nbase) - (kb0 << 9)) + (uint32_t)(E * lo);   // its NCO index, relative
     const bool hi8 = lane & 8, hi4 = lane & 4;
     const bool leader = (lane & 3) == 0;
@@ -637,7 +670,7 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
     for (int q = 0; q < PLX_PF; ++q) {
         const int t = q < nblk ? q : nblk - 1;
 #pragma unroll
-        for (int e = 0; e < E; ++e) { const float2 v = ub[(size_t)t * Dp + e]; pf[q][e] = v2f{v.x, v.y}; }
+        for (int e = 0; e < E; ++e) pf[q][e] = fetch((size_t)t * Dp + e);
     }
     v2f acc[WN];
 #pragma unroll
@@ -651,11 +684,14 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
             const int t = grp * G + i;
             v2f x[E];
 #pragma unroll
-            for (int e = 0; e < E; ++e) x[e] = pf[i % PLX_PF][e];
+            for (int e = 0; e < E; ++e) {
+                x[e] = pf[i % PLX_PF][e];
+                if (raw16) { const float2 c = sc16_to_f2(__float_as_uint(x[e].x), P.in_scale); x[e] = v2f{c.x, c.y}; }
+            }
             {   // keep PLX_PF blocks in flight (past the end of the segment: harmless re-read of its last block)
                 const int tn = t + PLX_PF < nblk ? t + PLX_PF : nblk - 1;
 #pragma unroll
-                for (int e = 0; e < E; ++e) { const float2 v = ub[(size_t)tn * Dp + e]; pf[i % PLX_PF][e] = v2f{v.x, v.y}; }
+                for (int e = 0; e < E; ++e) pf[i % PLX_PF][e] = fetch((size_t)tn * Dp + e);
             }
 #pragma unroll
             for (int e = 0; e < E; ++e) {   // rotator: phasor of sample k = T_hi[k >> 9] (x) T_lo[k & 511]
@@ -696,8 +732,8 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 
 // Edge scratch of one call: for every stream the ROTATED samples i0 .. i0 + len - 1 (absolute indices, i0 may be negative): zeros in
 // front of the stream, the carried (already rotated) history in front of this call's buffer, the buffer's head through the exact NCO
-template <bool PS = false>
-__global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len)
+template <bool PS, bool SC>
+__device__ __forceinline__ void pl_edge_stage_body(const DecimParams& P_, int64_t i0, uint32_t len)
 {
     ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
@@ -710,7 +746,7 @@ __global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int
         if (ui >= P.n0) {
             const uint64_t r = ui - P.n0;
             if (r < P.n) {
-                x = P.in[(size_t)b * P.in_stride + (size_t)r];
+                x = in_load_as<SC>(P, (size_t)b, (size_t)r);
                 const uint64_t kk = ui - P.rot_nbase;
                 x = cmul_fma(x, cmul_fma(sincos_turn(P.rot_acc + ((kk >> 9) << 9) * P.rot_inc), P.rot_lo[(uint32_t)kk & 511u]));
             }
@@ -720,6 +756,17 @@ __global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int
         }
     }
     P.pl_edge[(size_t)b * P.pl_edge_stride + j] = x;
+}
+
+template <bool PS = false>
+__global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, false>(P_, i0, len); }
+template <bool PS = false>
+__global__ __launch_bounds__(256) void k_pl_edge_stage_sc16(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, true>(P_, i0, len); }   // int16 input
+static void launch_pl_edge_stage(const DecimParams& q, int64_t i0, uint32_t len, int batch, hipStream_t s)
+{
+    const dim3 grid((len + 255) / 256, batch);
+    if (q.in_fmt == IN_SC16) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_sc16<true> : k_pl_edge_stage_sc16<false>, grid, dim3(256), 0, s, q, i0, len);
+    else hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, grid, dim3(256), 0, s, q, i0, len);
 }
 
 // One wave per output, checked fetches: zero in front of the stream, carried (already rotated) history in front of this
@@ -761,7 +808,7 @@ __global__ __launch_bounds__(256) void k_decim_pl_gen(const DecimParams P_, uint
                 if ((int64_t)rel >= n_before) {
                     if (inb) {
                         if (rel >= 0) {
-                            x = inb[rel];
+                            x = in_load(P, (size_t)b, (size_t)rel);
                             if (P.rot_enable) {
                                 const uint32_t kk = lo0 + (uint32_t)rel;
                                 if ((kk >> 9) != hi_blk) { hi_blk = kk >> 9; hi = sincos_turn(P.rot_acc + ((blk0 + hi_blk) << 9) * P.rot_inc); }
@@ -861,7 +908,7 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
         const int64_t i_last = (int64_t)(m_main - 1) * g.Dp;                   // last sample of the last edge block
         if (p.pl_edge && g.R == 1 && i_last - i0 + 1 <= (int64_t)p.pl_edge_cap) {
             const uint32_t len = (uint32_t)(i_last - i0 + 1);
-            hipLaunchKernelGGL(p.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, dim3((len + 255) / 256, batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, len);
+            launch_pl_edge_stage(q, i0, len, batch, p.pre_stream ? p.pre_stream : s);
             if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
             q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
             edge_unit = true;
@@ -889,7 +936,10 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
     q.pl_S = (uint32_t)S;
     q.pl_nseg = (uint32_t)((m_tail - m_main + S - 1) / S);
     const uint32_t units = q.pl_nseg * (uint32_t)batch + (edge_unit ? (uint32_t)batch : 0u);
-    if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+    if (p.in_fmt == IN_SC16) {
+        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+    } else if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
     else hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), dim3((units + 3) / 4), dim3(256), 0, s, q);
     return 0;
 }
@@ -971,14 +1021,14 @@ static uint32_t pm_pick_segment(uint64_t M, uint32_t batch, uint32_t cap, uint32
     }
     return best_S;
 }
-template <int J, int NS, int RP, bool K1, bool PS>
+template <int J, int NS, int RP, bool K1, bool PS, bool SC = false>
 static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
     // RP = ring pieces per wave (a power of two: one 16-block group -- 128 D bytes -- + what is in flight).
     // 4 waves per workgroup; at D = 50 four workgroups per CU (156 KB of LDS).  8-wave workgroups (two per CU, 144 KB: room for slim
     // recursion kernels of the previous call beside them) were measured: 7.24 ms against 6.57 ms alone, and no gain in the overlapped mode.
     constexpr int NW = QRL_PM_NW;
-    const auto kern = k_decim_pm<J, NS, RP, NW, K1, PS>;
+    const auto kern = k_decim_pm<J, NS, RP, NW, K1, PS, SC>;
     size_t lds = (size_t)NW * RP * 1024 + 512 * sizeof(float2) + NW * PM_NHI * sizeof(float2);
     // experiment (VERDICT r5 #4a): pad the dynamic LDS so that fewer front-end workgroups share a CU and a tail-chain workgroup of the previous call always
     // finds room beside them (QRL_PM_LDS_KB = total KB per workgroup; 45 -> three per CU with 25 KB to spare)
@@ -1015,6 +1065,11 @@ static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edg
 template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
 static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
+    // int16 input: the front ends only (three lag tiles); launch_decim_pm keeps the one-tile geometries on the per-output kernel
+    if constexpr (J > 16) {
+        if (q.in_fmt == IN_SC16)
+            return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, true>(q, M, batch, edge_unit, s);
+    }
     return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false>(q, M, batch, edge_unit, s);
 }
 int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
@@ -1031,8 +1086,12 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
     };
     // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces: rows 16-byte aligned, even sample counts
     // (what qrl_demod_process demands; the edge scratch is built that way).  Anything else: one thread per output.
-    const bool dma_ok = p.in && p.rot_enable && (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && (p.in_stride & 1u) == 0 && (p.n & 1u) == 0 &&
-                        p.pl_edge && (reinterpret_cast<uintptr_t>(p.pl_edge) & 15u) == 0 && (p.pl_edge_stride & 1u) == 0;
+    // int16 input (4-byte samples): whole pieces per row are multiples of FOUR samples
+    const uint32_t amask = p.in_fmt == IN_SC16 ? 3u : 1u;
+    const bool dma_ok = p.in && p.rot_enable && (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && (p.in_stride & amask) == 0 && (p.n & amask) == 0 &&
+                        p.pl_edge && (reinterpret_cast<uintptr_t>(p.pl_edge) & 15u) == 0 && (p.pl_edge_stride & 1u) == 0 &&
+                        !(p.in_fmt == IN_SC16 && J <= 16);   // (not reachable from the front-end stage, whose ~41.8 D taps give J > 16, and int16 input exists
+                                                             //  only there; kept so that a one-tile stage fed int16 would still be exact, through k_decim_pm_gen)
     if (!dma_ok) { gen(p.m0, m_end); return 0; }
     // interior segments start at outputs m == J - 1 (mod 16): their oldest block opens a 16-block group, and it lies in the buffer
     const uint64_t qb = p.n0 > 1 ? (p.n0 - 1 + D - 1) / D : 0;             // block qb + 1 is the first one whose samples are all >= n0
@@ -1050,7 +1109,7 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
         const int64_t i_last = (int64_t)(m_main - 1) * D;                  // last sample of the last edge output's newest block
         const int64_t len = ((i_last - i0 + 1) + 1) & ~(int64_t)1;
         if (len <= (int64_t)p.pl_edge_cap) {
-            hipLaunchKernelGGL(p.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, dim3((uint32_t)((len + 255) / 256), batch), dim3(256), 0, p.pre_stream ? p.pre_stream : s, q, i0, (uint32_t)len);
+            launch_pl_edge_stage(q, i0, (uint32_t)len, batch, p.pre_stream ? p.pre_stream : s);
             if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
             q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
             edge_unit = true;

@@ -45,7 +45,7 @@ __device__ __forceinline__ float2 decim_fetch(const DecimParams& P, int b, int64
     if (P.in) {
         if (ui >= P.n0 + P.n) return make_float2(0.f, 0.f);
         if (ui >= P.n0) {
-            float2 x = P.in[(size_t)b * P.in_stride + (size_t)(ui - P.n0)];
+            float2 x = in_load(P, (size_t)b, (size_t)(ui - P.n0));
             if (P.rot_enable) x = rot_apply(x, ui - P.rot_nbase, t_hi, kb0, t_lo);
             return x;
         }
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_decim(const DecimParams P_)
         const int a = (int)((i_first - (int64_t)P.n0) & 1);  // pairs start at s = -a so that (i - n0) is even
         // pairs k in [k_lo, k_hi): both samples inside the caller's buffer and inside the tile
         int k_lo = 0, k_hi = 0;
-        if (P.in) {
+        if (P.in && P.in_fmt == IN_CF32) {   // (int16 input: every sample through decim_fetch, which converts)
             int64_t lo = ((int64_t)P.n0 - i_first + a + 1) >> 1;                 // i0 >= n0
             int64_t hi = ((int64_t)(P.n0 + P.n) - i_first + a - 1) >> 1;         // i0 + 1 < n0 + n
             if (lo < a) lo = a;                                                  // s0 >= 0
@@ -245,8 +245,8 @@ void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
 }
 
 // ---- history keeper: hist_new[k] = rotated sample at absolute index n0 + n - H + k ----
-template <bool PS>
-__global__ __launch_bounds__(256) void k_hist(const HistParams P_)
+template <bool PS, bool SC>
+__device__ __forceinline__ void hist_body(const HistParams& P_)
 {
     ROT_VIEW(HistParams, PS, P, P_, blockIdx.y);
     const int b = blockIdx.y;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_hist(const HistParams P_)
     const int64_t i = (int64_t)(P.n0 + P.n) - (int64_t)P.hist_len + (int64_t)k;
     float2 x = make_float2(0.f, 0.f);
     if (i >= (int64_t)P.n0) {
-        x = P.in[(size_t)b * P.in_stride + (size_t)((uint64_t)i - P.n0)];
+        x = in_load_as<SC>(P, (size_t)b, (size_t)((uint64_t)i - P.n0));
         if (P.rot_enable) {
             const uint64_t kk = (uint64_t)i - P.rot_nbase;
             const float2 hi = sincos_turn(P.rot_acc + ((kk >> 9) << 9) * P.rot_inc);
@@ -267,11 +267,16 @@ __global__ __launch_bounds__(256) void k_hist(const HistParams P_)
     }
     P.hist_new[(size_t)b * P.hist_len + k] = x;
 }
+template <bool PS> __global__ __launch_bounds__(256) void k_hist(const HistParams P_) { hist_body<PS, false>(P_); }
+template <bool PS> __global__ __launch_bounds__(256) void k_hist_sc16(const HistParams P_) { hist_body<PS, true>(P_); }   // int16 input
 void launch_hist_save(const HistParams& p, int batch, hipStream_t s)
 {
     if (p.hist_len == 0) return;
     dim3 grid((p.hist_len + 255) / 256, batch), block(256);
-    if (p.rot_acc_s) hipLaunchKernelGGL(k_hist<true>, grid, block, 0, s, p);
+    if (p.in_fmt == IN_SC16) {
+        if (p.rot_acc_s) hipLaunchKernelGGL(k_hist_sc16<true>, grid, block, 0, s, p);
+        else hipLaunchKernelGGL(k_hist_sc16<false>, grid, block, 0, s, p);
+    } else if (p.rot_acc_s) hipLaunchKernelGGL(k_hist<true>, grid, block, 0, s, p);
     else hipLaunchKernelGGL(k_hist<false>, grid, block, 0, s, p);
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 
@@ -62,7 +63,7 @@ bool modem_two_branches(int m)   // gr_modem.cpp:1048-1058
 // ================================================================================================ gr_demod_base_hip
 struct gr_demod_base_hip::slot {
     gr_complex* h_iq = nullptr;                           // pinned [streams][chunk]
-    float* d_iq = nullptr;                                // device [streams][chunk] cf32
+    float* d_iq = nullptr;                                // device [streams][chunk] cf32 (an int16 call uses the first half of every buffer: 4-byte samples at the same pitch)
     bool const_copied = true;
     float *d_filt = nullptr, *d_const = nullptr; uint8_t *d_a = nullptr, *d_b = nullptr, *d_dmo = nullptr; uint32_t *d_cnt = nullptr, *d_dmocnt = nullptr;
     gr_complex* h_const = nullptr; uint8_t *h_a = nullptr, *h_b = nullptr, *h_dmo = nullptr; uint32_t *h_cnt = nullptr, *h_dmocnt = nullptr;   // pinned
@@ -137,6 +138,7 @@ void gr_demod_base_hip::open()
     c.batch = d_n; c.max_chunk = d_chunk; c.enable_side_outputs = 1;
     c.time_domain_samp_rate = d_scope_rate; c.time_domain_filter_width = d_scope_fw;
     chk(qrl_demod_create(d_rt.ctx(), &c, &d_h), "qrl_demod_create");
+    chk(qrl_demod_set_sc16_scale(d_h, d_sc16_scale), "qrl_demod_set_sc16_scale");
     if (d_per_stream) chk(qrl_demod_set_carrier_offsets(d_h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
     chk(qrl_demod_out_caps(d_h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
     chk(qrl_demod_audio_cap(d_h, d_chunk, &d_acap), "qrl_demod_audio_cap");
@@ -265,17 +267,35 @@ void gr_demod_base_hip::set_samp_rate(int device_samp_rate)   // gr_demod_base.c
     d_rate = device_samp_rate;
     if (d_mode >= 0) open();
 }
-void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n)
+void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, false); }
+// 16-bit integer I/Q as the SDR drivers deliver it (interleaved int16 I, Q): 4 bytes per sample are staged in the pinned buffer and uploaded,
+// and the device-rate front end converts (qrl_demod_process_sc16: x = (float)v * scale).  Replaces the driver's sc16 -> fc32 conversion.
+void gr_demod_base_hip::work(const int16_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, true); }
+void gr_demod_base_hip::set_sc16_scale(float scale)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_demod_base_hip::set_sc16_scale: finite, non-zero");
+    d_sc16_scale = scale;
+    if (d_h) chk(qrl_demod_set_sc16_scale(d_h, scale), "qrl_demod_set_sc16_scale");
+}
+void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (!d_h) throw std::runtime_error("gr_demod_base_hip::work before set_mode");
     if (n == 0) return;
     if (n > d_chunk || (n & 1)) throw std::invalid_argument("gr_demod_base_hip::work: n must be even and <= max_chunk");
+    if (sc16) {
+        // the C ABI would refuse the same (QRL_ERR_ARG); checked here before anything is staged or queued
+        if (d_rate < 2000000) throw std::invalid_argument("gr_demod_base_hip::work(int16): needs the device-rate front end (device_samp_rate >= 2000000)");
+        if (d_chunk & 3) throw std::invalid_argument("gr_demod_base_hip::work(int16): max_chunk (the row pitch) must be a multiple of 4 samples");
+        if (d_fft_on) throw std::invalid_argument("gr_demod_base_hip::work(int16): the spectrum tap reads cf32 samples; switch it off or feed cf32");
+    }
     if (!d_demod_on && !d_fft_on) return;                        // _demod_valve closed and nobody else listens: the samples are dropped
     const int cur = (int)(d_calls & 1);
     slot& sl = *d_slot[cur];
+    const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the pitch stays d_chunk samples
     // slot `cur` was last used by call k - 2, which work(k - 1) has harvested: its buffers are free
-    for (int s = 0; s < d_n; ++s) std::memcpy(sl.h_iq + (size_t)s * d_chunk, iq[s], n * sizeof(gr_complex));
+    for (int s = 0; s < d_n; ++s) std::memcpy(reinterpret_cast<char*>(sl.h_iq) + (size_t)s * d_chunk * sb, iq[s], n * sb);
     hipStream_t hs = static_cast<hipStream_t>(qrl_demod_stream(d_h)), cs = static_cast<hipStream_t>(d_copy);
     if (!d_demod_on) {                                           // _demod_valve closed (gr_demod_base.cpp:1150-1153): only the spectrum tap, which sits in front of it
         // everything of this call on the spectrum block's own stream (d_copy): the upload, the FFT fill behind it, and the host waits for THAT
@@ -285,7 +305,7 @@ void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n)
         hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");  // (d_calls does not advance: the next call takes the same slot; no harvest belongs to this call)
         return;
     }
-    hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sizeof(gr_complex), hipMemcpyHostToDevice, hs), "H2D");
+    hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, hs), "H2D");
     if (d_mode == QRL_MODEM_DMR) chk(qrl_demod_set_dmo_output(d_h, sl.d_dmo, kDmoCap, sl.d_dmocnt), "qrl_demod_set_dmo_output");
     sl.scoped = d_scope_on;
     chk(qrl_demod_set_time_domain_output(d_h, d_scope_on ? sl.d_scope : nullptr, d_scap, d_scope_on ? sl.d_scnt : nullptr), "qrl_demod_set_time_domain_output");
@@ -293,7 +313,8 @@ void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n)
     o.filtered = sl.d_filt; o.filtered_cap = d_fcap; o.constellation = sl.d_const; o.constellation_cap = d_ccap;
     o.bits_a = sl.d_a; o.bits_b = sl.d_b; o.bits_cap = d_bcap; o.counts = sl.d_cnt;
     o.audio = sl.d_audio; o.audio_cap = d_acap;
-    chk(qrl_demod_process(d_h, sl.d_iq, d_chunk, n, &o), "qrl_demod_process");
+    if (sc16) chk(qrl_demod_process_sc16(d_h, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n, &o), "qrl_demod_process_sc16");
+    else chk(qrl_demod_process(d_h, sl.d_iq, d_chunk, n, &o), "qrl_demod_process");
     chk(qrl_demod_stream_wait(d_h, cs), "qrl_demod_stream_wait");
     const size_t N = (size_t)d_n;
     if (d_acap) hchk(hipMemcpyAsync(sl.h_audio, sl.d_audio, N * d_acap * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");

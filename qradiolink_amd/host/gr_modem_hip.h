@@ -52,6 +52,10 @@ public:
     void stop() { flush(); }
     // one scheduler pass: n new samples (even, <= max_chunk) of every stream, iq[s] = host pointer of stream s
     void work(const gr_complex* const* iq, size_t n);
+    // the same for 16-bit integer I/Q (iq[s] = n interleaved int16 I, Q pairs): replaces the SDR driver's sc16 -> fc32 conversion.  Handles at
+    // device_samp_rate >= 2 Msps, max_chunk a multiple of 4, spectrum tap off; x = (float)v * scale, scale 1 / 32768 unless set_sc16_scale
+    void work(const int16_t* const* iq, size_t n);
+    void set_sc16_scale(float scale);
     void flush();                                              // waits for the call in flight and harvests it
     std::vector<unsigned char>* getData(int stream = 0) { return getData(1, stream); }
     virtual std::vector<unsigned char>* getData(int nr, int stream);   // nr = 1: bits A (port 2), nr = 2: bits B (port 3); nullptr = nothing yet (virtual: tests tap the bits)
@@ -128,6 +132,8 @@ private:
     float* d_fftout = nullptr; std::vector<float> d_level, d_fftlast;
     void* d_copy = nullptr;                                   // hipStream_t for the copy-out
     slot* d_slot[2] = {nullptr, nullptr};
+    void work_any(const void* const* iq, size_t n, bool sc16);   // both work() overloads
+    float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0, d_acap = 0;
     int d_squelch = -140; float d_agc_attack = 0.1f, d_agc_decay = 0.1f;
