@@ -280,6 +280,23 @@ size_t qrl_mod_samples_per_block(const qrl_mod* m, size_t* bytes_per_block);   /
  * iq[2*(b*out_stride + k)], k < nbytes*8*sps (device cf32).  State (scrambler, encoder, differential symbol, pulse-shaping
  * history) carries across calls; asynchronous on the handle's stream. */
 int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, float* iq, size_t out_stride);
+/* like qrl_mod_process, but iq is interleaved int16 I, Q (sc16, 4 bytes per sample: what UHD / SoapySDR / LimeSuite / HackRF put on the
+ * wire): sample k of stream b at iq[2*(b*out_stride + k)] (I) and iq[2*(b*out_stride + k) + 1] (Q).  Replaces the driver's own
+ * fc32 -> sc16 converter: the kernel that would store the cf32 sample converts it in registers in front of the store (half the output
+ * buffer, half the download, no device-rate cf32 copy in memory).  Per component r = rintf(x * scale) -- one rounded f32 multiply, round
+ * to nearest even -- saturated to [-32768, 32767]; NaN gives 0 (the float_to_short rule); x is exactly the float qrl_mod_process stores.
+ * scale: qrl_mod_set_sc16_scale, default 32767.0f (1.0 -> 32767); the setter takes effect from the next call and refuses a non-finite or
+ * zero value with QRL_ERR_ARG.  The format belongs to the CALL, not the handle: the carried state is cf32, so cf32 and sc16 calls may
+ * alternate on one handle and give the converted concatenated stream; counts, M17's multiples of 3 bytes, zero runs, carrier offsets,
+ * retune, reset and asynchrony are those of qrl_mod_process.  Every modem type, with or without the back end, every device rate.
+ * iq must be 4-byte aligned (one packed store per sample), else QRL_ERR_ARG; out_stride (samples) may be any value >= the call's sample
+ * count, nothing outside those samples of a row is written.
+ * qrl_mod_set_sc16_clip_counts: counts = device pointer to `batch` uint32, or NULL (the default: no counting).  Every following sc16 call
+ * ADDS to counts[b] the components of stream b whose r lay outside [-32768, 32767] (I and Q separately; +-inf counts, NaN does not); the
+ * caller zeroes the array; the values are valid once the handle's stream has passed the call.  cf32 calls never touch it. */
+int qrl_mod_process_sc16(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int16_t* iq, size_t out_stride);
+int qrl_mod_set_sc16_scale(qrl_mod* m, float scale);
+int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts);
 int qrl_mod_sync(qrl_mod* m);
 void* qrl_mod_stream(qrl_mod* m);
 
@@ -416,6 +433,12 @@ int qrl_synth_add_zero_runs(qrl_synth* h, const qrl_zero_run* runs, size_t n);
 int qrl_synth_set_bb_gain(qrl_synth* s, float value);
 size_t qrl_synth_out_cap(const qrl_synth* s, size_t n);
 int qrl_synth_process(qrl_synth* s, const int16_t* in, size_t stride, size_t n, float* iq, size_t out_stride, size_t* produced);
+/* sc16 output, as qrl_mod_process_sc16 (same rule, layout, alignment, default scale 32767.0f, clip counters per stream of the batch):
+ * `produced` and everything else as qrl_synth_process.  Multi-carrier: the synthesizer converts in its store.  Single carrier: the
+ * resampler's ring row of the call is converted by a small kernel of its own (250 ksps; the resampler is shared with the receivers). */
+int qrl_synth_process_sc16(qrl_synth* s, const int16_t* in, size_t stride, size_t n, int16_t* iq, size_t out_stride, size_t* produced);
+int qrl_synth_set_sc16_scale(qrl_synth* s, float scale);
+int qrl_synth_set_sc16_clip_counts(qrl_synth* s, uint32_t* counts);
 int qrl_synth_sync(qrl_synth* s);
 
 /* ---- device deframer (reference src/gr/gr_deframer_bb.cpp:24-48,83-185; instances gr_demod_base.cpp:171-178) -----------
@@ -566,6 +589,11 @@ size_t qrl_amod_samples_per_sample(const qrl_amod* m);
 size_t qrl_amod_last_count(const qrl_amod* m);
 size_t qrl_amod_out_cap(const qrl_amod* m, size_t n);
 int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, float* iq, size_t out_stride);
+/* sc16 output, as qrl_mod_process_sc16 (same rule, layout, alignment, default scale 32767.0f, clip counters): qrl_amod_last_count, SSB's
+ * whole chunks of 1024 and the out_stride bound (qrl_amod_out_cap) are those of qrl_amod_process. */
+int qrl_amod_process_sc16(qrl_amod* m, const float* audio, size_t stride, size_t n, int16_t* iq, size_t out_stride);
+int qrl_amod_set_sc16_scale(qrl_amod* m, float scale);
+int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts);
 int qrl_amod_sync(qrl_amod* m);
 void* qrl_amod_stream(qrl_amod* m);
 

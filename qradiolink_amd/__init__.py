@@ -117,6 +117,9 @@ def load_library():
     lib.qrl_amod_out_cap.argtypes = [vp, sz]
     lib.qrl_amod_out_cap.restype = sz
     lib.qrl_amod_process.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_amod_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_amod_set_sc16_scale.argtypes = [vp, C.c_float]
+    lib.qrl_amod_set_sc16_clip_counts.argtypes = [vp, vp]
     lib.qrl_amod_sync.argtypes = [vp]
     lib.qrl_amod_stream.argtypes = [vp]
     lib.qrl_amod_stream.restype = vp
@@ -172,6 +175,9 @@ def load_library():
     lib.qrl_mod_samples_per_byte.restype = sz
     lib.qrl_mod_samples_per_byte.argtypes = [vp]
     lib.qrl_mod_process.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_mod_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_mod_set_sc16_scale.argtypes = [vp, C.c_float]
+    lib.qrl_mod_set_sc16_clip_counts.argtypes = [vp, vp]
     lib.qrl_mod_sync.argtypes = [vp]
     lib.qrl_mod_stream.restype = vp
     lib.qrl_mod_stream.argtypes = [vp]
@@ -205,6 +211,9 @@ def load_library():
     lib.qrl_synth_out_cap.restype = sz
     lib.qrl_synth_out_cap.argtypes = [vp, sz]
     lib.qrl_synth_process.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(sz)]
+    lib.qrl_synth_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(sz)]
+    lib.qrl_synth_set_sc16_scale.argtypes = [vp, C.c_float]
+    lib.qrl_synth_set_sc16_clip_counts.argtypes = [vp, vp]
     lib.qrl_synth_sync.argtypes = [vp]
     lib.qrl_deframer_create.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.qrl_deframer_destroy.argtypes = [vp]
@@ -235,12 +244,12 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_destroy", "qrl_demod_reset", "qrl_demod_set_carrier_offset", "qrl_demod_set_carrier_offsets", "qrl_demod_set_option", "qrl_demod_set_dmo_output", "qrl_demod_stream_wait", "qrl_demod_out_caps",
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
-    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_sync", "qrl_amod_stream",
+    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
-    "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
+    "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_process_sc16", "qrl_mod_set_sc16_scale", "qrl_mod_set_sc16_clip_counts", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
     "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_sync",
-    "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process",
+    "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process", "qrl_synth_process_sc16", "qrl_synth_set_sc16_scale", "qrl_synth_set_sc16_clip_counts",
     "qrl_synth_sync",
     "qrl_rssi_create", "qrl_rssi_destroy", "qrl_rssi_reset", "qrl_rssi_set_level", "qrl_rssi_process", "qrl_rssi_sync", "qrl_rssi_stream",
     "qrl_fft_create", "qrl_fft_destroy", "qrl_fft_set_enabled", "qrl_fft_set_fft_size", "qrl_fft_get_fft_size", "qrl_fft_set_window_type",
@@ -761,7 +770,37 @@ class Fft:
             self.h = C.c_void_p()
 
 
-class Synth:
+class _Sc16Tx:
+    """int16 IQ (sc16) output of the transmitters: the setters of qrl_{mod,amod,synth}_set_sc16_*; `_sc16_abi` names the family."""
+    _sc16_clip = None
+
+    def set_sc16_scale(self, scale):
+        """r = rint(x * scale) per component for the int16 calls from the next one on (default 32767: 1.0 -> 32767)"""
+        name = "qrl_%s_set_sc16_scale" % self._sc16_abi
+        _check(getattr(self.lib, name)(self.h, C.c_float(scale)), name)
+
+    def set_sc16_clip_counts(self, counts):
+        """counts: a cuda int32 / uint32 tensor [batch] (the caller zeroes it) that every following process_sc16 call ADDS the clipped
+        components of each stream to, or None to switch counting off.  The object keeps a reference to it."""
+        name = "qrl_%s_set_sc16_clip_counts" % self._sc16_abi
+        if counts is not None:
+            assert counts.is_cuda and counts.element_size() == 4 and counts.dim() == 1 and counts.shape[0] == self.batch and counts.is_contiguous()
+        _check(getattr(self.lib, name)(self.h, None if counts is None else counts.data_ptr()), name)
+        self._sc16_clip = counts
+
+    def _sc16_out(self, out, count, device, bound=True):
+        """the [batch, stride, 2] int16 buffer of a call of `count` samples per stream: the caller's (its pitch is out_stride), or a fresh one.
+        bound=False: `count` is an upper bound only and the library checks out_stride against the call's own count"""
+        t = self.torch
+        if out is None:
+            return t.empty((self.batch, max(count, 1), 2), dtype=t.int16, device=device)
+        assert out.is_cuda and out.dtype == t.int16 and out.dim() == 3 and out.shape[0] == self.batch and out.shape[2] == 2
+        assert out.stride(2) == 1 and out.stride(1) == 2 and out.stride(0) % 2 == 0
+        assert not bound or out.shape[1] >= count
+        return out
+
+
+class Synth(_Sc16Tx):
     """Multi-carrier MMDVM transmitter: mirrors make_gr_mod_mmdvm_multi2 (reference src/gr/gr_mod_mmdvm_multi2.cpp).
     process(x) takes int16 cuda [batch, num_channels, n] (24 ksps FM baseband per channel) and returns complex64 cuda
     [batch, produced] at 250 ksps."""
@@ -787,6 +826,21 @@ class Synth:
         produced = C.c_size_t(0)
         t.cuda.current_stream().synchronize()
         _check(self.lib.qrl_synth_process(self.h, x.data_ptr(), n, n, out.data_ptr(), cap, C.byref(produced)), "qrl_synth_process")
+        _check(self.lib.qrl_synth_sync(self.h), "qrl_synth_sync")
+        return out[:, :produced.value]
+
+    _sc16_abi = "synth"
+
+    def process_sc16(self, x, out=None):
+        """process() with int16 IQ out: [batch, produced, 2] (qrl_synth_process_sc16); out: a preallocated [batch, stride, 2] int16 cuda tensor"""
+        t = self.torch
+        assert x.is_cuda and x.dtype == t.int16 and x.dim() == 3 and x.shape[0] == self.batch and x.shape[1] == self.nch
+        x = x.contiguous()
+        n = x.shape[2]
+        out = self._sc16_out(out, self.lib.qrl_synth_out_cap(self.h, n), x.device, bound=False)
+        produced = C.c_size_t(0)
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_synth_process_sc16(self.h, x.data_ptr(), n, n, out.data_ptr(), out.stride(0) // 2, C.byref(produced)), "qrl_synth_process_sc16")
         _check(self.lib.qrl_synth_sync(self.h), "qrl_synth_sync")
         return out[:, :produced.value]
 
@@ -842,7 +896,7 @@ class FrameSync:
             self.h = C.c_void_p()
 
 
-class Mod:
+class Mod(_Sc16Tx):
     """Batch TX modulator: mirrors make_gr_mod_qpsk (reference src/gr/gr_mod_qpsk.cpp:19-30).
     process(bytes) takes a torch cuda uint8 tensor [batch, nbytes] (packed bytes, as gr_byte_source hands them
     out) and returns a complex64 cuda tensor [batch, nbytes * 8 * sps]."""
@@ -888,6 +942,26 @@ class Mod:
         self.sync()
         return out
 
+    _sc16_abi = "mod"
+
+    def process_sc16_async(self, data, out=None):
+        """Queue one call with int16 IQ out (qrl_mod_process_sc16): returns the int16 cuda tensor [batch, count, 2], a view of `out` when a
+        preallocated [batch, stride, 2] buffer is given (its pitch is out_stride).  Valid after sync()."""
+        assert data.is_cuda and data.dtype == self.torch.uint8 and data.dim() == 2 and data.shape[0] == self.batch
+        assert data.stride(1) == 1
+        n = data.shape[1]
+        count = n // self.bytes_per_block * self.spblock
+        out = self._sc16_out(out, count, data.device)
+        self.torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_mod_process_sc16(self.h, data.data_ptr(), data.stride(0), n, out.data_ptr(), out.stride(0) // 2),
+               "qrl_mod_process_sc16")
+        return out[:, :count]
+
+    def process_sc16(self, data):
+        out = self.process_sc16_async(data)
+        self.sync()
+        return out
+
     def reset(self):
         _check(self.lib.qrl_mod_reset(self.h), "qrl_mod_reset")
 
@@ -914,7 +988,7 @@ class Mod:
             self.h = C.c_void_p()
 
 
-class AMod:
+class AMod(_Sc16Tx):
     """Batch analogue voice modulator: mirrors make_gr_mod_nbfm (src/gr/gr_mod_nbfm.cpp:19-77) and make_gr_mod_ssb (gr_mod_ssb.cpp:19-82).
     process(audio) takes a float32 cuda tensor [batch, n] at 8 ksps (NBFM: n a multiple of 4) and returns complex64 at 1 Msps:
     [batch, 125 n] for NBFM, 125 x the audio items of the 1024-chunks the call completed for SSB."""
@@ -936,6 +1010,19 @@ class AMod:
         _check(self.lib.qrl_amod_process(self.h, audio.data_ptr(), audio.stride(0), n, out.data_ptr(), out.stride(0)), "qrl_amod_process")
         _check(self.lib.qrl_amod_sync(self.h), "qrl_amod_sync")
         return out[:, :self.lib.qrl_amod_last_count(self.h)]     # SSB: whole chunks of 1024 audio items only (the cessb stretcher)
+
+    _sc16_abi = "amod"
+
+    def process_sc16(self, audio, out=None):
+        """process() with int16 IQ out: [batch, count, 2] (qrl_amod_process_sc16); out: a preallocated [batch, stride, 2] int16 cuda tensor"""
+        t = self.torch
+        assert audio.is_cuda and audio.dtype == t.float32 and audio.dim() == 2 and audio.shape[0] == self.batch and audio.stride(1) == 1
+        n = audio.shape[1]
+        out = self._sc16_out(out, self.lib.qrl_amod_out_cap(self.h, n), audio.device, bound=False)
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_amod_process_sc16(self.h, audio.data_ptr(), audio.stride(0), n, out.data_ptr(), out.stride(0) // 2), "qrl_amod_process_sc16")
+        _check(self.lib.qrl_amod_sync(self.h), "qrl_amod_sync")
+        return out[:, :self.lib.qrl_amod_last_count(self.h)]
 
     def set_bb_gain(self, g):
         _check(self.lib.qrl_amod_set_bb_gain(self.h, C.c_float(g)), "qrl_amod_set_bb_gain")

@@ -63,6 +63,7 @@ struct qrl_amod {
     bool backend = false; int be_interp = 1, be_nt = 0; DevBuf<float> be_taps;
     DevBuf<float2> bb, be_ring; size_t bb_stride = 0; uint32_t be_mask = 0;
     Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
+    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_amod_process_sc16 (the format itself belongs to the call)
     size_t cap_1msps(size_t n) const { return am ? n * (size_t)sps : ssb ? (n + 1024) * (size_t)sps : n * 25 / 4 * (size_t)sps; }
     int init_back_end()
     {
@@ -278,7 +279,10 @@ int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz)
 void* qrl_amod_stream(qrl_amod* m) { return m ? m->stream : nullptr; }
 int qrl_amod_sync(qrl_amod* m) { if (!m) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(m->stream)); return QRL_OK; }
 
-int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, float* iq, size_t out_stride)
+}  // extern "C"
+
+// qrl_amod_process / qrl_amod_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out), seen only by the kernel that stores to it
+static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, void* iq, size_t out_stride, const Sc16Out sc)
 {
     if (!m || (!audio && n && !m->cw) || (!iq && n)) return QRL_ERR_ARG;
     if (n > m->cfg.max_samples) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_samples");
@@ -291,17 +295,18 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
     // with the back end the chain's 1 Msps output goes to the handle's own linear buffer, and from there through the rotator (and the interpolator)
     float2* const mod_out = m->backend ? m->bb.p : reinterpret_cast<float2*>(iq);
     const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
+    const Sc16Out mod_sc = m->backend ? Sc16Out{} : sc;
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
         if (!m->backend || !n1) return;
         TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
         m->rot.fill(rp);
         if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
-        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
+        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; rp.sc = sc; }
         launch_tx_rot(rp, B, s);
         if (m->be_interp > 1) {
             TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = m->n_bb * (uint64_t)m->be_interp; bp.count = n1 * (uint32_t)m->be_interp;
             bp.taps = m->be_taps.p; bp.nt = m->be_nt; bp.interp = m->be_interp;
-            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride;
+            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride; bp.sc = sc;
             launch_tx_interp_c(bp, B, s);
         }
         m->n_bb += n1;
@@ -326,7 +331,7 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
         launch_scale_c(m1, m->n1m, c1m, 0.5f, B, s);                                // _amplify
         launch_scale_c(m1, m->n1m, c1m, m->bb_gain, B, s);                          // _bb_gain
         FirCccParams ff{}; ff.in = m1; ff.out = m2; ff.q0 = m->n1m; ff.count = c1m; ff.taps = m->t_chan.p; ff.nt = m->n_chan;
-        ff.port = mod_out; ff.port_cap = mod_stride;
+        ff.port = mod_out; ff.port_cap = mod_stride; ff.sc = mod_sc;
         launch_an_fir_ccc(ff, B, s);                                                // _filter: straight into the caller's buffer (or the back end's)
         back_end(c1m);
         HIPCHK(hipGetLastError());
@@ -360,7 +365,7 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
         launch_scale_c(c3, m->ns, cs, 0.9f, B, s);                                  // _amplify
         launch_scale_c(c3, m->ns, cs, m->bb_gain, B, s);                            // _bb_gain
         TxInterpCParams xp{}; xp.in = c3; xp.n0 = m->ns * (uint64_t)m->sps; xp.count = cs * (uint32_t)m->sps;
-        xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride;
+        xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride; xp.sc = mod_sc;
         if (xp.count) launch_tx_interp_c(xp, B, s);                                 // _resampler
         back_end(xp.count);
         HIPCHK(hipGetLastError());
@@ -392,7 +397,7 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
     launch_scale_c(flt, m->n50, c50, 0.8f, B, s);                                   // _amplify
     launch_scale_c(flt, m->n50, c50, m->bb_gain, B, s);                             // _bb_gain
     TxInterpCParams xp{}; xp.in = flt; xp.n0 = m->n50 * (uint64_t)m->sps; xp.count = c50 * (uint32_t)m->sps;
-    xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride;
+    xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride; xp.sc = mod_sc;
     launch_tx_interp_c(xp, B, s);                                                   // _resampler
     back_end(xp.count);
     HIPCHK(hipGetLastError());
@@ -400,5 +405,26 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
     m->n8 += c8; m->n50 += c50; m->last = (size_t)c50 * m->sps * m->be_interp;
     return QRL_OK;
 }
+
+extern "C" {
+
+int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, float* iq, size_t out_stride)
+{
+    return amod_process(m, audio, stride, n, iq, out_stride, Sc16Out{});
+}
+int qrl_amod_process_sc16(qrl_amod* m, const float* audio, size_t stride, size_t n, int16_t* iq, size_t out_stride)
+{
+    if (!m) return QRL_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_amod_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
+    return amod_process(m, audio, stride, n, iq, out_stride, Sc16Out{1, m->sc_scale, m->sc_clip});
+}
+int qrl_amod_set_sc16_scale(qrl_amod* m, float scale)
+{
+    if (!m) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_amod_set_sc16_scale: scale must be finite and non-zero");
+    m->sc_scale = scale;
+    return QRL_OK;
+}
+int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts) { if (!m) return QRL_ERR_ARG; m->sc_clip = counts; return QRL_OK; }
 
 }

@@ -109,6 +109,34 @@ __device__ __forceinline__ float branchless_clip(float x, float clip)
     return 0.5f * x1;
 }
 
+// ---- float -> int16 in front of the transmitters' sc16 stores (qrl_*_process_sc16): the float_to_short rule of the oracle's f2s ----
+// per component r = rintf(x * scale) (one rounded f32 multiply, round to nearest even), saturated to [-32768, 32767]; NaN gives 0.
+// nclip = components with r outside the int16 range (+-inf included, NaN not).  The pair is packed I low, Q high: one 4-byte store.
+__device__ __forceinline__ int sc16_sat(float r) { return r != r ? 0 : (int)fminf(fmaxf(r, -32768.0f), 32767.0f); }
+__device__ __forceinline__ uint32_t f2_to_sc16(float2 v, float scale, uint32_t& nclip)
+{
+    const float ri = rintf(v.x * scale), rq = rintf(v.y * scale);
+    nclip = (uint32_t)(ri > 32767.0f || ri < -32768.0f) + (uint32_t)(rq > 32767.0f || rq < -32768.0f);
+    return ((uint32_t)sc16_sat(ri) & 0xffffu) | ((uint32_t)sc16_sat(rq) << 16);
+}
+// The sc16 store of every terminal TX kernel: lane `valid` writes sample v to row[idx]; clip != nullptr adds the wave's clipped components
+// to *clip (the counter of this workgroup's stream) -- ballot + popcount, one atomicAdd by the first active lane, none when nothing clipped.
+// The ballots see the lanes that are active at the call, and the leader is the first of THOSE: under divergence each group of lanes reduces and adds
+// its own share, so the sum stays exact wherever this is called (lanes that left the kernel earlier, or that sit in another branch, are simply not in
+// it).  Calling it with the wave converged is a matter of cost only: then a wave issues at most one atomic per store.
+__device__ __forceinline__ void sc16_store(uint32_t* row, size_t idx, float2 v, bool valid, float scale, uint32_t* clip)
+{
+    uint32_t nclip;
+    const uint32_t w = f2_to_sc16(v, scale, nclip);
+    if (valid) row[idx] = w;
+    if (clip) {
+        if (!valid) nclip = 0;
+        const uint32_t n = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(nclip >= 1u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(nclip == 2u));
+        const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+        if (n && (int)__lane_id() == __ffsll((unsigned long long)act) - 1) atomicAdd(clip, n);
+    }
+}
+
 __device__ __forceinline__ float phase_wrap(float phase)
 {
     const double TWO_PI = 6.283185307179586476925286766559;

@@ -184,6 +184,7 @@ void launch_tx_qpsk_bits(const TxBitsParams& p, int batch, hipStream_t s)
     hipLaunchKernelGGL(k_tx_qpsk_bits, dim3(batch), dim3(64), lds, s, p);
 }
 
+template <bool SC>
 __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
 {
     __shared__ float taps_s[256];
@@ -208,7 +209,8 @@ __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
     }
     ar *= P.amp; ai *= P.amp;                          // multiply_const_cc(0.6)
     ar *= P.bb_gain; ai *= P.bb_gain;                  // multiply_const_cc(bb_gain)
-    P.out[(size_t)b * P.out_stride + t] = make_float2(ar, ai);
+    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else P.out[(size_t)b * P.out_stride + t] = make_float2(ar, ai);
 }
 
 // Small interpolation factors (QPSK-250k: 4 samples per symbol, 61 taps): one thread per SYMBOL writes its I output samples.
@@ -216,7 +218,8 @@ __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
 // ~16 byte loads and ~16 table loads per output sample (C5: 4.7 ms for 268 M samples, 0.45 TB/s of stores); the taps are scalar
 // operands (round 4: they were LDS broadcasts, 64 ds_reads per thread beside 64 packed fmas).
 // Same fmaf chain per output (j ascending); the zero-padded taps / the zero symbols in front of the stream add +0.
-template <int I, int J>
+// SC: the packed int16 pair is made where the ordered store reads ys[][] (256 contiguous bytes per wave and store instruction).
+template <int I, int J, bool SC>
 __global__ __launch_bounds__(256) void k_tx_interp_sym(const TxInterpParams P)
 {
     __shared__ float2 xs[256 + J];
@@ -255,10 +258,21 @@ __global__ __launch_bounds__(256) void k_tx_interp_sym(const TxInterpParams P)
     // 32-byte stride.  Through the LDS they leave in order, 512 contiguous bytes per store instruction (k_dec2_fir: same finding).
     float2* o = P.out + (size_t)b * P.out_stride + (size_t)s0 * I;
     const uint32_t nout = (nsym > s0 ? (nsym - s0 < 256u ? nsym - s0 : 256u) : 0u) * (uint32_t)I;
+    if constexpr (SC) {
+        uint32_t* o16 = reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride + (size_t)s0 * I;
+        uint32_t* clip = P.sc.clip ? P.sc.clip + b : nullptr;
 #pragma unroll
-    for (int k = 0; k < I; ++k) {
-        const uint32_t idx = (uint32_t)tid + 256u * k;            // output s0 * I + idx = (symbol idx / I, phase idx % I)
-        if (idx < nout) o[idx] = ys[idx % I][idx / I];
+        for (int k = 0; k < I; ++k) {
+            const uint32_t idx = (uint32_t)tid + 256u * k;
+            const bool ok = idx < nout;                           // (ys[] behind nout was never written: read column 0 there, the value is dropped)
+            sc16_store(o16, idx, ys[idx % I][ok ? idx / I : 0u], ok, P.sc.scale, clip);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < I; ++k) {
+            const uint32_t idx = (uint32_t)tid + 256u * k;            // output s0 * I + idx = (symbol idx / I, phase idx % I)
+            if (idx < nout) o[idx] = ys[idx % I][idx / I];
+        }
     }
 }
 
@@ -266,10 +280,13 @@ void launch_tx_interp(const TxInterpParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
     if (p.interp == 4 && p.nt <= 64 && p.n0 % 4 == 0 && p.count % 4 == 0) {
-        hipLaunchKernelGGL((k_tx_interp_sym<4, 16>), dim3((p.count / 4 + 255) / 256, batch), dim3(256), 0, s, p);
+        const dim3 grid((p.count / 4 + 255) / 256, batch);
+        if (p.sc.on) hipLaunchKernelGGL((k_tx_interp_sym<4, 16, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_tx_interp_sym<4, 16, false>), grid, dim3(256), 0, s, p);
         return;
     }
-    hipLaunchKernelGGL(k_tx_interp, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    if (p.sc.on) hipLaunchKernelGGL(k_tx_interp<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_tx_interp<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 // ---- FSK family (gr_mod_2fsk.cpp:63-99, gr_mod_gmsk.cpp:68-95):
@@ -353,6 +370,7 @@ void launch_tx_fm(const TxFmParams& p, int batch, hipStream_t s)
     hipLaunchKernelGGL(k_tx_fm, dim3((batch + 63) / 64), dim3(64), 0, s, p, batch);
 }
 
+template <bool SC>
 __global__ __launch_bounds__(256) void k_tx_interp_c(const TxInterpCParams P)
 {
     __shared__ float taps_s[2048];
@@ -376,7 +394,8 @@ __global__ __launch_bounds__(256) void k_tx_interp_c(const TxInterpCParams P)
         ar = fmaf(h, x.x, ar);
         ai = fmaf(h, x.y, ai);
     }
-    if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = make_float2(ar, ai);
+    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = make_float2(ar, ai);
     else P.out[(size_t)b * P.out_stride + t] = make_float2(ar, ai);
 }
 // gr_mod_m17 (reference src/gr/gr_mod_m17.cpp:47-58,77-80): packed_to_unpacked(1, MSB) -> pack_k_bits(2) -> map{2, 3, 1, 0}: four symbol
@@ -429,12 +448,13 @@ void launch_tx_f2c(RingF in, RingC out, uint64_t n0, uint32_t count, float g, in
 void launch_tx_interp_c(const TxInterpCParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    hipLaunchKernelGGL(k_tx_interp_c, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    if (p.sc.on && !p.out_ring.p) hipLaunchKernelGGL(k_tx_interp_c<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_tx_interp_c<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 // ---- gr_mod_base back end (reference src/gr/gr_mod_base.cpp:38,249-258): rotator_cc(2 pi offset / 1e6) at 1 Msps, then
 // rational_resampler_ccf(fs/1e6, 1, low_pass(I, fs, 480k, 20k, BH)) (k_tx_interp_c).  Exact 2^-64-turn NCO as on RX.
-template <bool PS>
+template <bool PS, bool SC>
 __global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P_)
 {
     ROT_VIEW(TxRotParams, PS, P, P_, blockIdx.y);
@@ -446,14 +466,16 @@ __global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P_)
     const uint64_t kk = n - P.rot_nbase;
     const float2 hi = sincos_turn(P.rot_acc + ((kk >> 9) << 9) * P.rot_inc);
     const float2 y = cmul_fma(x, cmul_fma(hi, P.rot_lo[(uint32_t)kk & 511u]));
-    if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = y;
+    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, y, true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = y;
     else P.out[(size_t)b * P.out_stride + t] = y;
 }
 void launch_tx_rot(const TxRotParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    if (p.rot_acc_s) hipLaunchKernelGGL(k_tx_rot<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(k_tx_rot<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    const bool sc = p.sc.on && !p.out_ring.p;   // the offset-only back end: the rotator is the terminal kernel
+    const auto kern = p.rot_acc_s ? (sc ? k_tx_rot<true, true> : k_tx_rot<true, false>) : (sc ? k_tx_rot<false, true> : k_tx_rot<false, false>);
+    hipLaunchKernelGGL(kern, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 }  // namespace qrl

@@ -2,6 +2,7 @@
 // per channel int16 -> FM modulator -> LPF -> x0.8 -> 25/24 resampler, then pfb_synthesizer_ccf(10) -> x(1/N) -> bb gain.
 #include "host_common.hpp"
 #include "firdes.hpp"
+#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <new>
@@ -17,6 +18,7 @@ struct qrl_synth {
     DevBuf<float> filt_taps, rs_taps, syn_taps, rA, phase; DevBuf<float2> twiddle, rB, rC, rD;
     uint32_t m1 = 0, m25 = 0; uint64_t n1 = 0, n25 = 0;
     int port_chan[16];
+    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_synth_process_sc16 (the format itself belongs to the call)
     std::vector<ZeroRun> zero_runs; DevBuf<ZeroRun> zero_dev;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
     ~qrl_synth() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int reset_state() {
@@ -120,7 +122,10 @@ int qrl_synth_add_zero_runs(qrl_synth* h, const qrl_zero_run* runs, size_t n)
 int qrl_synth_set_bb_gain(qrl_synth* h, float g) { if (!h) return QRL_ERR_ARG; h->bb_gain = g; return QRL_OK; }
 size_t qrl_synth_out_cap(const qrl_synth* h, size_t n) { return h ? (n * h->rs_I / h->rs_D + 2) * (h->single ? 1 : 10) : 0; }
 
-int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, float* iq, size_t out_stride, size_t* produced)
+}  // extern "C"
+
+// qrl_synth_process / qrl_synth_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out)
+static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, void* iq, size_t out_stride, size_t* produced, const Sc16Out sc)
 {
     if (!h || (!in && n) || (!iq && n)) return QRL_ERR_ARG;
     if (n > h->cfg.max_samples) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_samples");
@@ -147,9 +152,11 @@ int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, 
     if (h->single) launch_scale_c(ff.out, h->n1, c1, h->bb_gain, S, h->stream);                      // gr_mod_mmdvm.cpp:59-61: bb gain BEFORE the resampler
     ResampParams rp{}; rp.in = nullptr; rp.in_ring = ff.out; rp.n0 = h->n1; rp.n = c1;
     rp.out = RingC{h->rD.p, h->m25}; rp.q0 = h->n25; rp.q_count = c25; rp.taps = h->rs_taps.p; rp.I = h->rs_I; rp.D = h->rs_D; rp.Jp = h->rs_Jp;
-    if (h->single) { rp.port = reinterpret_cast<float2*>(iq); rp.port_cap = out_stride; }           // the resampler output IS the 250 ksps signal
+    if (h->single && !sc.on) { rp.port = reinterpret_cast<float2*>(iq); rp.port_cap = out_stride; }   // the resampler output IS the 250 ksps signal
     launch_resamp(rp, S, h->stream);
     if (h->single) {
+        // sc16: k_resamp is shared with the receivers and keeps its code; its ring row of this call is converted by a kernel of its own
+        if (sc.on) launch_ring_store_sc16(rp.out, h->n25, (uint32_t)std::min<size_t>(c25, out_stride), reinterpret_cast<uint32_t*>(iq), out_stride, sc, S, h->stream);
         HIPCHK(hipGetLastError());
     if (qrl::take_launch_error()) return QRL_ERR_HIP;
         h->n1 = n1_1; h->n25 = n25_1;
@@ -163,7 +170,7 @@ int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, 
     SynthParams yp{}; yp.in = rp.out; yp.nch = N; for (int p = 0; p < 16; ++p) yp.port_chan[p] = h->port_chan[p];
     yp.blk0 = h->n25; yp.nblk = c25; yp.taps = h->syn_taps.p; yp.twiddle = h->twiddle.p; yp.M = 10; yp.J = h->J;
     yp.level = 1.0f / (float)N; yp.bb_gain = h->bb_gain;                                             // _divide_level, _bb_gain :91-95
-    yp.out = reinterpret_cast<float2*>(iq); yp.out_stride = out_stride; yp.out_cap = out_stride;
+    yp.out = reinterpret_cast<float2*>(iq); yp.out_stride = out_stride; yp.out_cap = out_stride; yp.sc = sc;
     launch_pfb_synth(yp, B, h->stream);
     HIPCHK(hipGetLastError());
     if (qrl::take_launch_error()) return QRL_ERR_HIP;
@@ -171,6 +178,27 @@ int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, 
     if (produced) *produced = (size_t)c25 * 10;
     return QRL_OK;
 }
+
+extern "C" {
+
+int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, float* iq, size_t out_stride, size_t* produced)
+{
+    return synth_process(h, in, stride, n, iq, out_stride, produced, Sc16Out{});
+}
+int qrl_synth_process_sc16(qrl_synth* h, const int16_t* in, size_t stride, size_t n, int16_t* iq, size_t out_stride, size_t* produced)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_synth_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
+    return synth_process(h, in, stride, n, iq, out_stride, produced, Sc16Out{1, h->sc_scale, h->sc_clip});
+}
+int qrl_synth_set_sc16_scale(qrl_synth* h, float scale)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_synth_set_sc16_scale: scale must be finite and non-zero");
+    h->sc_scale = scale;
+    return QRL_OK;
+}
+int qrl_synth_set_sc16_clip_counts(qrl_synth* h, uint32_t* counts) { if (!h) return QRL_ERR_ARG; h->sc_clip = counts; return QRL_OK; }
 int qrl_synth_sync(qrl_synth* h)
 {
     if (!h) return QRL_ERR_ARG;

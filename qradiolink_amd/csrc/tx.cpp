@@ -41,6 +41,7 @@ struct qrl_mod {
     DevBuf<float2> bb; size_t bb_stride = 0;           // modulator output, linear, one call's worth
     DevBuf<float2> be_ring; uint32_t be_mask = 0;       // rotated 1 Msps signal (interpolator history)
     Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
+    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_mod_process_sc16: the format belongs to the call, these two to the handle
     ~qrl_mod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
     int init_state() {
         int r;
@@ -315,7 +316,10 @@ size_t qrl_mod_samples_per_byte(const qrl_mod* m)
     return spb1 * (size_t)m->be_interp;
 }
 
-int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, float* iq, size_t out_stride)
+}  // extern "C"
+
+// qrl_mod_process / qrl_mod_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out).  Only the kernel that stores to `iq` sees it.
+static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, void* iq, size_t out_stride, const Sc16Out sc)
 {
     if (!m || (!bytes && nbytes) || (!iq && nbytes)) return QRL_ERR_ARG;
     if (nbytes > m->cfg.max_bytes) return qrl_set_error(QRL_ERR_TOO_BIG, "nbytes exceeds max_bytes");
@@ -325,16 +329,17 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     const uint32_t nbits = (uint32_t)nbytes * 8;
     float2* mod_out = m->backend ? m->bb.p : reinterpret_cast<float2*>(iq);
     const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
+    const Sc16Out mod_sc = m->backend ? Sc16Out{} : sc;
     auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
         TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
         m->rot.fill(rp);
         if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
-        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; }
+        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; rp.sc = sc; }
         launch_tx_rot(rp, B, m->stream);
         if (m->be_interp > 1) {
             TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = m->n_bb * (uint64_t)m->be_interp; bp.count = n1 * (uint32_t)m->be_interp;
             bp.taps = m->be_taps.p; bp.nt = m->be_nt; bp.interp = m->be_interp;
-            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride;
+            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride; bp.sc = sc;
             launch_tx_interp_c(bp, B, m->stream);
         }
         m->n_bb += n1;
@@ -375,7 +380,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
         launch_scale_c(flt, n24, c24, 0.9f, B, m->stream);                              // _amplify
         launch_scale_c(flt, n24, c24, m->bb_gain, B, m->stream);                        // _bb_gain
         TxInterpCParams ip{}; ip.in = flt; ip.n0 = n24 / 3 * 125; ip.count = cout; ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = 125; ip.decim = 3;
-        ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride;
+        ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride; ip.sc = sc;
         launch_tx_interp_c(ip, B, m->stream);                                           // _resampler (125, 3)
         HIPCHK(hipGetLastError());
         if (qrl::take_launch_error()) return QRL_ERR_HIP;
@@ -403,7 +408,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
         rp.taps = m->ds_if_taps.p; rp.I = 50; rp.D = 13; rp.Jp = m->ds_if_Jp;
         launch_resamp(rp, B, m->stream);                                                 // _resampler_if (50, 13)
         TxInterpCParams ip{}; ip.in = r20; ip.n0 = n20 * 50ull; ip.count = c20 * 50u; ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = 50;
-        ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride;
+        ip.out = reinterpret_cast<float2*>(iq); ip.out_stride = out_stride; ip.sc = sc;
         launch_tx_interp_c(ip, B, m->stream);                                            // _resampler_rf (50, 1)
         HIPCHK(hipGetLastError());
         if (qrl::take_launch_error()) return QRL_ERR_HIP;
@@ -422,7 +427,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
         fp.phase = m->phase.p;
         launch_tx_fm(fp, B, m->stream);
         TxInterpCParams ip{}; ip.in = fp.out; ip.n0 = n1_0 * (uint64_t)m->interp2; ip.count = c1 * (uint32_t)m->interp2;
-        ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = m->interp2; ip.out = mod_out; ip.out_stride = mod_stride;
+        ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = m->interp2; ip.out = mod_out; ip.out_stride = mod_stride; ip.sc = mod_sc;
         launch_tx_interp_c(ip, B, m->stream);
         if (m->backend) back_end(ip.count);
         HIPCHK(hipGetLastError());
@@ -439,7 +444,7 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     q.table[2] = make_float2(0.707f, 0.707f);   q.table[3] = make_float2(0.707f, -0.707f);
     if (m->bpsk) { q.table[0] = make_float2(-1.0f, 0.0f); q.table[1] = make_float2(1.0f, 0.0f); }   // gr_mod_bpsk.cpp:33-35
     q.amp = 0.6f; q.bb_gain = m->bb_gain;
-    q.out = mod_out; q.out_stride = mod_stride;
+    q.out = mod_out; q.out_stride = mod_stride; q.sc = mod_sc;
     launch_tx_interp(q, B, m->stream);
     if (m->backend) back_end(q.count);
     HIPCHK(hipGetLastError());
@@ -447,6 +452,27 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
     m->nsym += nitems;
     return QRL_OK;
 }
+
+extern "C" {
+
+int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, float* iq, size_t out_stride)
+{
+    return mod_process(m, bytes, stride, nbytes, iq, out_stride, Sc16Out{});
+}
+int qrl_mod_process_sc16(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int16_t* iq, size_t out_stride)
+{
+    if (!m) return QRL_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_mod_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
+    return mod_process(m, bytes, stride, nbytes, iq, out_stride, Sc16Out{1, m->sc_scale, m->sc_clip});
+}
+int qrl_mod_set_sc16_scale(qrl_mod* m, float scale)
+{
+    if (!m) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_mod_set_sc16_scale: scale must be finite and non-zero");
+    m->sc_scale = scale;
+    return QRL_OK;
+}
+int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts) { if (!m) return QRL_ERR_ARG; m->sc_clip = counts; return QRL_OK; }
 int qrl_mod_sync(qrl_mod* m)
 {
     if (!m) return QRL_ERR_ARG;

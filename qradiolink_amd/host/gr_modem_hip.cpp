@@ -593,7 +593,7 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRData(int stream
 
 // ================================================================================================ gr_mod_base_hip
 gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_bytes)
-    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0)
+    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0), d_clipped((size_t)std::max(streams, 0), 0)
 {
     d_cw_n = std::min<size_t>(1024, d_max);   // a facade built for fewer than 1024 items per call must still key CW
 }
@@ -604,6 +604,7 @@ gr_mod_base_hip::~gr_mod_base_hip()
     if (d_bytes) (void)hipFree(d_bytes);
     if (d_audio) (void)hipFree(d_audio);
     if (d_iq) (void)hipFree(d_iq);
+    if (d_clip) (void)hipFree(d_clip);
 }
 static bool tx_mode_has_back_end(int mode)   // qrl_mod_create builds the gr_mod_base back end (rotator + interpolator) for every family but these (tx.cpp)
 {
@@ -629,6 +630,7 @@ void gr_mod_base_hip::open()
     if (d_per_stream && cfg_offset == 0.0) for (double f : d_offsets) if (f != 0.0) { cfg_offset = f; break; }
     qrl_mod* nh = nullptr; qrl_amod* nah = nullptr; uint8_t* nbytes = nullptr; float* naudio = nullptr; float* niq = nullptr;
     size_t spblock = 0, bpb = 1;
+    if (!d_clip) hchk(hipMalloc(reinterpret_cast<void**>(&d_clip), (size_t)d_n * sizeof(uint32_t)), "hipMalloc");   // one per stream, for the life of the facade
     try {
         if (analog_tx_mode(d_mode)) {
             qrl_amod_config c{};
@@ -640,6 +642,8 @@ void gr_mod_base_hip::open()
             if (d_ctcss_touched && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(nah, d_ctcss), "qrl_amod_set_ctcss");
             if (d_width.count(d_mode)) chk(qrl_amod_set_filter_width(nah, d_width[d_mode]), "qrl_amod_set_filter_width");
             if (d_mode == QRL_MODEM_CW600USB && d_cw_key) chk(qrl_amod_set_cw_k(nah, 1), "qrl_amod_set_cw_k");
+            chk(qrl_amod_set_sc16_scale(nah, d_sc16_scale), "qrl_amod_set_sc16_scale");
+            chk(qrl_amod_set_sc16_clip_counts(nah, d_clip), "qrl_amod_set_sc16_clip_counts");
             hchk(hipMalloc(reinterpret_cast<void**>(&naudio), (size_t)d_n * d_max * sizeof(float)), "hipMalloc");
             hchk(hipMalloc(reinterpret_cast<void**>(&niq), (size_t)d_n * qrl_amod_out_cap(nah, d_max) * sizeof(gr_complex)), "hipMalloc");
         } else {
@@ -647,6 +651,8 @@ void gr_mod_base_hip::open()
             c.modem_type = d_mode; c.use_mode_defaults = 1; c.batch = d_n; c.max_bytes = d_max; c.bb_gain = d_gain;
             c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
             chk(qrl_mod_create(d_rt.ctx(), &c, &nh), "qrl_mod_create");
+            chk(qrl_mod_set_sc16_scale(nh, d_sc16_scale), "qrl_mod_set_sc16_scale");
+            chk(qrl_mod_set_sc16_clip_counts(nh, d_clip), "qrl_mod_set_sc16_clip_counts");
             if (d_per_stream && backend && tx_mode_has_back_end(d_mode)) chk(qrl_mod_set_carrier_offsets(nh, d_offsets.data()), "qrl_mod_set_carrier_offsets");
             hchk(hipMalloc(reinterpret_cast<void**>(&nbytes), (size_t)d_n * d_max), "hipMalloc");
             spblock = qrl_mod_samples_per_block(nh, &bpb);     // M17: 2500 samples per 3 bytes; every other mode: samples per byte, 1
@@ -820,16 +826,51 @@ void gr_mod_base_hip::flush_sources()
     for (auto& q : d_aqueue) q.clear();
 }
 size_t gr_mod_base_hip::samples_per_byte() const { return d_h ? qrl_mod_samples_per_byte(d_h) : 0; }
-size_t gr_mod_base_hip::work(gr_complex* const* out)
+// int16 I/Q out (out[s] = interleaved int16 I, Q pairs): replaces the SDR driver's fc32 -> sc16 converter.  The modulator's last kernel converts
+// (qrl_mod_process_sc16 / qrl_amod_process_sc16: r = rintf(x * scale), saturated), the download copies 4 bytes per sample, and the per-stream counters of
+// clipped components come back with the samples (clipped()).
+void gr_mod_base_hip::set_sc16_scale(float scale)
 {
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_mod_base_hip::set_sc16_scale: finite, non-zero");
+    d_sc16_scale = scale;
+    if (d_h) chk(qrl_mod_set_sc16_scale(d_h, scale), "qrl_mod_set_sc16_scale");
+    if (d_ah) chk(qrl_amod_set_sc16_scale(d_ah, scale), "qrl_amod_set_sc16_scale");
+}
+uint64_t gr_mod_base_hip::clipped(int stream) const
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // work() adds to the totals under this lock: another thread may poll
+    return d_clipped.at((size_t)stream);
+}
+size_t gr_mod_base_hip::work(gr_complex* const* out) { return work_any(reinterpret_cast<void* const*>(out), false); }
+size_t gr_mod_base_hip::work(int16_t* const* out) { return work_any(reinterpret_cast<void* const*>(out), true); }
+size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
+{
+    const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the row pitch stays `stride` samples
+    // one call of the open analogue handle into d_iq, in the format asked for
+    auto amod = [&](const float* audio, size_t astride, size_t n, size_t stride) {
+        if (sc16) chk(qrl_amod_process_sc16(d_ah, audio, astride, n, reinterpret_cast<int16_t*>(d_iq), stride), "qrl_amod_process_sc16");
+        else chk(qrl_amod_process(d_ah, audio, astride, n, d_iq, stride), "qrl_amod_process");
+    };
+    // the samples of every stream, and for int16 the clip counters of this pass
+    auto download = [&](size_t ns, size_t stride) {
+        for (int s = 0; s < d_n && ns; ++s)
+            hchk(hipMemcpy(out[s], reinterpret_cast<const char*>(d_iq) + (size_t)s * stride * sb, ns * sb, hipMemcpyDeviceToHost), "D2H");
+        if (!sc16) return;
+        std::vector<uint32_t> c((size_t)d_n);
+        hchk(hipMemcpy(c.data(), d_clip, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
+        for (int s = 0; s < d_n; ++s) d_clipped[(size_t)s] += c[(size_t)s];
+    };
+    auto zero_clip = [&](hipStream_t ms) { if (sc16) hchk(hipMemsetAsync(d_clip, 0, (size_t)d_n * sizeof(uint32_t), ms), "hipMemsetAsync"); };
+
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // the handle and its zero-run list for the whole pass; the byte / audio queues stay under d_mutex
     if (d_ah && d_mode == QRL_MODEM_CW600USB) {   // the tone source lives on the device: nothing to upload
         const size_t stride = qrl_amod_out_cap(d_ah, d_max);
-        chk(qrl_amod_process(d_ah, nullptr, 0, d_cw_n, d_iq, stride), "qrl_amod_process");
+        zero_clip(static_cast<hipStream_t>(qrl_amod_stream(d_ah)));
+        amod(nullptr, 0, d_cw_n, stride);
         chk(qrl_amod_sync(d_ah), "qrl_amod_sync");
         const size_t ns = qrl_amod_last_count(d_ah);
-        for (int s = 0; s < d_n && ns; ++s)
-            hchk(hipMemcpy(out[s], d_iq + 2 * (size_t)s * stride, ns * sizeof(gr_complex), hipMemcpyDeviceToHost), "D2H");
+        download(ns, stride);
         return ns;
     }
     if (d_ah) {
@@ -849,11 +890,11 @@ size_t gr_mod_base_hip::work(gr_complex* const* out)
         hipStream_t ms = static_cast<hipStream_t>(qrl_amod_stream(d_ah));
         hchk(hipMemcpyAsync(d_audio, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, ms), "H2D");
         const size_t stride = qrl_amod_out_cap(d_ah, d_max);
-        chk(qrl_amod_process(d_ah, d_audio, d_max, na, d_iq, stride), "qrl_amod_process");
+        zero_clip(ms);
+        amod(d_audio, d_max, na, stride);
         chk(qrl_amod_sync(d_ah), "qrl_amod_sync");
         const size_t ns = qrl_amod_last_count(d_ah);
-        for (int s = 0; s < d_n && ns; ++s)
-            hchk(hipMemcpy(out[s], d_iq + 2 * (size_t)s * stride, ns * sizeof(gr_complex), hipMemcpyDeviceToHost), "D2H");
+        download(ns, stride);
         return ns;
     }
     if (!d_h) throw std::runtime_error("gr_mod_base_hip::work before set_mode");
@@ -874,10 +915,11 @@ size_t gr_mod_base_hip::work(gr_complex* const* out)
     hipStream_t ms = static_cast<hipStream_t>(qrl_mod_stream(d_h));
     hchk(hipMemcpyAsync(d_bytes, host.data(), host.size(), hipMemcpyHostToDevice, ms), "H2D");
     const size_t ns = nb / d_bpb * d_spblock, stride = (d_max / d_bpb + 1) * d_spblock;
-    chk(qrl_mod_process(d_h, d_bytes, d_max, nb, d_iq, stride), "qrl_mod_process");
+    zero_clip(ms);
+    if (sc16) chk(qrl_mod_process_sc16(d_h, d_bytes, d_max, nb, reinterpret_cast<int16_t*>(d_iq), stride), "qrl_mod_process_sc16");
+    else chk(qrl_mod_process(d_h, d_bytes, d_max, nb, d_iq, stride), "qrl_mod_process");
     chk(qrl_mod_sync(d_h), "qrl_mod_sync");
-    for (int s = 0; s < d_n; ++s)
-        hchk(hipMemcpy(out[s], d_iq + 2 * (size_t)s * stride, ns * sizeof(gr_complex), hipMemcpyDeviceToHost), "D2H");
+    download(ns, stride);
     return ns;
 }
 

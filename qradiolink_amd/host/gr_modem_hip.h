@@ -173,6 +173,12 @@ public:
     // one scheduler pass: consumes up to max_bytes queued bytes of every stream (zero padded to the longest) and returns the
     // samples per stream it produced; out[s] receives them (host, capacity >= samples_per_byte() * max_bytes)
     size_t work(gr_complex* const* out);
+    // the same with 16-bit integer I/Q out (out[s] = interleaved int16 I, Q pairs, 4 bytes per sample downloaded): replaces the SDR driver's fc32 -> sc16
+    // conversion.  Digital and analogue modes; r = rintf(x * scale) saturated to int16, scale 32767 unless set_sc16_scale (kept across set_mode).
+    // clipped(s): components of stream s that saturated in the int16 passes since construction (I and Q counted separately), read back with the samples.
+    size_t work(int16_t* const* out);
+    void set_sc16_scale(float scale);
+    uint64_t clipped(int stream) const;
     size_t samples_per_byte() const;
     int streams() const { return d_n; }
     // analogue voice modes (NBFM2500 / NBFM5000 / AM5000 / USB2500 / LSB2500; gr_mod_base.cpp:167-179): audio at 8 ksps in, 125 IQ samples per audio
@@ -194,6 +200,8 @@ public:
 
 private:
     void open();
+    size_t work_any(void* const* out, bool sc16);               // both work() overloads
+    float d_sc16_scale = 32767.0f;                              // re-applied by open()
     qrl_runtime& d_rt;
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_max; float d_gain = 1.0f;
     std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
@@ -203,11 +211,12 @@ private:
     bool d_cw_key = false; size_t d_cw_n = 1024;   // clamped to max_bytes by the constructor and by open()
     bool d_backend = false;   // the open handle has the gr_mod_base back end (device rate >= 2 Msps or a non-zero offset at open)
     size_t d_spblock = 0, d_bpb = 1;
-    std::recursive_mutex d_hmutex;   // the handle: work() holds it across a pass, every setter that touches the handle takes it.  Lock order: d_hmutex, then d_mutex
+    mutable std::recursive_mutex d_hmutex;   // the handle: work() holds it across a pass, every setter that touches the handle takes it.  Lock order: d_hmutex, then d_mutex
     std::mutex d_mutex;              // the byte / audio queues and d_sent
     std::vector<std::vector<uint8_t>> d_queue;
     std::vector<std::vector<float>> d_aqueue;
     std::vector<uint64_t> d_sent;   // bytes per stream handed to the modulator since set_mode (with the zero padding of short queues): positions of the zero runs
+    uint32_t* d_clip = nullptr; std::vector<uint64_t> d_clipped;   // device counters of one int16 pass (zeroed in front of it); totals per stream
 };
 
 // the Qt signals of gr_modem that the RX / TX paths emit (src/gr_modem.h:118-139); unset callbacks are skipped.  Buffers are only
