@@ -107,6 +107,7 @@ void   orc_fir_fff(const float* in, size_t n, const float* taps, int nt, float* 
 void   orc_fll_band_edge(const cf32* in, size_t n, float sps, float rolloff, int ntaps, float bw, cf32* out);
 void   orc_quad_demod(const cf32* in, size_t n, float gain, float* out);
 void   orc_agc2(const cf32* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, cf32* out);
+float  orc_agc2_run(const cf32* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, cf32* out);   /* the same, returns the final gain */
 void   orc_costas(const cf32* in, size_t n, float bw, int order, int use_snr, cf32* out);
 enum { ORC_TED_MM = 0, ORC_TED_MOD_MM = 1 };
 /* modified-M&M error formula: a named contract of include/qrl_contracts.h (QRL_TED_MODMM_*); < 0 restores the contract default.
@@ -233,12 +234,19 @@ void   orc_deemph_taps(int sample_rate, double tau, double a[2], double b[2]);
 void   orc_squelch_envelope(int ramp, float* env /* ramp + 1 */);
 size_t orc_pwr_squelch_cc(const cf32* in, size_t n, double db, double alpha, int ramp, int gate, cf32* out);
 void   orc_agc2_ff(const float* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, float* out);
+float  orc_agc2_ff_run(const float* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, float* out);   /* the same, returns the final gain */
+/* pwr_squelch_cc with set_threshold(db2) at input item sw_at; optional per-input-item trace (state | 0x80 mute) and the output count before count_at */
+size_t orc_pwr_squelch_cc_sw(const cf32* in, size_t n, double db, double db2, size_t sw_at, double alpha, int ramp, int gate, cf32* out,
+                             unsigned char* trace, size_t count_at, size_t* passed_before);
 void   orc_iir_ffd_2(const float* in, size_t n, const double ff[2], const double fb[2], int oldstyle, float* out);
 void   orc_set_tx_ctcss(float tone_hz);   /* gr_mod_nbfm::set_ctcss for the next orc_mod_nbfm calls: > 0 tone on, < 0 switched off again (x0.98), 0 = constructor */
 void   orc_fxpt_sine_table(float* tab /* 1024 x 2 */); uint32_t orc_fxpt_phase_inc(double fs, double freq);
 void   orc_sig_source_sin(double fs, double freq, double ampl, float offset, uint64_t k0, size_t n, float* out);   /* analog::sig_source_f(GR_SIN_WAVE, offset) [GR-MEM]: the CW key's tone */
 void   orc_sig_source_cos(double fs, double freq, double ampl, uint64_t k0, size_t n, float* out);   /* analog::sig_source_f(GR_COS_WAVE) [GR-MEM] */
 void   orc_set_rx_filter_width(int width);   /* gr_demod_nbfm / am / wbfm / ssb::set_filter_width for the next orc_demod_analog / orc_demod_ssb calls; 0 = constructor */
+void   orc_set_rx_squelch(double db, double db2, long long sw_at);   /* set_squelch for the next orc_demod_analog / orc_demod_ssb calls; db2 from squelch-input item sw_at on (< 0: never) */
+void   orc_set_rx_agc(float attack, float decay, float attack2, float decay2, long long sw_at);   /* set_agc_attack / _decay (AM, SSB); second pair from squelch-input item sw_at on (< 0: never) */
+void   orc_reset_rx_controls(void);                                 /* -140 dB, (0.1, 0.1) */
 void   orc_set_rx_gain(float k);             /* gr_demod_ssb::set_gain (_if_gain) for the next orc_demod_ssb calls; < 0 = the constructor's 0.9 */
 void   orc_set_tx_filter_width(int width);   /* gr_mod_nbfm / am / ssb::set_filter_width for the next orc_mod_nbfm / orc_mod_am / orc_mod_ssb calls; 0 = constructor */
 void   orc_set_ctcss(float tone_hz);   /* gr_demod_nbfm::set_ctcss for the next orc_demod_analog(kind 0) calls; 0 = off */

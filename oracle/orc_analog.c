@@ -65,15 +65,27 @@ void orc_squelch_envelope(int ramp, float* env)
  * (a complex product with (env, 0)); a MUTED item is dropped when gating, else emitted as zero.  Returns the output count. */
 size_t orc_pwr_squelch_cc(const cf32* in, size_t n, double db, double alpha, int ramp, int gate, cf32* out)
 {
+    return orc_pwr_squelch_cc_sw(in, n, db, db, n, alpha, ramp, gate, out, NULL, n, NULL);
+}
+/* The same block with pwr_squelch_cc::set_threshold(db2) called between two work() calls: from input item `sw_at` on the comparison
+ * value is 10^(db2 / 10); the power estimate, the state and the ramp position carry on (sw_at >= n: never).  Optional reports:
+ *   trace[i]       per INPUT item: the state after the item's step (0..3), + 0x80 when the item's mute flag was set
+ *   *passed_before the number of output items produced by the input items before `count_at` (gating: the items that passed) */
+size_t orc_pwr_squelch_cc_sw(const cf32* in, size_t n, double db, double db2, size_t sw_at, double alpha, int ramp, int gate, cf32* out,
+                             unsigned char* trace, size_t count_at, size_t* passed_before)
+{
     orc_trace_event("pwr_squelch_cc(%.17g,%.17g,%d,%d)", db, alpha, ramp, gate);
-    const double threshold = pow(10.0, db / 10);
+    double threshold = pow(10.0, db / 10);
     double pwr = 0.0;
     int state = 0, ramped = 0;
     float env = ramp ? 0.0f : 1.0f;
     float* tab = NEW(float, ramp + 1);
     if (ramp) orc_squelch_envelope(ramp, tab);
     size_t j = 0;
+    if (passed_before) *passed_before = 0;
     for (size_t i = 0; i < n; i++) {
+        if (i == sw_at) threshold = pow(10.0, db2 / 10);                         /* set_threshold */
+        if (i == count_at && passed_before) *passed_before = j;
         const float p = in[i].re * in[i].re + in[i].im * in[i].im;
         pwr = alpha * (double)p + (1.0 - alpha) * pwr;
         const int mute = pwr < threshold;
@@ -89,6 +101,7 @@ size_t orc_pwr_squelch_cc(const cf32* in, size_t n, double db, double alpha, int
             if (ramped == 0) state = 0;
             break;
         }
+        if (trace) trace[i] = (unsigned char)(state | (mute ? 0x80 : 0));
         if (state != 0) {
             out[j].re = in[i].re * env - in[i].im * 0.0f;
             out[j].im = in[i].re * 0.0f + in[i].im * env;
@@ -97,6 +110,7 @@ size_t orc_pwr_squelch_cc(const cf32* in, size_t n, double db, double alpha, int
             out[j].re = 0.0f; out[j].im = 0.0f; j++;
         }
     }
+    if (passed_before && count_at >= n) *passed_before = j;
     free(tab);
     return j;
 }
@@ -181,9 +195,8 @@ size_t orc_ctcss_squelch_ff(const float* in, size_t n, int rate, float freq, dou
 }
 
 /* agc2_ff(attack, decay, reference, gain), max gain 65536 */
-void orc_agc2_ff(const float* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, float* out)
+float orc_agc2_ff_run(const float* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, float* out)
 {
-    orc_trace_event("agc2_ff(%.9g,%.9g,%.9g,%.9g,%.9g)", attack, decay, ref, gain, max_gain);
     for (size_t i = 0; i < n; i++) {
         const float o = in[i] * gain;
         const float tmp = -ref + fabsf(o);
@@ -194,6 +207,12 @@ void orc_agc2_ff(const float* in, size_t n, float attack, float decay, float ref
         if (max_gain > 0.0f && gain > max_gain) gain = max_gain;
         out[i] = o;
     }
+    return gain;   /* the state set_attack_rate / set_decay_rate leave alone */
+}
+void orc_agc2_ff(const float* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, float* out)
+{
+    orc_trace_event("agc2_ff(%.9g,%.9g,%.9g,%.9g,%.9g)", attack, decay, ref, gain, max_gain);
+    (void)orc_agc2_ff_run(in, n, attack, decay, ref, gain, max_gain, out);
 }
 
 /* iir_filter_ffd with two feed-forward and two feedback taps: acc = ff0 x + ff1 x[-1] + fb1 y[-1] in double (y kept in double),
@@ -228,6 +247,33 @@ static int g_rx_fw_set = 0;
 static float g_rx_gain = -1.0f;
 void orc_set_rx_filter_width(int width) { g_rx_fw_set = width; }
 void orc_set_rx_gain(float k) { g_rx_gain = k; }
+/* gr_demod_nbfm / _am / _wbfm / _ssb::set_squelch(value) = _squelch->set_threshold(value) and gr_demod_am / _ssb::set_agc_attack / set_agc_decay =
+ * _agc->set_attack_rate / set_decay_rate (gr_demod_am.cpp:93-106, gr_demod_ssb.cpp:103-116) for the NEXT orc_demod_analog / orc_demod_ssb calls.
+ *   orc_set_rx_squelch(db, db2, sw_at): threshold db from the start of the stream, db2 from squelch-input item sw_at on (the item index of port 0;
+ *     sw_at < 0: no second threshold).  The power estimate and the state machine carry on, as between two work() calls.
+ *   orc_set_rx_agc(attack, decay, attack2, decay2, sw_at): the rates from the start, the second pair from squelch-input item sw_at on (sw_at < 0:
+ *     none).  The switch point is given as an index of the SQUELCH's input (= items of port 0 delivered so far, the one position a caller knows);
+ *     the oracle converts it to the AGC's own input index, the number of items that passed the gate before it.  The gain is kept.
+ *   orc_reset_rx_controls(): the constructors' -140 dB and (0.1, 0.1). */
+static double g_sq_db = -140, g_sq_db2 = -140;
+static long long g_sq_at = -1;
+static float g_agc[4] = {1e-1f, 1e-1f, 1e-1f, 1e-1f};
+static long long g_agc_at = -1;
+void orc_set_rx_squelch(double db, double db2, long long sw_at) { g_sq_db = db; g_sq_db2 = db2; g_sq_at = sw_at; }
+void orc_set_rx_agc(float attack, float decay, float attack2, float decay2, long long sw_at)
+{
+    g_agc[0] = attack; g_agc[1] = decay; g_agc[2] = attack2; g_agc[3] = decay2; g_agc_at = sw_at;
+}
+void orc_reset_rx_controls(void) { orc_set_rx_squelch(-140, -140, -1); orc_set_rx_agc(1e-1f, 1e-1f, 1e-1f, 1e-1f, -1); }
+/* the receivers' _squelch under these settings; *agc_sw = the AGC-input index of the rate switch (ng when there is none) */
+static size_t rx_squelch(const cf32* f, size_t n1, int ramp, cf32* g, size_t* agc_sw)
+{
+    const size_t sw = g_sq_at >= 0 ? (size_t)g_sq_at : n1;
+    const size_t ng = orc_pwr_squelch_cc_sw(f, n1, g_sq_db, g_sq_at >= 0 ? g_sq_db2 : g_sq_db, sw, 0.01, ramp, 1, g, NULL,
+                                            g_agc_at >= 0 ? (size_t)g_agc_at : n1, agc_sw);
+    if (g_agc_at < 0) *agc_sw = ng;
+    return ng;
+}
 /* kind: 0 NBFM, 1 AM, 2 WBFM.  filtered = port 0 (before the squelch), audio = port 1 (8 kHz). */
 void orc_demod_analog(const cf32* in, size_t n, int kind, int samp_rate, int filter_width,
                       cf32** filtered, size_t* n_filtered, float** audio, size_t* n_audio)
@@ -272,11 +318,16 @@ void orc_demod_analog(const cf32* in, size_t n, int kind, int samp_rate, int fil
     free(s1);
     *filtered = f; *n_filtered = n1;
     cf32* g = NEW(cf32, n1);
-    const size_t ng = orc_pwr_squelch_cc(f, n1, -140, 0.01, kind == 0 ? 320 : 0, 1, g);   /* _squelch (gating) */
+    size_t asw;
+    const size_t ng = rx_squelch(f, n1, kind == 0 ? 320 : 0, g, &asw);                      /* _squelch (gating) */
     float* d = NEW(float, ng);
     if (kind == 1) {
         for (size_t i = 0; i < ng; i++) d[i] = sqrtf(g[i].re * g[i].re + g[i].im * g[i].im);   /* _complex_to_mag */
-        orc_agc2_ff(d, ng, 1e-1f, 1e-1f, 1.0f, 1.0f, 65536.0f, d);                             /* _agc */
+        if (asw >= ng) orc_agc2_ff(d, ng, g_agc[0], g_agc[1], 1.0f, 1.0f, 65536.0f, d);        /* _agc */
+        else {                                                                                  /* ... with set_attack_rate / set_decay_rate at item asw */
+            const float gk = orc_agc2_ff_run(d, asw, g_agc[0], g_agc[1], 1.0f, 1.0f, 65536.0f, d);
+            (void)orc_agc2_ff_run(d + asw, ng - asw, g_agc[2], g_agc[3], 1.0f, gk, 65536.0f, d + asw);
+        }
         const double ff[2] = {1, -1}, fb[2] = {0, 0.9999};
         orc_iir_ffd_2(d, ng, ff, fb, 1, d);                                                     /* _iir_filter (DC block) */
         scale_f(d, ng, 0.99f);                                                                  /* _audio_gain */
@@ -396,9 +447,14 @@ void orc_demod_ssb(const cf32* in, size_t n, int samp_rate, int filter_width, in
     free(ft); free(s1);
     *filtered = f; *n_filtered = n1;
     cf32* g = NEW(cf32, n1);
-    const size_t ng = orc_pwr_squelch_cc(f, n1, -140, 0.01, 0, 1, g);                           /* _squelch */
+    size_t asw;
+    const size_t ng = rx_squelch(f, n1, 0, g, &asw);                                            /* _squelch */
     cf32* a = NEW(cf32, ng);
-    orc_agc2(g, ng, 1e-1f, 1e-1f, 0.25f, 1.0f, 65536.0f, a);                                    /* _agc */
+    if (asw >= ng) orc_agc2(g, ng, g_agc[0], g_agc[1], 0.25f, 1.0f, 65536.0f, a);               /* _agc */
+    else {
+        const float gk = orc_agc2_run(g, asw, g_agc[0], g_agc[1], 0.25f, 1.0f, 65536.0f, a);
+        (void)orc_agc2_run(g + asw, ng - asw, g_agc[2], g_agc[3], 0.25f, gk, 65536.0f, a + asw);
+    }
     orc_cessb_clipper(a, ng, 0.95f, g);                                                         /* _clipper */
     const size_t ns = orc_cessb_stretcher(g, ng, a);                                            /* _stretcher */
     float* r = NEW(float, ns);

@@ -533,9 +533,8 @@ void orc_quad_demod(const cf32* in, size_t n, float gain, float* out)
 }
 
 /* agc2_cc [gr-analog include/gnuradio/analog/agc2.h] */
-void orc_agc2(const cf32* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, cf32* out)
+float orc_agc2_run(const cf32* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, cf32* out)
 {
-    orc_trace_event("agc2_cc(%.9g,%.9g,%.9g,%.9g,%.9g)", attack, decay, ref, gain, max_gain);
     for (size_t i = 0; i < n; i++) {
         cf32 o; o.re = in[i].re * gain; o.im = in[i].im * gain;
         float tmp = -ref + sqrtf(o.re * o.re + o.im * o.im);
@@ -546,6 +545,12 @@ void orc_agc2(const cf32* in, size_t n, float attack, float decay, float ref, fl
         if (max_gain > 0.0f && gain > max_gain) gain = max_gain;
         out[i] = o;
     }
+    return gain;   /* carried across set_attack_rate / set_decay_rate */
+}
+void orc_agc2(const cf32* in, size_t n, float attack, float decay, float ref, float gain, float max_gain, cf32* out)
+{
+    orc_trace_event("agc2_cc(%.9g,%.9g,%.9g,%.9g,%.9g)", attack, decay, ref, gain, max_gain);
+    (void)orc_agc2_run(in, n, attack, decay, ref, gain, max_gain, out);
 }
 
 /* costas_loop_cc [gr-digital/lib/costas_loop_cc_impl.cc] */

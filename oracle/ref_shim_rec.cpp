@@ -46,7 +46,15 @@ static std::string g_text;
 // the build renames nanosleep (bursttimer.cpp / gr_mmdvm_source.cpp sleep in their work loops; nothing here runs them)
 extern "C" int qrl_stub_nanosleep(const struct timespec*, struct timespec*) { return 0; }
 
+#ifndef RR_SOURCE_ID
+#define RR_SOURCE_ID "unknown"
+#endif
+
 extern "C" {
+
+// first 16 hex digits of sha1(ref_shim_rec.cpp + rec_stub/gnuradio/recording.h) at build time (oracle/Makefile): lets the tests tell a library
+// built from this tree from one left over from another commit
+const char* rr_source_id() { return RR_SOURCE_ID; }
 
 // Builds reference hier block `kind` with the given constructor arguments and returns its construction log (one event per line);
 // nullptr for an unknown kind.  The returned pointer is valid until the next call.
@@ -101,6 +109,16 @@ const char* rr_construct(const char* kind, int sps, int samp_rate, int carrier_f
     else if (k == "mod_am.set_filter_width") { auto p = make_gr_mod_am(sps, samp_rate, carrier_freq, filter_width); s.lines.push_back("== set_filter_width"); p->set_filter_width(fm); }
     else if (k == "mod_usb.set_filter_width") { auto p = make_gr_mod_ssb(sps, samp_rate, carrier_freq, filter_width, 0); s.lines.push_back("== set_filter_width"); p->set_filter_width(fm); }
     else if (k == "mod_lsb.set_filter_width") { auto p = make_gr_mod_ssb(sps, samp_rate, carrier_freq, filter_width, 1); s.lines.push_back("== set_filter_width"); p->set_filter_width(fm); }
+    // "<kind>.set_squelch" / ".set_agc": the setters gr_demod_base::set_squelch / set_agc_attack / set_agc_decay forward to (src/gr/gr_demod_base.cpp:1186-1199, 1420-1461);
+    // the threshold in dB, or the rates in thousandths (attack = value / 1000, decay = value / 2000, to tell them apart), in the last argument slot
+    else if (k == "demod_nbfm.set_squelch") { auto p = make_gr_demod_nbfm(sps, samp_rate, carrier_freq, filter_width); s.lines.push_back("== set_squelch"); p->set_squelch(fm); }
+    else if (k == "demod_am.set_squelch") { auto p = make_gr_demod_am(sps, samp_rate, carrier_freq, filter_width); s.lines.push_back("== set_squelch"); p->set_squelch(fm); }
+    else if (k == "demod_wbfm.set_squelch") { auto p = make_gr_demod_wbfm(sps, samp_rate, carrier_freq, filter_width); s.lines.push_back("== set_squelch"); p->set_squelch(fm); }
+    else if (k == "demod_usb.set_squelch") { auto p = make_gr_demod_ssb(sps, samp_rate, carrier_freq, filter_width, 0); s.lines.push_back("== set_squelch"); p->set_squelch(fm); }
+    else if (k == "demod_lsb.set_squelch") { auto p = make_gr_demod_ssb(sps, samp_rate, carrier_freq, filter_width, 1); s.lines.push_back("== set_squelch"); p->set_squelch(fm); }
+    else if (k == "demod_am.set_agc") { auto p = make_gr_demod_am(sps, samp_rate, carrier_freq, filter_width); s.lines.push_back("== set_agc"); p->set_agc_attack((float)fm / 1000.0f); p->set_agc_decay((float)fm / 2000.0f); }
+    else if (k == "demod_usb.set_agc") { auto p = make_gr_demod_ssb(sps, samp_rate, carrier_freq, filter_width, 0); s.lines.push_back("== set_agc"); p->set_agc_attack((float)fm / 1000.0f); p->set_agc_decay((float)fm / 2000.0f); }
+    else if (k == "demod_lsb.set_agc") { auto p = make_gr_demod_ssb(sps, samp_rate, carrier_freq, filter_width, 1); s.lines.push_back("== set_agc"); p->set_agc_attack((float)fm / 1000.0f); p->set_agc_decay((float)fm / 2000.0f); }
     else ok = false;
     if (!ok) return nullptr;
     g_text.clear();

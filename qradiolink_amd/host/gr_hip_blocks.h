@@ -68,7 +68,7 @@ public:
     std::vector<gr_complex>* get_constellation_data();     // port 1; caller deletes
     std::vector<float>* get_audio_data();                  // analogue modes, port 1 (gr_audio_sink::get_data, src/gr/gr_audio_sink.cpp); caller deletes
     void set_squelch(int value);                           // gr_demod_nbfm/am/wbfm::set_squelch
-    void set_agc_attack(float value);                      // gr_demod_am::set_agc_attack / set_agc_decay
+    void set_agc_attack(float value);                      // gr_demod_am / gr_demod_ssb::set_agc_attack / set_agc_decay: the block's RATE, as it is (the GUI knob's mapping is gr_demod_base's, gr_modem_hip.h)
     void set_agc_decay(float value);
     void flush();                                          // qrl_demod_reset + drop mailboxes
     // gr_demod_base connects ports 2/3 of the 1k/2k/10k modes to gr_deframer_bb(2 | 1 | 3) (src/gr/gr_demod_base.cpp:171-178,

@@ -143,7 +143,7 @@ void gr_demod_base_hip::open()
     chk(qrl_demod_out_caps(d_h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
     chk(qrl_demod_audio_cap(d_h, d_chunk, &d_acap), "qrl_demod_audio_cap");
     if (d_acap) chk(qrl_demod_set_squelch(d_h, (double)d_squelch), "qrl_demod_set_squelch");
-    if (d_acap && d_mode == QRL_MODEM_AM5000) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
+    if (d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");   // the reference's _am, _usb and _lsb instances all keep the rates
     if (d_acap && d_ctcss != 0.0f && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_demod_set_ctcss(d_h, d_ctcss), "qrl_demod_set_ctcss");   // the reference's instances keep their tone across mode changes
     if (d_acap && d_width.count(d_mode)) chk(qrl_demod_set_filter_width(d_h, d_width[d_mode]), "qrl_demod_set_filter_width");   // ... and their set_filter_width designs
     if (d_acap && d_if_gain >= 0.0f && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(d_h, d_if_gain), "qrl_demod_set_gain");
@@ -466,17 +466,20 @@ void gr_demod_base_hip::set_gain(float value)   // gr_demod_base.cpp:1206-1210 -
     d_if_gain = value;
     if (d_h && d_acap && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(d_h, value), "qrl_demod_set_gain");
 }
-void gr_demod_base_hip::set_agc_attack(float value)   // :1428-1448
+// gr_demod_base::set_agc_attack(int) / set_agc_decay(int) (gr_demod_base.cpp:1420-1461): the GUI's integer knob becomes a rate here -- 0 -> 1, v < 0 -> 1 / -v,
+// v > 0 -> 20 v (attack) or v (decay) -- and goes to the AM and both SSB receivers (_am, _usb, _lsb)
+bool gr_demod_base_hip::has_agc() const { return d_mode == QRL_MODEM_AM5000 || d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500; }
+void gr_demod_base_hip::set_agc_attack(int value)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
-    d_agc_attack = value;
-    if (d_h && d_acap && d_mode == QRL_MODEM_AM5000) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
+    d_agc_attack = value == 0 ? 1.0f : value < 0 ? 1.0f / (float)-value : (float)value * 20.0f;
+    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
 }
-void gr_demod_base_hip::set_agc_decay(float value)   // :1450-1470
+void gr_demod_base_hip::set_agc_decay(int value)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
-    d_agc_decay = value;
-    if (d_h && d_acap && d_mode == QRL_MODEM_AM5000) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
+    d_agc_decay = value == 0 ? 1.0f : value < 0 ? 1.0f / (float)-value : (float)value;
+    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
 }
 std::vector<gr_complex>* gr_demod_base_hip::get_constellation_data(int stream)
 {

@@ -85,8 +85,8 @@ public:
     void enable_gui_const(bool value) { std::lock_guard<std::recursive_mutex> hg(d_hmutex); d_const_on = value; }
     void enable_demodulator(bool value) { std::lock_guard<std::recursive_mutex> hg(d_hmutex); d_demod_on = value; }   // closed: samples are dropped in front of the demodulator (its state does not advance); the spectrum tap still sees them
     void set_ctcss(float value);                               // gr_demod_base::set_ctcss (src/gr/gr_demod_base.cpp:1212-1218): the NBFM chains' tone squelch, 0 = off
-    void set_agc_attack(float value);                          // gr_demod_base::set_agc_attack / set_agc_decay (AM)
-    void set_agc_decay(float value);
+    void set_agc_attack(int value);                            // gr_demod_base::set_agc_attack / set_agc_decay (AM, USB, LSB): the GUI's knob, mapped to a rate as in the reference
+    void set_agc_decay(int value);
     // gr_demod_base::set_filter_width(filter_width, mode) (src/gr/gr_demod_base.cpp:1155-1185): forwarded to the analogue receiver of `mode` (WBFM, AM5000,
     // NBFM2500 / 5000, USB2500 / LSB2500; other modes: ignored, like the reference's default branch); the instance keeps it across mode changes
     void set_filter_width(int filter_width, int mode);
@@ -136,7 +136,8 @@ private:
     float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0, d_acap = 0;
-    int d_squelch = -140; float d_agc_attack = 0.1f, d_agc_decay = 0.1f;
+    int d_squelch = -140; float d_agc_attack = 0.1f, d_agc_decay = 0.1f;   // rates, behind the knob mapping (the constructors' 0.1 until a setter is called)
+    bool has_agc() const;
     std::map<int, int> d_width; float d_if_gain = -1.0f;     // per-mode set_filter_width values; set_gain (< 0: the constructor's)
     std::mutex d_mutex;                                       // the mailboxes (harvest vs the getters)
     // the C-ABI handles (qrl_demod / qrl_rssi / qrl_fft) are single-threaded objects: work() and every setter / GUI getter that

@@ -151,8 +151,8 @@ void gr_modem::setRxSensitivity(double, std::string) {}            // the SDR's
 void gr_modem::setBbGain(int value) { if (_gr_mod_base) _gr_mod_base->set_bb_gain((float)value / 5.0f); }   // :471-476
 void gr_modem::setGain(int value) { if (_gr_demod_base) _gr_demod_base->set_gain((float)value / 100.0f); }  // :478-483
 void gr_modem::setK(bool value) { if (_gr_mod_base) _gr_mod_base->set_cw_k(value); }
-void gr_modem::setAgcAttack(int value) { if (_gr_demod_base) _gr_demod_base->set_agc_attack((float)value); }
-void gr_modem::setAgcDecay(int value) { if (_gr_demod_base) _gr_demod_base->set_agc_decay((float)value); }
+void gr_modem::setAgcAttack(int value) { if (_gr_demod_base) _gr_demod_base->set_agc_attack(value); }
+void gr_modem::setAgcDecay(int value) { if (_gr_demod_base) _gr_demod_base->set_agc_decay(value); }
 void gr_modem::setSquelch(int value) { if (_gr_demod_base) _gr_demod_base->set_squelch(value); }
 void gr_modem::setFilterWidth(int width)   // :518-524
 {

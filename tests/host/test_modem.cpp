@@ -358,6 +358,51 @@ int main(int argc, char** argv)
             return 0;
         } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
     }
+    if (argc == 13 && !strcmp(argv[1], "controls")) {
+        // test_modem controls <modem_type> <streams> <iq.bin: [streams][n] cf32> <audio prefix> <when> <squelch> <attack knob> <decay knob> <squelch 2> <attack knob 2> <decay knob 2>:
+        // gr_demod_base's set_squelch / set_agc_attack / set_agc_decay on the facade, with the GUI's integers.  The first triple is set
+        //   when = 0: before the mode exists (open() applies it);  when = 1: on the open mode, then a detour through NBFM and back (the reference's
+        //   instances keep their settings across mode changes);  when = 2: on the open mode, before the first work().
+        // The second triple is set between two work() calls, at the first call boundary behind 45 % of the stream; "switch <samples>" reports where.
+        const int mode = atoi(argv[2]), N = atoi(argv[3]), when = atoi(argv[6]);
+        try {
+            qrl_runtime rt(0);
+            std::vector<std::vector<float>> audio(N);
+            gr_modem_events ev;
+            ev.pcmAudio = [&](int s, std::vector<float>* pcm) { audio[s].insert(audio[s].end(), pcm->begin(), pcm->end()); delete pcm; };
+            gr_demod_base_hip demod(rt, N, 1000000, 0.0, 1 << 16);
+            gr_modem_hip modem(&demod, nullptr, ev);
+            auto set = [&](int k) { demod.set_squelch(atoi(argv[k])); demod.set_agc_attack(atoi(argv[k + 1])); demod.set_agc_decay(atoi(argv[k + 2])); };
+            if (when == 0) set(7);
+            modem.toggleRxMode(mode);
+            if (when != 0) set(7);
+            if (when == 1) { modem.toggleRxMode(QRL_MODEM_NBFM5000); modem.toggleRxMode(mode); }
+            std::ifstream f(argv[4], std::ios::binary);
+            std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            const size_t n = raw.size() / sizeof(gr_complex) / (size_t)N;
+            const gr_complex* x = reinterpret_cast<const gr_complex*>(raw.data());
+            static const size_t sizes[] = {65536, 4096, 2, 33334, 20000, 300};
+            size_t pos = 0; unsigned k = 0; bool moved = false;
+            while (pos < n) {
+                if (!moved && pos * 100 >= n * 45) { set(10); moved = true; std::printf("switch %zu\n", pos); }
+                const size_t take = std::min(n - pos, sizes[k++ % 6]) & ~(size_t)1;
+                if (!take) break;
+                std::vector<const gr_complex*> ptr(N);
+                for (int s = 0; s < N; ++s) ptr[s] = x + (size_t)s * n + pos;
+                demod.work(ptr.data(), take);
+                pos += take;
+                for (int s = 0; s < N; ++s) while (modem.demodulateAnalog(s)) {}
+            }
+            demod.flush();
+            for (int s = 0; s < N; ++s) while (modem.demodulateAnalog(s)) {}
+            for (int s = 0; s < N; ++s) {
+                std::ofstream o(std::string(argv[5]) + std::to_string(s) + ".bin", std::ios::binary);
+                o.write(reinterpret_cast<const char*>(audio[s].data()), (std::streamsize)(audio[s].size() * sizeof(float)));
+            }
+            std::printf("controls ok\n");
+            return 0;
+        } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
+    }
     if (argc == 5 && !strcmp(argv[1], "hosttime")) {
         // test_modem hosttime <modem_type> <streams> <calls>: host CPU time of the RX boundary per work() call, with the reference's
         // per-bit loop on the host (set_device_framing(false)) and with the frame synchroniser on the device (the default): every

@@ -777,22 +777,68 @@ def ctcss_squelch_ff(x, rate=8000, freq=88.5, level=0.01, length=8000, ramp=160,
     return out[:n].copy()
 
 
-def demod_analog(x, kind, samp_rate=1000000, filter_width=5000, ctcss=0.0, set_width=0):
+_sig("orc_set_rx_squelch", None, C.c_double, C.c_double, C.c_longlong)
+_sig("orc_set_rx_agc", None, C.c_float, C.c_float, C.c_float, C.c_float, C.c_longlong)
+_sig("orc_reset_rx_controls", None)
+_sig("orc_pwr_squelch_cc_sw", _sz, _p, _sz, C.c_double, C.c_double, _sz, C.c_double, C.c_int, C.c_int, _p, _p, _sz, _p)
+_sig("orc_agc2_ff", None, _p, _sz, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _p)
+
+
+def _set_rx_controls(squelch, squelch_switch, agc, agc_switch):
+    """squelch: threshold in dB (None = the constructor's -140); squelch_switch = (item, db2): set_squelch(db2) when `item` items of port 0 had been
+    delivered; agc = (attack, decay) (None = the constructor's 0.1, 0.1); agc_switch = (item, attack2, decay2): the rates set when `item` items of port 0
+    had been delivered (the oracle converts that squelch-input index to the AGC's own, the gated count before it)"""
+    db = -140.0 if squelch is None else float(squelch)
+    at, db2 = (-1, db) if squelch_switch is None else (int(squelch_switch[0]), float(squelch_switch[1]))
+    lib.orc_set_rx_squelch(db, db2, at)
+    a, d = (0.1, 0.1) if agc is None else agc
+    at, a2, d2 = (-1, a, d) if agc_switch is None else (int(agc_switch[0]), agc_switch[1], agc_switch[2])
+    lib.orc_set_rx_agc(a, d, a2, d2, at)
+
+
+def demod_analog(x, kind, samp_rate=1000000, filter_width=5000, ctcss=0.0, set_width=0, squelch=None, squelch_switch=None, agc=None, agc_switch=None):
     """-> dict(filtered=cf32 port 0, audio=f32 port 1); ctcss != 0 (NBFM): gr_demod_nbfm::set_ctcss(tone) was called;
-    set_width != 0: gr_demod_X::set_filter_width(set_width) was called on the block constructed with filter_width"""
+    set_width != 0: gr_demod_X::set_filter_width(set_width) was called on the block constructed with filter_width;
+    squelch / squelch_switch / agc / agc_switch: set_squelch and (AM) set_agc_attack / set_agc_decay, see _set_rx_controls"""
     x = np.ascontiguousarray(x, cf32)
-    lib.orc_set_ctcss(C.c_float(ctcss))
-    lib.orc_set_rx_filter_width(int(set_width))
     f, a = C.c_void_p(), C.c_void_p()
     nf, na = C.c_size_t(), C.c_size_t()
-    lib.orc_demod_analog(_ptr(x), C.c_size_t(x.size), ANALOG_KINDS[kind], samp_rate, filter_width,
-                         C.byref(f), C.byref(nf), C.byref(a), C.byref(na))
+    lib.orc_set_ctcss(C.c_float(ctcss))
+    lib.orc_set_rx_filter_width(int(set_width))
+    try:
+        _set_rx_controls(squelch, squelch_switch, agc, agc_switch)
+        lib.orc_demod_analog(_ptr(x), C.c_size_t(x.size), ANALOG_KINDS[kind], samp_rate, filter_width,
+                             C.byref(f), C.byref(nf), C.byref(a), C.byref(na))
+    finally:
+        lib.orc_set_ctcss(C.c_float(0.0))
+        lib.orc_set_rx_filter_width(0)
+        lib.orc_reset_rx_controls()
     filt = np.ctypeslib.as_array(C.cast(f, C.POINTER(C.c_float)), (2 * nf.value,)).copy().view(cf32) if nf.value else np.zeros(0, cf32)
     aud = np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_float)), (na.value,)).copy() if na.value else np.zeros(0, np.float32)
     lib.orc_free(f); lib.orc_free(a)
-    lib.orc_set_ctcss(C.c_float(0.0))
-    lib.orc_set_rx_filter_width(0)
     return dict(filtered=filt, audio=aud)
+
+
+def agc2_ff(x, attack, decay, ref=1.0, gain=1.0, max_gain=65536.0):
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty(x.size, np.float32)
+    lib.orc_agc2_ff(_ptr(x), x.size, attack, decay, ref, gain, max_gain, _ptr(y))
+    return y
+
+
+def pwr_squelch_trace(x, db, ramp=0, switch=None, alpha=0.01):
+    """The gating pwr_squelch_cc(db, alpha, ramp) item by item: -> (passed, state, mute) per INPUT item -- passed = the item left the gate
+    (state != MUTED), state 0 MUTED / 1 ATTACK / 2 UNMUTED / 3 DECAY after the item's step, mute = the item's mute flag;
+    switch = (item, db2): set_threshold(db2) from that input item on"""
+    x = np.ascontiguousarray(x, cf32)
+    out = np.zeros(max(x.size, 1), cf32)
+    tr = np.zeros(max(x.size, 1), np.uint8)
+    at, db2 = (x.size, db) if switch is None else switch
+    n = lib.orc_pwr_squelch_cc_sw(_ptr(x), x.size, db, db2, at, alpha, ramp, 1, _ptr(out), _ptr(tr), x.size, None)
+    tr = tr[:x.size]
+    state = tr & 3
+    assert int(np.count_nonzero(state)) == n
+    return state != 0, state, (tr & 0x80) != 0
 
 
 def mod_nbfm(audio, sps=20, samp_rate=1000000, filter_width=5000, bb_gain=1.0, ctcss=0.0, set_width=0):
@@ -891,18 +937,21 @@ def preemph_taps(sample_rate, tau=50e-6):
     return list(a), list(b)
 
 
-def demod_ssb(x, sb=0, samp_rate=1000000, filter_width=2700, set_width=0, gain=None):
-    """set_width != 0: gr_demod_ssb::set_filter_width(set_width) was called; gain: gr_demod_ssb::set_gain(gain) (None = the constructor's 0.9)"""
+def demod_ssb(x, sb=0, samp_rate=1000000, filter_width=2700, set_width=0, gain=None, squelch=None, squelch_switch=None, agc=None, agc_switch=None):
+    """set_width != 0: gr_demod_ssb::set_filter_width(set_width) was called; gain: gr_demod_ssb::set_gain(gain) (None = the constructor's 0.9);
+    squelch / squelch_switch / agc / agc_switch: set_squelch, set_agc_attack / set_agc_decay, see _set_rx_controls"""
     x = np.ascontiguousarray(x, cf32)
     f, a = C.c_void_p(), C.c_void_p()
     nf, na = C.c_size_t(), C.c_size_t()
     lib.orc_set_rx_filter_width(int(set_width))
     lib.orc_set_rx_gain(C.c_float(-1.0 if gain is None else gain))
     try:
+        _set_rx_controls(squelch, squelch_switch, agc, agc_switch)
         lib.orc_demod_ssb(_ptr(x), C.c_size_t(x.size), samp_rate, filter_width, sb, C.byref(f), C.byref(nf), C.byref(a), C.byref(na))
     finally:
         lib.orc_set_rx_filter_width(0)
         lib.orc_set_rx_gain(C.c_float(-1.0))
+        lib.orc_reset_rx_controls()
     filt = np.ctypeslib.as_array(C.cast(f, C.POINTER(C.c_float)), (2 * nf.value,)).copy().view(cf32) if nf.value else np.zeros(0, cf32)
     aud = np.ctypeslib.as_array(C.cast(a, C.POINTER(C.c_float)), (na.value,)).copy() if na.value else np.zeros(0, np.float32)
     lib.orc_free(f); lib.orc_free(a)

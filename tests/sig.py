@@ -270,9 +270,38 @@ def make_dsss(info_bits, seed=1, amp=0.05, noise=0.0005, cfo=0.0):
     return z.astype(np.complex64)
 
 
-def make_analog(kind, n=400000, seed=1, amp=0.05, noise=0.0005, gap=None, fs=1000000.0):
+def fade_envelope(n, seed, item_rate, fs=1000000.0, depth=0.95, dropouts=(150, 260, 420, 900), burst=120, spans=None):
+    """Carrier amplitude factor of a fading channel, one value per sample: 1 + depth x (three tones of 10-40 Hz, weights 0.5 / 0.3 / 0.2, seeded
+    frequencies and phases), never below 0.02, with drop-outs (factor 0: noise only) of the given lengths at seeded positions.  Lengths are in items
+    of the receiver's squelch (item_rate: 20 ksps NBFM / AM, 200 ksps WBFM, 8 ksps SSB), whose power estimate settles in ~100 items whatever the
+    rate; the longest drop-out carries a short burst of signal (`burst` items) in its middle.  spans: a list that receives (start, stop) of every drop-out, in samples, longest first."""
+    rng = np.random.default_rng(1000 + seed)
+    f = rng.uniform(10.0, 40.0, 3)
+    ph = rng.uniform(0.0, 2 * np.pi, 3)
+    tc = np.arange(0, n + 100, 100) / fs                  # the tones on a 10 kHz grid, linear in between (they are 250 grid points per cycle at least)
+    coarse = 1.0 + depth * sum(w * np.sin(2 * np.pi * fk * tc + pk) for w, fk, pk in zip((0.5, 0.3, 0.2), f, ph))
+    env = np.maximum(np.interp(np.arange(n) / fs, tc, coarse), 0.02)
+    spi = int(round(fs / item_rate))            # samples per squelch item
+    if dropouts:
+        # one drop-out per equal share of the stream, at a seeded place inside it
+        share = n // len(dropouts)
+        for k, items in enumerate(rng.permutation(np.asarray(dropouts))):
+            length = int(items) * spi
+            start = k * share + int(rng.integers(0, max(share - length, 1)))
+            env[start:start + length] = 0.0
+            if spans is not None:
+                spans.append((start, start + length))
+                spans.sort(key=lambda se: se[0] - se[1])
+            if items == max(dropouts) and burst:
+                mid = start + length // 2
+                env[mid:mid + burst * spi] = 1.0
+    return env
+
+
+def make_analog(kind, n=400000, seed=1, amp=0.05, noise=0.0005, gap=None, fs=1000000.0, envelope=None):
     """Analogue voice test signal at 1 Msps: two audio tones, FM (deviation 2.5 kHz / 50 kHz for WBFM) or AM (60 % depth) on the
-    carrier at 0 Hz, AWGN; `gap` = (start, stop) zeroes that span completely (an idle channel: the gating squelch closes)."""
+    carrier at 0 Hz, AWGN; `gap` = (start, stop) zeroes that span completely (an idle channel: the gating squelch closes);
+    `envelope` = per-sample factor on the carrier amplitude (fade_envelope), the noise stays."""
     rng = np.random.default_rng(seed)
     t = np.arange(n) / fs
     audio = 0.6 * np.sin(2 * np.pi * (700.0 + 13 * seed) * t) + 0.3 * np.sin(2 * np.pi * (1900.0 + 7 * seed) * t + 0.4)
@@ -281,18 +310,23 @@ def make_analog(kind, n=400000, seed=1, amp=0.05, noise=0.0005, gap=None, fs=100
     else:
         dev = 50000.0 if kind == "wbfm" else 2500.0
         x = np.exp(2j * np.pi * dev * np.cumsum(audio) / fs)
+    if envelope is not None:
+        x = x * envelope
     y = amp * x + noise * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
     if gap:
         y[gap[0]:gap[1]] = 0
     return y.astype(np.complex64), audio
 
 
-def make_ssb(n=400000, seed=1, amp=0.05, noise=0.0003, lsb=False, gap=None, fs=1000000.0):
-    """SSB test signal at 1 Msps: two audio tones as complex exponentials above (USB) or below (LSB) the suppressed carrier at 0 Hz"""
+def make_ssb(n=400000, seed=1, amp=0.05, noise=0.0003, lsb=False, gap=None, fs=1000000.0, envelope=None):
+    """SSB test signal at 1 Msps: two audio tones as complex exponentials above (USB) or below (LSB) the suppressed carrier at 0 Hz;
+    `envelope` as in make_analog"""
     rng = np.random.default_rng(seed)
     t = np.arange(n) / fs
     sgn = -1.0 if lsb else 1.0
     x = 0.6 * np.exp(sgn * 2j * np.pi * (700.0 + 13 * seed) * t) + 0.3 * np.exp(sgn * 2j * np.pi * (1900.0 + 7 * seed) * t + 0.4j)
+    if envelope is not None:
+        x = x * envelope
     y = amp * x + noise * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
     if gap:
         y[gap[0]:gap[1]] = 0

@@ -453,3 +453,41 @@ def test_facade_rejected_settings_keep_the_handle_and_tx_setters_serialise(tmp_p
     want = orc.mod_dmr(data, zero_runs=tags)
     assert got.size == want.size
     assert np.array_equal((got.view(np.float32) + np.float32(0)).view(np.uint32), (want.view(np.float32) + np.float32(0)).view(np.uint32))
+
+
+@pytest.mark.parametrize("when", [0, 1, 2])
+@pytest.mark.parametrize("rx,knobs,knobs2", [("am", (-100, 5), (3, 2)), ("usb", (3, 2), (0, 0)), ("lsb", (0, 0), (-10, -10)), ("am", (1, 100), (-10, -10))])
+def test_facade_squelch_and_agc_knobs(tmp_path, rx, knobs, knobs2, when):
+    """gr_demod_base::set_squelch / set_agc_attack(int) / set_agc_decay(int) on the facade with the GUI's integers, set before the mode exists
+    (when = 0), kept across a mode change (1) or set on the open mode (2), and set again between two work() calls: the audio equals the
+    oracle's chain with the reference's knob mapping (src/gr/gr_demod_base.cpp:1420-1461), forwarded to AM, USB and LSB alike"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import analog_controls as ac
+    import orc
+    if not os.path.exists(EXE):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "qradiolink_amd", "csrc"), "adaptor"])
+    R = ac.RECEIVERS[rx]
+    sq, sq2 = int(ac.THRESHOLD), -130
+    iq = ac.batch(rx, 3, ac.agc_weak(rx))
+    (tmp_path / "iq.bin").write_bytes(iq.tobytes())
+    r = subprocess.run([EXE, "controls", str(R["modem"]), "3", str(tmp_path / "iq.bin"), str(tmp_path / "a"), str(when), str(sq), str(knobs[0]), str(knobs[1]),
+                        str(sq2), str(knobs2[0]), str(knobs2[1])], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    pos = int([line for line in r.stdout.splitlines() if line.startswith("switch ")][0].split()[1])
+    at = int(orc.lib.orc_decim_count(pos, 1, R["decim"]))            # items of port 0 delivered when the second triple was set
+    assert 0.45 * R["n"] <= pos < 0.55 * R["n"]
+    (a, d), (a2, d2) = ac.knob_rates(knobs), ac.knob_rates(knobs2)
+    sizes = []
+    for s in range(3):
+        got = np.fromfile(tmp_path / ("a%d.bin" % s), np.float32)
+        want = ac.oracle(rx, iq[s], squelch=sq, squelch_switch=(at, sq2), agc=(a, d), agc_switch=(at, a2, d2))["audio"]
+        # the audio sink hands out packets of 640 samples; what is left below one packet at the end stays in the mailbox
+        assert got.size == want.size // 640 * 640, (s, got.size, want.size)
+        ac.assert_bit_equal(got, want[:got.size], "audio, stream %d" % s)
+        sizes.append(got.size)
+        if s != 1:   # neither setting is idle: the chain at the first triple throughout, and at the constructor's rates, sound different
+            assert want.tobytes() != ac.oracle(rx, iq[s], squelch=sq, agc=(a, d))["audio"].tobytes()
+            assert want.tobytes() != ac.oracle(rx, iq[s], squelch=sq, squelch_switch=(at, sq2))["audio"].tobytes()
+    assert min(sizes[0], sizes[2]) >= 1280 and sizes[1] >= 640      # (stream 1 opens only once the threshold has come down)

@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_ref_chains as t  # noqa: E402
 
+assert t.LIVE, "needs oracle/_ref/libqrl_rec.so built from this tree (make -C oracle ref)"
 cases = t.all_cases()
 out = {t.fixture_key(k, a): t.ref_log(k, *a) for k, a in cases}
 path = os.path.join(ROOT, "tests", "golden", "ref", "chains.json")
