@@ -369,6 +369,20 @@ size_t qrl_chan_out_cap(const qrl_chan* c, size_t n);   /* int16 samples per cha
 /* replaces one scheduler pass of the multi-carrier graph: iq[b*stride + i] device cf32, n a multiple of num_channels;
  * out[(b*channel_count + c)*out_cap + k] device int16 @24 ksps, counts[b*channel_count + c] = samples written. */
 int qrl_chan_process(qrl_chan* c, const float* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts);
+/* like qrl_chan_process / qrl_chan_channelize, but iq is interleaved int16 I, Q (sc16, 4 bytes per sample: what a LimeSDR or UHD stream
+ * delivers): stream b at iq + 2*b*stride int16s.  The semantics are those of qrl_demod_process_sc16: x = (float)v * scale per component
+ * (one exact conversion, one rounded f32 multiply), bit for bit what the cf32 entry point computes when fed (float)v * scale -- int16
+ * channel samples, counts, RSSI tags, 4FSK dibits and constellation, and chan_out of the channelize half.  scale: qrl_chan_set_sc16_scale,
+ * default 1.0f / 32768; the setter takes effect from the next call and refuses a non-finite or zero value with QRL_ERR_ARG.  The format
+ * belongs to the CALL, not the handle: history and rings are cf32, so cf32 and sc16 calls may alternate on one handle and give the result
+ * of the concatenated stream; options, profiling (the same kernel names), channel ranges and the overlap of the internal streams work as
+ * with cf32.  Forms 0 (the 64-channel streaming kernel fetches the raw pairs with LDS-DMA and converts them as they land; docs/KERNELS.md),
+ * 1, 2 and the single carrier.  iq must be 16-byte aligned and stride a multiple of 4 samples, else QRL_ERR_ARG; the constraints on n are
+ * those of the cf32 call.  A form 3 handle (qrl_chan_process_channels) takes channel samples, not SDR samples: both calls return
+ * QRL_ERR_ARG on it (qrl_last_error says why), change nothing and leave the handle usable. */
+int qrl_chan_process_sc16(qrl_chan* c, const int16_t* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts);
+int qrl_chan_channelize_sc16(qrl_chan* c, const int16_t* iq, size_t stride, size_t n, float* chan_out, size_t pitch, int groups);
+int qrl_chan_set_sc16_scale(qrl_chan* c, float scale);
 int qrl_chan_sync(qrl_chan* c);
 /* ---- the two halves of qrl_chan_process for a CHANNEL-SHARDED multi-GPU job (PFB form: "channelize, then scatter the
  * channel streams"; reference: one channelizer feeds per-channel chains, src/gr/gr_demod_mmdvm_multi2.cpp:98-135, and every channel
@@ -519,6 +533,12 @@ unsigned qrl_fft_get_fft_size(const qrl_fft* f);             /* :166-169 */
 int qrl_fft_set_window_type(qrl_fft* f, int wintype);        /* :172-190 */
 int qrl_fft_get_window_type(const qrl_fft* f);               /* :193-196 */
 int qrl_fft_process(qrl_fft* f, const float* iq, size_t stride, size_t n);
+/* qrl_fft_process on interleaved int16 I, Q (sc16): stream b at iq + 2*b*stride int16s, x = (float)v * scale per component in front of the
+ * window multiply (scale: qrl_fft_set_sc16_scale, default 1.0f / 32768, a non-finite or zero value is QRL_ERR_ARG) -- the power spectrum
+ * and the fill / transform / hold state machine are bit for bit those of qrl_fft_process fed (float)v * scale; cf32 and sc16 calls may
+ * alternate.  iq must be 16-byte aligned and stride a multiple of 4 samples, else QRL_ERR_ARG. */
+int qrl_fft_process_sc16(qrl_fft* f, const int16_t* iq, size_t stride, size_t n);
+int qrl_fft_set_sc16_scale(qrl_fft* f, float scale);
 int qrl_fft_get_fft_data(qrl_fft* f, float* fft_points, size_t out_stride, unsigned* fft_size);
 int qrl_fft_sync(qrl_fft* f);
 void* qrl_fft_stream(qrl_fft* f);

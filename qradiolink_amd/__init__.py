@@ -152,6 +152,8 @@ def load_library():
     lib.qrl_fft_set_window_type.argtypes = [vp, C.c_int]
     lib.qrl_fft_get_window_type.argtypes = [vp]
     lib.qrl_fft_process.argtypes = [vp, vp, sz, sz]
+    lib.qrl_fft_process_sc16.argtypes = [vp, vp, sz, sz]
+    lib.qrl_fft_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_fft_get_fft_data.argtypes = [vp, vp, sz, C.POINTER(C.c_uint)]
     lib.qrl_fft_sync.argtypes = [vp]
     lib.qrl_demod_stream_wait.argtypes = [vp, vp]
@@ -191,6 +193,9 @@ def load_library():
     lib.qrl_chan_out_cap.restype = sz
     lib.qrl_chan_out_cap.argtypes = [vp, sz]
     lib.qrl_chan_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    lib.qrl_chan_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    lib.qrl_chan_channelize_sc16.argtypes = [vp, vp, sz, sz, vp, sz, C.c_int]
+    lib.qrl_chan_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_chan_sync.argtypes = [vp]
     lib.qrl_chan_stream_wait.argtypes = [vp, vp]
     lib.qrl_chan_stream.argtypes = [vp]
@@ -248,12 +253,12 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
     "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_process_sc16", "qrl_mod_set_sc16_scale", "qrl_mod_set_sc16_clip_counts", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
-    "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_sync",
+    "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_process_sc16", "qrl_chan_channelize_sc16", "qrl_chan_set_sc16_scale", "qrl_chan_sync",
     "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process", "qrl_synth_process_sc16", "qrl_synth_set_sc16_scale", "qrl_synth_set_sc16_clip_counts",
     "qrl_synth_sync",
     "qrl_rssi_create", "qrl_rssi_destroy", "qrl_rssi_reset", "qrl_rssi_set_level", "qrl_rssi_process", "qrl_rssi_sync", "qrl_rssi_stream",
     "qrl_fft_create", "qrl_fft_destroy", "qrl_fft_set_enabled", "qrl_fft_set_fft_size", "qrl_fft_get_fft_size", "qrl_fft_set_window_type",
-    "qrl_fft_get_window_type", "qrl_fft_process", "qrl_fft_get_fft_data", "qrl_fft_sync", "qrl_fft_stream",
+    "qrl_fft_get_window_type", "qrl_fft_process", "qrl_fft_process_sc16", "qrl_fft_set_sc16_scale", "qrl_fft_get_fft_data", "qrl_fft_sync", "qrl_fft_stream",
     "qrl_deframer_create", "qrl_deframer_destroy", "qrl_deframer_reset", "qrl_deframer_process", "qrl_deframer_sync",
     "qrl_framesync_create", "qrl_framesync_destroy", "qrl_framesync_reset", "qrl_framesync_frame_bytes", "qrl_framesync_process",
     "qrl_framesync_sync", "qrl_framesync_set_activity_output",
@@ -593,6 +598,35 @@ class Channelizer:
         _check(self.lib.qrl_chan_channelize(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1], chan_out.data_ptr(), chan_out.shape[3], groups),
                "qrl_chan_channelize")
 
+    def _sc16_rows(self, iq):
+        t = self.torch
+        assert iq.is_cuda and iq.dtype == t.int16 and iq.dim() == 2 and iq.shape[0] == self.batch
+        assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
+        return iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2
+
+    def process_sc16_async(self, iq):
+        """process_async over 16-bit integer IQ: iq is an int16 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_chan_process_sc16); forms 0, 1, 2
+        and the single carrier.  The row pitch must be a multiple of 4 samples and the base 16-byte aligned (the library refuses anything else)."""
+        ptr, stride, n = self._sc16_rows(iq)
+        self.torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_chan_process_sc16(self.h, ptr, stride, n, self.out.data_ptr(), self.cap, self.counts.data_ptr()), "qrl_chan_process_sc16")
+
+    def process_sc16(self, iq):
+        self.process_sc16_async(iq)
+        self.sync()
+        return self.out, self.counts
+
+    def channelize_sc16_async(self, iq, chan_out, groups):
+        """channelize_async over int16 IQ [batch, 2 * n] (qrl_chan_channelize_sc16); the same ordering rules"""
+        ptr, stride, n = self._sc16_rows(iq)
+        assert chan_out.is_cuda and chan_out.dtype == self.torch.complex64 and chan_out.is_contiguous()
+        assert tuple(chan_out.shape[:3]) == (groups, self.batch, self.cc // groups)
+        _check(self.lib.qrl_chan_channelize_sc16(self.h, ptr, stride, n, chan_out.data_ptr(), chan_out.shape[3], groups), "qrl_chan_channelize_sc16")
+
+    def set_sc16_scale(self, scale):
+        """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_chan_set_sc16_scale)"""
+        _check(self.lib.qrl_chan_set_sc16_scale(self.h, C.c_float(scale)), "qrl_chan_set_sc16_scale")
+
     def process_channels_async(self, chan_in, n1):
         """form 3 handle: the per-channel chain on chan_in complex64 cuda [batch, pitch] (n1 valid items per row).
         No host synchronisation with torch's stream (see channelize_async): call wait_for(stream) first when chan_in was produced there
@@ -754,6 +788,20 @@ class Fft:
         t.cuda.current_stream().synchronize()
         _check(self.lib.qrl_fft_process(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1]), "qrl_fft_process")
         _check(self.lib.qrl_fft_sync(self.h), "qrl_fft_sync")   # the handle's stream has read `iq`: the caller may free / reuse it
+
+    def process_sc16(self, iq):
+        """work() over 16-bit integer IQ: iq is an int16 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_fft_process_sc16); row pitch a multiple
+        of 4 samples, base 16-byte aligned"""
+        t = self.torch
+        assert iq.is_cuda and iq.dtype == t.int16 and iq.dim() == 2 and iq.shape[0] == self.batch
+        assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_fft_process_sc16(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2), "qrl_fft_process_sc16")
+        _check(self.lib.qrl_fft_sync(self.h), "qrl_fft_sync")
+
+    def set_sc16_scale(self, scale):
+        """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_fft_set_sc16_scale)"""
+        _check(self.lib.qrl_fft_set_sc16_scale(self.h, C.c_float(scale)), "qrl_fft_set_sc16_scale")
 
     def get_fft_data(self):
         t = self.torch

@@ -25,6 +25,7 @@ struct qrl_chan {
     DevBuf<float2> r1, r2, r3; DevBuf<float> r4; uint32_t m1 = 0, m2 = 0;
     uint64_t n_in = 0, n1 = 0, n2 = 0;
     float gain = 0, level = 1.0f, rssi_cal = 0.0f;
+    float sc16_scale = 1.0f / 32768.0f;   // qrl_chan_process_sc16 / qrl_chan_channelize_sc16: x = (float)v * sc16_scale
     bool tail_only = false;   // form 3: only the per-channel chain; its input = 25 ksps channel streams (qrl_chan_process_channels)
     bool xlat2 = false;   // form 2: N freq-xlating FIR decimators 1:N with the PFB prototype in front of the multi2 per-channel chain (BASELINE configs[3])
     hipEvent_t ev_user = nullptr, ev_user2 = nullptr, ev_ext = nullptr;
@@ -296,8 +297,37 @@ int qrl_chan_set_4fsk_output(qrl_chan* h, uint8_t* bits, size_t bits_cap, float*
 }
 size_t qrl_chan_out_cap(const qrl_chan* h, size_t n) { return h ? (n / (h->xlat2 ? h->xl_D : h->M) + 2) * h->rs_I / h->rs_D + 2 : 0; }
 
-static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts,
-                             float* chan_out, size_t chan_pitch, int chan_groups);
+static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts,
+                             float* chan_out, size_t chan_pitch, int chan_groups, int in_fmt = IN_CF32);
+// what the sc16 entry points check in front of chan_process_impl: the form (a form 3 handle's input is channel samples) and the rows' alignment
+static int chan_sc16_args(const qrl_chan* h, const char* who, const int16_t* iq, size_t stride)
+{
+    if (h->tail_only) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": a form 3 handle takes channel samples (qrl_chan_process_channels), not SDR samples");
+    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+    return QRL_OK;
+}
+int qrl_chan_process_sc16(qrl_chan* h, const int16_t* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (int r = chan_sc16_args(h, "qrl_chan_process_sc16", iq, stride)) return r;
+    return chan_process_impl(h, iq, stride, n, out, out_cap, counts, nullptr, 0, 0, IN_SC16);
+}
+int qrl_chan_channelize_sc16(qrl_chan* h, const int16_t* iq, size_t stride, size_t n, float* chan_out, size_t pitch, int groups)
+{
+    if (!h || !chan_out || groups < 1) return QRL_ERR_ARG;
+    if (int r = chan_sc16_args(h, "qrl_chan_channelize_sc16", iq, stride)) return r;
+    if (h->single || h->xlat || h->xlat2) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_channelize_sc16: PFB form (form 0, num_channels > 1) only");
+    if (h->cfg.channel_count % groups) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_channelize_sc16: groups must divide the channel count");
+    if (pitch < n / (size_t)h->M) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_channelize_sc16: pitch < n / num_channels");
+    return chan_process_impl(h, iq, stride, n, nullptr, 0, nullptr, chan_out, pitch, groups, IN_SC16);
+}
+int qrl_chan_set_sc16_scale(qrl_chan* h, float scale)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_set_sc16_scale: scale must be finite and non-zero");
+    h->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
+    return QRL_OK;
+}
 int qrl_chan_process(qrl_chan* h, const float* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts)
 {
     if (!h || h->tail_only) return QRL_ERR_ARG;
@@ -317,8 +347,8 @@ int qrl_chan_process_channels(qrl_chan* h, const float* chan_in, size_t pitch, s
     if (!h->tail_only) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_process_channels: form 3 handles only");
     return chan_process_impl(h, chan_in, pitch, n1, out, out_cap, counts, nullptr, 0, 0);
 }
-static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts,
-                             float* chan_out, size_t chan_pitch, int chan_groups)
+static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts,
+                             float* chan_out, size_t chan_pitch, int chan_groups, int in_fmt)
 {
     if (!h || (!iq && n)) return QRL_ERR_ARG;
     if (n > h->cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
@@ -328,7 +358,8 @@ static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t
     HIPCHK(hipSetDevice(h->ctx->device));
     (void)qrl::take_launch_error();
     const int B = h->cfg.batch, M = h->M, CC = h->cfg.channel_count, S = B * CC;
-    const float2* in = reinterpret_cast<const float2*>(iq);
+    const float2* in = static_cast<const float2*>(iq);   // (in_fmt IN_SC16: int16 pairs; only the kernels that read the caller's buffer know)
+    const float in_scale = h->sc16_scale;
     const float2* hist_old = h->flip ? h->hist_b.p : h->hist_a.p;
     float2* hist_new = h->flip ? h->hist_a.p : h->hist_b.p;
     // PFB: one output instant per M inputs; form 2: rational_resampler_ccf(1, N) -- output m exists once input m N does
@@ -352,6 +383,7 @@ static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t
     if (h->tail && h->tail_valid[slot2]) HIPCHK(hipStreamWaitEvent(ts, h->ev_tail[slot2], 0));   // symbol sync of call k - 2 done: its half of ring r6 is free
     ChanParams p{};
     p.in = in; p.in_stride = stride; p.n0 = h->n_in; p.n = (uint32_t)n; p.hist = hist_old; p.hist_len = h->hist_len;
+    p.in_fmt = in_fmt; p.in_scale = in_scale;
     p.out = RingC{h->r1.p, h->m1}; p.m0 = h->n1; p.m_count = (uint32_t)(n1_1 - h->n1);
     p.taps = h->taps.p; p.twiddle = h->twiddle.p; p.M = M; p.J = h->J; p.c_first = h->cfg.channel_first; p.c_count = CC;
     p.legacy = h->opt_legacy_pfb;
@@ -368,6 +400,7 @@ static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t
     HistParams hp{};
     hp.in = in; hp.in_stride = stride; hp.n0 = h->n_in; hp.n = (uint32_t)n;
     hp.hist_old = hist_old; hp.hist_new = hist_new; hp.hist_len = h->hist_len; hp.rot_enable = 0;
+    hp.in_fmt = in_fmt; hp.in_scale = in_scale;
     if (!h->tail_only) { launch_hist_save(hp, B, h->stream); h->flip = !h->flip; }
     if (chan_out) {   // channelizer only: the per-channel chain runs on the rank that owns the channel (qrl_chan_process_channels there)
         HIPCHK(hipGetLastError());
@@ -386,6 +419,7 @@ static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t
             dp.out = h->xlat2 ? RingC{h->r1.p, h->m1} : RingC{h->r2.p, h->m2}; dp.out_row_mul_m1 = (uint32_t)CC - 1u; dp.out_row_add = (uint32_t)cl;
             dp.m0 = h->xlat2 ? h->n1 : h->n2; dp.m_count = h->xlat2 ? (uint32_t)(n1_1 - h->n1) : c2; dp.D = h->xl_D; dp.gtab = h->xl_taps.p; dp.taps = h->xl_taps.p; dp.S = h->xl_S; dp.nt = h->xl_nt;
             dp.rot_enable = 1; dp.rot_acc = 0; dp.rot_inc = h->xl_inc[cl]; dp.rot_nbase = 0; dp.rot_lo = h->xl_rot_lo.p + (size_t)cl * 512;
+            dp.in_fmt = in_fmt; dp.in_scale = in_scale;
             if (launch_decim_mfma(dp, B, h->stream)) return qrl_set_error(QRL_ERR_HIP, "freq-xlating front end: hipFuncSetAttribute failed");
         }
         if (ev1) { HIPCHK(hipEventRecord(ev1, h->stream)); h->prof_events.emplace_back(ev0, ev1); }
@@ -393,7 +427,8 @@ static int chan_process_impl(qrl_chan* h, const float* iq, size_t stride, size_t
     if (use_mid) { HIPCHK(hipEventRecord(h->ev_pfb, h->stream)); HIPCHK(hipStreamWaitEvent(ts, h->ev_pfb, 0)); }
     ResampParams rp{};
     if (h->xlat) {
-    } else if (h->single) { rp.in = in; rp.in_stride = stride; rp.hist = hist_old; rp.hist_len = h->hist_len; rp.n0 = h->n_in; rp.n = (uint32_t)n; }
+    } else if (h->single) { rp.in = in; rp.in_stride = stride; rp.hist = hist_old; rp.hist_len = h->hist_len; rp.n0 = h->n_in; rp.n = (uint32_t)n;
+                            rp.in_fmt = in_fmt; rp.in_scale = in_scale; }
     else { rp.in = nullptr; rp.in_ring = RingC{h->r1.p, h->m1}; rp.n0 = h->n1; rp.n = (uint32_t)(n1_1 - h->n1); }
     rp.out = RingC{h->r2.p, h->m2}; rp.q0 = h->n2; rp.q_count = c2; rp.taps = h->rs_taps.p; rp.I = h->rs_I; rp.D = h->rs_D; rp.Jp = h->rs_Jp;
     if (!h->xlat && !fused) launch_resamp(rp, S, h->stream);

@@ -146,7 +146,9 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s);
 // ---- K2: rational resampler I/D on a ring (optionally with rotator on a caller buffer) ----
 struct ResampParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;  // caller IQ path (rotator-only front end)
+    int in_fmt;                           // ... IN_CF32 (0) | IN_SC16: what `in` points at (qrl_chan_process_sc16, single carrier); in what was padding, as in ChanParams
     const float2* hist; uint32_t hist_len;
+    float in_scale;
     RingC in_ring;                        // ring path
     RingC out;
     uint64_t q0; uint32_t q_count;        // outputs to produce
@@ -273,7 +275,10 @@ void launch_framesync(const FrameSyncParams& p, int batch, hipStream_t s);
 // ---- multi-carrier MMDVM RX (kernels_chan.hip) ----
 struct ChanParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;   // wideband caller IQ of this call (n multiple of M)
+    int in_fmt;                                                    // IN_CF32 (0, what a zeroed block means) | IN_SC16: what `in` points at (history stays cf32)
     const float2* hist; uint32_t hist_len;                         // last hist_len samples before n0
+    float in_scale;                                                // IN_SC16: x = (float)v * in_scale.  (Both sit in what was padding: the offsets of every other field,
+                                                                   // and so the kernel-argument loads of the cf32 kernels, are those of the block without them)
     RingC out; uint64_t m0; uint32_t m_count;                      // channel rings [batch * c_count], output instants
     const float* taps; const float2* twiddle;                      // taps[p + M k] zero padded to J*M; W[q] = e^{+j 2 pi q / M}
     int M, J, c_first, c_count;
@@ -437,7 +442,9 @@ struct RssiBlockParams {
     float* out; size_t out_cap; float* last; uint32_t* out_counts;
 };
 void launch_rssi(const RssiBlockParams& p, hipStream_t s);
-void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s);
+// in_fmt IN_SC16: `in` points at int16 I, Q pairs and a sample is converted ((float)v * in_scale) in front of the window multiply
+void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s,
+                     int in_fmt = IN_CF32, float in_scale = 0.0f);
 void launch_fft_power(const float2* X, float* out, uint32_t N, int batch, hipStream_t s);
 void launch_fft_shift(const float* pts, float* out, size_t out_stride, uint32_t N, int batch, hipStream_t s);
 

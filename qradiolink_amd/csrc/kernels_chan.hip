@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_pfb_chan(const ChanParams P)
         const int64_t a = first + i;
         float2 x = make_float2(0.f, 0.f);
         if (a >= 0 && (uint64_t)a < P.n0 + P.n) {
-            if ((uint64_t)a >= P.n0) x = P.in[(size_t)b * P.in_stride + (size_t)((uint64_t)a - P.n0)];
+            if ((uint64_t)a >= P.n0) x = in_load(P, (size_t)b, (size_t)((uint64_t)a - P.n0));   // cf32 or sc16 (qrl_chan_process_sc16); the history is cf32
             else {
                 const uint64_t d = P.n0 - (uint64_t)a;
                 if (d <= P.hist_len) x = P.hist[(size_t)b * P.hist_len + (P.hist_len - (uint32_t)d)];
@@ -159,12 +159,25 @@ __global__ __launch_bounds__(256) void k_pfb_chan(const ChanParams P)
 // Order inside a tile: issue the pieces of tile t + 2 -> FIRs -> barrier -> bin 32 and matrix phase -> s_waitcnt vmcnt(pieces just
 // issued): everything OLDER has completed, i.e. tile t + 1's pieces and the previous tile's stores -> this tile's stores -> barrier:
 // a wave never waits for the acknowledgement of stores it has just issued, and the count does not depend on how many stores ran.
+// SC = true (qrl_chan_process_sc16: the caller's buffer holds int16 I, Q pairs, 4 bytes per sample): CONVERT ON LANDING.  The same 1 KiB pieces
+// fetch the raw pairs -- a piece is then FOUR blocks, a tile's 16 blocks are four pieces, one per wave -- into a raw staging area of two tiles
+// (2 x 4 KiB) behind vs.  At the end of tile t, behind the counted wait that retires its own piece of tile t + 1, every wave converts THAT piece
+// (each lane the 16 bytes = 4 samples it fetched itself: one ds_read_b128, 4 x sc16_to_f2, two ds_write_b128) into a cf32 ring of 68 + 2 blocks; the
+// barrier that ends the tile publishes it.  Nobody reads the ring between the barrier after phase 1 and that one, and 16 landing + 35 halo blocks
+// <= 68, so nothing live is overwritten; a staging slot is private to its wave (no barrier of its own) and is refilled at the top of the next tile,
+// after its reads have returned.  Phase 1, phase 2 and the stores are the cf32 code, with the ring size a template constant.  The ragged last
+// tile of a call and the prologue convert in their element loads; the history is cf32.  LDS = 70 x 512 + 16 x 66 x 8 + 8192 = 52 480 bytes, the cf32
+// figure ((84 + 2) x 512 + 16 x 66 x 8): three workgroups per CU either way.
 #ifndef QRL_S64_AHEAD
 #define QRL_S64_AHEAD 2          // tiles of input in flight per workgroup (1 or 2)
 #endif
 constexpr int S64_T = 16, S64_VP = 66;
 constexpr int S64_AHEAD = QRL_S64_AHEAD;
 constexpr int S64_RB = S64_AHEAD == 1 ? 80 : 84;                 // ring blocks: >= 51 live + 16 AHEAD in flight, a multiple of 4
+constexpr int S64_RB_SC = 68;                                    // sc16: the pieces in flight lie in the staging area, the ring holds 51 live + 16 landing blocks
+constexpr size_t stream64_lds(bool sc) { return (size_t)(((sc ? S64_RB_SC : S64_RB) + 2) * 64 + S64_T * S64_VP) * sizeof(float2) + (sc ? 2 * 4096 : 0); }
+static_assert(3 * stream64_lds(true) <= 160 * 1024 && 3 * stream64_lds(false) <= 160 * 1024, "k_pfb_stream64: three workgroups per CU");
+static_assert(S64_RB_SC % 4 == 0 && S64_RB_SC >= 51 + 16, "sc16 ring: a 4-block piece never straddles the end; halo + tile + landing tile fit");
 typedef float v2f_ch __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(3))) v2f_ch* s64_lds_v2;
 __device__ __forceinline__ void s64_glds16(const void* gsrc, uint32_t lds_dst)
@@ -182,14 +195,18 @@ __device__ unsigned long long g_s64_prof[8];
 #else
 #define S64_STAMP(k) do { } while (0)
 #endif
-__device__ __forceinline__ int s64_wrap(int e) { return e >= S64_RB ? e - S64_RB : e; }
-template <int J>
+template <int RB> __device__ __forceinline__ int s64_wrap(int e) { return e >= RB ? e - RB : e; }
+template <int J, bool SC>
 __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uint32_t seg_len)
 {
+    static_assert(!SC || S64_AHEAD == 2, "sc16: one staging slot per tile in flight, two tiles ahead");
     constexpr int M = 64;
+    constexpr int RB = SC ? S64_RB_SC : S64_RB;                   // ring blocks
+    constexpr int RB0 = SC ? 40 : 64;                             // ring position of the segment's first tile: the prologue's 51 blocks end at RB0 + 15 < RB
+    constexpr uint32_t STG = (uint32_t)(((RB + 2) * 64 + S64_T * S64_VP) * sizeof(float2));   // SC: byte offset of the raw staging area [2 tiles][4 waves][1 KiB]
     extern __shared__ __align__(16) unsigned char ch_smem[];
     float2* xs = reinterpret_cast<float2*>(ch_smem);              // ring: RB blocks x 64 samples + 2 mirror blocks
-    float2* vs = xs + (S64_RB + 2) * 64;                          // [16 instants][VP] branch outputs
+    float2* vs = xs + (RB + 2) * 64;                              // [16 instants][VP] branch outputs
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint64_t m_end = P.m0 + P.m_count;
@@ -199,6 +216,11 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
     const int ntiles = (int)((m_hi - m_lo + S64_T - 1) / S64_T);
     const uint64_t nb_end = (P.n0 + P.n) >> 6;                    // blocks [n0 / 64, nb_end) lie in the caller's buffer
     const float2* row = P.in + (size_t)b * P.in_stride;
+    // sample r of this stream's row of the caller's buffer (element loads: prologue and ragged end)
+    auto in_at = [&](size_t r) -> float2 {
+        if constexpr (SC) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[(size_t)b * P.in_stride + r], P.in_scale);
+        else return row[r];
+    };
     const uint32_t xs_base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)xs;
     if (xs_base != 0) __builtin_trap();                          // the kernel has no static LDS: the dynamic segment (= the ring) starts at 0
     // taps of this lane's branch and the wave's DFT operand (rows = bins 16 bb + (lane & 15), k = 4 s + (lane >> 4)): registers, once
@@ -216,37 +238,62 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
     }
     // the 16 blocks of the tile that starts at instant a0 into ring positions r0 .. (mod RB): LDS-DMA when they lie inside the caller's
     // buffer (returns the number of pieces THIS wave issued), checked element loads otherwise (ragged end of a call; returns 0)
+    auto fill_tile = [&](uint64_t a0, int r0) {
+        for (int i = tid; i < 16 * 64; i += 256) {
+            const uint64_t sa_ = a0 * 64 + (uint64_t)i;
+            const float2 x = sa_ < P.n0 + P.n ? in_at((size_t)(sa_ - P.n0)) : make_float2(0.f, 0.f);
+            const int pos = s64_wrap<RB>(r0 + (i >> 6));
+            xs[pos * 64 + (i & 63)] = x;
+            if (pos < 2) xs[(RB + pos) * 64 + (i & 63)] = x;
+        }
+    };
     auto fetch_tile = [&](uint64_t a0, int r0) -> int {
         if (a0 + 16 <= nb_end) {
             const unsigned char* g = reinterpret_cast<const unsigned char*>(row + (a0 * 64 - P.n0)) + lane * 16;
             int nd = 0;
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const int j = wv + 4 * jj, pos = s64_wrap(r0 + 2 * j);            // even: a piece never straddles the ring's end
+                const int j = wv + 4 * jj, pos = s64_wrap<RB>(r0 + 2 * j);        // even: a piece never straddles the ring's end
                 s64_glds16(g + j * 1024, (uint32_t)pos * 512u);
                 ++nd;
-                if (pos == 0) { s64_glds16(g + j * 1024, (uint32_t)S64_RB * 512u); ++nd; }   // mirror of positions 0, 1
+                if (pos == 0) { s64_glds16(g + j * 1024, (uint32_t)RB * 512u); ++nd; }   // mirror of positions 0, 1
             }
             return nd;
         }
-        for (int i = tid; i < 16 * 64; i += 256) {
-            const uint64_t sa_ = a0 * 64 + (uint64_t)i;
-            const float2 x = sa_ < P.n0 + P.n ? row[(size_t)(sa_ - P.n0)] : make_float2(0.f, 0.f);
-            const int pos = s64_wrap(r0 + (i >> 6));
-            xs[pos * 64 + (i & 63)] = x;
-            if (pos < 2) xs[(S64_RB + pos) * 64 + (i & 63)] = x;
-        }
+        fill_tile(a0, r0);
         return 0;
+    };
+    // SC: this wave's piece (blocks 4 wv .. 4 wv + 3, 4 bytes per sample) of the tile that starts at instant a0 into staging slot `slot`; returns the
+    // pieces issued (0: a ragged tile, element loads when it lands) ...
+    auto fetch_raw = [&](uint64_t a0, int slot) -> int {
+        if (a0 + 16 > nb_end) return 0;
+        const unsigned char* g = reinterpret_cast<const unsigned char*>(reinterpret_cast<const uint32_t*>(P.in) + (size_t)b * P.in_stride + (a0 * 64 - P.n0));
+        s64_glds16(g + wv * 1024 + lane * 16, STG + (uint32_t)slot * 4096u + (uint32_t)wv * 1024u);
+        return 1;
+    };
+    // ... and, once the wave's counted wait has retired that piece, its conversion into ring positions r0 + 4 wv .. (r0 and RB are multiples of 4:
+    // the four blocks do not wrap apart).  Lane = the 4 samples it fetched: block (lane >> 4) of the piece, samples 4 (lane & 15) ..
+    auto land_tile = [&](uint64_t a0, int r0, int slot) {
+        if (a0 + 16 > nb_end) { fill_tile(a0, r0); return; }
+        const uint4 raw = *reinterpret_cast<const uint4*>(ch_smem + STG + (uint32_t)slot * 4096u + (uint32_t)wv * 1024u + (uint32_t)lane * 16u);
+        const int pos = s64_wrap<RB>(r0 + 4 * wv) + (lane >> 4);
+        const float2 f0 = sc16_to_f2(raw.x, P.in_scale), f1 = sc16_to_f2(raw.y, P.in_scale), f2 = sc16_to_f2(raw.z, P.in_scale), f3 = sc16_to_f2(raw.w, P.in_scale);
+        float4* dst = reinterpret_cast<float4*>(xs + pos * 64 + (lane & 15) * 4);
+        dst[0] = make_float4(f0.x, f0.y, f1.x, f1.y); dst[1] = make_float4(f2.x, f2.y, f3.x, f3.y);
+        if (pos < 2) {                                            // mirror of positions 0, 1
+            float4* mir = dst + RB * 64 / 2;
+            mir[0] = make_float4(f0.x, f0.y, f1.x, f1.y); mir[1] = make_float4(f2.x, f2.y, f3.x, f3.y);
+        }
     };
     // prologue: halo blocks m_lo - 35 .. m_lo - 1 and the first tile's 16 blocks (ring positions 29 .. 79), checked element loads
     {
-        const int64_t beta0 = (int64_t)m_lo - 64;
+        const int64_t beta0 = (int64_t)m_lo - RB0;
         for (int i = tid; i < 51 * 64; i += 256) {
-            const int rel = 29 + (i >> 6);
+            const int rel = RB0 - 35 + (i >> 6);
             const int64_t a = (beta0 + rel) * 64 + (i & 63);
             float2 x = make_float2(0.f, 0.f);
             if (a >= 0 && (uint64_t)a < P.n0 + P.n) {
-                if ((uint64_t)a >= P.n0) x = row[(size_t)((uint64_t)a - P.n0)];
+                if ((uint64_t)a >= P.n0) x = in_at((size_t)((uint64_t)a - P.n0));
                 else {
                     const uint64_t d = P.n0 - (uint64_t)a;
                     if (d <= P.hist_len) x = P.hist[(size_t)b * P.hist_len + (P.hist_len - (uint32_t)d)];
@@ -255,7 +302,8 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
             xs[rel * 64 + (i & 63)] = x;
         }
     }
-    if (S64_AHEAD == 2 && ntiles > 1) (void)fetch_tile(m_lo + 16, s64_wrap(64 + 16));   // tile 1 (waited for at the end of tile 0)
+    if constexpr (SC) { if (ntiles > 1) (void)fetch_raw(m_lo + 16, 1); }                      // tile 1 -> staging slot 1 (converted at the end of tile 0)
+    else if (S64_AHEAD == 2 && ntiles > 1) (void)fetch_tile(m_lo + 16, s64_wrap<RB>(RB0 + 16));   // tile 1 (waited for at the end of tile 0)
     const uint32_t vlane = lane == 0 ? 512u : (uint32_t)(64 - lane) * 8u;      // byte offset relative to block (m - k - 1)
     // output rows of this lane's four matrix results: low columns (n16 < 8) -> bin 16 bb + 4 k4 + r, high columns -> its mirror image 64 - bin
     // (chan_out_addr's row arithmetic, once per workgroup: per tile only the column changes)
@@ -284,19 +332,22 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
     unsigned long long tprev = __builtin_readcyclecounter();
 #endif
     __syncthreads();
-    int rb = 64;                                                  // ring position of the tile's first block: (64 + 16 t) mod RB
+    int rb = RB0;                                                 // ring position of the tile's first block: (RB0 + 16 t) mod RB
     for (int t = 0; t < ntiles; ++t) {
         const uint64_t a = m_lo + (uint64_t)t * S64_T;            // first instant of the tile
         // the tile AHEAD: its positions hold blocks a + 16 AHEAD - RB ..: older than the oldest live block a - 35
         int nd = 0;
-        if (t + S64_AHEAD < ntiles) nd = fetch_tile(a + 16 * S64_AHEAD, s64_wrap(s64_wrap(rb + 16 * S64_AHEAD)));
+        if (t + S64_AHEAD < ntiles) {
+            if constexpr (SC) nd = fetch_raw(a + 16 * S64_AHEAD, t & 1);     // (slot t & 1 held tile t: converted, by this wave, at the end of tile t - 1)
+            else nd = fetch_tile(a + 16 * S64_AHEAD, s64_wrap<RB>(s64_wrap<RB>(rb + 16 * S64_AHEAD)));
+        }
         S64_STAMP(0);
         // ---- phase 1: branch FIRs of instants a + 4 wv + r
         {
             v2f_ch acc[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[r] = v2f_ch{0.f, 0.f};
-            const int e0 = rb + 4 * wv + (S64_RB - 1);            // (block m - k - 1 of r = k; + RB keeps the sum positive)
+            const int e0 = rb + 4 * wv + (RB - 1);            // (block m - k - 1 of r = k; + RB keeps the sum positive)
             // the J + 3 samples the four windows share, read in groups of NBATCH that are issued one group ahead of their use (left to
             // itself the compiler keeps two reads in flight and the phase waits for the LDS latency 19 times: 3700 of 9400 cycles per tile)
             constexpr int NX = J + 3, NBATCH = 10, NG = (NX + NBATCH - 1) / NBATCH;
@@ -304,7 +355,7 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
             auto load_group = [&](int g) {
 #pragma unroll
                 for (int i = g * NBATCH; i < (g + 1) * NBATCH && i < NX; ++i) {
-                    const int e = s64_wrap(s64_wrap(e0 + 3 - i)); // wave uniform: scalar ALU
+                    const int e = s64_wrap<RB>(s64_wrap<RB>(e0 + 3 - i)); // wave uniform: scalar ALU
                     xv[i] = *(s64_lds_v2)(uintptr_t)((uint32_t)e * 512u + vlane);
                 }
             };
@@ -374,9 +425,13 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
         // everything older than the pieces issued at the top of this tile has completed: the next tile's pieces (this wave's) have landed,
         // and the stores waited for are the PREVIOUS tile's -- a wave never waits for the acknowledgement of stores it has just issued
         if (S64_AHEAD == 1 || nd == 0) s64_wait_vm<0>();
+        else if (SC) s64_wait_vm<1>();
         else if (nd == 2) s64_wait_vm<2>();
         else if (nd == 3) s64_wait_vm<3>();
         else s64_wait_vm<4>();
+        // SC: this wave's piece of tile t + 1 has landed in its staging slot: convert it into the ring (phase 1 of this tile is behind the barrier above,
+        // the barrier below publishes the blocks)
+        if constexpr (SC) { if (t + 1 < ntiles) land_tile(a + S64_T, s64_wrap<RB>(rb + 16), (t + 1) & 1); }
         S64_STAMP(4);
         {
             const uint64_t m = a + 8 * oct + col;
@@ -399,7 +454,7 @@ __global__ __launch_bounds__(256, 3) void k_pfb_stream64(const ChanParams P, uin
         S64_STAMP(5);
         __syncthreads();                                          // everybody's pieces have landed; vs is free again
         S64_STAMP(6);
-        rb = s64_wrap(rb + 16);
+        rb = s64_wrap<RB>(rb + 16);
     }
 #ifdef QRL_S64_PROF
     if (lane == 0) { for (int k = 0; k < 7; ++k) atomicAdd(&g_s64_prof[k], pc[k]); atomicAdd(&g_s64_prof[7], (unsigned long long)ntiles); }
@@ -414,7 +469,7 @@ extern "C" void qrl_s64_prof_read(unsigned long long* out8)
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_s64_prof), z, sizeof z);
 }
 #endif
-size_t stream64_lds_bytes() { return (size_t)((S64_RB + 2) * 64 + S64_T * S64_VP) * sizeof(float2); }
+size_t stream64_lds_bytes(bool sc16) { return stream64_lds(sc16); }
 
 // caller buffer [rows][pitch] -> engine ring rows at absolute items [q0, q0 + count): how the per-channel-only handle (form 3) takes
 // the channel samples an all-to-all delivered
@@ -456,19 +511,22 @@ void launch_pfb_chan(const ChanParams& p, int batch, hipStream_t s)
     // M = 64: the streaming kernel (rows 16-byte aligned, as qrl_chan_process demands of device buffers in practice); everything else -- other channel counts,
     // unaligned rows, ragged sample counts, and QRL_CHAN_OPT_LEGACY_PFB = 1 for the parity test of that path -- the general-M kernel.  (Round 3's tiled
     // 64-channel kernel k_pfb_chan64 was deleted in round 6: superseded, its A/B is on record in docs/KERNELS.md 5.)
-    const bool aligned = (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && (p.in_stride & 1u) == 0 && (p.n0 & 63u) == 0 && (p.n & 63u) == 0;
+    // (sc16, 4-byte samples: the same rule -- 16-byte rows need a stride that is a multiple of 4 samples, which qrl_chan_process_sc16 demands)
+    const bool sc = p.in_fmt == IN_SC16;
+    const bool aligned = (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && (p.in_stride & (sc ? 3u : 1u)) == 0 && (p.n0 & 63u) == 0 && (p.n & 63u) == 0;
     if (p.M == 64 && p.J == 35 && p.legacy == 0 && aligned) {
-        const auto kern = k_pfb_stream64<35>;
+        const auto kern = sc ? k_pfb_stream64<35, true> : k_pfb_stream64<35, false>;
         if (dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
         // segments: as many workgroups as the chip holds at once (occupancy x CUs), at least 4 tiles each
-        static std::mutex mu; static int slots_cache[16];
+        static std::mutex mu; static int slots_caches[2][16];
+        int* slots_cache = slots_caches[sc ? 1 : 0];
         int dev = 0, slots;
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return;
         {
             std::lock_guard<std::mutex> lk(mu);
             if (!slots_cache[dev]) {
                 int nb = 0; hipDeviceProp_t pr;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, stream64_lds_bytes()) != hipSuccess || nb < 1) nb = 1;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, stream64_lds_bytes(sc)) != hipSuccess || nb < 1) nb = 1;
                 if (const char* e = std::getenv("QRL_PFB_WG_PER_CU")) { const int v = std::atoi(e); if (v >= 1 && v < nb) nb = v; }   // experiment: fewer persistent workgroups per CU (room for the per-channel kernel beside them)
                 slots_cache[dev] = nb * (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256);
             }
@@ -479,7 +537,7 @@ void launch_pfb_chan(const ChanParams& p, int batch, hipStream_t s)
         if (nseg > max_seg) nseg = max_seg;
         const uint32_t seg_len = ((p.m_count + nseg - 1) / nseg + S64_T - 1) / S64_T * S64_T;
         nseg = (p.m_count + seg_len - 1) / seg_len;
-        hipLaunchKernelGGL(kern, dim3(nseg, batch), dim3(256), stream64_lds_bytes(), s, p, seg_len);
+        hipLaunchKernelGGL(kern, dim3(nseg, batch), dim3(256), stream64_lds_bytes(sc), s, p, seg_len);
         return;
     }
     const dim3 grid((p.m_count + CH_TI - 1) / CH_TI, batch);

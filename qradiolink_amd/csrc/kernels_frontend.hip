@@ -282,6 +282,8 @@ void launch_hist_save(const HistParams& p, int batch, hipStream_t s)
 
 // ---- K2: rational resampler I/D.  One fmaf chain per output, j ascending (oracle orc_resamp_ccf).
 // Tile of 256 outputs; the input span is staged in LDS once (coalesced), taps [I][Jp] in LDS.
+// SC: the caller's buffer holds int16 pairs (qrl_chan_process_sc16 on a single-carrier handle); history and rings are cf32
+template <bool SC>
 __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int64_t i)
 {
     if (i < 0) return make_float2(0.f, 0.f);
@@ -289,7 +291,7 @@ __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int
     if (P.in) {
         if (ui >= P.n0 + P.n) return make_float2(0.f, 0.f);
         if (ui >= P.n0) {
-            float2 x = P.in[(size_t)b * P.in_stride + (size_t)(ui - P.n0)];
+            float2 x = in_load_as<SC>(P, (size_t)b, (size_t)(ui - P.n0));
             if (P.rot_enable) {
                 const uint64_t kk = ui - P.rot_nbase;
                 const float2 hi = sincos_turn(P.rot_acc + ((kk >> 9) << 9) * P.rot_inc);
@@ -305,7 +307,7 @@ __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int
     return P.in_ring.p[(size_t)b * (P.in_ring.mask + 1u) + ((uint32_t)ui & P.in_ring.mask)];
 }
 
-template <bool PS>
+template <bool PS, bool SC>
 __global__ __launch_bounds__(256) void k_resamp(const ResampParams P_, int span)
 {
     ROT_VIEW(ResampParams, PS, P, P_, blockIdx.y);
@@ -320,7 +322,7 @@ __global__ __launch_bounds__(256) void k_resamp(const ResampParams P_, int span)
     // input index of output q: c(q) = floor(q*D/I); the tile needs [c(q_first) - (Jp-1), c(q_last)]
     const int64_t c_first = (int64_t)((q_first * (uint64_t)P.D) / (uint64_t)P.I);
     const int64_t base = c_first - (P.Jp - 1);
-    for (int k = tid; k < span; k += (int)T) xs[k] = resamp_fetch(P, b, base + k);
+    for (int k = tid; k < span; k += (int)T) xs[k] = resamp_fetch<SC>(P, b, base + k);
     __syncthreads();
     const uint64_t q = q_first + tid;
     if (q >= P.q0 + P.q_count) return;
@@ -350,7 +352,8 @@ void launch_resamp(const ResampParams& p, int batch, hipStream_t s)
     int span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2;
     if ((size_t)span * sizeof(float2) > 48 * 1024) { T = 64; span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2; }
     const size_t lds = (size_t)((p.I * p.Jp + 3) & ~3) * sizeof(float) + (size_t)span * sizeof(float2);
-    const auto kern = p.rot_acc_s ? k_resamp<true> : k_resamp<false>;
+    const bool sc = p.in && p.in_fmt == IN_SC16;
+    const auto kern = sc ? (p.rot_acc_s ? k_resamp<true, true> : k_resamp<false, true>) : (p.rot_acc_s ? k_resamp<true, false> : k_resamp<false, false>);
     if (dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
     dim3 grid((p.q_count + T - 1) / T, batch), block(T);
     hipLaunchKernelGGL(kern, grid, block, lds, s, p, span);

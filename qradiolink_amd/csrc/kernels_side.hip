@@ -101,14 +101,18 @@ void launch_rssi(const RssiBlockParams& p, hipStream_t s)
 }
 
 // ---- rx_fft_c
-// in[i] * window[counter + i] into the FFT input buffer of every stream (rx_fft.cpp:95)
+// in[i] * window[counter + i] into the FFT input buffer of every stream (rx_fft.cpp:95).  SC: `in` points at int16 I, Q pairs
+// (qrl_fft_process_sc16): convert, x = (float)v * in_scale, then window
+template <bool SC>
 __global__ __launch_bounds__(256) void k_fft_fill(const float2* __restrict__ in, size_t in_stride, uint32_t i0, uint32_t count, const float* __restrict__ win,
-                                                  uint32_t counter, float2* __restrict__ buf, uint32_t N)
+                                                  uint32_t counter, float2* __restrict__ buf, uint32_t N, float in_scale)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= count) return;
     const int b = blockIdx.y;
-    const float2 x = in[(size_t)b * in_stride + i0 + j];
+    float2 x;
+    if constexpr (SC) x = sc16_to_f2(reinterpret_cast<const uint32_t*>(in)[(size_t)b * in_stride + i0 + j], in_scale);
+    else x = in[(size_t)b * in_stride + i0 + j];
     const float w = win[counter + j];
     buf[(size_t)b * N + counter + j] = make_float2(x.x * w, x.y * w);
 }
@@ -132,9 +136,12 @@ __global__ __launch_bounds__(256) void k_fft_shift(const float* __restrict__ pts
     const uint32_t h = N / 2;
     out[(size_t)b * out_stride + j] = pts[(size_t)b * N + (j < h ? j + (N - h) : j - h)];
 }
-void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s)
+void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s,
+                     int in_fmt, float in_scale)
 {
-    if (count) hipLaunchKernelGGL(k_fft_fill, dim3((count + 255) / 256, batch), dim3(256), 0, s, in, in_stride, i0, count, win, counter, buf, N);
+    if (!count) return;
+    const auto kern = in_fmt == IN_SC16 ? k_fft_fill<true> : k_fft_fill<false>;
+    hipLaunchKernelGGL(kern, dim3((count + 255) / 256, batch), dim3(256), 0, s, in, in_stride, i0, count, win, counter, buf, N, in_scale);
 }
 void launch_fft_power(const float2* X, float* out, uint32_t N, int batch, hipStream_t s)
 {

@@ -35,6 +35,7 @@ struct qrl_fft {
     hipfftHandle plan = 0; bool have_plan = false;
     DevBuf<float> win, points; DevBuf<float2> buf, spec;
     unsigned counter = 0; int push = 0; bool data_ready = false, enabled = false;
+    float sc16_scale = 1.0f / 32768.0f;   // qrl_fft_process_sc16: x = (float)v * sc16_scale
     void drop_plan() { if (have_plan) { (void)hipfftDestroy(plan); have_plan = false; } }
     ~qrl_fft() {
         drop_plan();
@@ -180,14 +181,13 @@ unsigned qrl_fft_get_fft_size(const qrl_fft* h) { return h ? h->fftsize : 0; }
 int qrl_fft_set_window_type(qrl_fft* h, int wintype) { if (!h) return QRL_ERR_ARG; return fft_configure(h, h->fftsize, wintype); }
 int qrl_fft_get_window_type(const qrl_fft* h) { return h ? h->wintype : -1; }
 
-// rx_fft_c::work (rx_fft.cpp:71-100) on n new samples of every stream
-int qrl_fft_process(qrl_fft* h, const float* iq, size_t stride, size_t n)
+// rx_fft_c::work (rx_fft.cpp:71-100) on n new samples of every stream; fmt = what iq points at (the window buffer and everything behind it are cf32)
+static int fft_process_impl(qrl_fft* h, const void* iq, size_t stride, size_t n, int fmt)
 {
-    if (!h || !iq) return QRL_ERR_ARG;
     if (n > 0xFFFFFFFFull) return qrl_set_error(QRL_ERR_TOO_BIG, "n too large");
     if (h->push > 0 || !h->enabled) return QRL_OK;             // nobody reads: do not fill the buffer
     HIPCHK(hipSetDevice(h->ctx->device));
-    const float2* in = reinterpret_cast<const float2*>(iq);
+    const float2* in = static_cast<const float2*>(iq);
     const unsigned N = h->fftsize;
     size_t i = 0;
     while (i < n) {
@@ -199,11 +199,29 @@ int qrl_fft_process(qrl_fft* h, const float* iq, size_t stride, size_t n)
             h->push++;
         }
         const size_t chunk = std::min(n - i, (size_t)(N - h->counter));
-        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win.p, h->counter, h->buf.p, N, h->batch, h->stream);
+        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win.p, h->counter, h->buf.p, N, h->batch, h->stream, fmt, h->sc16_scale);
         h->counter += (unsigned)chunk;
         i += chunk;
     }
     HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+int qrl_fft_process(qrl_fft* h, const float* iq, size_t stride, size_t n)
+{
+    if (!h || !iq) return QRL_ERR_ARG;
+    return fft_process_impl(h, iq, stride, n, IN_CF32);
+}
+int qrl_fft_process_sc16(qrl_fft* h, const int16_t* iq, size_t stride, size_t n)
+{
+    if (!h || !iq) return QRL_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, "qrl_fft_process_sc16: sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+    return fft_process_impl(h, iq, stride, n, IN_SC16);
+}
+int qrl_fft_set_sc16_scale(qrl_fft* h, float scale)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_fft_set_sc16_scale: scale must be finite and non-zero");
+    h->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
     return QRL_OK;
 }
 // rx_fft_c::get_fft_data (rx_fft.cpp:113-131): fft_points[b * out_stride + i] (device), *fft_size = 0 when nothing is ready

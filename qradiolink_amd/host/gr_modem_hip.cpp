@@ -152,6 +152,7 @@ void gr_demod_base_hip::open()
     chk(qrl_rssi_create(d_rt.ctx(), d_n, d_rssi_cal, d_copy, &d_rssi), "qrl_rssi_create");
     chk(qrl_fft_create(d_rt.ctx(), d_n, d_fftsize, 5 /* WIN_BLACKMAN_HARRIS */, d_copy, &d_fft), "qrl_fft_create");
     chk(qrl_fft_set_enabled(d_fft, d_fft_on ? 1 : 0), "qrl_fft_set_enabled");
+    chk(qrl_fft_set_sc16_scale(d_fft, d_sc16_scale), "qrl_fft_set_sc16_scale");
     d_level.assign(N, 0.0f);
     // L1 frame synchronisers on the copy stream, behind the demodulator (digital modes with gr_modem framing: not DMR, not analogue)
     const bool fs_on = d_want_fs && !d_acap && d_mode != QRL_MODEM_DMR;
@@ -277,6 +278,7 @@ void gr_demod_base_hip::set_sc16_scale(float scale)
     if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_demod_base_hip::set_sc16_scale: finite, non-zero");
     d_sc16_scale = scale;
     if (d_h) chk(qrl_demod_set_sc16_scale(d_h, scale), "qrl_demod_set_sc16_scale");
+    if (d_fft) chk(qrl_fft_set_sc16_scale(d_fft, scale), "qrl_fft_set_sc16_scale");   // the spectrum tap reads the same int16 slot
 }
 void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
 {
@@ -288,7 +290,6 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         // the C ABI would refuse the same (QRL_ERR_ARG); checked here before anything is staged or queued
         if (d_rate < 2000000) throw std::invalid_argument("gr_demod_base_hip::work(int16): needs the device-rate front end (device_samp_rate >= 2000000)");
         if (d_chunk & 3) throw std::invalid_argument("gr_demod_base_hip::work(int16): max_chunk (the row pitch) must be a multiple of 4 samples");
-        if (d_fft_on) throw std::invalid_argument("gr_demod_base_hip::work(int16): the spectrum tap reads cf32 samples; switch it off or feed cf32");
     }
     if (!d_demod_on && !d_fft_on) return;                        // _demod_valve closed and nobody else listens: the samples are dropped
     const int cur = (int)(d_calls & 1);
@@ -300,8 +301,9 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     if (!d_demod_on) {                                           // _demod_valve closed (gr_demod_base.cpp:1150-1153): only the spectrum tap, which sits in front of it
         // everything of this call on the spectrum block's own stream (d_copy): the upload, the FFT fill behind it, and the host waits for THAT
         // stream before the slot is reused (the upload used to go on the demodulator's stream, which nothing ordered the FFT behind)
-        hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sizeof(gr_complex), hipMemcpyHostToDevice, cs), "H2D");
-        chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
+        hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, cs), "H2D");
+        if (sc16) chk(qrl_fft_process_sc16(d_fft, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n), "qrl_fft_process_sc16");
+        else chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
         hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");  // (d_calls does not advance: the next call takes the same slot; no harvest belongs to this call)
         return;
     }
@@ -351,7 +353,10 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         chk(qrl_rssi_process(d_rssi, sl.d_filt, d_fcap, d_fcap, sl.d_cnt, 4, nullptr, 0, sl.d_rssi, nullptr), "qrl_rssi_process");
         hchk(hipMemcpyAsync(sl.h_rssi, sl.d_rssi, N * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");
     }
-    if (d_fft_on) chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
+    if (d_fft_on) {
+        if (sc16) chk(qrl_fft_process_sc16(d_fft, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n), "qrl_fft_process_sc16");
+        else chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
+    }
     hchk(hipEventRecord(sl.done, cs), "hipEventRecord");
     const int prev = d_inflight;
     d_inflight = cur;

@@ -53,7 +53,8 @@ public:
     // one scheduler pass: n new samples (even, <= max_chunk) of every stream, iq[s] = host pointer of stream s
     void work(const gr_complex* const* iq, size_t n);
     // the same for 16-bit integer I/Q (iq[s] = n interleaved int16 I, Q pairs): replaces the SDR driver's sc16 -> fc32 conversion.  Handles at
-    // device_samp_rate >= 2 Msps, max_chunk a multiple of 4, spectrum tap off; x = (float)v * scale, scale 1 / 32768 unless set_sc16_scale
+    // device_samp_rate >= 2 Msps, max_chunk a multiple of 4; x = (float)v * scale, scale 1 / 32768 unless set_sc16_scale.  The spectrum tap
+    // (enable_gui_fft) reads the same uploaded int16 slot (qrl_fft_process_sc16), with the demodulator valve open or closed
     void work(const int16_t* const* iq, size_t n);
     void set_sc16_scale(float scale);
     void flush();                                              // waits for the call in flight and harvests it
