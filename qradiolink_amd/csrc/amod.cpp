@@ -7,14 +7,11 @@
 // Kernels: k_am_load, k_fir_fff, k_am_iir, k_an_resamp (host-side counts), k_tx_fm, k_fir_ccf, k_scale_c, k_tx_interp_c.
 // Arithmetic = oracle/orc_chains.c orc_mod_nbfm, bit for bit, independent of how the audio is cut into calls (multiples of 4 samples:
 // the 25:4 resampler then produces whole groups of 25).
-#include "host_common.hpp"
+#include "tx_common.hpp"
 #include "firdes.hpp"
 #include <cmath>
-#include <cstring>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace qrl;
 
@@ -45,7 +42,7 @@ uint32_t fxpt_phase_inc(double fs, double freq)
 struct qrl_amod {
     qrl_ctx* ctx = nullptr;
     qrl_amod_config cfg{};
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     int sps = 20, fw = 5000; bool ssb = false, lsb = false, am = false;
     bool cw = false; double cw_ampl = 0.001;   // QRL_MODEM_CW600USB: the SSB chain fed by sig_source_f(8000, GR_SIN_WAVE, 600, 0.001, 1) (gr_mod_base.cpp:144,180,679-683)
     DevBuf<float> am_gain; DevBuf<float2> t_chan, m1, m2; int n_chan = 0; uint32_t mm = 0; uint64_t n1m = 0;   // AM: agc gain per stream, 1 Msps rings, channel filter
@@ -59,33 +56,10 @@ struct qrl_amod {
     DevBuf<AmIirState> iir; DevBuf<float> phase;
     double pb[2] = {0, 0}, pa[2] = {0, 0};
     uint64_t n8 = 0, n50 = 0;
-    // gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258), as behind the digital modulators (tx.cpp): rotator at 1 Msps, then the interpolator to the device rate
-    bool backend = false; int be_interp = 1, be_nt = 0; DevBuf<float> be_taps;
-    DevBuf<float2> bb, be_ring; size_t bb_stride = 0; uint32_t be_mask = 0;
-    Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
-    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_amod_process_sc16 (the format itself belongs to the call)
+    TxBackEnd be;   // gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258), as behind the digital modulators (tx.cpp)
+    Sc16Sink sc;    // qrl_amod_process_sc16
     size_t cap_1msps(size_t n) const { return am ? n * (size_t)sps : ssb ? (n + 1024) * (size_t)sps : n * 25 / 4 * (size_t)sps; }
-    int init_back_end()
-    {
-        const int rate = cfg.device_samp_rate;
-        if (rate != 0 && rate != 1000000 && (rate < 2000000 || rate % 1000000 != 0 || rate > 64000000))
-            return qrl_set_error(QRL_ERR_ARG, "amod: device_samp_rate must be 1e6 or a multiple of 1e6 in [2e6, 64e6]");
-        be_interp = rate >= 2000000 ? rate / 1000000 : 1;
-        backend = be_interp > 1 || cfg.carrier_offset_hz != 0.0;
-        if (!backend) return QRL_OK;
-        int r;
-        bb_stride = cap_1msps(cfg.max_samples);
-        if ((r = bb.alloc((size_t)cfg.batch * bb_stride)) || (r = rot.init(phase_inc_to_turn(2 * M_PI * cfg.carrier_offset_hz / 1000000.0)))) return r;
-        if (be_interp > 1) {
-            const std::vector<float> lp = low_pass(be_interp, rate, 480000, 20000, WIN_BLACKMAN_HARRIS);   // gr_mod_base.cpp:215-258
-            be_nt = (int)lp.size();
-            if ((r = be_taps.upload(lp))) return r;
-            be_mask = pow2_at_least(bb_stride + (size_t)be_nt / be_interp + 64, 1024) - 1;
-            if ((r = be_ring.alloc((size_t)cfg.batch * (be_mask + 1)))) return r;
-        }
-        return QRL_OK;
-    }
-    ~qrl_amod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    int init_back_end() { return be.init("amod", "analogue modulator", cfg.device_samp_rate, cfg.carrier_offset_hz, cfg.batch, cap_1msps(cfg.max_samples)); }
     int init_state(bool keep_tone_phase = false)
     {
         int r;
@@ -99,9 +73,7 @@ struct qrl_amod {
         }
         n8 = n50 = ns = 0; last = 0;
         if (!keep_tone_phase) tone_k = cw_k = 0;   // qrl_amod_set_filter_width restarts the chain but the reference's sig_source_f keeps running
-        if (be_ring.p && (r = be_ring.zero())) return r;
-        n_bb = 0;
-        return rot.reset(stream);   // per-stream phases restart too; the offsets stay
+        return be.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -124,8 +96,7 @@ int qrl_amod_create(qrl_ctx* ctx, const qrl_amod_config* cfg, qrl_amod** outp)
     default: return qrl_set_error(QRL_ERR_ARG, "amod: modem_type must be QRL_MODEM_NBFM2500 / NBFM5000 / USB2500 / LSB2500 / CW600USB / AM5000");
     }
     HIPCHK(hipSetDevice(ctx->device));
-    if (cfg->hip_stream) m->stream = static_cast<hipStream_t>(cfg->hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)); m->own_stream = true; }
+    if (int r0 = m->stream.open(cfg->hip_stream)) return r0;
     const int fw = m->fw, B = cfg->batch;
     if (m->am) {
         // gr_mod_am.cpp:40-57: audio band-pass, interpolator low_pass(sps, samp_rate, fw, fw) (Hamming), channel filter complex_band_pass_2
@@ -257,26 +228,12 @@ int qrl_amod_set_filter_width(qrl_amod* m, int width)
     // built with the setter's designs.
     return m->init_state(true);
 }
-size_t qrl_amod_samples_per_sample(const qrl_amod* m) { return m ? ((m->ssb || m->am) ? (size_t)m->sps : (size_t)25 * m->sps / 4) * (size_t)m->be_interp : 0; }
+size_t qrl_amod_samples_per_sample(const qrl_amod* m) { return m ? ((m->ssb || m->am) ? (size_t)m->sps : (size_t)25 * m->sps / 4) * (size_t)m->be.interp() : 0; }
 size_t qrl_amod_last_count(const qrl_amod* m) { return m ? m->last : 0; }
-size_t qrl_amod_out_cap(const qrl_amod* m, size_t n) { return m ? m->cap_1msps(n) * (size_t)m->be_interp : 0; }
-int qrl_amod_set_carrier_offset(qrl_amod* m, double hz)
-{
-    if (!m) return QRL_ERR_ARG;
-    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
-    HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    return m->rot.retune(m->n_bb, phase_inc_to_turn(2 * M_PI * hz / 1000000.0), m->stream);   // phase-continuous, like rotator_cc::set_phase_inc
-}
-int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz)
-{
-    if (!m || !hz) return QRL_ERR_ARG;
-    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "analogue modulator was created without the gr_mod_base back end");
-    std::vector<uint64_t> ni;
-    if (int r = carrier_incs(hz, m->cfg.batch, 1.0, 1000000.0, ni)) return r;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return m->rot.retune_streams(m->n_bb, ni, m->stream);
-}
-void* qrl_amod_stream(qrl_amod* m) { return m ? m->stream : nullptr; }
+size_t qrl_amod_out_cap(const qrl_amod* m, size_t n) { return m ? m->cap_1msps(n) * (size_t)m->be.interp() : 0; }
+int qrl_amod_set_carrier_offset(qrl_amod* m, double hz) { return m ? m->be.retune(hz, m->stream) : QRL_ERR_ARG; }
+int qrl_amod_set_carrier_offsets(qrl_amod* m, const double* hz) { return m && hz ? m->be.retune_streams(hz, m->cfg.batch, m->stream) : QRL_ERR_ARG; }
+void* qrl_amod_stream(qrl_amod* m) { return m ? (hipStream_t)m->stream : nullptr; }
 int qrl_amod_sync(qrl_amod* m) { if (!m) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(m->stream)); return QRL_OK; }
 
 }  // extern "C"
@@ -293,30 +250,14 @@ static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n
     const int B = m->cfg.batch;
     hipStream_t s = m->stream;
     // with the back end the chain's 1 Msps output goes to the handle's own linear buffer, and from there through the rotator (and the interpolator)
-    float2* const mod_out = m->backend ? m->bb.p : reinterpret_cast<float2*>(iq);
-    const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
-    const Sc16Out mod_sc = m->backend ? Sc16Out{} : sc;
-    auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
-        if (!m->backend || !n1) return;
-        TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        m->rot.fill(rp);
-        if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
-        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; rp.sc = sc; }
-        launch_tx_rot(rp, B, s);
-        if (m->be_interp > 1) {
-            TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = m->n_bb * (uint64_t)m->be_interp; bp.count = n1 * (uint32_t)m->be_interp;
-            bp.taps = m->be_taps.p; bp.nt = m->be_nt; bp.interp = m->be_interp;
-            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride; bp.sc = sc;
-            launch_tx_interp_c(bp, B, s);
-        }
-        m->n_bb += n1;
-    };
+    const TxBackEnd::Target to = m->be.target(iq, out_stride, sc);
+    auto back_end = [&](uint32_t n1) { m->be.run(n1, iq, out_stride, sc, B, s); };   // n1 samples per stream at 1 Msps are in bb
     if (m->am) {   // gr_mod_am.cpp:66-77 in connection order
         RingF a0{m->a0.p, m->m8}, a1{m->a1.p, m->m8}, a2{m->a2.p, m->m8};
         RingC c1{m->c1.p, m->m8}, m1{m->m1.p, m->mm}, m2{m->m2.p, m->mm};
         const uint32_t c8 = (uint32_t)n, c1m = (uint32_t)(n * (size_t)m->sps);
         // (every batch size: out_stride is the capacity of the final filter's output port, a smaller one would silently truncate -- ADVICE r4)
-        if ((size_t)c1m * m->be_interp > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
+        if ((size_t)c1m * m->be.interp() > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
         AmLoadParams lp{}; lp.in = audio; lp.in_stride = stride; lp.out = a0; lp.n0 = m->n8; lp.count = c8;
         launch_am_load(lp, B, s);
         AmAgcParams ap{}; ap.in = a0; ap.out = a1; ap.n0 = m->n8; ap.count = c8; ap.attack = 1e-2f; ap.decay = 1e-4f; ap.ref = 1.0f; ap.max_gain = 1.0f;
@@ -331,12 +272,12 @@ static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n
         launch_scale_c(m1, m->n1m, c1m, 0.5f, B, s);                                // _amplify
         launch_scale_c(m1, m->n1m, c1m, m->bb_gain, B, s);                          // _bb_gain
         FirCccParams ff{}; ff.in = m1; ff.out = m2; ff.q0 = m->n1m; ff.count = c1m; ff.taps = m->t_chan.p; ff.nt = m->n_chan;
-        ff.port = mod_out; ff.port_cap = mod_stride; ff.sc = mod_sc;
+        ff.port = to.out; ff.port_cap = to.stride; ff.sc = to.sc;
         launch_an_fir_ccc(ff, B, s);                                                // _filter: straight into the caller's buffer (or the back end's)
         back_end(c1m);
         HIPCHK(hipGetLastError());
         if (qrl::take_launch_error()) return QRL_ERR_HIP;
-        m->n8 += c8; m->n1m += c1m; m->last = (size_t)c1m * m->be_interp;
+        m->n8 += c8; m->n1m += c1m; m->last = (size_t)c1m * m->be.interp();
         return QRL_OK;
     }
     if (m->ssb) {
@@ -346,7 +287,7 @@ static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n
         const uint64_t n8_1 = m->n8 + n;
         const uint64_t ns_1 = n8_1 >= 2 ? 1024 * ((n8_1 - 2) / 1024) : 0;        // stretcher: whole chunks, two items of look-ahead
         const uint32_t cs = (uint32_t)(ns_1 - m->ns);
-        if ((size_t)cs * m->sps * m->be_interp > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
+        if ((size_t)cs * m->sps * m->be.interp() > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
         if (m->cw) {   // the key's tone source instead of the caller's audio (which is ignored): amplitude 0.001 / 0.98 by qrl_amod_set_cw_k, offset 1
             AmToneParams tp{}; tp.out = a0; tp.n0 = m->n8; tp.count = c8; tp.tab = m->tone_tab.p; tp.inc = m->tone_inc; tp.k0 = m->cw_k; tp.ampl = m->cw_ampl; tp.offset = 1.0f;
             launch_am_tone(tp, B, s);
@@ -365,19 +306,19 @@ static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n
         launch_scale_c(c3, m->ns, cs, 0.9f, B, s);                                  // _amplify
         launch_scale_c(c3, m->ns, cs, m->bb_gain, B, s);                            // _bb_gain
         TxInterpCParams xp{}; xp.in = c3; xp.n0 = m->ns * (uint64_t)m->sps; xp.count = cs * (uint32_t)m->sps;
-        xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride; xp.sc = mod_sc;
+        xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = to.out; xp.out_stride = to.stride; xp.sc = to.sc;
         if (xp.count) launch_tx_interp_c(xp, B, s);                                 // _resampler
         back_end(xp.count);
         HIPCHK(hipGetLastError());
         if (qrl::take_launch_error()) return QRL_ERR_HIP;
-        m->n8 = n8_1; m->ns = ns_1; m->last = (size_t)cs * m->sps * m->be_interp;
+        m->n8 = n8_1; m->ns = ns_1; m->last = (size_t)cs * m->sps * m->be.interp();
         if (m->cw) m->cw_k += c8;
         return QRL_OK;
     }
     RingF a0{m->a0.p, m->m8}, a1{m->a1.p, m->m8}, a2{m->a2.p, m->m8}, r50{m->r50.p, m->m50};
     RingC fmv{m->fmv.p, m->m50}, flt{m->flt.p, m->m50};
     const uint32_t c8 = (uint32_t)n, c50 = (uint32_t)(n * 25 / 4);
-    if ((size_t)c50 * m->sps * m->be_interp > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
+    if ((size_t)c50 * m->sps * m->be.interp() > out_stride) return qrl_set_error(QRL_ERR_ARG, "amod: out_stride smaller than this call's output (qrl_amod_out_cap)");
     AmLoadParams lp{}; lp.in = audio; lp.in_stride = stride; lp.out = a0; lp.n0 = m->n8; lp.count = c8;
     launch_am_load(lp, B, s);
     const bool tone_on = m->tone_hz > 0.0f;
@@ -397,12 +338,12 @@ static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n
     launch_scale_c(flt, m->n50, c50, 0.8f, B, s);                                   // _amplify
     launch_scale_c(flt, m->n50, c50, m->bb_gain, B, s);                             // _bb_gain
     TxInterpCParams xp{}; xp.in = flt; xp.n0 = m->n50 * (uint64_t)m->sps; xp.count = c50 * (uint32_t)m->sps;
-    xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = mod_out; xp.out_stride = mod_stride; xp.sc = mod_sc;
+    xp.taps = m->t_interp.p; xp.nt = m->n_interp; xp.interp = m->sps; xp.out = to.out; xp.out_stride = to.stride; xp.sc = to.sc;
     launch_tx_interp_c(xp, B, s);                                                   // _resampler
     back_end(xp.count);
     HIPCHK(hipGetLastError());
     if (qrl::take_launch_error()) return QRL_ERR_HIP;
-    m->n8 += c8; m->n50 += c50; m->last = (size_t)c50 * m->sps * m->be_interp;
+    m->n8 += c8; m->n50 += c50; m->last = (size_t)c50 * m->sps * m->be.interp();
     return QRL_OK;
 }
 
@@ -414,17 +355,11 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
 }
 int qrl_amod_process_sc16(qrl_amod* m, const float* audio, size_t stride, size_t n, int16_t* iq, size_t out_stride)
 {
-    if (!m) return QRL_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_amod_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
-    return amod_process(m, audio, stride, n, iq, out_stride, Sc16Out{1, m->sc_scale, m->sc_clip});
+    Sc16Out sc;
+    if (int r = m ? m->sc.for_call("qrl_amod_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
+    return amod_process(m, audio, stride, n, iq, out_stride, sc);
 }
-int qrl_amod_set_sc16_scale(qrl_amod* m, float scale)
-{
-    if (!m) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_amod_set_sc16_scale: scale must be finite and non-zero");
-    m->sc_scale = scale;
-    return QRL_OK;
-}
-int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts) { if (!m) return QRL_ERR_ARG; m->sc_clip = counts; return QRL_OK; }
+int qrl_amod_set_sc16_scale(qrl_amod* m, float scale) { return m ? m->sc.set_scale("qrl_amod_set_sc16_scale", scale) : QRL_ERR_ARG; }
+int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts) { return m ? m->sc.set_clip(counts) : QRL_ERR_ARG; }
 
 }

@@ -303,8 +303,7 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
 static int chan_sc16_args(const qrl_chan* h, const char* who, const int16_t* iq, size_t stride)
 {
     if (h->tail_only) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": a form 3 handle takes channel samples (qrl_chan_process_channels), not SDR samples");
-    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
-    return QRL_OK;
+    return sc16_rows_ok(who, iq, stride) ? QRL_OK : QRL_ERR_ARG;
 }
 int qrl_chan_process_sc16(qrl_chan* h, const int16_t* iq, size_t stride, size_t n, int16_t* out, size_t out_cap, uint32_t* counts)
 {
@@ -324,7 +323,7 @@ int qrl_chan_channelize_sc16(qrl_chan* h, const int16_t* iq, size_t stride, size
 int qrl_chan_set_sc16_scale(qrl_chan* h, float scale)
 {
     if (!h) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_chan_set_sc16_scale: scale must be finite and non-zero");
+    if (!sc16_scale_ok("qrl_chan_set_sc16_scale", scale)) return QRL_ERR_ARG;
     h->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
     return QRL_OK;
 }

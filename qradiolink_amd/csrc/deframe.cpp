@@ -2,16 +2,14 @@
 #include "host_common.hpp"
 #include <memory>
 #include <new>
-#include <string>
 
 using namespace qrl;
 
 struct qrl_deframer {
     qrl_ctx* ctx = nullptr;
     int type = 1, batch = 1;
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     DevBuf<DeframeState> st;
-    ~qrl_deframer() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 
 extern "C" {
@@ -25,8 +23,7 @@ int qrl_deframer_create(qrl_ctx* ctx, int deframer_type, int batch, void* hip_st
     if (!h) return QRL_ERR_NOMEM;
     h->ctx = ctx; h->type = deframer_type; h->batch = batch;
     HIPCHK(hipSetDevice(ctx->device));
-    if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    if (int r0 = h->stream.open(hip_stream)) return r0;
     if (int r = h->st.alloc(batch)) return r;
     *out = h.release();
     return QRL_OK;
@@ -64,9 +61,8 @@ int qrl_deframer_sync(qrl_deframer* h)
 
 struct qrl_framesync {
     qrl_ctx* ctx = nullptr; int batch = 1, cls = 2; uint32_t bit_buf_len = 64, frame_length = 7;
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     DevBuf<FrameSyncState> st; DevBuf<uint8_t> bitbuf; size_t bitbuf_stride = 0; uint32_t* activity = nullptr;
-    ~qrl_framesync() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 // mode table of gr_modem::toggleRxMode (src/gr_modem.cpp:203-322) and the sync-word classes of gr_modem::findSync (:1183-1282)
 static int framesync_geometry(int modem_type, uint32_t& bits, uint32_t& len)
@@ -95,8 +91,7 @@ int qrl_framesync_create(qrl_ctx* ctx, int modem_type, int batch, void* hip_stre
     h->ctx = ctx; h->batch = batch;
     h->cls = framesync_geometry(modem_type, h->bit_buf_len, h->frame_length);
     HIPCHK(hipSetDevice(ctx->device));
-    if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    if (int r0 = h->stream.open(hip_stream)) return r0;
     h->bitbuf_stride = (h->bit_buf_len + 15u) & ~15u;
     int r;
     if ((r = h->st.alloc(batch)) || (r = h->bitbuf.alloc((size_t)batch * h->bitbuf_stride))) return r;

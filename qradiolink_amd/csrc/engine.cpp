@@ -329,7 +329,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         return qrl_set_error(QRL_ERR_ARG, "qrl_demod_process_sc16: int16 input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps");
     if (n > cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
     if (fmt == IN_SC16) {
-        if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, "sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+        if (!sc16_rows_ok("qrl_demod_process_sc16", iq, stride)) return QRL_ERR_ARG;
     } else if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return qrl_set_error(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
     const int B = cfg.batch;
     uint32_t* counts = (out && out->counts) ? out->counts : counts_scratch.p;
@@ -841,7 +841,7 @@ int qrl_demod_process_sc16(qrl_demod* d, const int16_t* iq, size_t stride, size_
 int qrl_demod_set_sc16_scale(qrl_demod* d, float scale)
 {
     if (!d) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_demod_set_sc16_scale: scale must be finite and non-zero");
+    if (!sc16_scale_ok("qrl_demod_set_sc16_scale", scale)) return QRL_ERR_ARG;
     d->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
     return QRL_OK;
 }
@@ -891,47 +891,38 @@ int qrl_demod_profile_read(qrl_demod* d, double* kernel_ms, uint64_t* launches, 
 void qrl_debug_decim_prof(unsigned long long* out8) { decim_mfma_prof_read(out8); }
 void qrl_debug_decim_prof_enable(int on) { decim_mfma_prof_enable(on); }
 
-int qrl_demod_process_host(qrl_demod* d, const float* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
-                           uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
+// one call from and to host memory through scratch buffers of its own: `esz` bytes per sample, device rows padded to a multiple of `round` samples
+static int process_host(qrl_demod* d, const void* iq_host, size_t stride, size_t n, uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap,
+                        uint32_t* counts_host, size_t esz, size_t round, int fmt)
 {
     if (!d || !iq_host || !counts_host) return QRL_ERR_ARG;
+    HIPCHK(hipSetDevice(d->ctx->device));
+    (void)take_launch_error();
+    if (fmt == IN_SC16 && !d->fe.used) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
     const size_t B = (size_t)d->cfg.batch;
-    const size_t st = (n + 1) & ~(size_t)1;
-    DevBuf<float2> iq; DevBuf<uint8_t> ba, bb; DevBuf<uint32_t> cnt;
+    const size_t st = (n + round - 1) / round * round;
+    DevBuf<unsigned char> iq; DevBuf<uint8_t> ba, bb; DevBuf<uint32_t> cnt;
     int r;
-    if ((r = iq.alloc(B * st)) || (r = ba.alloc(B * bits_cap)) || (r = bb.alloc(B * bits_cap)) || (r = cnt.alloc(B * 4))) return r;
-    HIPCHK(hipMemcpy2D(iq.p, st * sizeof(float2), iq_host, stride * sizeof(float2), n * sizeof(float2), B, hipMemcpyHostToDevice));
+    if ((r = iq.alloc(B * st * esz)) || (r = ba.alloc(B * bits_cap)) || (r = bb.alloc(B * bits_cap)) || (r = cnt.alloc(B * 4))) return r;
+    HIPCHK(hipMemcpy2D(iq.p, st * esz, iq_host, stride * esz, n * esz, B, hipMemcpyHostToDevice));
     qrl_demod_out o{};
     o.bits_a = ba.p; o.bits_b = bb.p; o.bits_cap = bits_cap; o.counts = cnt.p;
-    if ((r = d->process(reinterpret_cast<const float*>(iq.p), st, n, &o))) return r;
+    if ((r = d->process(iq.p, st, n, &o, fmt))) return r;
     if (int rs = d->sync_all()) return rs;
     if (bits_a_host) HIPCHK(hipMemcpy(bits_a_host, ba.p, B * bits_cap, hipMemcpyDeviceToHost));
     if (bits_b_host) HIPCHK(hipMemcpy(bits_b_host, bb.p, B * bits_cap, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(counts_host, cnt.p, B * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return QRL_OK;
 }
-
+int qrl_demod_process_host(qrl_demod* d, const float* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
+                           uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
+{
+    return process_host(d, iq_host, stride, n, bits_a_host, bits_b_host, bits_cap, counts_host, sizeof(float2), 2, IN_CF32);
+}
 int qrl_demod_process_sc16_host(qrl_demod* d, const int16_t* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
                                 uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
 {
-    if (!d || !iq_host || !counts_host) return QRL_ERR_ARG;
-    HIPCHK(hipSetDevice(d->ctx->device));
-    (void)take_launch_error();
-    if (!d->fe.used) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
-    const size_t B = (size_t)d->cfg.batch;
-    const size_t st = (n + 3) & ~(size_t)3;
-    DevBuf<uint32_t> iq, cnt; DevBuf<uint8_t> ba, bb;
-    int r;
-    if ((r = iq.alloc(B * st)) || (r = ba.alloc(B * bits_cap)) || (r = bb.alloc(B * bits_cap)) || (r = cnt.alloc(B * 4))) return r;
-    HIPCHK(hipMemcpy2D(iq.p, st * 4, iq_host, stride * 4, n * 4, B, hipMemcpyHostToDevice));
-    qrl_demod_out o{};
-    o.bits_a = ba.p; o.bits_b = bb.p; o.bits_cap = bits_cap; o.counts = cnt.p;
-    if ((r = d->process(iq.p, st, n, &o, IN_SC16))) return r;
-    if (int rs = d->sync_all()) return rs;
-    if (bits_a_host) HIPCHK(hipMemcpy(bits_a_host, ba.p, B * bits_cap, hipMemcpyDeviceToHost));
-    if (bits_b_host) HIPCHK(hipMemcpy(bits_b_host, bb.p, B * bits_cap, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(counts_host, cnt.p, B * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return QRL_OK;
+    return process_host(d, iq_host, stride, n, bits_a_host, bits_b_host, bits_cap, counts_host, 4, 4, IN_SC16);
 }
 
 // ---- host-only design helpers

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "zero_runs.hpp"   // struct ZeroRun
 
 namespace qrl {
 
@@ -329,7 +330,6 @@ struct SynthParams {
 };
 void launch_s2f_in(const S2fInParams& p, int streams, hipStream_t s);
 void launch_scale_c(RingC r, uint64_t q0, uint32_t count, float k, int streams, hipStream_t s);
-struct ZeroRun { uint32_t row; uint32_t pad; uint64_t start, count; };   // ring row, absolute item range [start, start + count)
 void launch_zero_runs(RingC r, const ZeroRun* runs, uint32_t nruns, uint64_t lo, uint64_t hi, hipStream_t s);   // gr_zero_idle_bursts
 void launch_pfb_synth(const SynthParams& p, int batch, hipStream_t s);
 // items [q0, q0 + count) of every ring row, converted, to out[row * out_stride + t] (qrl_synth single carrier: the resampler's ring -> the caller's sc16 buffer)

@@ -1,4 +1,4 @@
-// host_common.cpp — what every host translation unit of libqrl_hip.so links against: error text, launch-error marks, role streams, the carrier NCO.
+// host_common.cpp — what every host translation unit of libqrl_hip.so links against: error text, launch-error marks, streams, the sc16 input checks, the carrier NCO.
 #include "host_common.hpp"
 #include "firdes.hpp"
 #include <cmath>
@@ -43,6 +43,27 @@ int create_role_stream(hipStream_t* s, int priority, const char* role)
     }
     if (err != hipSuccess) { qrl_set_error(QRL_ERR_HIP, std::string("stream creation: ") + hipGetErrorString(err)); return QRL_ERR_HIP; }
     return QRL_OK;
+}
+
+int HandleStream::open(void* user_stream, const char* role)
+{
+    if (user_stream) { s = static_cast<hipStream_t>(user_stream); return QRL_OK; }
+    if (role && std::getenv((std::string("QRL_CU_") + role).c_str())) { if (int r = create_role_stream(&s, 0, role)) return r; }
+    else HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    own = true;
+    return QRL_OK;
+}
+bool sc16_scale_ok(const char* who, float scale)
+{
+    if (std::isfinite(scale) && scale != 0.0f) return true;
+    qrl_set_error(QRL_ERR_ARG, std::string(who) + ": scale must be finite and non-zero");
+    return false;
+}
+bool sc16_rows_ok(const char* who, const void* iq, size_t stride)
+{
+    if (!(reinterpret_cast<uintptr_t>(iq) & 15u) && !(stride & 3u)) return true;
+    qrl_set_error(QRL_ERR_ARG, std::string(who) + ": sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+    return false;
 }
 
 std::vector<float2> rot_fine_table(uint64_t inc)

@@ -1,5 +1,5 @@
 // host_common.hpp — what every host translation unit of libqrl_hip.so shares: the context, error reporting, the owning device
-// buffer and the carrier NCO of a handle.  Host only: no .hip file includes it.
+// buffer, the stream and the carrier NCO of a handle, the checks of an sc16 input.  Host only: no .hip file includes it.
 #pragma once
 #include "../../include/qrl_hip.h"
 #include "engine.hpp"
@@ -56,6 +56,23 @@ template <class T> struct DevBuf {
         return hipMemcpy(p, h.data(), h.size(), hipMemcpyHostToDevice) == hipSuccess ? QRL_OK : QRL_ERR_HIP;
     }
 };
+
+// The stream of a single-stream handle: the caller's, or one of the handle's own (hipStreamNonBlocking; with a role, the QRL_CU_<ROLE> stream
+// of create_role_stream when that variable is set).  Destroys only what it made.
+struct HandleStream {
+    HandleStream() = default;
+    HandleStream(const HandleStream&) = delete; HandleStream& operator=(const HandleStream&) = delete;
+    ~HandleStream() { if (own && s) (void)hipStreamDestroy(s); }
+    int open(void* user_stream, const char* role = nullptr);
+    operator hipStream_t() const { return s; }
+    bool owned() const { return own; }
+private:
+    hipStream_t s = nullptr; bool own = false;
+};
+
+// ---- sc16 input (qrl_*_process_sc16 of the receivers and the spectrum tap): false = refused, with the error text set ----
+bool sc16_scale_ok(const char* who, float scale);                       // finite and non-zero
+bool sc16_rows_ok(const char* who, const void* iq, size_t stride);     // 16-byte aligned base, stride a multiple of 4 samples
 
 // ---- the carrier NCO of a handle (qrl_demod, qrl_mod, qrl_amod): exact 2^-64-turn accumulator, phase continuous across retunes ----
 // Shared form: one (acc, inc) for every stream, phase of sample n = acc + (n - nbase) inc, and the 512-entry fine table of inc.

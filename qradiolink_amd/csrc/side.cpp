@@ -10,8 +10,6 @@
 #include <cmath>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace qrl;
 
@@ -23,24 +21,20 @@ using namespace qrl;
 
 struct qrl_rssi {
     qrl_ctx* ctx = nullptr; int batch = 1; float level = 0.f;
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     DevBuf<RssiState> st; DevBuf<float> ring;
-    ~qrl_rssi() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
 };
 
 struct qrl_fft {
     qrl_ctx* ctx = nullptr; int batch = 1;
     unsigned fftsize = 0; int wintype = -1;
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     hipfftHandle plan = 0; bool have_plan = false;
     DevBuf<float> win, points; DevBuf<float2> buf, spec;
     unsigned counter = 0; int push = 0; bool data_ready = false, enabled = false;
     float sc16_scale = 1.0f / 32768.0f;   // qrl_fft_process_sc16: x = (float)v * sc16_scale
     void drop_plan() { if (have_plan) { (void)hipfftDestroy(plan); have_plan = false; } }
-    ~qrl_fft() {
-        drop_plan();
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    ~qrl_fft() { drop_plan(); }
 };
 
 // gr::fft::window::build(type, ntaps, beta) [GR-MEM]: the cosine-sum windows over M = ntaps - 1, Kaiser by I0, Bartlett, flat top
@@ -117,8 +111,7 @@ int qrl_rssi_create(qrl_ctx* ctx, int batch, float level, void* hip_stream, qrl_
     if (!h) return QRL_ERR_NOMEM;
     h->ctx = ctx; h->batch = batch; h->level = level;
     HIPCHK(hipSetDevice(ctx->device));
-    if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    if (int r0 = h->stream.open(hip_stream)) return r0;
     int r;
     if ((r = h->st.alloc(batch)) || (r = h->ring.alloc((size_t)batch * RSSI_RING))) return r;
     *out = h.release();
@@ -152,7 +145,7 @@ int qrl_rssi_process(qrl_rssi* h, const float* filtered, size_t stride, size_t n
     return QRL_OK;
 }
 int qrl_rssi_sync(qrl_rssi* h) { if (!h) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(h->stream)); return QRL_OK; }
-void* qrl_rssi_stream(qrl_rssi* h) { return h ? h->stream : nullptr; }
+void* qrl_rssi_stream(qrl_rssi* h) { return h ? (hipStream_t)h->stream : nullptr; }
 
 int qrl_fft_create(qrl_ctx* ctx, int batch, unsigned fftsize, int wintype, void* hip_stream, qrl_fft** out)
 {
@@ -162,8 +155,7 @@ int qrl_fft_create(qrl_ctx* ctx, int batch, unsigned fftsize, int wintype, void*
     if (!h) return QRL_ERR_NOMEM;
     h->ctx = ctx; h->batch = batch;
     HIPCHK(hipSetDevice(ctx->device));
-    if (hip_stream) h->stream = static_cast<hipStream_t>(hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    if (int r0 = h->stream.open(hip_stream)) return r0;
     if (int r = fft_configure(h.get(), fftsize, wintype)) return r;
     *out = h.release();
     return QRL_OK;
@@ -214,13 +206,13 @@ int qrl_fft_process(qrl_fft* h, const float* iq, size_t stride, size_t n)
 int qrl_fft_process_sc16(qrl_fft* h, const int16_t* iq, size_t stride, size_t n)
 {
     if (!h || !iq) return QRL_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 3u)) return qrl_set_error(QRL_ERR_ARG, "qrl_fft_process_sc16: sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
+    if (!sc16_rows_ok("qrl_fft_process_sc16", iq, stride)) return QRL_ERR_ARG;
     return fft_process_impl(h, iq, stride, n, IN_SC16);
 }
 int qrl_fft_set_sc16_scale(qrl_fft* h, float scale)
 {
     if (!h) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_fft_set_sc16_scale: scale must be finite and non-zero");
+    if (!sc16_scale_ok("qrl_fft_set_sc16_scale", scale)) return QRL_ERR_ARG;
     h->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
     return QRL_OK;
 }
@@ -239,6 +231,6 @@ int qrl_fft_get_fft_data(qrl_fft* h, float* fft_points, size_t out_stride, unsig
     return QRL_OK;
 }
 int qrl_fft_sync(qrl_fft* h) { if (!h) return QRL_ERR_ARG; HIPCHK(hipStreamSynchronize(h->stream)); return QRL_OK; }
-void* qrl_fft_stream(qrl_fft* h) { return h ? h->stream : nullptr; }
+void* qrl_fft_stream(qrl_fft* h) { return h ? (hipStream_t)h->stream : nullptr; }
 
 }  // extern "C"

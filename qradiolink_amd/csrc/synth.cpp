@@ -1,47 +1,26 @@
 // synth.cpp — host side of the multi-carrier MMDVM transmitter (reference src/gr/gr_mod_mmdvm_multi2.cpp:30-128):
 // per channel int16 -> FM modulator -> LPF -> x0.8 -> 25/24 resampler, then pfb_synthesizer_ccf(10) -> x(1/N) -> bb gain.
-#include "host_common.hpp"
+#include "tx_common.hpp"
 #include "firdes.hpp"
-#include <algorithm>
 #include <cmath>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace qrl;
 
 struct qrl_synth {
     qrl_ctx* ctx = nullptr; qrl_synth_config cfg{};
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream;
     int N = 3, J = 0, filt_nt = 0, rs_Jp = 0; float bb_gain = 1.0f; bool single = false; int rs_I = 25, rs_D = 24;
     DevBuf<float> filt_taps, rs_taps, syn_taps, rA, phase; DevBuf<float2> twiddle, rB, rC, rD;
     uint32_t m1 = 0, m25 = 0; uint64_t n1 = 0, n25 = 0;
     int port_chan[16];
-    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_synth_process_sc16 (the format itself belongs to the call)
-    std::vector<ZeroRun> zero_runs; DevBuf<ZeroRun> zero_dev;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
-    ~qrl_synth() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    Sc16Sink sc;     // qrl_synth_process_sc16
+    ZeroRuns zero;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
     int reset_state() {
         if (rA.zero() || rB.zero() || rC.zero() || rD.zero() || phase.zero()) return QRL_ERR_HIP;
         n1 = n25 = 0;
-        zero_runs.clear();
-        return QRL_OK;
-    }
-    // the runs that touch [lo, hi) go to the device and are applied to ring r; runs that end before hi are dropped afterwards
-    int apply_zero_runs(RingC r, uint64_t lo, uint64_t hi) {
-        std::vector<ZeroRun> live;
-        for (const ZeroRun& z : zero_runs) if (z.start < hi && z.start + z.count > lo) live.push_back(z);
-        if (!live.empty()) {
-            if (live.size() > zero_dev.n) {
-                if (int rr = zero_dev.alloc(live.size() + 16)) return rr;
-            }
-            if (hipMemcpyAsync(zero_dev.p, live.data(), live.size() * sizeof(ZeroRun), hipMemcpyHostToDevice, stream) != hipSuccess) return QRL_ERR_HIP;
-            if (hipStreamSynchronize(stream) != hipSuccess) return QRL_ERR_HIP;   // `live` is a stack vector: the copy must be through
-            launch_zero_runs(r, zero_dev.p, (uint32_t)live.size(), lo, hi, stream);
-        }
-        std::vector<ZeroRun> keep;
-        for (const ZeroRun& z : zero_runs) if (z.start + z.count > hi) keep.push_back(z);
-        zero_runs.swap(keep);
+        zero.clear();
         return QRL_OK;
     }
 };
@@ -62,8 +41,7 @@ int qrl_synth_create(qrl_ctx* ctx, const qrl_synth_config* cfg, qrl_synth** outp
     h->bb_gain = cfg->bb_gain == 0.0f ? 1.0f : cfg->bb_gain;
     const int fw = cfg->filter_width > 0 ? cfg->filter_width : 5000, M = 10;
     HIPCHK(hipSetDevice(ctx->device));
-    if (cfg->hip_stream) h->stream = static_cast<hipStream_t>(cfg->hip_stream);
-    else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    if (int r0 = h->stream.open(cfg->hip_stream)) return r0;
     int r;
     const std::vector<float> ft = low_pass_2(1, 24000, fw, 2000, 60, WIN_BLACKMAN_HARRIS);          // _filter, :52-53
     h->filt_nt = (int)ft.size();
@@ -107,15 +85,7 @@ int qrl_synth_add_zero_runs(qrl_synth* h, const qrl_zero_run* runs, size_t n)
     for (size_t i = 0; i < n; ++i) {
         if (runs[i].stream < 0 || runs[i].stream >= h->cfg.batch || runs[i].channel < 0 || runs[i].channel >= h->N)
             return qrl_set_error(QRL_ERR_ARG, "zero run: stream / channel out of range");
-        // gr_zero_idle_bursts keeps ONE counter per stream and a tag overwrites it (gr_zero_idle_bursts.cpp:62-69): a run that starts
-        // inside another one ends it there -- the zeroed set is [s_i, min(s_i + c_i, s_next)) over the tags in offset order
-        ZeroRun z{(uint32_t)(runs[i].stream * h->N + runs[i].channel), 0u, runs[i].start, runs[i].count};
-        for (ZeroRun& o : h->zero_runs) {
-            if (o.row != z.row) continue;
-            if (o.start < z.start && o.start + o.count > z.start) o.count = z.start - o.start;
-            else if (z.start < o.start && z.start + z.count > o.start) z.count = o.start - z.start;
-        }
-        h->zero_runs.push_back(z);
+        h->zero.add((uint32_t)(runs[i].stream * h->N + runs[i].channel), runs[i].start, runs[i].count);   // one ring row per (stream, channel)
     }
     return QRL_OK;
 }
@@ -142,10 +112,7 @@ static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t 
     TxFmParams fp{}; fp.in = sp.out; fp.out = RingC{h->rB.p, h->m1}; fp.n0 = h->n1; fp.count = c1;
     fp.k = (float)(2 * M_PI * 12500.0f / 24000.0f); fp.amp = 1.0f; fp.phase = h->phase.p;            // _fm_modulator, :64-66
     launch_tx_fm(fp, S, h->stream);
-    if (h->single && !h->zero_runs.empty()) {   // gr_mod_mmdvm.cpp:57-58: zero_idle_bursts between the FM modulator and the filter (24 ksps)
-        const int zr = h->apply_zero_runs(fp.out, h->n1, n1_1);
-        if (zr) return zr;
-    }
+    if (int zr = h->single ? h->zero.apply(fp.out, h->n1, n1_1, h->stream) : QRL_OK) return zr;   // gr_mod_mmdvm.cpp:57-58: zero_idle_bursts between the FM modulator and the filter (24 ksps)
     FirCcfParams ff{}; ff.in = fp.out; ff.out = RingC{h->rC.p, h->m1}; ff.q0 = h->n1; ff.count = c1; ff.taps = h->filt_taps.p; ff.nt = h->filt_nt;
     launch_fir_ccf(ff, S, h->stream);
     launch_scale_c(ff.out, h->n1, c1, 0.8f, S, h->stream);                                           // _amplify, :77-79
@@ -158,15 +125,12 @@ static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t 
         // sc16: k_resamp is shared with the receivers and keeps its code; its ring row of this call is converted by a kernel of its own
         if (sc.on) launch_ring_store_sc16(rp.out, h->n25, (uint32_t)std::min<size_t>(c25, out_stride), reinterpret_cast<uint32_t*>(iq), out_stride, sc, S, h->stream);
         HIPCHK(hipGetLastError());
-    if (qrl::take_launch_error()) return QRL_ERR_HIP;
+        if (qrl::take_launch_error()) return QRL_ERR_HIP;
         h->n1 = n1_1; h->n25 = n25_1;
         if (produced) *produced = (size_t)c25;
         return QRL_OK;
     }
-    if (!h->zero_runs.empty()) {   // gr_mod_mmdvm_multi2.cpp:108: zero_idle_bursts behind the 25/24 resampler (25 ksps)
-        const int zr = h->apply_zero_runs(rp.out, h->n25, n25_1);
-        if (zr) return zr;
-    }
+    if (int zr = h->zero.apply(rp.out, h->n25, n25_1, h->stream)) return zr;   // gr_mod_mmdvm_multi2.cpp:108: zero_idle_bursts behind the 25/24 resampler (25 ksps)
     SynthParams yp{}; yp.in = rp.out; yp.nch = N; for (int p = 0; p < 16; ++p) yp.port_chan[p] = h->port_chan[p];
     yp.blk0 = h->n25; yp.nblk = c25; yp.taps = h->syn_taps.p; yp.twiddle = h->twiddle.p; yp.M = 10; yp.J = h->J;
     yp.level = 1.0f / (float)N; yp.bb_gain = h->bb_gain;                                             // _divide_level, _bb_gain :91-95
@@ -187,18 +151,12 @@ int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, 
 }
 int qrl_synth_process_sc16(qrl_synth* h, const int16_t* in, size_t stride, size_t n, int16_t* iq, size_t out_stride, size_t* produced)
 {
-    if (!h) return QRL_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_synth_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
-    return synth_process(h, in, stride, n, iq, out_stride, produced, Sc16Out{1, h->sc_scale, h->sc_clip});
+    Sc16Out sc;
+    if (int r = h ? h->sc.for_call("qrl_synth_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
+    return synth_process(h, in, stride, n, iq, out_stride, produced, sc);
 }
-int qrl_synth_set_sc16_scale(qrl_synth* h, float scale)
-{
-    if (!h) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_synth_set_sc16_scale: scale must be finite and non-zero");
-    h->sc_scale = scale;
-    return QRL_OK;
-}
-int qrl_synth_set_sc16_clip_counts(qrl_synth* h, uint32_t* counts) { if (!h) return QRL_ERR_ARG; h->sc_clip = counts; return QRL_OK; }
+int qrl_synth_set_sc16_scale(qrl_synth* h, float scale) { return h ? h->sc.set_scale("qrl_synth_set_sc16_scale", scale) : QRL_ERR_ARG; }
+int qrl_synth_set_sc16_clip_counts(qrl_synth* h, uint32_t* counts) { return h ? h->sc.set_clip(counts) : QRL_ERR_ARG; }
 int qrl_synth_sync(qrl_synth* h)
 {
     if (!h) return QRL_ERR_ARG;

@@ -1,28 +1,24 @@
 // tx.cpp — host side of the TX half of libqrl_hip.so: the "modulator" top_block of the reference
 // (src/gr/gr_mod_base.cpp:25,175; src/gr/gr_mod_qpsk.cpp:56-89) as a two-kernel pipeline per call.
-#include "host_common.hpp"
+#include "tx_common.hpp"
 #include "firdes.hpp"
 #include <cmath>
-#include <cstring>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace qrl;
 
 struct qrl_mod {
     qrl_ctx* ctx = nullptr;
     qrl_mod_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    HandleStream stream;
     enum { F_QPSK, F_FSK } fam = F_QPSK;   // F_QPSK: symbols -> RRC interpolator (QPSK, BPSK); F_FSK: shape -> FM -> interpolator
     bool bpsk = false, fsk4 = false; float shape_scale = 0.0f;
     // gr_mod_m17: raw dibits -> RRC x5 -> FM -> channel filter -> gains -> 125 / 3 (2500 samples per 3 bytes)
     bool m17 = false; DevBuf<float> m17_filt; int m17_nf = 0; DevBuf<float2> m17_flt;
     // gr_mod_dmr (src/gr/gr_mod_dmr.cpp:26-90): the m17 path with the DMR pulse and deviation; gr_zero_idle_bursts(62) in the place of the channel
     // filter = the stream 2 x 720 - 1 items late (the block's history, gr_zero_idle_bursts.cpp:34-37,76) + the tagged runs zeroed `delay` items early
-    bool dmr = false; std::vector<ZeroRun> zero_runs; DevBuf<ZeroRun> zero_dev;
+    bool dmr = false; ZeroRuns zero;
     static constexpr uint32_t kDmrHist = 2 * 720 - 1, kDmrTagDelay = 62;
     // gr_mod_dsss: coded bits -> Barker-13 chips -> RRC x25 (5200 sps) -> gains -> 50 / 13 (20 ksps) -> 1:50; 1 000 000 samples per byte
     bool dsss = false; DevBuf<uint8_t> ds_chips; uint32_t ds_chip_mask = 0; DevBuf<float> ds_shaped; DevBuf<float2> ds_c52, ds_c20;
@@ -36,13 +32,10 @@ struct qrl_mod {
     DevBuf<TxState> st;
     DevBuf<uint8_t> sym; uint32_t sym_mask = 0;
     uint64_t nsym = 0;   // symbols (= input bits) so far
-    // gr_mod_base back end (gr_mod_base.cpp:38,215-258): rotator at 1 Msps, then interpolation to the device rate
-    bool backend = false; int be_interp = 1; DevBuf<float> be_taps; int be_nt = 0;
-    DevBuf<float2> bb; size_t bb_stride = 0;           // modulator output, linear, one call's worth
-    DevBuf<float2> be_ring; uint32_t be_mask = 0;       // rotated 1 Msps signal (interpolator history)
-    Rotator rot; uint64_t n_bb = 0;   // carrier NCO at 1 Msps; n_bb: samples through it so far
-    float sc_scale = 32767.0f; uint32_t* sc_clip = nullptr;   // qrl_mod_process_sc16: the format belongs to the call, these two to the handle
-    ~qrl_mod() { if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    TxBackEnd be;   // gr_mod_base back end (gr_mod_base.cpp:38,215-258): rotator at 1 Msps, then interpolation to the device rate
+    Sc16Sink sc;    // qrl_mod_process_sc16
+    size_t spb_1msps() const   // 1 Msps samples per byte of the chains that may have a back end; 0 for m17 / dmr / dsss, which have none
+    { return m17 || dsss ? 0 : fsk4 ? (size_t)8 * sps * interp2 : fam == F_FSK ? (size_t)16 * sps * interp2 : (size_t)(bpsk ? 16 : 8) * sps; }
     int init_state() {
         int r;
         const TxState x{0x7F, 0, 0, 0};   // scrambler seed 0x7F (gr_mod_qpsk.cpp:62)
@@ -53,10 +46,9 @@ struct qrl_mod {
         if (dsss) {
             if ((r = ds_chips.zero()) || (r = ds_shaped.zero()) || (r = ds_c52.zero()) || (r = ds_c20.zero())) return r;
         }
-        if (be_ring.p && (r = be_ring.zero())) return r;
-        nsym = 0; n_bb = 0;
-        zero_runs.clear();
-        return rot.reset(stream);   // per-stream phases restart too; the offsets stay
+        nsym = 0;
+        zero.clear();
+        return be.reset(stream);   // per-stream phases restart too; the offsets stay
     }
 };
 
@@ -140,14 +132,7 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
     m->sps = c.sps;
     m->bb_gain = c.bb_gain == 0.0f ? 1.0f : c.bb_gain;
     HIPCHK(hipSetDevice(ctx->device));
-    if (c.hip_stream) m->stream = static_cast<hipStream_t>(c.hip_stream);
-    else {
-        int r0;
-        if (std::getenv("QRL_CU_TX")) { if ((r0 = qrl::create_role_stream(&m->stream, 0, "TX"))) return r0; }
-        else HIPCHK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
-    constexpr size_t kTapPad = 64;   // zeros behind every tap table: k_tx_interp_sym reads its I x J = 64 taps unguarded
+    if (int r0 = m->stream.open(c.hip_stream, "TX")) return r0;
     size_t ring_items = c.max_bytes * 8 + 256;   // symbol ring: one item per input bit (QPSK) or per coded bit (FSK: x2)
     if (m->dsss) {   // gr_mod_dsss.cpp:60-76
         const int fw = c.filter_width;
@@ -232,24 +217,7 @@ int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** outp)
             if ((r0 = m->m17_flt.alloc((size_t)c.batch * cap1))) return r0;
         }
     }
-    if (c.device_samp_rate != 0 && c.device_samp_rate != 1000000 &&
-        (c.device_samp_rate < 2000000 || c.device_samp_rate % 1000000 != 0 || c.device_samp_rate > 64000000))
-        return qrl_set_error(QRL_ERR_ARG, "modulator: device_samp_rate must be 1e6 or a multiple of 1e6 in [2e6, 64e6]");
-    m->be_interp = c.device_samp_rate >= 2000000 ? c.device_samp_rate / 1000000 : 1;
-    m->backend = m->be_interp > 1 || c.carrier_offset_hz != 0.0;
-    if (m->backend) {
-        const size_t spb1 = fsk4 ? (size_t)8 * m->sps * m->interp2 : fsk ? (size_t)16 * m->sps * m->interp2 : (size_t)(bpsk ? 16 : 8) * m->sps;
-        m->bb_stride = c.max_bytes * spb1;
-        int r0;
-        if ((r0 = m->bb.alloc((size_t)c.batch * m->bb_stride)) || (r0 = m->rot.init(phase_inc_to_turn(2 * M_PI * c.carrier_offset_hz / 1000000.0)))) return r0;
-        if (m->be_interp > 1) {
-            const std::vector<float> lp = low_pass(m->be_interp, c.device_samp_rate, 480000, 20000, WIN_BLACKMAN_HARRIS);
-            m->be_nt = (int)lp.size();
-            if ((r0 = m->be_taps.upload(lp, kTapPad))) return r0;
-            m->be_mask = pow2_at_least(m->bb_stride + (size_t)m->be_nt / m->be_interp + 64, 1024) - 1;
-            if ((r0 = m->be_ring.alloc((size_t)c.batch * (m->be_mask + 1)))) return r0;
-        }
-    }
+    if (int r0 = m->be.init("modulator", "modulator", c.device_samp_rate, c.carrier_offset_hz, c.batch, c.max_bytes * m->spb_1msps())) return r0;
     m->sym_mask = pow2_at_least(ring_items, 1024) - 1;
     int r;
     if ((r = m->st.alloc(c.batch)) || (r = m->sym.alloc((size_t)c.batch * (m->sym_mask + 1))) || (r = m->init_state())) return r;
@@ -263,22 +231,8 @@ int qrl_mod_reset(qrl_mod* m)
     HIPCHK(hipStreamSynchronize(m->stream));
     return m->init_state();
 }
-int qrl_mod_set_carrier_offset(qrl_mod* m, double hz)
-{
-    if (!m) return QRL_ERR_ARG;
-    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
-    HIPCHK(hipStreamSynchronize(m->stream));   // rot_lo is rewritten below
-    return m->rot.retune(m->n_bb, phase_inc_to_turn(2 * M_PI * hz / 1000000.0), m->stream);   // phase-continuous, like rotator_cc::set_phase_inc
-}
-int qrl_mod_set_carrier_offsets(qrl_mod* m, const double* hz)
-{
-    if (!m || !hz) return QRL_ERR_ARG;
-    if (!m->backend) return qrl_set_error(QRL_ERR_ARG, "modulator was created without the gr_mod_base back end");
-    std::vector<uint64_t> ni;
-    if (int r = carrier_incs(hz, m->cfg.batch, 1.0, 1000000.0, ni)) return r;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    return m->rot.retune_streams(m->n_bb, ni, m->stream);
-}
+int qrl_mod_set_carrier_offset(qrl_mod* m, double hz) { return m ? m->be.retune(hz, m->stream) : QRL_ERR_ARG; }
+int qrl_mod_set_carrier_offsets(qrl_mod* m, const double* hz) { return m && hz ? m->be.retune_streams(hz, m->cfg.batch, m->stream) : QRL_ERR_ARG; }
 int qrl_mod_set_bb_gain(qrl_mod* m, float g) { if (!m) return QRL_ERR_ARG; m->bb_gain = g; return QRL_OK; }
 int qrl_mod_add_zero_runs(qrl_mod* m, const qrl_zero_run* runs, size_t n)
 {
@@ -287,14 +241,8 @@ int qrl_mod_add_zero_runs(qrl_mod* m, const qrl_zero_run* runs, size_t n)
     for (size_t i = 0; i < n; ++i) {
         if (runs[i].stream < 0 || runs[i].stream >= m->cfg.batch) return qrl_set_error(QRL_ERR_ARG, "zero run: stream out of range");
         if (runs[i].start < qrl_mod::kDmrTagDelay) continue;                            // `tag.offset == nitems + i + _delay` has no item to match (gr_zero_idle_bursts.cpp:64)
-        // the counter is loaded at OUTPUT item T - delay; one counter per stream, a later tag overwrites it (as qrl_synth_add_zero_runs)
-        ZeroRun z{(uint32_t)runs[i].stream, 0u, runs[i].start - qrl_mod::kDmrTagDelay, runs[i].count};
-        for (ZeroRun& o : m->zero_runs) {
-            if (o.row != z.row) continue;
-            if (o.start < z.start && o.start + o.count > z.start) o.count = z.start - o.start;
-            else if (z.start < o.start && z.start + z.count > o.start) z.count = o.start - z.start;
-        }
-        m->zero_runs.push_back(z);
+        // the counter is loaded at OUTPUT item T - delay; one counter per stream, a later tag overwrites it (ZeroRunList::add)
+        m->zero.add((uint32_t)runs[i].stream, runs[i].start - qrl_mod::kDmrTagDelay, runs[i].count);
     }
     return QRL_OK;
 }
@@ -311,9 +259,7 @@ size_t qrl_mod_samples_per_byte(const qrl_mod* m)
     if (!m) return 0;
     if (m->m17) return 0;   // 833 1/3: see qrl_mod_samples_per_block
     if (m->dsss) return 1000000;   // 16 coded bits x 13 chips x 25 x 50 / 13 x 50
-    const size_t spb1 = m->fsk4 ? (size_t)8 * m->sps * m->interp2 : m->fam == qrl_mod::F_FSK ? (size_t)16 * m->sps * m->interp2
-                                : (size_t)(m->bpsk ? 16 : 8) * m->sps;
-    return spb1 * (size_t)m->be_interp;
+    return m->spb_1msps() * (size_t)m->be.interp();
 }
 
 }  // extern "C"
@@ -327,23 +273,7 @@ static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t n
     HIPCHK(hipSetDevice(m->ctx->device));
     const int B = m->cfg.batch;
     const uint32_t nbits = (uint32_t)nbytes * 8;
-    float2* mod_out = m->backend ? m->bb.p : reinterpret_cast<float2*>(iq);
-    const size_t mod_stride = m->backend ? m->bb_stride : out_stride;
-    const Sc16Out mod_sc = m->backend ? Sc16Out{} : sc;
-    auto back_end = [&](uint32_t n1) {   // n1 samples per stream at 1 Msps are in bb
-        TxRotParams rp{}; rp.in = m->bb.p; rp.in_stride = m->bb_stride; rp.n0 = m->n_bb; rp.count = n1;
-        m->rot.fill(rp);
-        if (m->be_interp > 1) rp.out_ring = RingC{m->be_ring.p, m->be_mask};
-        else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; rp.sc = sc; }
-        launch_tx_rot(rp, B, m->stream);
-        if (m->be_interp > 1) {
-            TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = m->n_bb * (uint64_t)m->be_interp; bp.count = n1 * (uint32_t)m->be_interp;
-            bp.taps = m->be_taps.p; bp.nt = m->be_nt; bp.interp = m->be_interp;
-            bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride; bp.sc = sc;
-            launch_tx_interp_c(bp, B, m->stream);
-        }
-        m->n_bb += n1;
-    };
+    const TxBackEnd::Target to = m->be.target(iq, out_stride, sc);   // where the 1 Msps chain ends: the caller's buffer, or the back end's
     if (m->m17) {
         if (nbytes % 3) return qrl_set_error(QRL_ERR_ARG, "modulator: m17 takes multiples of 3 bytes per call (2500 samples per 3 bytes)");
         const uint32_t nsy = (uint32_t)nbytes * 4, c24 = nsy * 5, cout = c24 / 3 * 125;
@@ -359,24 +289,7 @@ static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t n
         RingC flt{m->m17_flt.p, m->r1_mask};
         FirCcfParams cf{}; cf.in = fp.out; cf.out = flt; cf.q0 = n24; cf.count = c24; cf.taps = m->m17_filt.p; cf.nt = m->m17_nf;
         launch_fir_ccf(cf, B, m->stream);                                               // _filter (gr_mod_dmr: the history delay of _zero_idle)
-        if (m->dmr && !m->zero_runs.empty()) {                                          // _zero_idle: the tagged runs of this call's items
-            const uint64_t lo = n24, hi = n24 + c24;
-            std::vector<ZeroRun> live, keep;
-            for (const ZeroRun& z : m->zero_runs) {
-                if (z.start < hi && z.start + z.count > lo) live.push_back(z);
-                if (z.start + z.count > hi) keep.push_back(z);
-            }
-            if (!live.empty()) {
-                if (live.size() > m->zero_dev.n) {
-                    HIPCHK(hipStreamSynchronize(m->stream));
-                    if (int rz = m->zero_dev.grow(live.size() * 2)) return rz;
-                }
-                HIPCHK(hipMemcpyAsync(m->zero_dev.p, live.data(), live.size() * sizeof(ZeroRun), hipMemcpyHostToDevice, m->stream));
-                HIPCHK(hipStreamSynchronize(m->stream));                                // (`live` is pageable host memory: the copy has left it)
-                launch_zero_runs(flt, m->zero_dev.p, (uint32_t)live.size(), lo, hi, m->stream);
-            }
-            m->zero_runs.swap(keep);
-        }
+        if (int rz = m->zero.apply(flt, n24, n24 + c24, m->stream)) return rz;         // _zero_idle: the tagged runs of this call's items (DMR only has any)
         launch_scale_c(flt, n24, c24, 0.9f, B, m->stream);                              // _amplify
         launch_scale_c(flt, n24, c24, m->bb_gain, B, m->stream);                        // _bb_gain
         TxInterpCParams ip{}; ip.in = flt; ip.n0 = n24 / 3 * 125; ip.count = cout; ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = 125; ip.decim = 3;
@@ -427,11 +340,11 @@ static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t n
         fp.phase = m->phase.p;
         launch_tx_fm(fp, B, m->stream);
         TxInterpCParams ip{}; ip.in = fp.out; ip.n0 = n1_0 * (uint64_t)m->interp2; ip.count = c1 * (uint32_t)m->interp2;
-        ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = m->interp2; ip.out = mod_out; ip.out_stride = mod_stride; ip.sc = mod_sc;
+        ip.taps = m->taps.p; ip.nt = m->nt; ip.interp = m->interp2; ip.out = to.out; ip.out_stride = to.stride; ip.sc = to.sc;
         launch_tx_interp_c(ip, B, m->stream);
-        if (m->backend) back_end(ip.count);
+        m->be.run(ip.count, iq, out_stride, sc, B, m->stream);
         HIPCHK(hipGetLastError());
-    if (qrl::take_launch_error()) return QRL_ERR_HIP;
+        if (qrl::take_launch_error()) return QRL_ERR_HIP;
         m->nsym += ncoded;
         return QRL_OK;
     }
@@ -444,9 +357,9 @@ static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t n
     q.table[2] = make_float2(0.707f, 0.707f);   q.table[3] = make_float2(0.707f, -0.707f);
     if (m->bpsk) { q.table[0] = make_float2(-1.0f, 0.0f); q.table[1] = make_float2(1.0f, 0.0f); }   // gr_mod_bpsk.cpp:33-35
     q.amp = 0.6f; q.bb_gain = m->bb_gain;
-    q.out = mod_out; q.out_stride = mod_stride; q.sc = mod_sc;
+    q.out = to.out; q.out_stride = to.stride; q.sc = to.sc;
     launch_tx_interp(q, B, m->stream);
-    if (m->backend) back_end(q.count);
+    m->be.run(q.count, iq, out_stride, sc, B, m->stream);
     HIPCHK(hipGetLastError());
     if (qrl::take_launch_error()) return QRL_ERR_HIP;
     m->nsym += nitems;
@@ -461,24 +374,18 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
 }
 int qrl_mod_process_sc16(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int16_t* iq, size_t out_stride)
 {
-    if (!m) return QRL_ERR_ARG;
-    if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, "qrl_mod_process_sc16: iq must be 4-byte aligned (one packed store per sample)");
-    return mod_process(m, bytes, stride, nbytes, iq, out_stride, Sc16Out{1, m->sc_scale, m->sc_clip});
+    Sc16Out sc;
+    if (int r = m ? m->sc.for_call("qrl_mod_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
+    return mod_process(m, bytes, stride, nbytes, iq, out_stride, sc);
 }
-int qrl_mod_set_sc16_scale(qrl_mod* m, float scale)
-{
-    if (!m) return QRL_ERR_ARG;
-    if (!std::isfinite(scale) || scale == 0.0f) return qrl_set_error(QRL_ERR_ARG, "qrl_mod_set_sc16_scale: scale must be finite and non-zero");
-    m->sc_scale = scale;
-    return QRL_OK;
-}
-int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts) { if (!m) return QRL_ERR_ARG; m->sc_clip = counts; return QRL_OK; }
+int qrl_mod_set_sc16_scale(qrl_mod* m, float scale) { return m ? m->sc.set_scale("qrl_mod_set_sc16_scale", scale) : QRL_ERR_ARG; }
+int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts) { return m ? m->sc.set_clip(counts) : QRL_ERR_ARG; }
 int qrl_mod_sync(qrl_mod* m)
 {
     if (!m) return QRL_ERR_ARG;
     HIPCHK(hipStreamSynchronize(m->stream));
     return QRL_OK;
 }
-void* qrl_mod_stream(qrl_mod* m) { return m ? m->stream : nullptr; }
+void* qrl_mod_stream(qrl_mod* m) { return m ? (hipStream_t)m->stream : nullptr; }
 
 }  // extern "C"

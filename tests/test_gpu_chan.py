@@ -402,6 +402,32 @@ def test_mmdvm_tx_zero_idle_bursts_bit_exact(qrl_ctx, single):
     assert not np.array_equal(plain, ref)            # the runs did something
 
 
+@pytest.mark.parametrize("single", [False, True])
+def test_mmdvm_tx_zero_run_buffer_grows_between_calls_bit_exact(qrl_ctx, single):
+    """the device copy of the run list is sized by the first call that has a live run (here one, on stream 1) and has to grow for the second (20
+    short disjoint runs on stream 0, none on stream 1) while the stream may still hold the first call's work: both calls equal the oracle"""
+    import torch
+    import qradiolink_amd as q
+    N = 1 if single else 3
+    n = 6000                                          # two calls of 3000: the runs' items [0, 3000) and [3000, 6000) at 24 ksps, x 25 / 24 behind the resampler
+    x = np.stack([_audio(N, n, seed=80 + b) for b in range(2)])
+    runs = [(1, 0, 1000, 300)] + [(0, k % N, 3300 + 120 * k, 40) for k in range(20)]   # (stream, channel, start, count)
+    syn = q.Synth(qrl_ctx, N, batch=2, max_samples=3000, bb_gain=1.0, single_carrier=single)
+    syn.add_zero_runs(runs)
+    d = torch.from_numpy(x).cuda()
+    got = np.concatenate([syn.process(d[:, :, pos:pos + 3000]).cpu().numpy() for pos in (0, 3000)], axis=1)
+    syn.close()
+    for b in range(2):
+        orc.set_zero_runs([(ch, st, cnt) for s, ch, st, cnt in runs if s == b])
+        ref = orc.mod_mmdvm(x[b, 0], bb_gain=1.0) if single else orc.mod_mmdvm_multi(x[b])
+        orc.set_zero_runs(None)
+        assert got[b].size == ref.size
+        g, w = got[b].view(np.float32) + np.float32(0), ref.view(np.float32) + np.float32(0)
+        assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), "stream %d differs" % b
+        plain = orc.mod_mmdvm(x[b, 0], bb_gain=1.0) if single else orc.mod_mmdvm_multi(x[b])
+        assert not np.array_equal(plain, ref)        # the runs did something
+
+
 # ---- BASELINE.json configs[3] taken literally: 64 x freq-xlating FIR 1:64 (2181-tap prototype) + per-channel chain + 4FSK demod
 @pytest.mark.parametrize("chunk", [64 * 2500, 64 * 625 + 2])
 def test_literal_c4_freq_xlating_bank_64_channels_bit_exact(qrl_ctx, chunk):

@@ -486,6 +486,27 @@ def test_dmr_modulator_bit_exact(qrl_ctx, chunk):
     assert np.abs(w[lo:hi]).max() < 1e-3 and np.abs(w[hi + 6000:hi + 12000]).mean() > 0.3
 
 
+def test_dmr_zero_run_buffer_grows_between_calls_bit_exact(qrl_ctx):
+    """the device copy of the run list is sized by the first call that has a live run (here one, on stream 1) and has to grow for the second (20
+    short disjoint runs on stream 0, none on stream 1) while the stream may still hold the first call's work: both calls equal the oracle"""
+    import torch
+    import qradiolink_amd as q
+    rng = np.random.default_rng(18)
+    nb = 264                                          # two calls of 132 bytes: items [0, 2640) and [2640, 5280) at 24 ksps
+    data = rng.integers(0, 256, (2, nb), dtype=np.uint8)
+    tags = {0: [(2640 + 62 + 100 + 120 * k, 40) for k in range(20)], 1: [(1439 + 62 + 300, 200)]}   # (behind the 1439 items of silence of the block's history)
+    mod = q.Mod(qrl_ctx, q.MODEM_DMR, batch=2, max_bytes=nb, bb_gain=0.9)
+    mod.add_zero_runs([(s, t, c) for s, l in tags.items() for t, c in l])
+    got = np.concatenate([mod.process(torch.from_numpy(np.ascontiguousarray(data[:, s:s + 132])).cuda()).cpu().numpy() for s in (0, 132)], axis=1)
+    mod.close()
+    assert got.shape == (2, nb // 3 * 2500)
+    for b in range(2):
+        want = orc.mod_dmr(data[b], bb_gain=0.9, zero_runs=tags[b])
+        g, w = got[b].view(np.float32) + np.float32(0), want.view(np.float32) + np.float32(0)
+        assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), "stream %d differs" % b
+        assert not np.array_equal(want, orc.mod_dmr(data[b], bb_gain=0.9))            # the runs did something
+
+
 def test_dmr_tx_rx_dibit_loopback_on_gpu(qrl_ctx):
     """bytes -> gr_mod_dmr -> gr_demod_dmr: the dibits that went in come out of the receiver's symbol port (device TX, device RX)"""
     import torch
