@@ -244,7 +244,12 @@ typedef struct {
     float bb_gain;           /* gr_mod_qpsk::set_bb_gain, 0 = 1.0 */
     /* gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258): modulator (1 Msps) -> rotator_cc(2 pi offset / 1e6) ->
      * rational_resampler_ccf(fs/1e6, 1, low_pass(I, fs, 480k, 20k, BLACKMAN_HARRIS)) when fs >= 2 Msps -> SDR sink */
-    int device_samp_rate;    /* gr_mod_base::set_samp_rate: 0 / 1e6 = no resampler, else a multiple of 1e6 in [2e6, 64e6] */
+    /* device_samp_rate: gr_mod_base::set_samp_rate: 0 / 1e6 = no resampler, else a multiple of 1e6 in [2e6, 183e6], the receivers' range (anything
+     * else: QRL_ERR_ARG).  Output counts are 32-bit: a handle whose largest call (max_bytes) would produce 2^32 or more device-rate samples per
+     * stream is refused with QRL_ERR_TOO_BIG.  Finite input gives the reference's sum bit for bit at every rate.  From 4e6 up the interpolator
+     * runs on the matrix pipe with its 209-tap phases padded to 210 lags by zero taps, and a zero tap times inf / NaN is NaN: a NON-FINITE
+     * 1 Msps sample can reach the outputs of one more 1 Msps sample than in the reference (the only departure). */
+    int device_samp_rate;
     double carrier_offset_hz;/* gr_mod_base::set_carrier_offset (rotator at 1 Msps) */
 } qrl_mod_config;
 int qrl_mod_create(qrl_ctx* ctx, const qrl_mod_config* cfg, qrl_mod** out);
@@ -570,7 +575,9 @@ typedef struct qrl_amod_config {
     float bb_gain;         /* gr_mod_nbfm::set_bb_gain; 0 = 1.0 */
     /* gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258), as in qrl_mod_config: 0 / 1000000 = none; >= 2e6 (a multiple of 1e6): the chain's 1 Msps
      * output goes through rotator_cc(2 pi offset / 1e6) and rational_resampler_ccf(rate / 1e6, 1, low_pass(interp, rate, 480000, 20000, BH)); a non-zero
-     * initial offset alone gives the rotator only.  All sample counts (samples_per_sample, out_cap, last_count) then count device-rate samples. */
+     * initial offset alone gives the rotator only.  All sample counts (samples_per_sample, out_cap, last_count) then count device-rate samples.
+     * device_samp_rate: a multiple of 1e6 in [2e6, 183e6], else QRL_ERR_ARG; QRL_ERR_TOO_BIG when max_samples would give 2^32 or more device-rate
+     * samples per stream and call; the same note on non-finite samples as at qrl_mod_config.device_samp_rate. */
     int device_samp_rate;
     double carrier_offset_hz;
 } qrl_amod_config;

@@ -355,6 +355,13 @@ struct TxShapeParams { RingB sym; RingF out; uint64_t n0; uint32_t count; int sp
 struct TxFmParams { RingF in; RingC out; uint64_t n0; uint32_t count; float k, amp; float* phase; };
 struct TxInterpCParams { RingC in; uint64_t n0; uint32_t count; const float* taps; int nt; int interp; float2* out; size_t out_stride;
                          int decim; RingC out_ring; Sc16Out sc; };   // out_ring.p != nullptr: the samples go to ring item n0 + t instead of out (gr_mod_am: a filter follows)   // decim > 1: rational_resampler_ccf(interp, decim) (gr_mod_m17: 125 / 3)
+// k_tx_interp_mfma (kernels_tx_mfma.hip): the back-end interpolator on the f32 matrix pipe.  taps: the layout of tx_mfma_taps (tx_common.cpp),
+// [phase tile][lag][phase in tile], kTxMfmaLags x kTxMfmaPhases floats per tile, zero where ph + lag I >= nt and for phases >= I.
+// in: the rotated 1 Msps ring; sample n0 + c of it, c < n1, gives outputs c I .. c I + I - 1 of this call in out (cf32, or sc16 when sc.on).
+constexpr int kTxMfmaPhases = 32, kTxMfmaLags = 210;   // an MFMA tile's rows; lags per phase of low_pass(I, I * 1e6, 480k, 20k, BH) (209 or 210), even
+struct TxInterpMfmaParams { RingC in; uint64_t n0; uint32_t n1; const float* taps; int interp; uint32_t cpw;   // cpw: blocks per workgroup (launcher)
+                            float2* out; size_t out_stride; Sc16Out sc; };
+void launch_tx_interp_mfma(const TxInterpMfmaParams& p, int batch, hipStream_t s);
 void launch_tx_spread(RingB coded, RingB chips, uint64_t c0, uint32_t ncoded, int batch, hipStream_t s);   // gr_mod_dsss: Barker-13 spreading
 void launch_tx_f2c(RingF in, RingC out, uint64_t n0, uint32_t count, float g, int batch, hipStream_t s);
 void launch_tx_raw_dibits(const uint8_t* bytes, size_t stride, uint32_t nbytes, RingB sym, uint64_t s0, int batch, hipStream_t s);

@@ -5,21 +5,39 @@
 
 namespace qrl {
 
+std::vector<float> tx_mfma_taps(const std::vector<float>& h, int interp)
+{
+    const int tiles = (interp + kTxMfmaPhases - 1) / kTxMfmaPhases;
+    std::vector<float> lay((size_t)tiles * kTxMfmaLags * kTxMfmaPhases, 0.0f);
+    for (size_t k = 0; k < h.size(); ++k) {
+        const size_t ph = k % (size_t)interp, j = k / (size_t)interp;
+        lay[((ph / kTxMfmaPhases) * kTxMfmaLags + j) * kTxMfmaPhases + ph % kTxMfmaPhases] = h[k];
+    }
+    return lay;
+}
+
 int TxBackEnd::init(const char* who, const char* noun, int rate, double offset_hz, int batch, size_t stride)
 {
     noun_ = noun;
-    if (rate != 0 && rate != 1000000 && (rate < 2000000 || rate % 1000000 != 0 || rate > 64000000))
-        return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": device_samp_rate must be 1e6 or a multiple of 1e6 in [2e6, 64e6]");
+    if (rate != 0 && rate != 1000000 && (rate < 2000000 || rate % 1000000 != 0 || rate > kTxMaxRate))
+        return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": device_samp_rate must be 1e6 or a multiple of 1e6 in [2e6, 183e6]");
     interp_ = rate >= 2000000 ? rate / 1000000 : 1;
     on_ = interp_ > 1 || offset_hz != 0.0;
     if (!on_) return QRL_OK;
+    // the interpolator's output count of a call (n1 * interp) and its ring mask (n1 + the filter's history, to a power of two) are 32-bit
+    if (interp_ > 1 && ((uint64_t)stride + 1024) * (uint64_t)interp_ >= (1ull << 32))
+        return qrl_set_error(QRL_ERR_TOO_BIG, std::string(who) + ": the largest call would produce " + std::to_string(stride) + " x " + std::to_string(interp_) +
+                             " device-rate samples per stream, which with the filter's history reaches 2^32 (output counts are 32-bit): lower the per-call maximum");
     int r;
     bb_stride = stride;
     if ((r = bb.alloc((size_t)batch * bb_stride)) || (r = rot.init(phase_inc_to_turn(2 * M_PI * offset_hz / 1000000.0)))) return r;
     if (interp_ > 1) {
         const std::vector<float> lp = low_pass(interp_, rate, 480000, 20000, WIN_BLACKMAN_HARRIS);
         nt = (int)lp.size();
-        if ((r = taps.upload(lp, kTapPad))) return r;
+        mfma_ = interp_ >= kTxMfmaMinInterp;
+        if (mfma_ && (nt + interp_ - 1) / interp_ > kTxMfmaLags)
+            return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": back-end filter longer than " + std::to_string(kTxMfmaLags) + " taps per phase");
+        if ((r = taps.upload(mfma_ ? tx_mfma_taps(lp, interp_) : lp, kTapPad))) return r;
         mask = pow2_at_least(bb_stride + (size_t)nt / interp_ + 64, 1024) - 1;
         if ((r = ring.alloc((size_t)batch * (mask + 1)))) return r;
     }
@@ -53,7 +71,11 @@ void TxBackEnd::run(uint32_t n1, void* iq, size_t out_stride, Sc16Out sc, int ba
     if (interp_ > 1) rp.out_ring = RingC{ring.p, mask};
     else { rp.out = reinterpret_cast<float2*>(iq); rp.out_stride = out_stride; rp.sc = sc; }
     launch_tx_rot(rp, batch, s);
-    if (interp_ > 1) {
+    if (mfma_) {
+        TxInterpMfmaParams mp{}; mp.in = rp.out_ring; mp.n0 = n_bb; mp.n1 = n1; mp.taps = taps.p; mp.interp = interp_;
+        mp.out = reinterpret_cast<float2*>(iq); mp.out_stride = out_stride; mp.sc = sc;
+        launch_tx_interp_mfma(mp, batch, s);
+    } else if (interp_ > 1) {
         TxInterpCParams bp{}; bp.in = rp.out_ring; bp.n0 = n_bb * (uint64_t)interp_; bp.count = n1 * (uint32_t)interp_;
         bp.taps = taps.p; bp.nt = nt; bp.interp = interp_;
         bp.out = reinterpret_cast<float2*>(iq); bp.out_stride = out_stride; bp.sc = sc;

@@ -7,6 +7,14 @@ namespace qrl {
 
 constexpr size_t kTapPad = 64;   // zeros behind every tap table of the transmitters: k_tx_interp_sym reads its I x J = 64 taps unguarded
 
+constexpr int kTxMaxRate = 183000000;   // device rates: 1e6, or a multiple of 1e6 in [2e6, 183e6], as on the receivers
+// Which kernel interpolates to the device rate: k_tx_interp_mfma (kernels_tx_mfma.hip) from this many device samples per 1 Msps sample up,
+// k_tx_interp_c (kernels_tx.hip) below.  A 32-row phase tile is mostly padding at small ratios; docs/MEASUREMENT.md, "TX back end rates",
+// has the A/B behind the value.  Both kernels give the same bits.
+constexpr int kTxMfmaMinInterp = 4;
+// the taps h of the back-end interpolator in k_tx_interp_mfma's layout [phase tile][lag][phase in tile] (engine.hpp)
+std::vector<float> tx_mfma_taps(const std::vector<float>& h, int interp);
+
 // gr_mod_base back end (reference src/gr/gr_mod_base.cpp:38,215-258) behind a modulator chain that ends at 1 Msps: the carrier rotator,
 // then the interpolator to the device rate.  Off (rate 0 or 1e6 and a zero offset): the chain's last kernel stores to the caller's buffer.
 struct TxBackEnd {
@@ -28,7 +36,7 @@ struct TxBackEnd {
     int interp() const { return interp_; }   // device samples per 1 Msps sample
 private:
     const char* noun_ = "";
-    bool on_ = false; int interp_ = 1, nt = 0; DevBuf<float> taps;
+    bool on_ = false, mfma_ = false; int interp_ = 1, nt = 0; DevBuf<float> taps;   // taps: h, or tx_mfma_taps(h) when mfma_
     DevBuf<float2> bb; size_t bb_stride = 0;       // the chain's output, linear, one call's worth
     DevBuf<float2> ring; uint32_t mask = 0;        // rotated 1 Msps signal (interpolator history)
     Rotator rot; uint64_t n_bb = 0;                // carrier NCO at 1 Msps; n_bb: samples through it so far
