@@ -614,6 +614,17 @@ _sig("orc_golay1987_syndrome", C.c_uint32, C.c_uint32)
 DMO_STATE_BYTES = 4 * 5 + 2 * 5 + 2 + 4 * 9 + 8 + 4 * 1440   # sizeof(orc_dmo_state) with natural alignment (checked below)
 
 
+class _DmoState(C.Structure):     # orc_dmo_state of oracle/orc.h, field for field
+    _fields_ = [("bitBuffer", C.c_uint32 * 5),
+                ("bitPtr", C.c_uint16), ("dataPtr", C.c_uint16), ("syncPtr", C.c_uint16), ("startPtr", C.c_uint16), ("endPtr", C.c_uint16),
+                ("maxCorr", C.c_float), ("centre", C.c_float * 4), ("threshold", C.c_float * 4),
+                ("averagePtr", C.c_uint8), ("syncCount", C.c_uint8), ("state", C.c_uint8), ("control", C.c_uint8), ("n", C.c_uint8), ("colorCode", C.c_uint8),
+                ("buffer", C.c_float * 1440)]
+
+
+assert C.sizeof(_DmoState) == DMO_STATE_BYTES
+
+
 def golay1987_table():
     t = np.zeros(2048, np.uint32)
     lib.orc_golay1987_table(_ptr(t))
@@ -645,6 +656,12 @@ class DmoSink:
         n = lib.orc_dmo_process(_ptr(self.state), _ptr(self.table), _ptr(x), x.size, _ptr(out), cap)
         assert n <= cap
         return [(int(out[40 * i]), int(out[40 * i + 1]), int(out[40 * i + 2]), out[40 * i + 4:40 * i + 37].tobytes()) for i in range(n)]
+
+    def peek(self, field):
+        """read-only copy of one field of the block's state as it stands after the last process(): syncPtr, endPtr, state, syncCount (ints),
+        centre, threshold (four float32 each), ... -- the names of orc_dmo_state"""
+        v = getattr(_DmoState.from_buffer_copy(self.state[:DMO_STATE_BYTES].tobytes()), field)
+        return v if isinstance(v, (int, float)) else np.array(v[:], np.float32 if isinstance(v[0], float) else np.uint32)
 
 
 def cc_decode_k7(soft):

@@ -331,3 +331,96 @@ def make_ssb(n=400000, seed=1, amp=0.05, noise=0.0003, lsb=False, gap=None, fs=1
     if gap:
         y[gap[0]:gap[1]] = 0
     return y.astype(np.complex64)
+
+
+# ---------------------------------------------------------------- named DMO scenarios for the slicer's state machine (a37b)
+# What each one is for is written beside it; tests/test_dmo_scenarios.py asserts, from the oracle's records and state alone, that the
+# branch is reached, and tests/test_gpu_dmo_adverse.py runs the same streams through k_dmo_sink.
+DMO_LEAD_SYMBOLS = 320      # unmodulated carrier in front: more than one lap (1440 samples = 288 symbols) of the slicer's ring, which the
+#                             reference block reads uninitialised during its first lap (tests/test_ref_blocks.py)
+DMO_SLOT_SYMBOLS = 288      # one DMO burst period: 132 symbols of burst, 156 of carrier
+DMO_SCENARIOS = ("data_call", "long_voice_call", "lost_sync", "drifting_level", "after_reset")
+# REJECTIONS, the impaired group: the long voice call behind (noise sigma per component at amp 0.3, fade seed or None).  Levels picked on the oracle
+# (seed 0, no delay): white noise alone leaves every sync of a call standing up to sigma 0.7 and only damages bits, so the streams that must lose
+# syncs carry a fade (sig.fade_envelope: 10-40 Hz tones of depth 0.95 and two drop-outs of 700 / 1500 port-3 samples).  Records of the oracle / of
+# them intact, of 10 bursts sent: 10 / 9, 10 / 3, 10 / 8, then 9 / 8, 9 / 8 (header refused), 9 / 3 (terminator lost), 9 / 8, 9 / 3 (header refused).
+DMO_IMPAIRED = ((0.45, None), (0.7, None), (0.05, 1), (0.1, 2), (0.1, 19), (0.3, 22), (0.1, 34), (0.3, 36))
+
+
+def _dmo_burst_levels(frame, scale=1.0, offset=0.0):
+    lv = dmr_levels([frame], lead_symbols=0)
+    lv[:132] = lv[:132] * scale + offset
+    return lv
+
+
+def dmo_scenario(name, seed=0):
+    """One named scenario: (frames, levels) -- the 33-byte bursts that are sent, in order, and the symbol levels for make_4fsk(levels=...),
+    DMO_LEAD_SYMBOLS of carrier first.  seed picks the payload bits and the colour code (1 + seed % 15; the second call of lost_sync: + 1)."""
+    rng = np.random.default_rng(7000 + seed)
+    cc = 1 + seed % 15
+
+    def data(dt, c=cc):
+        return dmr_frame(rng.integers(0, 2, 196), DMR_MS_DATA_SYNC, c, dt)
+
+    def vsync():
+        return dmr_frame(rng.integers(0, 2, 216), DMR_MS_VOICE_SYNC)
+
+    def voice():
+        return dmr_frame(rng.integers(0, 2, 264))
+
+    lead = [np.zeros(DMO_LEAD_SYMBOLS)]
+    if name == "data_call":
+        # DATA CONTINUATION: header 0x06 opens RECV_DATA, rate 1/2, 3/4 and 1 data (0x07, 0x08, 0x0A) are written only in that state;
+        # TERMINATOR IN THE WRONG STATE: 0x02 outside RECV_VOICE is not written and does not reset; the CSBK (0x03) is written and resets
+        frames = [data(dt) for dt in (0x06, 0x07, 0x08, 0x0A, 0x02, 0x03)]
+        levels = lead + [_dmo_burst_levels(f) for f in frames]
+    elif name == "long_voice_call":
+        # FRAME NUMBER WRAP: seven voice frames without sync behind one voice sync: s.n runs 1, 2, 3, 4, 5, 0, 1
+        frames = [data(0x01), vsync()] + [voice() for _ in range(7)] + [data(0x02)]
+        levels = lead + [_dmo_burst_levels(f) for f in frames]
+    elif name == "lost_sync":
+        # LOST SYNC: two voice frames without sync, then 14 slot periods of carrier: the slicer goes on cutting "voice" frames out of the
+        # silence until syncCount reaches 13 and dmo_reset runs; the next call (other colour code, 0.7 of the deviation, a DC offset) is
+        # acquired through the first = true path again, at the ring position the absolute sample index gives
+        cc2 = 1 + (cc % 15)
+        first = [data(0x01), vsync(), voice(), voice()]
+        second = [data(0x01, cc2), vsync(), voice()]
+        frames = first + second
+        levels = lead + [_dmo_burst_levels(f) for f in first] + [np.zeros(14 * DMO_SLOT_SYMBOLS)] + [_dmo_burst_levels(f, 0.7, 0.08) for f in second]
+    elif name == "drifting_level":
+        # UNEQUAL AVERAGES: every burst at its own deviation (0.6 .. 1.0 of nominal), so the four centre / threshold slots differ
+        frames = [data(0x01), vsync()] + [voice() for _ in range(5)] + [vsync(), voice(), data(0x02)]
+        scales = [1.0, 0.9, 0.85, 0.8, 0.75, 0.7, 0.65, 0.8, 0.7, 0.6]
+        offsets = [0.0, 0.03, 0.0, 0.0, 0.0, 0.0, 0.0, -0.04, 0.0, 0.05]
+        levels = lead + [_dmo_burst_levels(f, s, o) for f, s, o in zip(frames, scales, offsets)]
+    elif name == "after_reset":
+        # the other side of two conditions: DATA CONTINUATION outside RECV_DATA (0x07, 0x0A behind a CSBK, 0x07 behind a terminator) is not
+        # written, and a burst right behind a dmo_reset (CSBK, terminator) is acquired while the ring still holds the burst before.  The
+        # second burst comes OFF the slot grid, 172 symbols behind the first instead of 288 (another station keys up): the lap-early read of its
+        # 132nd symbol then lands before the reset, so a ring position that restarted with the reset would show (the kernel takes it from
+        # the running sample index, the oracle carries it as state)
+        frames = [data(dt) for dt in (0x03, 0x07, 0x0A, 0x06, 0x08, 0x03, 0x01, 0x02, 0x07)]
+        levels = lead + [_dmo_burst_levels(frames[0])[:172]] + [_dmo_burst_levels(f) for f in frames[1:]]
+    else:
+        raise KeyError(name)
+    levels = np.concatenate(levels)
+    return frames, levels[:levels.size - 120]      # (the carrier behind the last burst: 36 symbols are enough for its slot to be cut)
+
+
+def dmo_iq(name, seed=0, delay=0, cfo=0.0, noise=0.002, fade=None):
+    """IQ of one scenario at 1 Msps: (frames, iq complex64 of even length).  delay: that many more IQ samples of carrier in front (moves
+    the slicer's ring alignment and, since 125 IQ samples are 3 port-3 samples, the sampling phase); noise: sigma per component; fade: a
+    seed for fade_envelope on the carrier (the noise stays), None = no fade.  name "impaired<k>": the long voice call under DMO_IMPAIRED[k]."""
+    if name.startswith("impaired"):
+        noise, fade = DMO_IMPAIRED[int(name[8:])]
+        name = "long_voice_call"
+    frames, levels = dmo_scenario(name, seed)
+    more = -(-delay * 48 // 10000)                                  # whole symbols that cover the delay
+    x, _ = make_4fsk(levels=np.concatenate([np.zeros(more), levels]), seed=1000 + seed, noise=0.0, cfo=cfo)
+    x = x[int(round(more * 1e6 / 4800.0)) - delay:]
+    x = x[:x.size & ~1]
+    if fade is not None:
+        x = x * fade_envelope(x.size, fade, 24000.0, dropouts=(700, 1500)).astype(np.float32)
+    rng = np.random.default_rng(2000 + seed)
+    x = x + (noise * (rng.standard_normal(x.size) + 1j * rng.standard_normal(x.size))).astype(np.complex64)
+    return frames, x.astype(np.complex64)

@@ -165,3 +165,62 @@ def test_demod_to_frames_on_device(qrl_ctx):
         _, payloads = sig.make_stream("gmsk10k", 3, 1000000, 25000.0, 31 + 101 * b, 0.05, lead=37 * b)
         best = max(sum(any(ft == 0xED89 and p[1:] == want for ft, p in frames[k][b]) for want in payloads) for k in (0, 1))
         assert best == len(payloads)
+
+
+def _call_sizes(kind, n, first_sync, frame_bits):
+    """call sizes that add up to n: "129s" = [129] * k; "mixed" = 1, 63, 64, 65, 7, ... in a cycle (the search's 64-bit blocks cut everywhere);
+    "tiny" = 1-bit and 2-bit calls from just before the first sync word over the word and the frame that follows it (its first 300 bits
+    where the frame is longer: the 1516-byte modes would need 8000 launches), 129s elsewhere"""
+    sizes = []
+    if kind == "tiny":
+        sizes.append(first_sync - 4)
+        while sum(sizes) < first_sync + 40 + min(frame_bits, 300):
+            sizes.append(1 + len(sizes) % 2)
+    cycle = [1, 63, 64, 65, 7, 129, 2, 200, 31] if kind == "mixed" else [129]
+    while sum(sizes) < n:
+        sizes.append(cycle[len(sizes) % len(cycle)])
+    sizes[-1] -= sum(sizes) - n
+    return [c for c in sizes if c > 0]
+
+
+@pytest.mark.parametrize("modem", [18, 22, 17, 26, 27, 5, 40])
+@pytest.mark.parametrize("kind", ["129s", "mixed", "tiny"])
+def test_framesync_across_many_launches(qrl_ctx, modem, kind):
+    """an open frame's bits wait in bitbuf (carry / fstart of k_framesync) across MANY launches, not two: calls far shorter than a frame, down
+    to single bits over the sync word itself, and ragged per-stream counts (stream b takes c - b % 3 bits of a call of c, the rest are
+    skipped, as behind a demodulator that delivered less); the oracle is fed exactly the bits each stream took"""
+    import ctypes
+    import torch
+    import qradiolink_amd as q
+    rng = np.random.default_rng(modem * 10 + len(kind))
+    B, lead = 5, 70
+    bl = ctypes.c_int()
+    orc.lib.orc_modem_sync_geometry(modem, ctypes.byref(bl), ctypes.byref(ctypes.c_int()))
+    streams = [np.concatenate([rng.integers(0, 2, lead - 3, dtype=np.uint8), _bits_with_frames(rng, modem, 4, noise_bits=4)]) for _ in range(B)]
+    n = min(s.size for s in streams)
+    data = np.stack([s[:n] for s in streams])
+    fs = q.FrameSync(qrl_ctx, modem, B)
+    refs = [orc.ModemSync(modem) for _ in range(B)]
+    d = torch.from_numpy(data).cuda()
+    got = [[] for _ in range(B)]
+    want = [[] for _ in range(B)]
+    pos = 0
+    for c in _call_sizes(kind, n, lead, bl.value):
+        counts = np.array([max(c - (b % 3), 0) for b in range(B)], np.int32)
+        out, oc = fs.process(d[:, pos:pos + c].contiguous(), counts=torch.from_numpy(counts).cuda(), count_stride=1, n=c)
+        out, oc, act = out.cpu().numpy(), oc.cpu().numpy(), fs.activity.cpu().numpy()
+        for b in range(B):
+            got[b].append(out[b, :oc[b, 0]].copy())
+            want[b].append(refs[b].feed_raw(data[b, pos:pos + counts[b]]))
+            assert int(act[b]) == refs[b].collected, (b, pos, c)
+        pos += c
+    fs.close()
+    assert pos == n
+    total = 0
+    for b in range(B):
+        g, w = np.concatenate(got[b]), np.concatenate(want[b])
+        assert g.size == w.size and np.array_equal(g, w), "stream %d" % b
+        total += len(orc.parse_frames(w))
+    # streams 0 and 3 take every bit: at least their first three frames come back (the fourth may be cut by the common length); the
+    # others lose bits inside sync words and frames and give what the oracle gives
+    assert total >= 2 * 3
