@@ -242,6 +242,7 @@ void   orc_iir_ffd_2(const float* in, size_t n, const double ff[2], const double
 void   orc_set_tx_ctcss(float tone_hz);   /* gr_mod_nbfm::set_ctcss for the next orc_mod_nbfm calls: > 0 tone on, < 0 switched off again (x0.98), 0 = constructor */
 void   orc_fxpt_sine_table(float* tab /* 1024 x 2 */); uint32_t orc_fxpt_phase_inc(double fs, double freq);
 void   orc_sig_source_sin(double fs, double freq, double ampl, float offset, uint64_t k0, size_t n, float* out);   /* analog::sig_source_f(GR_SIN_WAVE, offset) [GR-MEM]: the CW key's tone */
+void   orc_set_tx_ctcss_k0(uint64_t k0);   /* sample index of the CTCSS tone source at the first audio item of the next orc_mod_nbfm calls (0 = a new graph) */
 void   orc_sig_source_cos(double fs, double freq, double ampl, uint64_t k0, size_t n, float* out);   /* analog::sig_source_f(GR_COS_WAVE) [GR-MEM] */
 void   orc_set_rx_filter_width(int width);   /* gr_demod_nbfm / am / wbfm / ssb::set_filter_width for the next orc_demod_analog / orc_demod_ssb calls; 0 = constructor */
 void   orc_set_rx_squelch(double db, double db2, long long sw_at);   /* set_squelch for the next orc_demod_analog / orc_demod_ssb calls; db2 from squelch-input item sw_at on (< 0: never) */
@@ -273,6 +274,7 @@ void     orc_m17_decode_frame(const uint8_t frame[48], uint8_t rec[40]);
 void     orc_m17_encode_frame(const uint8_t rec[40], uint8_t frame[48]);
 uint16_t orc_m17_crc16(const uint8_t* p, size_t n);
 float orc_det_log2f(float x);
+float orc_det_log10f(float x);   /* rssi_tag_block's log10f, the same bits as the device's det_log10f */
 void orc_rssi_block(const cf32* in, size_t n, float level, float* out);
 void orc_power_spectrum(const cf32* in, const float* window, size_t n, float* out);
 

@@ -873,7 +873,7 @@ size_t orc_clock_recovery_mm_cc(const cf32* in, size_t n, float omega, float gai
 }
 
 /* rssi_tag_block::work (reference src/gr/rssi_tag_block.cpp:43-68): every 300 samples one value
- * 10*log10f(sqrt(sum(|x|^4) / 300) + 1e-20) + calibration; the sum is a serial float accumulation.  Returns the count. */
+ * 10*log10f(sqrt(sum(|x|^4) / 300) + 1e-20) + calibration; the sum is a serial float accumulation, log10f = orc_det_log10f.  Returns the count. */
 size_t orc_rssi_tag(const cf32* in, size_t n, float calibration, float* db)
 {
     float sum = 0.0f; int nitems = 0; size_t k = 0;
@@ -883,7 +883,7 @@ size_t orc_rssi_tag(const cf32* in, size_t n, float calibration, float* db)
         nitems += 1;
         if (nitems >= 300) {
             const float level = sqrtf(sum / (float)nitems);
-            if (db) db[k] = (float)(10.0f * log10f(level + 1.0e-20f)) + calibration;
+            if (db) db[k] = (float)(10.0f * orc_det_log10f(level + 1.0e-20f)) + calibration;   /* libm's log10f and the device's differ in the last place: both sides take the deterministic one */
             k++;
             sum = 0; nitems = 0;
         }

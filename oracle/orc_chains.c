@@ -350,6 +350,10 @@ void orc_sig_source_cos(double fs, double freq, double ampl, uint64_t k0, size_t
  * 0: the constructor's graph. */
 static float g_tx_ctcss = 0.0f;
 void orc_set_tx_ctcss(float tone_hz) { g_tx_ctcss = tone_hz; }
+/* the tone source's sample index at the first audio item of the NEXT orc_mod_nbfm calls: sig_source_f free-runs, so behind a set_filter_width in
+ * mid-stream (which restarts the filters) the tone goes on where it was; 0 = a new graph */
+static uint64_t g_tx_ctcss_k0 = 0;
+void orc_set_tx_ctcss_k0(uint64_t k0) { g_tx_ctcss_k0 = k0; }
 /* gr_mod_nbfm / gr_mod_am / gr_mod_ssb::set_filter_width(width) (what gr_mod_base::set_filter_width(width, mode) forwards, src/gr/gr_mod_base.cpp:878-905) for
  * the NEXT orc_mod_nbfm / orc_mod_am / orc_mod_ssb calls; 0 = the constructor's graph.  The setters do not repeat the constructors' designs:
  *   gr_mod_nbfm.cpp:78-93   _if_resampler low_pass_2(25, 200000, w, w, 60, BH), _filter low_pass_2(1, 50000, w, 1200, 60, BH), _resampler low_pass_2(sps, fs, w, w, 60, BH),
@@ -373,7 +377,7 @@ size_t orc_mod_nbfm(const float* audio, size_t n, int sps, int samp_rate, int fi
     if (tone_on) orc_band_pass_2(1, 8000, 300, 3500, 200, 35, ORC_WIN_BLACKMAN_HARRIS, at);
     else orc_low_pass_2(1, 8000, 3500, 200, 35, ORC_WIN_BLACKMAN_HARRIS, at);
     float* tone = NEW(float, n + 1);
-    if (tone_on) orc_sig_source_cos(8000, (double)g_tx_ctcss, 0.15, 0, n, tone);
+    if (tone_on) orc_sig_source_cos(8000, (double)g_tx_ctcss, 0.15, g_tx_ctcss_k0, n, tone);
     float* a1 = NEW(float, n);
     orc_fir_fff(audio, n, at, na, a1);                                           /* _audio_filter */
     free(at);

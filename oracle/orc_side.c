@@ -36,6 +36,31 @@ float orc_det_log2f(float x)
     s = s * t;
     return (float)((double)e + s * 1.4426950408889634);
 }
+/* the same double-precision log10 as the device (devmath.hpp det_log10f): the log2 above kept in double, times log10(2), rounded to float once */
+float orc_det_log10f(float x)
+{
+    if (!(x > 0.0f)) return x == 0.0f ? -INFINITY : NAN;
+    if (x > 3.4028234e38f) return INFINITY;
+    int adj = 0;
+    if (x < 1.17549435e-38f) { x *= 18446744073709551616.0f; adj = -64; }
+    unsigned bits; memcpy(&bits, &x, 4);
+    int e = (int)(bits >> 23) - 127 + adj;
+    unsigned mb = (bits & 0x007fffffu) | 0x3f800000u;
+    float m; memcpy(&m, &mb, 4);
+    if (m > 1.41421354f) { m *= 0.5f; e += 1; }
+    const double md = (double)m;
+    const double t = (md - 1.0) / (md + 1.0);
+    const double t2 = t * t;
+    double s = 2.0 / 13.0;
+    s = s * t2 + 2.0 / 11.0;
+    s = s * t2 + 2.0 / 9.0;
+    s = s * t2 + 2.0 / 7.0;
+    s = s * t2 + 2.0 / 5.0;
+    s = s * t2 + 2.0 / 3.0;
+    s = s * t2 + 2.0;
+    s = s * t;
+    return (float)(((double)e + s * 1.4426950408889634) * 0.30102999566398120);
+}
 
 /* whole stream at once; a fresh moving-average sum at every absolute multiple of 2000 outputs (max_iter) */
 void orc_rssi_block(const cf32* in, size_t n, float level, float* out)

@@ -897,6 +897,10 @@ class Synth(_Sc16Tx):
         arr = (_ZeroRun * len(runs))(*[_ZeroRun(*r) for r in runs])
         _check(self.lib.qrl_synth_add_zero_runs(self.h, arr, len(runs)), "qrl_synth_add_zero_runs")
 
+    def reset(self):
+        """back to the state of a new handle (filter histories, FM phases, the item count; pending zero runs are dropped): qrl_synth_reset"""
+        _check(self.lib.qrl_synth_reset(self.h), "qrl_synth_reset")
+
     def close(self):
         if self.h:
             self.lib.qrl_synth_destroy(self.h)

@@ -411,6 +411,8 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
     const uint64_t RI = (uint64_t)h->rs_I, RD = (uint64_t)h->rs_D;
     const uint64_t n2_1 = n1_1 ? ((n1_1 - 1) * RI + (RI - 1)) / RD + 1 : 0;   // outputs q with q*D/I <= n1_1 - 1
     const uint32_t c2 = (uint32_t)(n2_1 - h->n2);
+    // a call too short for one output launches none of the kernels that write the int16 counts: they must not keep the call before's
+    if (counts && c2 == 0) HIPCHK(hipMemsetAsync(counts, 0, (size_t)S * sizeof(uint32_t), fused ? ts : h->stream));
     if (h->xlat || h->xlat2) {   // one front-end launch per channel: same input, that channel's rotator, rows b * CC + cl of ring r2 (form 2: r1)
         for (int cl = 0; cl < CC; ++cl) {
             DecimParams dp{};

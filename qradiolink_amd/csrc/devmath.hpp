@@ -175,4 +175,31 @@ __host__ __device__ inline float det_log2f(float x)
     return (float)((double)e + s * 1.4426950408889634);
 }
 
+// log10 of a positive finite float, the same bits on the host (oracle/orc_side.c orc_det_log10f) and on the device: the log2 above kept in double,
+// times log10(2), rounded to float once (within half a unit in the last place of the true value but for double-rounding ties; libm's log10f and
+// the device library's differ from each other in the last place).  rssi_tag_block's 10 log10f(level + 1e-20) takes it: the argument is >= 1e-20.
+__host__ __device__ inline float det_log10f(float x)
+{
+    if (!(x > 0.0f)) return x == 0.0f ? -__builtin_inff() : __builtin_nanf("");
+    if (x > 3.4028234e38f) return __builtin_inff();
+    int adj = 0;
+    if (x < 1.17549435e-38f) { x *= 18446744073709551616.0f; adj = -64; }
+    unsigned bits = __builtin_bit_cast(unsigned, x);
+    int e = (int)(bits >> 23) - 127 + adj;
+    float m = __builtin_bit_cast(float, (bits & 0x007fffffu) | 0x3f800000u);
+    if (m > 1.41421354f) { m *= 0.5f; e += 1; }
+    const double md = (double)m;
+    const double t = (md - 1.0) / (md + 1.0);
+    const double t2 = t * t;
+    double s = 2.0 / 13.0;
+    s = s * t2 + 2.0 / 11.0;
+    s = s * t2 + 2.0 / 9.0;
+    s = s * t2 + 2.0 / 7.0;
+    s = s * t2 + 2.0 / 5.0;
+    s = s * t2 + 2.0 / 3.0;
+    s = s * t2 + 2.0;
+    s = s * t;
+    return (float)(((double)e + s * 1.4426950408889634) * 0.30102999566398120);
+}
+
 }  // namespace qrl

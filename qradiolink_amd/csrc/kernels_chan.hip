@@ -586,7 +586,7 @@ __global__ __launch_bounds__(64) void k_rssi_tag(const RssiParams P)
         sum += pwr * pwr;
     }
     const float level = sqrtf(sum / 300.0f);
-    const float db = 10.0f * log10f(level + 1.0e-20f) + P.calibration;
+    const float db = 10.0f * det_log10f(level + 1.0e-20f) + P.calibration;
     if (t < P.cap) P.out[(size_t)b * P.cap + t] = db;
     if (t == 0 && P.counts) P.counts[b] = P.count < P.cap ? P.count : (uint32_t)P.cap;
 }

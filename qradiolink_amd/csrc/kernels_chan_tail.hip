@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256, QRL_CT_WPE) void k_chan_tail(const ChanTailPar
                     for (int u = 0; u < 5; ++u) { sum += v[u].x; sum += v[u].y; sum += v[u].z; sum += v[u].w; }
                 }
                 const float level = sqrtf(sum / 300.0f);
-                const float db = 10.0f * log10f(level + 1.0e-20f) + P.rssi_cal;
+                const float db = 10.0f * det_log10f(level + 1.0e-20f) + P.rssi_cal;
                 const uint64_t t = (uint64_t)j - P.tag0;
                 if (t < P.rssi_cap) P.rssi[(size_t)row * P.rssi_cap + t] = db;
             }

@@ -858,13 +858,14 @@ def pwr_squelch_trace(x, db, ramp=0, switch=None, alpha=0.01):
     return state != 0, state, (tr & 0x80) != 0
 
 
-def mod_nbfm(audio, sps=20, samp_rate=1000000, filter_width=5000, bb_gain=1.0, ctcss=0.0, set_width=0):
+def mod_nbfm(audio, sps=20, samp_rate=1000000, filter_width=5000, bb_gain=1.0, ctcss=0.0, set_width=0, tone_k0=0):
     """ctcss > 0: gr_mod_nbfm::set_ctcss(tone) was called; < 0: set_ctcss(0) after it had been on (x0.98); 0: the constructor's graph;
-    set_width != 0: gr_mod_nbfm::set_filter_width(set_width) was called"""
+    set_width != 0: gr_mod_nbfm::set_filter_width(set_width) was called; tone_k0: audio items the tone source had made before (it free-runs)"""
     audio = np.ascontiguousarray(audio, np.float32)
     lib.orc_mod_nbfm.restype = C.c_size_t
     args = (_ptr(audio), C.c_size_t(audio.size), sps, samp_rate, filter_width, C.c_float(bb_gain))
     lib.orc_set_tx_ctcss(C.c_float(ctcss))
+    lib.orc_set_tx_ctcss_k0(C.c_uint64(tone_k0))
     lib.orc_set_tx_filter_width(int(set_width))
     try:
         n = lib.orc_mod_nbfm(*args, None)
@@ -872,6 +873,7 @@ def mod_nbfm(audio, sps=20, samp_rate=1000000, filter_width=5000, bb_gain=1.0, c
         m = lib.orc_mod_nbfm(*args, _ptr(y))
     finally:
         lib.orc_set_tx_ctcss(C.c_float(0.0))
+        lib.orc_set_tx_ctcss_k0(C.c_uint64(0))
         lib.orc_set_tx_filter_width(0)
     return y[:m]
 
