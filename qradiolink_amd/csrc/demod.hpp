@@ -7,8 +7,6 @@
 
 namespace qrl {
 
-inline uint64_t decim_count(uint64_t n, int I, int D) { return n ? ((n - 1) * (uint64_t)I + (uint64_t)I - 1) / (uint64_t)D + 1 : 0; }
-
 // polyphase layout for k_decim: taps[p*Jpad + j] = h[p + j*D]
 inline std::vector<float> decim_layout(const std::vector<float>& h, int D, int Jpad)
 {
@@ -30,55 +28,45 @@ inline std::vector<float2> to_f2(const std::vector<std::complex<float>>& v)
 }
 
 struct DecimStage {
-    bool used = false, mfma = false, pl = false, pm = false;
-    int D = 1, Jpad = 0, variant = DECIM_R4_J12, nt = 0, S = 0;
+    bool used = false;
+    DecimChoice c{DECIM_CLASS_GENERIC, DECIM_R4_J12, 0};   // kernel class of the geometry (decim_plan.hpp)
+    int D = 1, nt = 0, S = 0;
     DevBuf<float> taps;
     DevBuf<float2> edge, edge_b; uint32_t edge_len = 0;   // phase-lane kernels: per-stream scratch for the call's edge outputs (two: staged a call ahead)
     int alloc_edge(int B, bool two = false) {
-        if (!pl && !pm) return QRL_OK;
-        edge_len = (uint32_t)(pm ? decim_pm_edge_len(nt, D) : decim_pl_edge_len(nt, D));
+        edge_len = (uint32_t)(c.cls == DECIM_CLASS_PM ? decim_pm_edge_len(nt, D) : c.cls == DECIM_CLASS_PL ? decim_pl_edge_len(nt, D) : 0);
         if (!edge_len) return QRL_OK;
         if (int r = edge.alloc((size_t)B * edge_len)) return r;
         return two ? edge_b.alloc((size_t)B * edge_len) : QRL_OK;
     }
     int plan(const std::vector<float>& h, int D_) {
         used = true; D = D_; nt = (int)h.size();
-        if (decim_uses_pm(nt, D)) {   // phase-major matrix-pipe kernel (the 1:50 first stages)
-            pm = true;
-            return taps.upload(decim_pm_layout(h, D));
-        }
-        if (decim_uses_pl(nt, D)) {   // register-resident phase-lane kernel (the 100:1 front end)
-            pl = true;
-            return taps.upload(decim_pl_layout(h, D));
-        }
-        if (decim_uses_mfma(nt, D)) {
+        c = decim_choose(nt, D);
+        switch (c.cls) {
+        case DECIM_CLASS_PM: return taps.upload(decim_pm_layout(h, D));
+        case DECIM_CLASS_PL: return taps.upload(decim_pl_layout(h, D));
+        case DECIM_CLASS_M16: {
             // zero-padded tap vector the MFMA A operands are read from: hp[k + (4S - nt + 1)] = h[k]
-            mfma = true;
             S = decim_mfma_steps(nt, D);
             std::vector<float> g((size_t)decim_mfma_hpn(nt, D), 0.0f);
             for (int k = 0; k < nt; ++k) g[(size_t)k + (size_t)(4 * S - nt + 1)] = h[k];
             return taps.upload(g);
         }
-        const int J = (nt + D - 1) / D;
-        const size_t kLds2 = 80 * 1024;  // two workgroups per CU
-        auto pad = [&](int v) { const int jc = decim_jc(v); return (J + jc - 1) / jc * jc; };
-        variant = -1;
-        if (J <= 10 && decim_lds_bytes(D, pad(DECIM_R2_J10), DECIM_R2_J10) <= kLds2) variant = DECIM_R2_J10;
-        else if (J > 36 && J <= 44 && decim_lds_bytes(D, 44, DECIM_R4_J44) <= kLds2) variant = DECIM_R4_J44;
-        else if (decim_lds_bytes(D, pad(DECIM_R4_J12), DECIM_R4_J12) <= kLds2) variant = DECIM_R4_J12;
-        else variant = DECIM_R1_J14;
-        Jpad = pad(variant);
-        if (decim_lds_bytes(D, Jpad, variant) > 160 * 1024) return QRL_ERR_ARG;
-        return taps.upload(decim_layout(h, D, Jpad));
+        case DECIM_CLASS_GENERIC: return taps.upload(decim_layout(h, D, c.Jpad));
+        default: return QRL_ERR_ARG;
+        }
     }
-    uint32_t lookback() const { return pm ? decim_pm_lookback(nt, D) : pl ? (uint32_t)(((nt + D - 1) / D + 1) * D) : mfma ? (uint32_t)(nt + D) : (uint32_t)(Jpad * D); }
+    uint32_t lookback() const { return decim_lookback(c, nt, D); }
+    const char* kernel_name() const { return c.cls == DECIM_CLASS_PM ? "k_decim_pm" : c.cls == DECIM_CLASS_PL ? "k_decim_plx" : c.cls == DECIM_CLASS_M16 ? "k_decim_mfma" : "k_decim"; }
     int launch(DecimParams& p, int B, hipStream_t s, int parity = 0) const {
         p.nt = nt;
         float2* e = parity && edge_b.p ? edge_b.p : edge.p;
-        if (pm) { p.pl_taps = taps.p; p.pl_edge = e; p.pl_edge_stride = edge_len; p.pl_edge_cap = edge_len; return launch_decim_pm(p, B, s); }
-        if (pl) { p.pl_taps = taps.p; p.pl_edge = e; p.pl_edge_stride = edge_len; p.pl_edge_cap = edge_len; return launch_decim_pl(p, B, s); }
-        if (mfma) { p.gtab = taps.p; p.S = S; return launch_decim_mfma(p, B, s); }
-        launch_decim(p, B, variant, s);
+        if (c.cls == DECIM_CLASS_PM || c.cls == DECIM_CLASS_PL) {
+            p.pl_taps = taps.p; p.pl_edge = e; p.pl_edge_stride = edge_len; p.pl_edge_cap = edge_len;
+            return c.cls == DECIM_CLASS_PM ? launch_decim_pm(p, B, s) : launch_decim_pl(p, B, s);
+        }
+        if (c.cls == DECIM_CLASS_M16) { p.gtab = taps.p; p.S = S; return launch_decim_mfma(p, B, s); }
+        launch_decim(p, B, c.variant, s);
         return 0;
     }
 };

@@ -369,7 +369,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         p.in = in; p.in_stride = stride; p.n0 = n_in0; p.n = (uint32_t)n;
         p.hist = hist_old; p.hist_len = hist_len;
         p.out = RingC{s1.p, s1_mask}; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
-        p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.Jpad;
+        p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.c.Jpad;
         p.rot_enable = 1; rot.fill(p);
         p.in_fmt = fmt; p.in_scale = sc16_scale;
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
@@ -383,7 +383,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         DecimParams p{};
         input_source(p, in, stride, hist_old, src0, src1);
         p.out = r2; p.m0 = n2_0; p.m_count = (uint32_t)(n2_1 - n2_0);
-        p.taps = first.taps.p; p.D = first.D; p.Jpad = first.Jpad;
+        p.taps = first.taps.p; p.D = first.D; p.Jpad = first.c.Jpad;
         if (d2f) {   // + _shaping_filter -> port 0 and the filtered ring, in the same kernel
             Dec2FirParams f{};
             f.d = p; f.taps = d2f_taps.p; f.out = RingC{s2f.p, s2_mask};
@@ -410,7 +410,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         DecimParams p{};
         input_source(p, in, stride, hist_old, src0, src1);
         p.out = RingC{s_scope.p, scope_mask}; p.m0 = n_scope; p.m_count = (uint32_t)(ns_1 - n_scope);
-        p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.Jpad;
+        p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.c.Jpad;
         if (scope.launch(p, B, stream)) return qrl_set_error(QRL_ERR_HIP, "scope launch: hipFuncSetAttribute failed");
         launch_ring_store(RingC{s_scope.p, scope_mask}, n_scope, (uint32_t)(ns_1 - n_scope), scope_out, scope_cap, scope_counts, B, stream);
         n_scope = ns_1;
@@ -881,7 +881,7 @@ int qrl_demod_profile_read(qrl_demod* d, double* kernel_ms, uint64_t* launches, 
     if (kernel_name) {
         const DecimStage& st = d->fe.used ? d->fe : d->first;
         *kernel_name = (!d->fe.used && d->d2f) ? "k_dec2_fir"
-                     : (d->fe.used || d->interp == 1) ? (st.pm ? "k_decim_pm" : st.pl ? "k_decim_plx" : st.mfma ? "k_decim_mfma" : "k_decim") : "k_resamp";
+                     : (d->fe.used || d->interp == 1) ? st.kernel_name() : "k_resamp";
     }
     d->prof_events.clear();
     return QRL_OK;

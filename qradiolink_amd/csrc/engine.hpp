@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <vector>
 #include "zero_runs.hpp"   // struct ZeroRun
+#include "decim_plan.hpp"  // which decimator a geometry gets, its sizes, the split of a call: host arithmetic free of HIP
 
 namespace qrl {
 
@@ -120,27 +121,14 @@ uint32_t dec2_fir_lookback();
 std::vector<float> dec2_fir_table(const std::vector<float>& h1, const std::vector<float>& h2);
 void launch_dec2_fir(const Dec2FirParams& p, int batch, hipStream_t s);
 void launch_hist_save(const HistParams& p, int batch, hipStream_t s);
-size_t decim_lds_bytes(int D, int Jpad, int variant);
-enum { DECIM_R4_J44 = 0, DECIM_R4_J12 = 1, DECIM_R2_J10 = 2, DECIM_R1_J14 = 3 };
-int decim_jc(int variant);
 // f32-MFMA decimator (D >= 8): contract "m16" of oracle/orc_blocks.c
-bool decim_uses_mfma(int nt, int D);
-int decim_mfma_steps(int nt, int D);
-int decim_mfma_na(int nt, int D);
-int decim_mfma_hpn(int nt, int D);
-size_t decim_mfma_lds_bytes(int nt, int D);
 int launch_decim_mfma(const DecimParams& p, int batch, hipStream_t s);   // 0, or -1 when the kernel attribute could not be set
 void decim_mfma_prof_read(unsigned long long* out8);
 void decim_mfma_prof_enable(int on);
 // register-resident phase-lane decimator (32 < D <= 64, <= 16 taps per phase): contract "pl" of oracle/orc_blocks.c
-bool decim_uses_pl(int nt, int D);
-size_t decim_pl_edge_len(int nt, int D);   // samples of edge scratch per stream (0: geometry without the register kernel)
 std::vector<float> decim_pl_layout(const std::vector<float>& h, int D);
 int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s);
 // phase-major matrix-pipe decimator (32 < D <= 52, <= 16 taps per phase): contract "pm" of oracle/orc_blocks.c
-bool decim_uses_pm(int nt, int D);
-size_t decim_pm_edge_len(int nt, int D);
-uint32_t decim_pm_lookback(int nt, int D);
 std::vector<float> decim_pm_layout(const std::vector<float>& h, int D);
 int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s);
 

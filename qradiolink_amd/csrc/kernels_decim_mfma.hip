@@ -24,9 +24,7 @@
 // tile t out of LDS, the 16-byte global loads of tile t+1 are already in flight into registers (all
 // LDS operands use lgkmcnt, so nothing in the MFMA phase waits on vmcnt); they are rotated and
 // written to LDS after the phase.  Staging is a straight copy, no transposition.
-#include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include "devmath.hpp"
 #include "engine.hpp"
 
@@ -422,36 +420,6 @@ void decim_mfma_prof_read(unsigned long long* out8)
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mf_prof), z, sizeof z);
 }
-int decim_mfma_steps(int nt, int D)
-{
-    const int S = (nt + 15 * D + 3) / 4;
-    return (S + 3) / 4 * 4;
-}
-int decim_mfma_hpn(int nt, int D) { return (15 * D + 4 * decim_mfma_steps(nt, D) + 4 + 3) & ~3; }
-static long long mfma_jtot(int nt, int D, int NA) { return (long long)(NA - 1) * 16 * D + 4LL * decim_mfma_steps(nt, D); }
-static int mfma_nhi(int nt, int D, int NA, int) { return (int)(mfma_jtot(nt, D, NA) / 512 + 3); }
-static size_t mfma_lds(int nt, int D, int NA, int tpw)
-{
-    const long long Jtot = mfma_jtot(nt, D, NA);
-    const long long npos = Jtot + 2 * (Jtot / (16LL * D)) + 4 + 512 + 16;   // + dump slots (+ pad slack of the unpredicated commit)
-    return (size_t)(512 + ((mfma_nhi(nt, D, NA, tpw) + 1) & ~1) + npos) * sizeof(float2) + (size_t)decim_mfma_hpn(nt, D) * sizeof(float);
-}
-// rule shared with oracle/orc_blocks.c orc_decim_uses_m16
-bool decim_uses_mfma(int nt, int D)
-{
-    if (D < 8) return false;
-    const long long samples = 7LL * 16 * D + 4LL * decim_mfma_steps(nt, D);
-    return (samples + 2 * (samples / (16LL * D)) + 64) * 8 <= 150 * 1024;
-}
-constexpr int kTpwMax = 16;
-// 16 output blocks per tile when two workgroups of that size fit the 160 KB of a CU, else 8
-int decim_mfma_na(int nt, int D)
-{
-    if (mfma_lds(nt, D, 16, kTpwMax) <= 80 * 1024) return 16;    // two (or more) workgroups per CU with the efficient tile
-    if (mfma_lds(nt, D, 8, kTpwMax) <= 160 * 1024) return 8;   // (4-block tiles with three workgroups per CU were measured slower)
-    return 4;   // very long filters (100:1 front end, 4181 taps): only the 4-block tile fits the 160 KB of a CU
-}
-size_t decim_mfma_lds_bytes(int nt, int D) { return mfma_lds(nt, D, decim_mfma_na(nt, D), kTpwMax); }
 
 template <int NA, int NLD, bool FAST, int WPE = 2, int NTH = 256>
 static hipError_t launch_k(const DecimParams& q, dim3 grid, size_t lds, hipStream_t s)
@@ -462,54 +430,36 @@ static hipError_t launch_k(const DecimParams& q, dim3 grid, size_t lds, hipStrea
     hipLaunchKernelGGL(kern, grid, dim3(NTH), lds + (NTH - 256) * 2 * sizeof(float2), s, q);
     return hipSuccess;
 }
-template <int NA, int NLD>
-static hipError_t launch_one(const DecimParams& q, dim3 grid, size_t lds, hipStream_t s)
-{
-    // FAST: the tile comes from the caller's buffer through register-prefetched 16-byte loads (cf32 only; int16 input is converted
-    // sample by sample in mf_fetch)
-    if (q.in && q.in_fmt == IN_CF32 && q.n >= 2 && q.n < (1u << 28)) return launch_k<NA, NLD, true>(q, grid, lds, s);
-    return launch_k<NA, 1, false>(q, grid, lds, s);
-}
 
 int launch_decim_mfma(const DecimParams& p, int batch, hipStream_t s)
 {
     if (p.m_count == 0) return 0;
-    const int NA = decim_mfma_na(p.nt, p.D);
-    const uint32_t T = 16 * NA;
-    const uint32_t tiles = (uint32_t)((p.m0 + p.m_count + T - 1) / T - p.m0 / T);
+    // FAST: the tile comes from the caller's buffer through register-prefetched 16-byte loads (cf32 only; int16 input is converted
+    // sample by sample in mf_fetch)
+    const bool fast = p.in && p.in_fmt == IN_CF32 && p.n >= 2 && p.n < (1u << 28);
+    const MfmaPlan pl = decim_mfma_plan(p.nt, p.D, p.m0, p.m_count, batch, fast);
     DecimParams q = p;
-    q.tiles = tiles;
-    // consecutive tiles per workgroup: enough to amortise the un-overlapped first load, few enough to keep >= ~4k workgroups
-    const uint64_t total = (uint64_t)tiles * (uint64_t)batch;
-    uint32_t tpw = (uint32_t)std::min<uint64_t>(kTpwMax, std::max<uint64_t>(1, total / 4096));
-    q.tpw = tpw;
-    q.nhi = mfma_nhi(p.nt, p.D, NA, tpw);
+    q.tiles = pl.tiles;
+    q.tpw = pl.tpw;
+    q.nhi = pl.nhi;
     q.magic_blk = (uint32_t)((0x100000000ull + 16u * (uint32_t)p.D - 1) / (16u * (uint32_t)p.D));
     q.magic_seg = (uint32_t)((0x100000000ull + 4u * (uint32_t)p.D - 1) / (4u * (uint32_t)p.D));
-    const uint32_t chunks = (tiles + tpw - 1) / tpw;
-    q.nchunks = chunks;
+    q.nchunks = pl.nchunks;
     q.dbg = g_mf_prof_on.load(std::memory_order_relaxed);
+    q.nld = pl.nld;
     // never pad a short grid.x to 8: the padding blocks would leave whole XCDs idle
-    dim3 grid(chunks >= 64 ? (chunks + 7) / 8 * 8 : chunks, batch);
-    const size_t lds = mfma_lds(p.nt, p.D, NA, tpw);
-    const long long pairs = (mfma_jtot(p.nt, p.D, NA) + 2) / 2;
-    const int nld = (int)((pairs + 255) / 256);
-    const bool fast = q.in && q.in_fmt == IN_CF32 && q.n >= 2 && q.n < (1u << 28);
-    // More than 16 loads per thread (front ends beyond ~40:1): a 36-load variant would need 144 prefetch registers, more than
-    // the accumulator half of the register file holds, and hipcc then spills registers whose asm-issued loads are still in
-    // flight.  Those tiles run with 512 threads (<= 16 loads per thread); anything larger takes the slow per-sample staging.
-    const int nld512 = (int)((pairs + 511) / 512);
-    const bool big = fast && nld > 16 && nld512 <= 16;
-    q.nld = big ? nld512 : nld;
+    const dim3 grid(pl.nchunks >= 64 ? (pl.nchunks + 7) / 8 * 8 : pl.nchunks, batch);
+    const int NA = pl.NA;
+    const size_t lds = pl.lds;
     hipError_t e;
-    if (fast && nld > 16 && !big) {
+    if (!fast || pl.slow) {   // every sample through mf_fetch
         e = NA == 16 ? launch_k<16, 1, false>(q, grid, lds, s) : NA == 8 ? launch_k<8, 1, false>(q, grid, lds, s) : launch_k<4, 1, false>(q, grid, lds, s);
     } else if (NA == 16) {
-        e = big ? launch_k<16, 16, true, 2, 512>(q, grid, lds, s) : launch_one<16, 16>(q, grid, lds, s);
+        e = pl.big ? launch_k<16, 16, true, 2, 512>(q, grid, lds, s) : launch_k<16, 16, true>(q, grid, lds, s);
     } else if (NA == 4) {
-        e = big ? launch_k<4, 16, true, 2, 512>(q, grid, lds, s) : (nld <= 8 && fast) ? launch_k<4, 8, true, 3>(q, grid, lds, s) : launch_one<4, 16>(q, grid, lds, s);
+        e = pl.big ? launch_k<4, 16, true, 2, 512>(q, grid, lds, s) : pl.nld <= 8 ? launch_k<4, 8, true, 3>(q, grid, lds, s) : launch_k<4, 16, true>(q, grid, lds, s);
     } else {
-        e = big ? launch_k<8, 16, true, 2, 512>(q, grid, lds, s) : launch_one<8, 16>(q, grid, lds, s);
+        e = pl.big ? launch_k<8, 16, true, 2, 512>(q, grid, lds, s) : launch_k<8, 16, true>(q, grid, lds, s);
     }
     return e == hipSuccess ? 0 : -1;
 }

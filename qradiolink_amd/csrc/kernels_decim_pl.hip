@@ -25,7 +25,6 @@
 // Summation contract "pl" (oracle/orc_blocks.c orc_decim_fir_ccf_pl): slot(i) = (i-1) mod D; per slot one chain, oldest
 // sample first, first term a plain product, then fmaf; 64 slots (unused = +0) meet as v[l] += v[l+h], h = 32,16,...,1.
 #include <vector>
-#include <cstdlib>
 #include <mutex>
 #include "devmath.hpp"
 #include "engine.hpp"
@@ -557,7 +556,6 @@ __global__ __launch_bounds__(256) void k_decim_pm_gen(const DecimParams P_, uint
 //  runs per SIMD: a lone wave issues one VALU per ~4-5 cycles, and v_pk_fma_f32 (re and im in one instruction) is what keeps the
 //  f32 pipe busy at that rate (32 lanes per clock: two v_fma_f32 = one v_pk_fma_f32 = 4 cycles).
 constexpr int PLX_PF = 4;          // blocks in flight per wave (two waves per SIMD: 247 VGPRs at 4, 276 at 8)
-constexpr int PLX_NHI = 256;       // coarse rotator entries per wave: a segment spans <= 255 x 512 samples
 
 // cmul_fma (devmath.hpp) on register pairs: {fma(a.x, b.x, -(a.y b.y)), fma(a.x, b.y, a.y b.x)} = two packed instructions
 __device__ __forceinline__ v2f plx_cmul_fma(v2f a, v2f b)
@@ -762,11 +760,26 @@ template <bool PS = false>
 __global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, false>(P_, i0, len); }
 template <bool PS = false>
 __global__ __launch_bounds__(256) void k_pl_edge_stage_sc16(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, true>(P_, i0, len); }   // int16 input
-static void launch_pl_edge_stage(const DecimParams& q, int64_t i0, uint32_t len, int batch, hipStream_t s)
+// Everything of a call but the streaming kernel's launch.  Names the main and the edge range in the parameter block, stages the edge scratch
+// (on the handle's pre-stream when it has one: the kernel reads the caller's buffer and the carried history, nothing the call before
+// produces on the launch stream) and runs the per-output kernel `gen`, `per_wg` outputs per workgroup, on the two ranges left to it.
+// false: nothing for the streaming kernel to do
+typedef void (*DecimGenKernel)(const DecimParams, uint64_t, uint32_t);
+static bool launch_split(DecimParams& q, const DecimSplit& sp, DecimGenKernel gen, uint32_t per_wg, int batch, hipStream_t s)
 {
-    const dim3 grid((len + 255) / 256, batch);
-    if (q.in_fmt == IN_SC16) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_sc16<true> : k_pl_edge_stage_sc16<false>, grid, dim3(256), 0, s, q, i0, len);
-    else hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, grid, dim3(256), 0, s, q, i0, len);
+    q.pl_m_begin = sp.main.lo; q.pl_m_end = sp.main.hi;
+    q.pl_batch = (uint32_t)batch;
+    if (!sp.edge.empty()) {
+        const hipStream_t st = q.pre_stream ? q.pre_stream : s;
+        const dim3 grid((sp.edge_len + 255) / 256, batch);
+        if (q.in_fmt == IN_SC16) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_sc16<true> : k_pl_edge_stage_sc16<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
+        else hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
+        if (q.pre_stream) { (void)hipEventRecord(q.pre_event, q.pre_stream); (void)hipStreamWaitEvent(s, q.pre_event, 0); }
+        q.pl_edge_ms = sp.edge.lo; q.pl_edge_me = sp.edge.hi;
+    }
+    for (const OutRange& r : {sp.gen_head, sp.gen_tail})
+        if (!r.empty()) hipLaunchKernelGGL(gen, dim3((uint32_t)((r.count() + per_wg - 1) / per_wg), batch), dim3(256), 0, s, q, r.lo, (uint32_t)r.count());
+    return !sp.main.empty() || !sp.edge.empty();
 }
 
 // One wave per output, checked fetches: zero in front of the stream, carried (already rotated) history in front of this
@@ -835,31 +848,6 @@ __global__ __launch_bounds__(256) void k_decim_pl_gen(const DecimParams P_, uint
         P.out.p[((size_t)b * (P.out_row_mul_m1 + 1u) + P.out_row_add) * (P.out.mask + 1u) + ((uint32_t)m & P.out.mask)] = make_float2(vr, vi);
 }
 
-// geometry of the "pl" contract (oracle/orc_blocks.c orc_pl_geometry) and the instantiated kernels
-struct PlGeom { int R, Dp, E, U, Upad, WU; bool ok; };
-static PlGeom pl_geom(int nt, int D)
-{
-    PlGeom g{};
-    g.R = D <= 32 ? 64 / D : 1;
-    g.Dp = g.R * D;
-    g.E = (g.Dp + 63) / 64;
-    g.U = (nt + g.Dp - 1) / D;
-    g.Upad = g.U;
-    if (g.E == 1 && g.R == 1) g.ok = false;   // 32 < D <= 64: the phase-major matrix-pipe kernel (decim_uses_pm) or the generic paths
-    else if (g.E == 2 && g.R == 1) { g.ok = (D % 2) == 0 && g.U <= 42; g.Upad = 42; }   // (the front-end filters have 41.8 D taps: U = 42 for every D)
-    else g.ok = false;
-    g.WU = (g.Upad - 1) / g.R;
-    return g;
-}
-// rule shared with oracle/orc_blocks.c orc_decim_uses_pl
-bool decim_uses_pl(int nt, int D) { return pl_geom(nt, D).ok; }
-
-size_t decim_pl_edge_len(int nt, int D)
-{
-    const PlGeom g = pl_geom(nt, D);
-    return g.ok ? (size_t)(2 * g.WU + 4) * g.Dp : 0;   // warm-up blocks + the blocks of <= (WU + 1) R + 1 edge outputs
-}
-
 // lane tap table [Upad][E][64]: lane l, sample e of a block (r = E l + e) meets output u + 1 with h[(u + 1) D - 1 - r];
 // the raw taps follow (k_decim_pl_gen reads them by index)
 std::vector<float> decim_pl_layout(const std::vector<float>& h, int D)
@@ -881,66 +869,20 @@ std::vector<float> decim_pl_layout(const std::vector<float>& h, int D)
 int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
 {
     if (p.m_count == 0) return 0;
-    const int D = p.D;
-    const PlGeom g = pl_geom(p.nt, D);
+    const PlGeom g = pl_geom(p.nt, p.D);
+    const DecimSplit sp = decim_pl_split(p.n0, p.n, p.m0, p.m_count, p.nt, p.D, p.pl_edge ? p.pl_edge_cap : 0u, p.in && p.rot_enable);
+    const DecimSegments sg = pl_segments(sp.main.count(), (uint32_t)batch, g, !sp.edge.empty());
     DecimParams q = p;
     q.pl_J = g.Upad; q.pl_E = g.E; q.pl_R = g.R;
     q.pl_hraw = p.pl_taps + (size_t)g.Upad * g.E * 64;
-    const uint64_t m_end = p.m0 + p.m_count;
-    uint64_t m_main = m_end, m_tail = m_end;   // [m_main, m_tail): the register kernel; the rest: one wave per output
-    if (p.in && p.rot_enable) {
-        // interior outputs: every sample the lanes touch lies in this call's buffer.  First block of a segment starting at output
-        // ms = (cs - 1) R + 1 is cs - WU, its first sample (cs - WU - 1) D' + 1 >= n0
-        const uint64_t qb = p.n0 > 1 ? (p.n0 - 1 + g.Dp - 1) / g.Dp : 0;
-        m_main = (qb + g.WU) * g.R + 1;
-        if (m_main < p.m0) m_main = p.m0 + (g.R - 1 - (p.m0 + g.R - 2) % g.R);   // next m == 1 (mod R)
-        // last block must end inside the buffer: c D' <= n0 + n - 1
-        const uint64_t c_max = (p.n0 + p.n - 1) / g.Dp;
-        m_tail = c_max * g.R + 1;
-        if (m_tail > m_end) m_tail = m_end;
-        if (m_main > m_tail) m_main = m_tail;
-    }
-    bool edge_unit = false;
-    if (m_main > p.m0) {
-        // head edge: through the register kernel out of a staged scratch when it fits (R = 1 geometries), else one wave per output
-        const int64_t c_first = (int64_t)p.m0 - g.WU;                         // (R = 1) block of output m0 minus the warm-up blocks
-        const int64_t i0 = (c_first - 1) * (int64_t)g.Dp + 1;
-        const int64_t i_last = (int64_t)(m_main - 1) * g.Dp;                   // last sample of the last edge block
-        if (p.pl_edge && g.R == 1 && i_last - i0 + 1 <= (int64_t)p.pl_edge_cap) {
-            const uint32_t len = (uint32_t)(i_last - i0 + 1);
-            launch_pl_edge_stage(q, i0, len, batch, p.pre_stream ? p.pre_stream : s);
-            if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
-            q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
-            edge_unit = true;
-        } else {
-            const uint32_t cnt = (uint32_t)(m_main - p.m0);
-            hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, p.m0, cnt);
-        }
-    }
-    if (m_tail < m_end && m_tail >= m_main) {
-        const uint32_t cnt = (uint32_t)(m_end - m_tail);
-        hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, dim3((cnt + 3) / 4, batch), dim3(256), 0, s, q, m_tail, cnt);
-    }
-    if (m_main >= m_tail && !edge_unit) return 0;
-    const uint64_t total = (m_tail - m_main) * (uint64_t)batch;
-    q.pl_m_begin = m_main; q.pl_m_end = m_tail;
-    q.pl_batch = (uint32_t)batch;
-    // generalised geometry: two waves per SIMD (<= 256 VGPRs), ~3 segments per wave slot of the chip; a segment stays inside
-    // the wave's coarse rotator table and is a multiple of 16 outputs
-    uint64_t S = total / (2048u * 3u);
-    const uint64_t s_cap = (uint64_t)(((PLX_NHI - 2) * 512) / g.Dp - g.WU) * g.R / 16 * 16;
-    if (S > 2048) S = 2048;
-    if (S > s_cap) S = s_cap;
-    S = S / 16 * 16;
-    if (S < 16) S = 16;
-    q.pl_S = (uint32_t)S;
-    q.pl_nseg = (uint32_t)((m_tail - m_main + S - 1) / S);
-    const uint32_t units = q.pl_nseg * (uint32_t)batch + (edge_unit ? (uint32_t)batch : 0u);
+    q.pl_S = sg.S; q.pl_nseg = sg.nseg;
+    if (!launch_split(q, sp, p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, 4, batch, s)) return 0;
+    const dim3 grid((sg.units + 3) / 4);
     if (p.in_fmt == IN_SC16) {
-        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
-    } else if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), dim3((units + 3) / 4), dim3(256), 0, s, q);
-    else hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), dim3((units + 3) / 4), dim3(256), 0, s, q);
+        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, true>), grid, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, true>), grid, dim3(256), 0, s, q);
+    } else if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), grid, dim3(256), 0, s, q);
     return 0;
 }
 
@@ -953,33 +895,9 @@ extern "C" void qrl_pm_prof_read(unsigned long long* out8)
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pm_prof), z, sizeof z);
 }
 #endif
-// ---- "pm" contract: rule (shared with oracle/orc_blocks.c orc_decim_uses_pm), tables, launcher ---------------------------------------
-bool decim_uses_pm(int nt, int D)
-{
-    const int J = (nt + D - 1) / D, NS = (D + 3) / 4;
-    if (D > 32 && D <= 52 && J <= 16) return true;                // one lag tile: the 1:50 first stages of a 1 Msps device
-    // up to three lag tiles: the device-rate front ends (41.8 D taps) at 10:1, 20:1, 25:1, 50:1, 100:1
-    return J > 16 && J <= 48 && (NS == 3 || NS == 5 || NS == 7 || NS == 13 || NS == 25);
-}
-// block lags the instantiated kernel walks (its table is zero beyond the filter's own J): segment alignment, edge unit and look-back
-// are all counted in THESE lags
-static int pm_kernel_lags(int nt, int D)
-{
-    const int J = (nt + D - 1) / D, NS = (D + 3) / 4;
-    if (J <= 16) return J == 9 && NS == 13 ? 9 : 16;
-    return J <= 42 ? 42 : 48;
-}
-size_t decim_pm_edge_len(int nt, int D)
-{
-    // the edge unit of a call starts at the 16-block group of block m0 - (J - 1) and ends with the last output in front of the first
-    // aligned segment: at most 15 + (J - 1) + (J + 16) blocks
-    const int J = pm_kernel_lags(nt, D);
-    return decim_uses_pm(nt, D) ? (size_t)(((2 * J + 32) * D + 1) & ~1) : 0;
-}
-uint32_t decim_pm_lookback(int nt, int D) { return (uint32_t)((pm_kernel_lags(nt, D) + 18) * D); }
+// ---- "pm" contract: tables, launcher (the rule and the sizes: decim_plan.hpp) ----
 // A-operand table [NT][NS][64]: lane l (j = 16 t + (l & 15), k = l >> 4) of step s, tile t holds H[p = 4 s + k][j] = h[j D + D - 1 - p];
 // the raw taps follow
-static int pm_tiles(int J) { return J <= 16 ? 1 : 3; }
 std::vector<float> decim_pm_layout(const std::vector<float>& h, int D)
 {
     const int nt = (int)h.size(), J = (nt + D - 1) / D, NS = (D + 3) / 4, NT = pm_tiles(J);
@@ -1002,25 +920,6 @@ std::vector<float> decim_pm_layout(const std::vector<float>& h, int D)
 #ifndef QRL_PM_RP_SMALL
 #define QRL_PM_RP_SMALL 8   // ring pieces per wave for D <= 28 (a group is <= 3.5 KiB there)
 #endif
-// Segments: a multiple of 16 outputs each (every segment then starts on a group boundary).  Every segment re-reads `warm` blocks of
-// warm-up, and the call ends when the last wave does: with `cap` waves resident on the chip the cost of a split into nseg segments per
-// stream is  ceil(nseg x batch / cap)  rounds of  S + warm + 16  blocks.  Take the cheapest split; ties go to the finer one.
-// mult > 1 (per-stream offsets): only segment counts that are multiples of mult, each stream's units then fill whole workgroups (idle units counted)
-static uint32_t pm_pick_segment(uint64_t M, uint32_t batch, uint32_t cap, uint32_t warm, uint32_t mult = 1)
-{
-    if (M <= 16) return 16;
-    uint64_t best_cost = ~0ull; uint32_t best_S = 16;
-    uint32_t n_lo = (uint32_t)((M + 4095) / 4096);
-    const uint32_t n_hi = (uint32_t)((M + 127) / 128);
-    n_lo = (n_lo + mult - 1) / mult * mult;
-    for (uint32_t nseg = n_lo; nseg <= (n_hi > n_lo ? n_hi : n_lo); nseg += mult) {
-        const uint32_t S = (uint32_t)(((M + nseg - 1) / nseg + 15) / 16 * 16);
-        const uint64_t units = (mult > 1 ? nseg : (M + S - 1) / S) * (uint64_t)batch;
-        const uint64_t cost = ((units + cap - 1) / cap) * (uint64_t)(S + warm + 16);
-        if (cost <= best_cost) { best_cost = cost; best_S = S; }
-    }
-    return best_S;
-}
 template <int J, int NS, int RP, bool K1, bool PS, bool SC = false>
 static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
@@ -1029,11 +928,7 @@ static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edg
     // recursion kernels of the previous call beside them) were measured: 7.24 ms against 6.57 ms alone, and no gain in the overlapped mode.
     constexpr int NW = QRL_PM_NW;
     const auto kern = k_decim_pm<J, NS, RP, NW, K1, PS, SC>;
-    size_t lds = (size_t)NW * RP * 1024 + 512 * sizeof(float2) + NW * PM_NHI * sizeof(float2);
-    // experiment (VERDICT r5 #4a): pad the dynamic LDS so that fewer front-end workgroups share a CU and a tail-chain workgroup of the previous call always
-    // finds room beside them (QRL_PM_LDS_KB = total KB per workgroup; 45 -> three per CU with 25 KB to spare)
-    static const size_t lds_min = [] { const char* e = std::getenv("QRL_PM_LDS_KB"); return e ? (size_t)std::atoi(e) * 1024 : (size_t)0; }();
-    if (lds_min > lds && lds_min <= 160 * 1024) lds = lds_min;
+    const size_t lds = (size_t)NW * RP * 1024 + 512 * sizeof(float2) + NW * PM_NHI * sizeof(float2);
     // occupancy and CU count per (instantiation, device): a second device in the process gets its own LDS attribute (dyn_lds_limit
     // de-duplicates per kernel and device) and its own geometry; first calls may race, hence the lock
     static std::mutex mu; static int wg_cache[16], cu_cache[16];
@@ -1052,14 +947,9 @@ static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edg
         }
         wg_per_cu = wg_cache[dev]; n_cu = cu_cache[dev];
     }
-    // per-stream offsets: a multiple of NW segments per stream (whole workgroups per stream: one fine table each; segments past the end idle)
-    const uint32_t S = pm_pick_segment(M, batch, (uint32_t)(wg_per_cu * n_cu * NW), (uint32_t)(J - 1), PS ? (uint32_t)NW : 1u);
-    uint32_t nseg = M ? (uint32_t)((M + S - 1) / S) : 0u;
-    if (PS) nseg = (nseg + NW - 1) / NW * NW;
-    q.pl_S = S;
-    q.pl_nseg = nseg;
-    const uint32_t units = q.pl_nseg * batch + (edge_unit ? batch : 0u);
-    hipLaunchKernelGGL(kern, dim3((units + NW - 1) / NW), dim3(NW * 64), lds, s, q);
+    const DecimSegments sg = pm_segments(M, batch, (uint32_t)(wg_per_cu * n_cu * NW), J, PS ? (uint32_t)NW : 1u, edge_unit);
+    q.pl_S = sg.S; q.pl_nseg = sg.nseg;
+    hipLaunchKernelGGL(kern, dim3((sg.units + NW - 1) / NW), dim3(NW * 64), lds, s, q);
     return 0;
 }
 template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
@@ -1080,10 +970,6 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
     DecimParams q = p;
     q.pl_J = J; q.pl_E = 1; q.pl_R = 1;
     q.pl_hraw = p.pl_taps + (size_t)pm_tiles(J) * NS * 64;
-    const uint64_t m_end = p.m0 + p.m_count;
-    auto gen = [&](uint64_t first, uint64_t last) {
-        if (last > first) hipLaunchKernelGGL(p.rot_acc_s ? k_decim_pm_gen<true> : k_decim_pm_gen<false>, dim3((uint32_t)((last - first + 255) / 256), batch), dim3(256), 0, s, q, first, (uint32_t)(last - first));
-    };
     // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces: rows 16-byte aligned, even sample counts
     // (what qrl_demod_process demands; the edge scratch is built that way).  Anything else: one thread per output.
     // int16 input (4-byte samples): whole pieces per row are multiples of FOUR samples
@@ -1092,34 +978,10 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
                         p.pl_edge && (reinterpret_cast<uintptr_t>(p.pl_edge) & 15u) == 0 && (p.pl_edge_stride & 1u) == 0 &&
                         !(p.in_fmt == IN_SC16 && J <= 16);   // (not reachable from the front-end stage, whose ~41.8 D taps give J > 16, and int16 input exists
                                                              //  only there; kept so that a one-tile stage fed int16 would still be exact, through k_decim_pm_gen)
-    if (!dma_ok) { gen(p.m0, m_end); return 0; }
-    // interior segments start at outputs m == J - 1 (mod 16): their oldest block opens a 16-block group, and it lies in the buffer
-    const uint64_t qb = p.n0 > 1 ? (p.n0 - 1 + D - 1) / D : 0;             // block qb + 1 is the first one whose samples are all >= n0
-    uint64_t m_main = (qb + 1 + 15) / 16 * 16 + (uint64_t)(J - 1);
-    if (m_main < p.m0) m_main = p.m0 + (uint64_t)((((J - 1) % 16) - (int)(p.m0 % 16) + 16) % 16);
-    const uint64_t c_max = (p.n0 + p.n - 1) / D;                           // last block that ends inside the buffer
-    uint64_t m_tail = c_max + 1 < m_end ? c_max + 1 : m_end;
-    if (m_tail < p.m0) m_tail = p.m0;
-    if (m_main > m_tail) m_main = m_tail;
-    bool edge_unit = false;
-    if (m_main > p.m0) {
-        const int64_t cfs = (int64_t)p.m0 - (J - 1);
-        const int64_t G0 = cfs >= 0 ? cfs / 16 : -((-cfs + 15) / 16);
-        const int64_t i0 = (G0 * 16 - 1) * (int64_t)D + 1;
-        const int64_t i_last = (int64_t)(m_main - 1) * D;                  // last sample of the last edge output's newest block
-        const int64_t len = ((i_last - i0 + 1) + 1) & ~(int64_t)1;
-        if (len <= (int64_t)p.pl_edge_cap) {
-            launch_pl_edge_stage(q, i0, (uint32_t)len, batch, p.pre_stream ? p.pre_stream : s);
-            if (p.pre_stream) { (void)hipEventRecord(p.pre_event, p.pre_stream); (void)hipStreamWaitEvent(s, p.pre_event, 0); }
-            q.pl_edge_ms = p.m0; q.pl_edge_me = m_main;
-            edge_unit = true;
-        } else gen(p.m0, m_main);
-    }
-    gen(m_tail, m_end);
-    if (m_main >= m_tail && !edge_unit) return 0;
-    q.pl_m_begin = m_main; q.pl_m_end = m_tail;
-    q.pl_batch = (uint32_t)batch;
-    const uint64_t M = m_tail - m_main;
+    const DecimSplit sp = decim_pm_split(p.n0, p.n, p.m0, p.m_count, nt, D, p.pl_edge_cap, dma_ok);
+    if (!launch_split(q, sp, p.rot_acc_s ? k_decim_pm_gen<true> : k_decim_pm_gen<false>, 256, batch, s)) return 0;
+    const bool edge_unit = !sp.edge.empty();
+    const uint64_t M = sp.main.count();
     const uint32_t Bn = (uint32_t)batch;
     if (J == 9) return pm_launch_main<9, 13>(q, M, Bn, edge_unit, s);   // the 1:50, 419-tap stage
     if (J > 16) {   // device-rate front ends: 42 block lags (the table is zero beyond J; J <= 48 runs the same code)

@@ -195,28 +195,6 @@ __global__ __launch_bounds__(256) void k_decim(const DecimParams P_)
     }
 }
 
-static void decim_variant(int variant, int& R, int& JC)
-{
-    switch (variant) {
-    case DECIM_R4_J44: R = 4; JC = 44; break;
-    case DECIM_R4_J12: R = 4; JC = 12; break;
-    case DECIM_R2_J10: R = 2; JC = 10; break;
-    default: R = 1; JC = 14; break;
-    }
-}
-int decim_jc(int variant) { int R, JC; decim_variant(variant, R, JC); return JC; }
-
-size_t decim_lds_bytes(int D, int Jpad, int variant)
-{
-    int R, JC;
-    decim_variant(variant, R, JC);
-    const int TILE = 64 * R;
-    const int W = TILE + Jpad;
-    const int Wq = (W + R - 1) / R;
-    const int PT = (R * Wq) | 1;
-    return (size_t)(512 + 64 + 4 * TILE + D * PT) * sizeof(float2);
-}
-
 void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
 {
     int R, JC;
