@@ -645,6 +645,31 @@ int qrl_m17_decode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* frames,
  * stream-frame bytes = frame number (EOS bit in its top bit) + 16 payload bytes, and the 6-byte LICH segment = 5 LSF bytes +
  * segment number) -> 48-byte frames.  Frame numbering, the LICH round robin and the LSF CRC are per-stream state: host work. */
 int qrl_m17_encode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* records, size_t n, uint8_t* frames);
+/* DMR layer 2, the stateless per-burst work behind the DMO slicer's mailbox (qrl_demod_set_dmo_output): what the reference does to every
+ * burst gr_dmr_dmo_sink::get_data() returns -- DMRFrame::DMRFrame (slot type, Golay(20,8)), DMRFrame::validate (reference
+ * src/DMR/dmrframe.cpp:115-246: BPTC(196,96) + RS(12,9) or CRC-CCITT per data type, the rate 3/4 trellis, the burst re-encoded from the
+ * corrected payload), DMRFrame::runAudioFEC (:248, CAMBEFEC::regenerateDMR) and CDMREMB::putData (QR(16,7,6), src/DMR/dmrcontrol.cpp:247).
+ * records / counts are the slicer's mailbox; slot i of stream b is decoded when i < min(counts[b], cap_frames) (counts == NULL: every
+ * slot), every other output slot is 80 zero bytes.  Runs behind qrl_demod_process on qrl_demod_stream() without a host synchronisation.
+ * The 80-byte record (each byte = one accessor of the reference's DMRFrame after those calls; host/dmr_frame_hip.h reads it):
+ *   0 frame type, 1 FN (copied) | 2 colour code (data: slot type; voice A: input byte 2; voice B-F: EMB) | 3 getDataType(): 0..15, or
+ *   QRL_DMR_DT_VOICE_SYNC / QRL_DMR_DT_VOICE | 4 validate() | 5 runAudioFEC() (voice, audio_fec != 0) | 6 EMB PI, 7 EMB LCSS (voice B-F)
+ *   | 8 payload length: 12 BPTC types, 18 rate 3/4, 27 voice, 0 invalid / rate 1 | 9 getFLCO(), 10 getFID(), 11 zero | 12..15 getSrcId(),
+ *   16..19 getDstId(), little endian | 20..52 getData(): the regenerated burst, or the input burst where validate() returns before
+ *   rewriting it | 53..79 payload, zero padded: the 12 BPTC bytes as the class keeps them after put() (masks in place), the 18 trellis
+ *   bytes, or the 27 getVoice() bytes after the FEC.
+ * The protocol state above this (DMRControl, the four-burst embedded LC) stays host work. */
+#define QRL_DMR_L2_RECORD_BYTES 80
+#define QRL_DMR_DT_VOICE_SYNC 0xF0
+#define QRL_DMR_DT_VOICE 0xF1
+int qrl_dmr_l2_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records /* [batch][cap_frames][40] */, const uint32_t* counts /* [batch] or NULL */,
+                      size_t batch, size_t cap_frames, int audio_fec, uint8_t* out /* [batch][cap_frames][80] */);
+/* CDMRTrellis::decode / encode (reference src/MMDVM/DMRTrellis.cpp:50-107) on bare bursts: the 196 code bits of a rate 3/4 burst -> 49
+ * constellation points -> checkCode, and for a burst that fails it the two-go fixCode search (16 candidate points of a round in 16 lanes)
+ * -> 18 payload bytes, ok = 1; a burst the search gives up on gets ok = 0 and a zero payload.  encode writes the code bits of the
+ * payload into the burst and keeps its 68 middle bits. */
+int qrl_dmr_trellis34_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* bursts /* [n][33] */, size_t n, uint8_t* payloads /* [n][18] */, uint8_t* ok /* [n] */);
+int qrl_dmr_trellis34_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* payloads /* [n][18] */, size_t n, uint8_t* bursts /* [n][33] in/out */);
 
 /* ---- developer aids (NOT part of the drop-in surface; tools/prof_phases.py): shader-clock phase profile of k_decim_mfma ---- */
 void qrl_debug_decim_prof(unsigned long long* out8);

@@ -125,6 +125,9 @@ def load_library():
     lib.qrl_amod_stream.restype = vp
     for name in ("qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames"):
         getattr(lib, name).argtypes = [vp, vp, vp, sz, vp]
+    lib.qrl_dmr_l2_decode.argtypes = [vp, vp, vp, vp, sz, sz, C.c_int, vp]
+    lib.qrl_dmr_trellis34_decode.argtypes = [vp, vp, vp, sz, vp, vp]
+    lib.qrl_dmr_trellis34_encode.argtypes = [vp, vp, vp, sz, vp]
     lib.qrl_demod_set_squelch.argtypes = [vp, C.c_double]
     lib.qrl_demod_set_agc.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_set_filter_width.argtypes = [vp, C.c_int]
@@ -249,6 +252,7 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_destroy", "qrl_demod_reset", "qrl_demod_set_carrier_offset", "qrl_demod_set_carrier_offsets", "qrl_demod_set_option", "qrl_demod_set_dmo_output", "qrl_demod_stream_wait", "qrl_demod_out_caps",
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
+    "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
@@ -412,6 +416,7 @@ class Demod:
         self.torch.cuda.current_stream().synchronize()   # the handle runs on its own HIP streams: whatever produced iq must be done
         _check(self.lib.qrl_demod_process(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1], C.byref(self._out)),
                "qrl_demod_process")
+        self._dmo_l2_async()
 
     def sync(self):
         _check(self.lib.qrl_demod_sync(self.h), "qrl_demod_sync")
@@ -429,6 +434,7 @@ class Demod:
         self.torch.cuda.current_stream().synchronize()
         _check(self.lib.qrl_demod_process_sc16(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2, C.byref(self._out)),
                "qrl_demod_process_sc16")
+        self._dmo_l2_async()
 
     def process_sc16(self, iq):
         self.process_sc16_async(iq)
@@ -505,6 +511,25 @@ class Demod:
         self.dmo_counts = t.zeros((self.batch,), dtype=t.int32, device=dev)
         _check(self.lib.qrl_demod_set_dmo_output(self.h, self.dmo_frames.data_ptr(), cap_frames, self.dmo_counts.data_ptr()),
                "qrl_demod_set_dmo_output")
+
+    def enable_dmo_l2(self, audio_fec=True):
+        """DMR layer 2 behind the DMO sink (enable_dmo_sink first): every process() also fills self.dmo_l2 uint8 [batch, cap, 80], the
+        validated / FEC'd record of each burst of the call (qrl_dmr_l2_decode), queued on the handle's stream right behind the call with no
+        host synchronisation in between; slots at or past dmo_counts[b] are zero."""
+        if getattr(self, "dmo_frames", None) is None:
+            raise RuntimeError("enable_dmo_l2: enable_dmo_sink() first")
+        t = self.torch
+        self.dmo_l2 = t.zeros((self.batch, self.dmo_frames.shape[1], 80), dtype=t.uint8, device=self.dmo_frames.device)
+        t.cuda.current_stream().synchronize()   # the zero fill is done before the handle's stream writes the buffer
+        self._dmo_l2_fec = 1 if audio_fec else 0
+
+    def _dmo_l2_async(self):
+        if getattr(self, "dmo_l2", None) is None:
+            return
+        s = self.stream
+        self.stream_wait(s)   # the slicer may run on another of the handle's streams: an on-device wait, the host goes on
+        _check(self.lib.qrl_dmr_l2_decode(self.ctx.h, C.c_void_p(s), self.dmo_frames.data_ptr(), self.dmo_counts.data_ptr(), self.batch,
+                                          self.dmo_frames.shape[1], self._dmo_l2_fec, self.dmo_l2.data_ptr()), "qrl_dmr_l2_decode")
 
     def dmo_records(self):
         """host copy of the last call's records: per stream a list of (type, fn, colour code, 33 bytes)"""
@@ -1135,6 +1160,47 @@ def bptc19696_encode(ctx, payloads, bursts):
     assert payloads.is_contiguous() and bursts.is_contiguous() and payloads.dtype == torch.uint8 and bursts.dtype == torch.uint8
     torch.cuda.current_stream().synchronize()
     _check(ctx.lib.qrl_bptc19696_encode(ctx.h, None, payloads.data_ptr(), payloads.shape[0], bursts.data_ptr()), "qrl_bptc19696_encode")
+    torch.cuda.synchronize()
+    return bursts
+
+
+def dmr_l2_decode(ctx, frames, counts=None, audio_fec=True):
+    """[batch, cap, 40] uint8 cuda tensor of DMO slicer records (+ counts: [batch] int32 / uint32 cuda tensor, None = every slot holds a
+    record) -> [batch, cap, 80] layer-2 records (qrl_dmr_l2_decode: DMRFrame::validate / runAudioFEC, CDMREMB::putData)"""
+    import torch
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3 and frames.shape[2] == 40 and frames.is_contiguous()
+    if counts is not None:
+        assert counts.is_cuda and counts.dtype in (torch.int32, torch.uint32) and counts.shape == (frames.shape[0],) and counts.is_contiguous()
+    out = torch.zeros((frames.shape[0], frames.shape[1], 80), dtype=torch.uint8, device=frames.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_dmr_l2_decode(ctx.h, None, frames.data_ptr(), counts.data_ptr() if counts is not None else None, frames.shape[0],
+                                     frames.shape[1], 1 if audio_fec else 0, out.data_ptr()), "qrl_dmr_l2_decode")
+    torch.cuda.synchronize()
+    return out
+
+
+def dmr_trellis34_decode(ctx, bursts):
+    """[n, 33] uint8 cuda tensor of rate 3/4 bursts -> ([n, 18] payloads, [n] ok) (CDMRTrellis::decode; ok 0 = a zero payload)"""
+    import torch
+    assert bursts.is_cuda and bursts.dtype == torch.uint8 and bursts.dim() == 2 and bursts.shape[1] == 33 and bursts.is_contiguous()
+    n = bursts.shape[0]
+    payloads = torch.zeros((max(n, 1), 18), dtype=torch.uint8, device=bursts.device)
+    ok = torch.zeros((max(n, 1),), dtype=torch.uint8, device=bursts.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_dmr_trellis34_decode(ctx.h, None, bursts.data_ptr() if n else payloads.data_ptr(), n, payloads.data_ptr(), ok.data_ptr()),
+           "qrl_dmr_trellis34_decode")
+    torch.cuda.synchronize()
+    return payloads[:n], ok[:n]
+
+
+def dmr_trellis34_encode(ctx, payloads, bursts):
+    """[n, 18] payloads written into the code bits of [n, 33] bursts in place (CDMRTrellis::encode; the 68 middle bits are kept); returns bursts"""
+    import torch
+    assert payloads.is_cuda and bursts.is_cuda and payloads.dim() == 2 and payloads.shape[1] == 18 and bursts.shape == (payloads.shape[0], 33)
+    assert payloads.is_contiguous() and bursts.is_contiguous() and payloads.dtype == torch.uint8 and bursts.dtype == torch.uint8
+    torch.cuda.current_stream().synchronize()
+    if payloads.shape[0]:
+        _check(ctx.lib.qrl_dmr_trellis34_encode(ctx.h, None, payloads.data_ptr(), payloads.shape[0], bursts.data_ptr()), "qrl_dmr_trellis34_encode")
     torch.cuda.synchronize()
     return bursts
 

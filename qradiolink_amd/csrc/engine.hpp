@@ -425,6 +425,10 @@ void launch_bptc_decode(const uint8_t* bursts, size_t n, uint8_t* payloads, hipS
 void launch_bptc_encode(const uint8_t* payloads, size_t n, uint8_t* bursts, hipStream_t s);
 void launch_m17_decode(const uint8_t* frames, size_t n, uint8_t* records, hipStream_t s);
 void launch_m17_encode(const uint8_t* records, size_t n, uint8_t* frames, hipStream_t s);
+// ---- DMR layer 2 (kernels_dmr_l2.hip): mailbox records [batch][cap][40] -> [batch][cap][80]; rate 3/4 bursts [n][33] <-> payloads [n][18] ----
+void launch_dmr_l2(const uint8_t* records, const uint32_t* counts, size_t batch, size_t cap, int audio_fec, uint8_t* out, hipStream_t s);
+void launch_trellis34_decode(const uint8_t* bursts, size_t n, uint8_t* payloads, uint8_t* ok, hipStream_t s);
+void launch_trellis34_encode(const uint8_t* payloads, size_t n, uint8_t* bursts, hipStream_t s);
 
 // ---- side outputs (kernels_side.hip): rssi_block on port 0, rx_fft_c on the device-rate IQ ----
 constexpr uint32_t RSSI_RING = 4096;   // |x|^2 look-back ring per stream (moving_average_ff(2000) reads 1999 items back)

@@ -1,6 +1,9 @@
 // framefec.cpp — C ABI of the frame FEC kernels (kernels_framefec.hip): stateless batch calls on a caller-chosen HIP stream.
 //   qrl_bptc19696_decode / _encode   CBPTC19696::decode / encode    reference src/MMDVM/BPTC19696.cpp:47-87
 //   qrl_m17_decode_frames            M17FrameDecoder::decodeFrame   reference src/M17/M17/M17FrameDecoder.cpp:44-215
+//   qrl_dmr_l2_decode                DMRFrame::DMRFrame / validate / runAudioFEC, CDMREMB::putData   reference src/DMR/dmrframe.cpp:36-253,
+//                                    src/DMR/dmrcontrol.cpp:233-248 (kernels_dmr_l2.hip)
+//   qrl_dmr_trellis34_decode / _encode   CDMRTrellis::decode / encode   reference src/MMDVM/DMRTrellis.cpp:50-107
 #include "host_common.hpp"
 #include <string>
 
@@ -37,6 +40,31 @@ int qrl_m17_decode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* frames,
     if (!ctx || (n && (!frames || !records))) return qrl_set_error(QRL_ERR_ARG, "qrl_m17_decode_frames: null argument");
     HIPCHK(hipSetDevice(ctx->device));
     launch_m17_decode(frames, n, records, static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+int qrl_dmr_l2_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records, const uint32_t* counts, size_t batch, size_t cap_frames,
+                      int audio_fec, uint8_t* out)
+{
+    if (!ctx || !records || !out || !batch || !cap_frames) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_l2_decode: null argument or empty mailbox");
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_dmr_l2(records, counts, batch, cap_frames, audio_fec, out, static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+int qrl_dmr_trellis34_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* bursts, size_t n, uint8_t* payloads, uint8_t* ok)
+{
+    if (!ctx || !bursts || !payloads || !ok) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_trellis34_decode: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_trellis34_decode(bursts, n, payloads, ok, static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+int qrl_dmr_trellis34_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* payloads, size_t n, uint8_t* bursts)
+{
+    if (!ctx || !payloads || !bursts) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_trellis34_encode: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_trellis34_encode(payloads, n, bursts, static_cast<hipStream_t>(hip_stream));
     HIPCHK(hipGetLastError());
     return QRL_OK;
 }

@@ -72,13 +72,14 @@ struct gr_demod_base_hip::slot {
     float *d_scope = nullptr; gr_complex* h_scope = nullptr; uint32_t *d_scnt = nullptr, *h_scnt = nullptr; bool scoped = false;   // time-domain scope items of the call
     uint8_t *d_fr[2] = {nullptr, nullptr}, *h_fr[2] = {nullptr, nullptr}; uint32_t *d_frcnt[2] = {nullptr, nullptr}, *h_frcnt[2] = {nullptr, nullptr};   // framed records of bits A / B
     bool framed = false, bits_copied = true;
+    uint8_t *d_l2 = nullptr, *h_l2 = nullptr; bool l2 = false;   // DMR layer 2 records of the call's bursts (set_dmr_l2; device / pinned)
     hipEvent_t done = nullptr;
 };
 static constexpr size_t kDmoCap = 16;
 
 gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_chunk)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_chunk(max_chunk & ~(size_t)1),
-      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams)
+      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams), d_boxl(streams)
 {
     d_boxf[0].resize(streams); d_boxf[1].resize(streams); d_boxs.resize(streams);
     for (int k = 0; k < 2; ++k) { d_fbits[k].assign(streams, 0); d_fact[k].assign(streams, 0); }
@@ -124,6 +125,8 @@ void gr_demod_base_hip::close()
             if (p) (void)hipFree(p);
         for (void* p : {(void*)sp->h_iq, (void*)sp->h_const, (void*)sp->h_a, (void*)sp->h_b, (void*)sp->h_dmo, (void*)sp->h_cnt, (void*)sp->h_dmocnt})
             if (p) (void)hipHostFree(p);
+        if (sp->d_l2) (void)hipFree(sp->d_l2);
+        if (sp->h_l2) (void)hipHostFree(sp->h_l2);
         if (sp->done) (void)hipEventDestroy(sp->done);
         delete sp;
         sp = nullptr;
@@ -196,6 +199,8 @@ void gr_demod_base_hip::open()
             hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_dmocnt), N * sizeof(uint32_t)), "hipMalloc");
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_dmo), N * kDmoCap * QRL_DMO_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_dmocnt), N * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES), "hipMalloc");
+            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
         }
         hchk(hipEventCreateWithFlags(&sp->done, hipEventDisableTiming), "hipEventCreate");
     }
@@ -214,7 +219,7 @@ void gr_demod_base_hip::set_mode(int mode)   // gr_demod_base::set_mode (src/gr/
         throw std::invalid_argument(std::string("gr_demod_base_hip::set_mode: time-domain settings rejected and reset to the defaults (the mode is open): ") + e.what());
     }
     std::lock_guard<std::mutex> g(d_mutex);
-    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
+    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxl[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
 }
 void gr_demod_base_hip::enable_device_framing(bool value)
 {
@@ -347,6 +352,11 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     if (d_mode == QRL_MODEM_DMR) {
         hchk(hipMemcpyAsync(sl.h_dmocnt, sl.d_dmocnt, N * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
         hchk(hipMemcpyAsync(sl.h_dmo, sl.d_dmo, N * kDmoCap * QRL_DMO_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        sl.l2 = d_l2_on;
+        if (sl.l2) {   // layer 2 on the copy stream, which waits for the slicer on the device: validate / FEC of the call's bursts, no host synchronisation
+            chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, sl.d_dmo, sl.d_dmocnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.d_l2), "qrl_dmr_l2_decode");
+            hchk(hipMemcpyAsync(sl.h_l2, sl.d_l2, N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        }
     }
     sl.rssi_valid = d_rssi_on;
     if (d_rssi_on) {   // rssi_valve open: port 0 of this call through rssi_block, the probe keeps the latest value
@@ -412,6 +422,10 @@ void gr_demod_base_hip::harvest(int which)
             for (uint32_t i = 0; i < sl.h_dmocnt[s] && i < kDmoCap; ++i) {
                 const uint8_t* r = sl.h_dmo + ((size_t)s * kDmoCap + i) * QRL_DMO_RECORD_BYTES;
                 d_boxd[s].emplace_back(r, r + QRL_DMO_RECORD_BYTES);
+                if (sl.l2) {
+                    const uint8_t* r2 = sl.h_l2 + ((size_t)s * kDmoCap + i) * QRL_DMR_L2_RECORD_BYTES;
+                    d_boxl[s].emplace_back(r2, r2 + QRL_DMR_L2_RECORD_BYTES);
+                }
             }
         }
     }
@@ -596,6 +610,13 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRData(int stream
     std::lock_guard<std::mutex> g(d_mutex);
     std::vector<std::vector<unsigned char>> out;
     out.swap(d_boxd[stream]);
+    return out;
+}
+std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRDecoded(int stream)
+{
+    std::lock_guard<std::mutex> g(d_mutex);
+    std::vector<std::vector<unsigned char>> out;
+    out.swap(d_boxl[stream]);
     return out;
 }
 
@@ -972,6 +993,8 @@ bool gr_modem_hip::demodulate(int stream)   // gr_modem.cpp:1019-1117
         auto frames = _gr_demod_base->getDMRData(stream);
         if (frames.empty()) return false;
         if (_ev.dmrFrames) _ev.dmrFrames(stream, frames);
+        auto decoded = _gr_demod_base->getDMRDecoded(stream);   // set_dmr_l2: the same bursts validated and FEC'd on the device (DMRFrame::validate / runAudioFEC)
+        if (!decoded.empty() && _ev.dmrFramesDecoded) _ev.dmrFramesDecoded(stream, decoded);
         return true;
     }
     const bool two = modem_two_branches(_modem_type_rx);

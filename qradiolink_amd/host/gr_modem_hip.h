@@ -77,6 +77,10 @@ public:
     bool takeFrames(int nr, int stream, std::vector<frame_record>& frames, size_t& bits, size_t& collected);
     size_t peekFrameBits(int nr, int stream);
     std::vector<std::vector<unsigned char>> getDMRData(int stream = 0);   // DMR mode: 40-byte DMO records (QRL_DMO_RECORD_BYTES)
+    // DMR layer 2 (qrl_dmr_l2_decode), off by default: when on, every burst of getDMRData also arrives as an 80-byte record (QRL_DMR_L2_RECORD_BYTES;
+    // host/dmr_frame_hip.h reads it) -- what DMRFrame::validate / runAudioFEC and CDMREMB::putData make of it (reference src/DMR/dmrcontrol.cpp:233-248, :630)
+    void set_dmr_l2(bool on, bool audio_fec = true) { std::lock_guard<std::recursive_mutex> hg(d_hmutex); d_l2_on = on; d_l2_fec = audio_fec; }
+    std::vector<std::vector<unsigned char>> getDMRDecoded(int stream = 0);
     uint64_t dmr_bursts_dropped() const { return d_dmo_dropped; }        // bursts beyond the 16-per-call record buffer (a call longer than 0.48 s of signal)
     // analogue voice modes (NBFM2500 / NBFM5000 / AM5000 / WBFM): port 1 = audio at 8 ksps (gr_demod_base::getAudio :968-976; caller deletes)
     std::vector<float>* getAudio(int stream = 0);
@@ -149,6 +153,8 @@ private:
     std::vector<std::vector<unsigned char>> d_box1, d_box2;
     std::vector<std::vector<gr_complex>> d_boxc;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxd;
+    std::vector<std::vector<std::vector<unsigned char>>> d_boxl;   // layer 2 records, one per record of d_boxd while set_dmr_l2 is on
+    bool d_l2_on = false, d_l2_fec = true;
     uint64_t d_dmo_dropped = 0;   // DMR bursts found beyond the per-call record buffer (16 per stream and call): not delivered
 };
 
@@ -232,6 +238,7 @@ struct gr_modem_events {
     std::function<void(int stream, uint64_t frame_type, const unsigned char* data, int size)> m17Frame;   // raw M17 frames
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records)> dmrFrames;     // DMO slicer bursts
     std::function<void(int stream, std::vector<float>* pcm)> pcmAudio;   // analogue modes (gr_modem::pcmAudio); the slot owns pcm
+    std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records80)> dmrFramesDecoded;   // the same bursts through DMR layer 2 (set_dmr_l2)
 };
 
 class gr_modem_hip {
@@ -257,6 +264,8 @@ public:
     void transmitTextData(const std::string& text, int frame_type = FrameTypeText, int stream = 0);
     void transmitBinData(const std::vector<unsigned char>& bin_data, int frame_type = FrameTypeProto, int stream = 0);
     void set_burst_ip_modem(bool v) { _burst_ip_modem = v; }
+    // DMR layer 2 on the device, off by default: dmrFramesDecoded(stream, records80) fires beside dmrFrames (the demodulator's set_dmr_l2)
+    void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
     // two-branch modes (both Viterbi alignments decoded): BranchRuleBoth (default) runs the frame synchroniser on both
     // branches, BranchRuleReference applies gr_modem.cpp:1080-1090 literally (see demodulate())
     enum branch_rule { BranchRuleBoth = 0, BranchRuleReference = 1 };
