@@ -274,7 +274,8 @@ typedef struct { int stream; int channel; uint64_t start; uint64_t count; } qrl_
  * T - 62 ... T - 62 + count - 1 (a later tag ends an earlier run).  qrl_mod_add_zero_runs hands over those tags (T in the block's 24 ksps
  * input coordinates = 20 x the byte offset gr_dmr_source put the tag on; `channel` ignored); they apply to the following qrl_mod_process calls.
  * (Across scheduler calls the reference only matches tags inside a call's own window, so it misses tags within the first 62 items of a window:
- * not restated.)  The DMR frame / CACH / slot-timing layer that produces bytes and tags (gr_dmr_source, src/DMR/) stays with the caller. */
+ * not restated.)  The bursts themselves can be built on the device (qrl_dmr_l2_encode / qrl_dmr_voice_call_encode, below); CACH, the slot
+ * timing and the tags of gr_dmr_source stay with the caller. */
 int qrl_mod_add_zero_runs(qrl_mod* m, const qrl_zero_run* runs, size_t n);
 /* QRL_MODEM_M17 (replaces make_gr_mod_m17(), reference src/gr/gr_mod_m17.cpp:19-81, gr_mod_base.cpp:206): its 125 / 3 output resampler
  * makes 833 1/3 samples per byte, so calls take multiples of 3 bytes (an M17 frame is 48) and return 2500 samples per 3 bytes;
@@ -670,6 +671,34 @@ int qrl_dmr_l2_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records /* 
  * payload into the burst and keeps its 68 middle bits. */
 int qrl_dmr_trellis34_decode(qrl_ctx* ctx, void* hip_stream, const uint8_t* bursts /* [n][33] */, size_t n, uint8_t* payloads /* [n][18] */, uint8_t* ok /* [n] */);
 int qrl_dmr_trellis34_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* payloads /* [n][18] */, size_t n, uint8_t* bursts /* [n][33] in/out */);
+/* DMR layer 2, transmit side: the stateless per-burst work in front of the DMR modulator's bytes (QRL_MODEM_DMR), what the reference's frame
+ * layer does before gr_mod_base::setDMRData -- DMRFrame::constructLCFrame / constructCSBKFrame (src/DMR/dmrframe.cpp:460-487: RS(12,9) or
+ * CRC-CCITT, BPTC(196,96), slot type through Golay(20,8), data sync), CDMRDataHeader::get, CBPTC19696::encode, CDMRTrellis::encode,
+ * DMRFrame::setVoice + addVoiceSync (:399-411, :498-501) and setEmbeddedData (:413-421: the fragment of the embedded LC -- seven Hamming
+ * (16,11,4) rows, column parity, 5-bit checksum, column interleave -- and the EMB through QR(16,7,6)).
+ * qrl_dmr_l2_encode: one 48-byte TX record per output slot.
+ *   0 kind | 1 FN | 2 colour code | 3 data type (slot type; kind 1 also picks the header (1) / terminator (2) mask by it, any other value
+ *   gives a zero burst) | 4..12 the nine LC bytes as CDMRLC(const unsigned char*) reads them | 13..15 zero | 16..42 payload | 43..47 zero
+ *   kind 0 empty frame (33 zero bytes) | 1 full LC of bytes 4..12 | 2 CSBK, payload 10 bytes | 3 data header, 10 | 4 rate 1/2 block, 12 |
+ *   5 rate 3/4 block, 18 | 7 voice A, 27 | 8 voice B-F, 27: FN 1..4 carries fragment FN of the embedded form of the LC in bytes 4..12
+ *   (LCSS 1, 3, 3, 2), any other FN a null fragment with LCSS 0.  Kinds 6 and 9..255 are reserved and give 33 zero bytes.
+ * qrl_dmr_voice_call_encode: the voice bursts of a call from a 40-byte call descriptor and the codec frames.  Slot i of stream b is voice
+ * burst k = first[b] + i of its call: FN = k mod 6 (0 = voice A), superframe (k div 6) mod 5 carries the call's LC, then the talker-alias
+ * header and blocks 1..3, exactly as DMRControl::getTxAudio rotates them (src/DMR/dmrcontrol.cpp:128-223); a function of k alone, so a
+ * call may be cut into calls of any length.  Descriptor: 0..2 source id, 3..5 destination id (high byte first) | 6 FLCO | 7 FID |
+ * 8 colour code | 9..35 talker alias, zero padded | 36..39 zero.
+ * Output: slot i of stream b at out + b * out_stride + i * slot_bytes: the 33-byte burst, then zeros up to slot_bytes (slot_bytes = 72:
+ * the 39 idle bytes gr_dmr_source appends, rows qrl_mod_process takes as they are).  Slots i >= min(counts[b], cap_frames) are slot_bytes
+ * zeros (counts == NULL: every slot holds a record).  Bytes of a row behind cap_frames * slot_bytes are not written.  Stateless,
+ * asynchronous on hip_stream.  QRL_ERR_ARG: a null pointer, an empty batch, slot_bytes < 33, out_stride < cap_frames * slot_bytes.
+ * CACH, the slot timing, rate 1 data and the CRCs of data messages stay host work. */
+#define QRL_DMR_TX_RECORD_BYTES 48
+#define QRL_DMR_CALL_BYTES 40
+int qrl_dmr_l2_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records /* [batch][cap_frames][48] */, const uint32_t* counts /* [batch] or NULL */,
+                      size_t batch, size_t cap_frames, uint8_t* out, size_t out_stride /* bytes per stream */, size_t slot_bytes /* >= 33 */);
+int qrl_dmr_voice_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls /* [batch][40] */, const uint8_t* voice /* [batch][n][27] */,
+                              const uint32_t* first /* [batch]: absolute index of voice[b][0] in its call, or NULL = 0 */, size_t batch, size_t n,
+                              uint8_t* out, size_t out_stride, size_t slot_bytes);
 
 /* ---- developer aids (NOT part of the drop-in surface; tools/prof_phases.py): shader-clock phase profile of k_decim_mfma ---- */
 void qrl_debug_decim_prof(unsigned long long* out8);

@@ -128,6 +128,8 @@ def load_library():
     lib.qrl_dmr_l2_decode.argtypes = [vp, vp, vp, vp, sz, sz, C.c_int, vp]
     lib.qrl_dmr_trellis34_decode.argtypes = [vp, vp, vp, sz, vp, vp]
     lib.qrl_dmr_trellis34_encode.argtypes = [vp, vp, vp, sz, vp]
+    lib.qrl_dmr_l2_encode.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, sz]
+    lib.qrl_dmr_voice_call_encode.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, sz]
     lib.qrl_demod_set_squelch.argtypes = [vp, C.c_double]
     lib.qrl_demod_set_agc.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_set_filter_width.argtypes = [vp, C.c_int]
@@ -252,7 +254,7 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_destroy", "qrl_demod_reset", "qrl_demod_set_carrier_offset", "qrl_demod_set_carrier_offsets", "qrl_demod_set_option", "qrl_demod_set_dmo_output", "qrl_demod_stream_wait", "qrl_demod_out_caps",
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
-    "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode",
+    "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode", "qrl_dmr_l2_encode", "qrl_dmr_voice_call_encode",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
@@ -1203,6 +1205,125 @@ def dmr_trellis34_encode(ctx, payloads, bursts):
         _check(ctx.lib.qrl_dmr_trellis34_encode(ctx.h, None, payloads.data_ptr(), payloads.shape[0], bursts.data_ptr()), "qrl_dmr_trellis34_encode")
     torch.cuda.synchronize()
     return bursts
+
+
+DMR_TX_RECORD_BYTES, DMR_CALL_BYTES, DMR_SLOT_BYTES = 48, 40, 72   # DMR_SLOT_BYTES: a burst and the 39 idle bytes gr_dmr_source appends
+DMR_TX_EMPTY, DMR_TX_LC, DMR_TX_CSBK, DMR_TX_DATA_HEADER, DMR_TX_RATE12, DMR_TX_RATE34, DMR_TX_VOICE_SYNC, DMR_TX_VOICE = 0, 1, 2, 3, 4, 5, 7, 8
+
+
+def _dmr_tx_out(out, batch, slots, slot_bytes, device):
+    """the output tensor of the two encoders: the caller's [batch, >= slots * slot_bytes] rows, or fresh [batch, slots, slot_bytes]"""
+    import torch
+    assert slot_bytes >= 33
+    if out is None:
+        return torch.zeros((batch, slots, slot_bytes), dtype=torch.uint8, device=device), slots * slot_bytes
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == batch and out.stride(1) == 1
+    assert out.shape[1] >= slots * slot_bytes and (batch == 1 or out.stride(0) >= out.shape[1])
+    return out, out.stride(0) if batch > 1 else out.shape[1]
+
+
+def dmr_l2_encode(ctx, records, counts=None, slot_bytes=33, out=None):
+    """[batch, cap, 48] uint8 cuda tensor of TX records (+ counts: [batch] int32 / uint32 cuda tensor, None = every slot holds a record) ->
+    [batch, cap, slot_bytes] bursts: 33 bytes and zeros up to slot_bytes (qrl_dmr_l2_encode: DMRFrame::constructLCFrame / constructCSBKFrame /
+    setVoice / setEmbeddedData).  out: a [batch, width] uint8 cuda tensor to write into instead, width >= cap * slot_bytes; its row stride is
+    the call's out_stride and the bytes of a row behind cap * slot_bytes are left alone."""
+    import torch
+    assert records.is_cuda and records.dtype == torch.uint8 and records.dim() == 3 and records.shape[2] == DMR_TX_RECORD_BYTES and records.is_contiguous()
+    batch, cap = records.shape[0], records.shape[1]
+    if counts is not None:
+        assert counts.is_cuda and counts.dtype in (torch.int32, torch.uint32) and counts.shape == (batch,) and counts.is_contiguous()
+    out, stride = _dmr_tx_out(out, batch, cap, slot_bytes, records.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_dmr_l2_encode(ctx.h, None, records.data_ptr(), counts.data_ptr() if counts is not None else None, batch, cap, out.data_ptr(),
+                                     stride, slot_bytes), "qrl_dmr_l2_encode")
+    torch.cuda.synchronize()
+    return out
+
+
+def dmr_voice_call_encode(ctx, calls, voice, first=None, slot_bytes=33, out=None):
+    """calls [batch, 40] call descriptors (dmr_call_descriptor), voice [batch, n, 27] codec frames, first [batch] int32 / uint32: the index
+    of voice[b][0] within its call (None = 0) -> [batch, n, slot_bytes] voice bursts A..F with the embedded LC / talker-alias rotation of
+    DMRControl::getTxAudio (qrl_dmr_voice_call_encode); out as in dmr_l2_encode.  All cuda uint8 tensors."""
+    import torch
+    assert calls.is_cuda and calls.dtype == torch.uint8 and calls.dim() == 2 and calls.shape[1] == DMR_CALL_BYTES and calls.is_contiguous()
+    batch = calls.shape[0]
+    assert voice.is_cuda and voice.dtype == torch.uint8 and voice.dim() == 3 and voice.shape[0] == batch and voice.shape[2] == 27 and voice.is_contiguous()
+    n = voice.shape[1]
+    if first is not None:
+        assert first.is_cuda and first.dtype in (torch.int32, torch.uint32) and first.shape == (batch,) and first.is_contiguous()
+    out, stride = _dmr_tx_out(out, batch, n, slot_bytes, calls.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_dmr_voice_call_encode(ctx.h, None, calls.data_ptr(), voice.data_ptr(), first.data_ptr() if first is not None else None, batch, n,
+                                             out.data_ptr(), stride, slot_bytes), "qrl_dmr_voice_call_encode")
+    torch.cuda.synchronize()
+    return out
+
+
+def dmr_call_descriptor(src_id, dst_id, group=True, fid=0, color_code=1, alias=b""):
+    """the 40-byte call descriptor of qrl_dmr_voice_call_encode as a numpy array: ids, FLCO (0 group, 3 private), FID (0xC2: Codec2 voice),
+    colour code, the talker alias cut / zero padded to 27 bytes"""
+    alias = bytes(alias)[:27]
+    d = np.zeros(DMR_CALL_BYTES, np.uint8)
+    d[0:3] = [(src_id >> 16) & 255, (src_id >> 8) & 255, src_id & 255]
+    d[3:6] = [(dst_id >> 16) & 255, (dst_id >> 8) & 255, dst_id & 255]
+    d[6], d[7], d[8] = 0 if group else 3, fid & 255, color_code & 255
+    d[9:9 + len(alias)] = np.frombuffer(alias, np.uint8)
+    return d
+
+
+def dmr_voice_call_records(call, n, first=0):
+    """the TX records of voice bursts first .. first + n - 1 of a call, payloads left zero: the host form of the rule
+    qrl_dmr_voice_call_encode applies on the device ([n, 48] numpy uint8)"""
+    call = np.asarray(call, np.uint8)
+    rec = np.zeros((n, DMR_TX_RECORD_BYTES), np.uint8)
+    alias = call[9:36]
+    for j in range(n):
+        k = first + j
+        fn, s = k % 6, (k // 6) % 5
+        rec[j, 0], rec[j, 1], rec[j, 2] = (DMR_TX_VOICE if fn else DMR_TX_VOICE_SYNC), fn, call[8]
+        if s == 0:
+            rec[j, 4], rec[j, 5] = call[6], call[7]
+            rec[j, 7:10], rec[j, 10:13] = call[3:6], call[0:3]
+        elif s == 1:
+            rec[j, 4], rec[j, 6] = 4, (1 << 6) | (0x1B << 1)
+            rec[j, 7:13] = alias[0:6]
+        else:
+            rec[j, 4] = 3 + s
+            rec[j, 6:13] = alias[6 * (s - 1):6 * (s - 1) + 7]
+    return rec
+
+
+def dmr_call_slots(call, voice, repeater=False, slot_bytes=DMR_SLOT_BYTES, stream=0, first_byte=0):
+    """One whole call as the reference sends it, as TX records for dmr_l2_encode: 3 BS-downlink-activate CSBKs in repeater mode
+    (DMRControl::getStartCSBK), the LC header twice (getVoiceHeader), the voice bursts of voice [n, 27] (getTxAudio), the terminator twice and
+    two empty frames (gr_modem::transmitDMR).  The terminator's LC carries FID 0 whatever the call's FID, as getVoiceTerminator builds it.
+    -> (records [slots, 48] numpy uint8, zero_runs): zero_runs = [(stream, T, count), ...] for Mod.add_zero_runs, one per slot, the tag
+    gr_dmr_source puts on the first idle byte of every slot, with the slots laid out slot_bytes apart from byte first_byte of the modulator's
+    input; pure arithmetic on the slot positions, no device work."""
+    call = np.asarray(call, np.uint8)
+    voice = np.asarray(voice, np.uint8).reshape(-1, 27)
+    assert call.shape == (DMR_CALL_BYTES,) and slot_bytes >= 33
+    head = []
+    if repeater:
+        csbk = np.zeros(DMR_TX_RECORD_BYTES, np.uint8)
+        csbk[0], csbk[2], csbk[3] = DMR_TX_CSBK, call[8], 3
+        csbk[16] = 0x80 | 0x38                            # last block, CSBKO_BSDWNACT; setDstId / setSrcId fill bytes 4..6 / 7..9 of the block
+        csbk[20:23], csbk[23:26] = call[3:6], call[0:3]
+        head += [csbk] * 3
+    lc = np.zeros(DMR_TX_RECORD_BYTES, np.uint8)
+    lc[0], lc[2], lc[3] = DMR_TX_LC, call[8], 1
+    lc[4], lc[5] = call[6], call[7]
+    lc[7:10], lc[10:13] = call[3:6], call[0:3]
+    head += [lc, lc]
+    term = lc.copy()
+    term[3], term[5] = 2, 0
+    vrec = dmr_voice_call_records(call, voice.shape[0])
+    vrec[:, 16:43] = voice
+    empty = np.zeros(DMR_TX_RECORD_BYTES, np.uint8)
+    records = np.stack(head + list(vrec) + [term, term, empty, empty])
+    idle = slot_bytes - 33
+    runs = [(stream, 20 * (first_byte + i * slot_bytes + 33), idle * 20) for i in range(records.shape[0])] if idle else []
+    return records, runs
 
 
 def m17_decode_frames(ctx, frames):

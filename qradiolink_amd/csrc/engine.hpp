@@ -429,6 +429,12 @@ void launch_m17_encode(const uint8_t* records, size_t n, uint8_t* frames, hipStr
 void launch_dmr_l2(const uint8_t* records, const uint32_t* counts, size_t batch, size_t cap, int audio_fec, uint8_t* out, hipStream_t s);
 void launch_trellis34_decode(const uint8_t* bursts, size_t n, uint8_t* payloads, uint8_t* ok, hipStream_t s);
 void launch_trellis34_encode(const uint8_t* payloads, size_t n, uint8_t* bursts, hipStream_t s);
+// ---- DMR layer 2 transmit (kernels_dmr_tx.hip): TX records [batch][cap][48], or calls [batch][40] + codec frames [batch][n][27], -> bursts
+//      out[b * out_stride + i * slot_bytes], 33 bytes and zeros up to slot_bytes ----
+void launch_dmr_tx(const uint8_t* records, const uint32_t* counts, size_t batch, size_t cap, uint8_t* out, size_t out_stride, size_t slot_bytes,
+                   hipStream_t s);
+void launch_dmr_tx_call(const uint8_t* calls, const uint8_t* voice, const uint32_t* first, size_t batch, size_t n_bursts, uint8_t* out,
+                        size_t out_stride, size_t slot_bytes, hipStream_t s);
 
 // ---- side outputs (kernels_side.hip): rssi_block on port 0, rx_fft_c on the device-rate IQ ----
 constexpr uint32_t RSSI_RING = 4096;   // |x|^2 look-back ring per stream (moving_average_ff(2000) reads 1999 items back)

@@ -4,7 +4,10 @@
 //   qrl_dmr_l2_decode                DMRFrame::DMRFrame / validate / runAudioFEC, CDMREMB::putData   reference src/DMR/dmrframe.cpp:36-253,
 //                                    src/DMR/dmrcontrol.cpp:233-248 (kernels_dmr_l2.hip)
 //   qrl_dmr_trellis34_decode / _encode   CDMRTrellis::decode / encode   reference src/MMDVM/DMRTrellis.cpp:50-107
+//   qrl_dmr_l2_encode / qrl_dmr_voice_call_encode   DMRFrame::constructLCFrame / constructCSBKFrame / setVoice / setEmbeddedData, DMRControl::getTxAudio
+//                                    reference src/DMR/dmrframe.cpp:399-501, src/DMR/dmrcontrol.cpp:128-223 (kernels_dmr_tx.hip)
 #include "host_common.hpp"
+#include <cstdint>
 #include <string>
 
 using namespace qrl;
@@ -65,6 +68,33 @@ int qrl_dmr_trellis34_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* payl
     if (!ctx || !payloads || !bursts) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_trellis34_encode: null argument");
     HIPCHK(hipSetDevice(ctx->device));
     launch_trellis34_encode(payloads, n, bursts, static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+// what both encoders ask of their output geometry: slots of at least a burst, rows that hold their slots
+static bool dmr_tx_geometry_ok(size_t batch, size_t slots, size_t out_stride, size_t slot_bytes)
+{
+    return batch && slots && slot_bytes >= 33 && slots <= SIZE_MAX / slot_bytes && out_stride >= slots * slot_bytes;
+}
+int qrl_dmr_l2_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records, const uint32_t* counts, size_t batch, size_t cap_frames,
+                      uint8_t* out, size_t out_stride, size_t slot_bytes)
+{
+    if (!ctx || !records || !out) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_l2_encode: null argument");
+    if (!dmr_tx_geometry_ok(batch, cap_frames, out_stride, slot_bytes))
+        return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_l2_encode: empty batch, slot_bytes < 33 or out_stride < cap_frames * slot_bytes");
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_dmr_tx(records, counts, batch, cap_frames, out, out_stride, slot_bytes, static_cast<hipStream_t>(hip_stream));
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+int qrl_dmr_voice_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls, const uint8_t* voice, const uint32_t* first, size_t batch,
+                              size_t n, uint8_t* out, size_t out_stride, size_t slot_bytes)
+{
+    if (!ctx || !calls || !voice || !out) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_voice_call_encode: null argument");
+    if (!dmr_tx_geometry_ok(batch, n, out_stride, slot_bytes))
+        return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_voice_call_encode: empty batch, slot_bytes < 33 or out_stride < n * slot_bytes");
+    HIPCHK(hipSetDevice(ctx->device));
+    launch_dmr_tx_call(calls, voice, first, batch, n, out, out_stride, slot_bytes, static_cast<hipStream_t>(hip_stream));
     HIPCHK(hipGetLastError());
     return QRL_OK;
 }

@@ -622,7 +622,8 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRDecoded(int str
 
 // ================================================================================================ gr_mod_base_hip
 gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_bytes)
-    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0), d_clipped((size_t)std::max(streams, 0), 0)
+    : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0), d_clipped((size_t)std::max(streams, 0), 0),
+      d_dmr_jobs((size_t)std::max(streams, 0)), d_dmr_call((size_t)std::max(streams, 0)), d_dmr_next((size_t)std::max(streams, 0), 0)
 {
     d_cw_n = std::min<size_t>(1024, d_max);   // a facade built for fewer than 1024 items per call must still key CW
 }
@@ -634,6 +635,7 @@ gr_mod_base_hip::~gr_mod_base_hip()
     if (d_audio) (void)hipFree(d_audio);
     if (d_iq) (void)hipFree(d_iq);
     if (d_clip) (void)hipFree(d_clip);
+    if (d_dmr_dev) (void)hipFree(d_dmr_dev);
 }
 static bool tx_mode_has_back_end(int mode)   // qrl_mod_create builds the gr_mod_base back end (rotator + interpolator) for every family but these (tx.cpp)
 {
@@ -707,6 +709,7 @@ void gr_mod_base_hip::open()
     std::lock_guard<std::mutex> g(d_mutex);
     for (auto& q : d_queue) q.clear();
     for (auto& q : d_aqueue) q.clear();
+    for (auto& j : d_dmr_jobs) j.clear();
     for (auto& v : d_sent) v = 0;
 }
 void gr_mod_base_hip::set_mode(int mode)   // gr_mod_base::set_mode (src/gr/gr_mod_base.cpp:354-763): new graph, queued bytes dropped
@@ -741,6 +744,104 @@ int gr_mod_base_hip::setDMRData(const std::vector<std::vector<uint8_t>>& frames,
         throw std::runtime_error(std::string("qrl_mod_add_zero_runs: ") + qrl_last_error());
     }
     return 0;
+}
+void gr_mod_base_hip::setDMRCall(const uint8_t* descriptor40, int stream)   // the call of the stream's next voice bursts; DMRControl::initVoiceTX
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (d_mode != QRL_MODEM_DMR || !d_h) throw std::runtime_error("gr_mod_base_hip::setDMRCall outside DMR mode");
+    std::lock_guard<std::mutex> g(d_mutex);
+    d_dmr_call.at((size_t)stream).assign(descriptor40, descriptor40 + QRL_DMR_CALL_BYTES);
+    d_dmr_next[(size_t)stream] = 0;
+}
+int gr_mod_base_hip::txDMRVoice(const uint8_t* voice, size_t n, int stream)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // as in setDMRData: slots and their zero runs become visible to a pass together
+    if (d_mode != QRL_MODEM_DMR || !d_h) throw std::runtime_error("gr_mod_base_hip::txDMRVoice outside DMR mode");
+    if (d_dmr_call.at((size_t)stream).empty()) throw std::runtime_error("gr_mod_base_hip::txDMRVoice before setDMRCall");
+    if (!n) return 0;
+    constexpr size_t kSlot = 33 + 39, kZeroBytes = 39;   // a burst and gr_dmr_source's idle bytes (setDMRData)
+    std::lock_guard<std::mutex> g(d_mutex);
+    auto& q = d_queue[(size_t)stream];
+    dmr_tx_job job;
+    job.pos = d_sent[(size_t)stream] + q.size();
+    job.first = d_dmr_next[(size_t)stream];
+    job.n = n;
+    job.call = d_dmr_call[(size_t)stream];
+    job.voice.assign(voice, voice + 27 * n);
+    std::vector<qrl_zero_run> runs(n);
+    for (size_t i = 0; i < n; ++i) {
+        runs[i] = qrl_zero_run{};
+        runs[i].stream = stream; runs[i].start = (job.pos + i * kSlot + 33) * 20u; runs[i].count = kZeroBytes * 4u * 5u;
+    }
+    if (qrl_mod_add_zero_runs(d_h, runs.data(), runs.size()) != QRL_OK) throw std::runtime_error(std::string("qrl_mod_add_zero_runs: ") + qrl_last_error());
+    q.insert(q.end(), n * kSlot, (uint8_t)0);   // the slots: zeros here, the bursts are written on the device by the pass that sends them
+    d_dmr_jobs[(size_t)stream].push_back(std::move(job));
+    d_dmr_next[(size_t)stream] += (uint32_t)n;
+    return (int)n;
+}
+// The part of every queued voice job that lies in this pass's window [window0[s], window0[s] + nb) of stream s, encoded into d_bytes on the
+// modulator's stream behind the upload of the queue's bytes.  Runs of whole slots go straight into the modulator's input; a slot the window
+// cuts is encoded into the staging buffer and its bytes inside the window are copied over (the pass that holds the rest encodes it again).
+void gr_mod_base_hip::encode_dmr_jobs(const std::vector<uint64_t>& window0, size_t nb, void* stream)
+{
+    constexpr size_t kSlot = 72;
+    hipStream_t ms = static_cast<hipStream_t>(stream);
+    struct piece { size_t call, first, voice, n, dst, slot, skip, len; bool cut; };   // offsets into the staging buffer; dst into d_bytes
+    std::vector<uint8_t> stage;
+    std::vector<piece> pieces;
+    auto put = [&](const void* p, size_t len) {
+        const size_t o = (stage.size() + 3) & ~(size_t)3;
+        stage.resize(o + len, 0);
+        if (p) std::memcpy(stage.data() + o, p, len);
+        return o;
+    };
+    {
+        std::lock_guard<std::mutex> g(d_mutex);
+        for (int s = 0; s < d_n; ++s) {
+            auto& jobs = d_dmr_jobs[(size_t)s];
+            const uint64_t a = window0[(size_t)s], b = a + nb;
+            for (const auto& j : jobs) {
+                if (j.pos >= b) break;
+                const size_t k0 = j.pos >= a ? 0 : (size_t)((a - j.pos) / kSlot), k1 = std::min<uint64_t>(j.n, (b - j.pos + kSlot - 1) / kSlot);
+                if (k0 >= k1) continue;
+                const size_t call = put(j.call.data(), QRL_DMR_CALL_BYTES);
+                auto emit = [&](size_t ka, size_t kb, bool cut) {   // slots ka .. kb - 1
+                    const uint32_t first = j.first + (uint32_t)ka;
+                    const uint64_t p = j.pos + ka * kSlot, lo = std::max(a, p), hi = std::min<uint64_t>(b, p + (kb - ka) * kSlot);
+                    piece pc{};
+                    pc.call = call; pc.first = put(&first, sizeof first); pc.voice = put(j.voice.data() + 27 * ka, 27 * (kb - ka)); pc.n = kb - ka;
+                    pc.dst = (size_t)s * d_max + (size_t)(lo - a); pc.cut = cut;
+                    if (cut) { pc.slot = put(nullptr, kSlot); pc.skip = (size_t)(lo - p); pc.len = (size_t)(hi - lo); }
+                    pieces.push_back(pc);
+                };
+                size_t run = k0;   // first slot of the current run of whole slots
+                for (size_t k = k0; k < k1; ++k) {
+                    const uint64_t p = j.pos + k * kSlot;
+                    if (p >= a && p + kSlot <= b) continue;
+                    if (k > run) emit(run, k, false);
+                    if (std::min<uint64_t>(b, p + kSlot) > std::max(a, p)) emit(k, k + 1, true);
+                    run = k + 1;
+                }
+                if (k1 > run) emit(run, k1, false);
+            }
+            jobs.erase(std::remove_if(jobs.begin(), jobs.end(), [&](const dmr_tx_job& j) { return j.pos + j.n * kSlot <= b; }), jobs.end());
+        }
+    }
+    if (pieces.empty()) return;
+    if (stage.size() > d_dmr_cap) {   // nothing of an earlier pass is in flight: every pass ends behind qrl_mod_sync
+        if (d_dmr_dev) (void)hipFree(d_dmr_dev);
+        d_dmr_dev = nullptr; d_dmr_cap = 0;
+        hchk(hipMalloc(reinterpret_cast<void**>(&d_dmr_dev), 2 * stage.size()), "hipMalloc");
+        d_dmr_cap = 2 * stage.size();
+    }
+    hchk(hipMemcpyAsync(d_dmr_dev, stage.data(), stage.size(), hipMemcpyHostToDevice, ms), "H2D");
+    for (const auto& pc : pieces) {
+        uint8_t* out = pc.cut ? d_dmr_dev + pc.slot : d_bytes + pc.dst;
+        chk(qrl_dmr_voice_call_encode(d_rt.ctx(), ms, d_dmr_dev + pc.call, d_dmr_dev + pc.voice, reinterpret_cast<const uint32_t*>(d_dmr_dev + pc.first), 1,
+                                      pc.n, out, pc.n * kSlot, kSlot), "qrl_dmr_voice_call_encode");
+        if (pc.cut) hchk(hipMemcpyAsync(d_bytes + pc.dst, d_dmr_dev + pc.slot + pc.skip, pc.len, hipMemcpyDeviceToDevice, ms), "D2D");
+    }
+    hchk(hipStreamSynchronize(ms), "hipStreamSynchronize");   // the staging bytes are this function's
 }
 int gr_mod_base_hip::set_audio(std::vector<float>* data, int stream)   // gr_mod_base.cpp:793-797 -> gr_audio_source::set_data (gr_audio_source.cpp:55-66)
 {
@@ -853,6 +954,7 @@ void gr_mod_base_hip::flush_sources()
     // (bytes already counted into d_sent stay counted: the positions of later zero runs are stream positions of the modulator)
     for (auto& q : d_queue) q.clear();
     for (auto& q : d_aqueue) q.clear();
+    for (auto& j : d_dmr_jobs) j.clear();   // their slots went with the queue
 }
 size_t gr_mod_base_hip::samples_per_byte() const { return d_h ? qrl_mod_samples_per_byte(d_h) : 0; }
 // int16 I/Q out (out[s] = interleaved int16 I, Q pairs): replaces the SDR driver's fc32 -> sc16 converter.  The modulator's last kernel converts
@@ -929,6 +1031,7 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
     if (!d_h) throw std::runtime_error("gr_mod_base_hip::work before set_mode");
     size_t nb = 0;
     std::vector<uint8_t> host((size_t)d_n * d_max, 0);
+    std::vector<uint64_t> window0(d_sent);   // the stream position of this pass's first byte
     {
         std::lock_guard<std::mutex> g(d_mutex);
         for (auto& q : d_queue) nb = std::max(nb, std::min(q.size(), d_max));
@@ -943,6 +1046,7 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
     }
     hipStream_t ms = static_cast<hipStream_t>(qrl_mod_stream(d_h));
     hchk(hipMemcpyAsync(d_bytes, host.data(), host.size(), hipMemcpyHostToDevice, ms), "H2D");
+    if (d_mode == QRL_MODEM_DMR) encode_dmr_jobs(window0, nb, ms);
     const size_t ns = nb / d_bpb * d_spblock, stride = (d_max / d_bpb + 1) * d_spblock;
     zero_clip(ms);
     if (sc16) chk(qrl_mod_process_sc16(d_h, d_bytes, d_max, nb, reinterpret_cast<int16_t*>(d_iq), stride), "qrl_mod_process_sc16");

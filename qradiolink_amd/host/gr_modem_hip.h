@@ -169,6 +169,14 @@ public:
     // 39 x 4 x 5 = 780 items sits on the first of them -- here a zero run of the DMR modulator (qrl_mod_add_zero_runs) at 20 items per byte (4 symbols x 5
     // samples at the zero-idle block's 24 ksps input).  The source's tx_time tags belong to the SDR sink and are not produced.  QRL_MODEM_DMR mode only.
     int setDMRData(const std::vector<std::vector<uint8_t>>& frames, int stream = 0);
+    // The voice bursts of a call built on the device (qrl_dmr_voice_call_encode) straight into the modulator's input, beside setDMRData: what
+    // DMRControl::getTxAudio + setDMRData do per burst in the reference (src/DMR/dmrcontrol.cpp:128-223, src/gr_modem.cpp:766-802).
+    // setDMRCall takes the 40-byte call descriptor (host/dmr_frame_hip.h: dmr_call_descriptor) and starts the call's burst count at 0, like
+    // DMRControl::initVoiceTX.  txDMRVoice queues n voice bursts (voice = n x 27 codec bytes) for the stream: 72-byte slots with the same
+    // zero runs as setDMRData's; their bytes are written by the device in the work() pass that sends them, whatever else is queued around
+    // them and however the passes cut the slots.  Returns the number of bursts queued.  QRL_MODEM_DMR mode only.
+    void setDMRCall(const uint8_t* descriptor40, int stream = 0);
+    int txDMRVoice(const uint8_t* voice, size_t n, int stream = 0);
     void set_bb_gain(float value);
     void set_carrier_offset(double hz);                        // every stream
     void set_carrier_offset(double hz, int stream);            // one radio (gr_modem::setTxCarrierOffset of radio `stream`); kept across set_mode / set_samp_rate
@@ -225,6 +233,12 @@ private:
     std::vector<std::vector<float>> d_aqueue;
     std::vector<uint64_t> d_sent;   // bytes per stream handed to the modulator since set_mode (with the zero padding of short queues): positions of the zero runs
     uint32_t* d_clip = nullptr; std::vector<uint64_t> d_clipped;   // device counters of one int16 pass (zeroed in front of it); totals per stream
+    // txDMRVoice: bursts whose slots are queued as zeros and encoded on the device by the pass that sends them (under d_mutex, like the queues)
+    struct dmr_tx_job { uint64_t pos; uint32_t first; size_t n; std::vector<uint8_t> call, voice; };   // pos: the stream's byte index of slot 0
+    std::vector<std::vector<dmr_tx_job>> d_dmr_jobs;
+    std::vector<std::vector<uint8_t>> d_dmr_call; std::vector<uint32_t> d_dmr_next;   // per stream: descriptor, index of the next voice burst
+    uint8_t* d_dmr_dev = nullptr; size_t d_dmr_cap = 0;   // device staging of a pass: descriptors, first indices, codec bytes, straddling slots
+    void encode_dmr_jobs(const std::vector<uint64_t>& window0, size_t nb, void* stream);
 };
 
 // the Qt signals of gr_modem that the RX / TX paths emit (src/gr_modem.h:118-139); unset callbacks are skipped.  Buffers are only
@@ -266,6 +280,10 @@ public:
     void set_burst_ip_modem(bool v) { _burst_ip_modem = v; }
     // DMR layer 2 on the device, off by default: dmrFramesDecoded(stream, records80) fires beside dmrFrames (the demodulator's set_dmr_l2)
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
+    // DMR voice bursts built on the device from a call descriptor and codec bytes (the modulator's setDMRCall / txDMRVoice): what
+    // gr_modem::transmitDMR does through DMRControl::getTxAudio and setDMRData (src/gr_modem.cpp:766-802)
+    void setDMRCall(const uint8_t* descriptor40, int stream = 0) { if (_gr_mod_base) _gr_mod_base->setDMRCall(descriptor40, stream); }
+    int txDMRVoice(const uint8_t* voice, size_t n, int stream = 0) { return _gr_mod_base ? _gr_mod_base->txDMRVoice(voice, n, stream) : 0; }
     // two-branch modes (both Viterbi alignments decoded): BranchRuleBoth (default) runs the frame synchroniser on both
     // branches, BranchRuleReference applies gr_modem.cpp:1080-1090 literally (see demodulate())
     enum branch_rule { BranchRuleBoth = 0, BranchRuleReference = 1 };
