@@ -659,7 +659,7 @@ int qrl_m17_encode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* records
  *   16..19 getDstId(), little endian | 20..52 getData(): the regenerated burst, or the input burst where validate() returns before
  *   rewriting it | 53..79 payload, zero padded: the 12 BPTC bytes as the class keeps them after put() (masks in place), the 18 trellis
  *   bytes, or the 27 getVoice() bytes after the FEC.
- * The protocol state above this (DMRControl, the four-burst embedded LC) stays host work. */
+ * The protocol state above this (DMRControl, the four-burst embedded LC) is qrl_dmr_rx_process, below. */
 #define QRL_DMR_L2_RECORD_BYTES 80
 #define QRL_DMR_DT_VOICE_SYNC 0xF0
 #define QRL_DMR_DT_VOICE 0xF1
@@ -699,6 +699,58 @@ int qrl_dmr_l2_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* records /* 
 int qrl_dmr_voice_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls /* [batch][40] */, const uint8_t* voice /* [batch][n][27] */,
                               const uint32_t* first /* [batch]: absolute index of voice[b][0] in its call, or NULL = 0 */, size_t batch, size_t n,
                               uint8_t* out, size_t out_stride, size_t slot_bytes);
+
+/* DMR receive call layer: the per-stream protocol state above layer 2, the receive half of the reference's DMRControl in DMO mode with an
+ * idle transmitter (src/DMR/dmrcontrol.cpp: addFrames :625-665, processVoiceHeader / processTerminator / processDataHeader / processCSBK /
+ * processAudio, processColorCode, processEmbeddedData, the completion rule of processTalkerAlias) and CDMREmbeddedData's receive side
+ * (src/MMDVM/DMREmbeddedData.cpp:47-109, :213-322: the LCSS state machine, the column de-interleave, seven Hamming (16,11,4) rows with
+ * single-error correction, the column parity, the 5-bit checksum).  The receive counterpart of qrl_dmr_voice_call_encode: a handle keeps the
+ * state of `batch` streams on the device between calls; qrl_dmr_rx_process walks, per stream, slots i < min(counts[b], cap_frames) of the
+ * records qrl_dmr_l2_decode wrote (counts == NULL: every slot), in order, and writes one 128-byte record per slot; every other output slot is
+ * 128 zero bytes.  It runs behind qrl_dmr_l2_decode on the same HIP stream with no host synchronisation; the calls of one handle must be
+ * ordered by the caller (one stream, or events).  The reference is reproduced as it stands: without promiscuous mode a burst of another
+ * colour code is refused whatever its type; a voice burst is checked with _color_code_RX, not its own colour code, so late entry works in
+ * promiscuous mode and, with a fixed colour code other than 0, only behind a header; a terminator with source and destination 0 is passed over.
+ * The output record (nothing is compacted: slot i answers slot i of the layer-2 records):
+ *   0..1 flags, little endian: QRL_DMR_RX_VALID the burst passed validate() | _PROCESSED its process* call returned true (also set for a
+ *   valid burst addFrames has no call for) | _HEADER_VOICE, _HEADER_DATA headerReceived fired | _TERMINATOR terminatorReceived | _END_BEEP
+ *   endBeep | _AUDIO digitalAudio: the 27 codec bytes are bytes 53..79 of the layer-2 record of the same slot | _EMBEDDED an embedded LC
+ *   completed and was valid, processEmbeddedData ran | _TALKER_ALIAS talkerAlias fired | _GPS gpsInfo fired | _UNKNOWN_FLCO an embedded FLCO
+ *   the reference only logs
+ *   | 2 receiver state after the burst (RECEIVER_STATE: 0 idle, 1 late entry, 2 audio, 3 data) | 3 _color_code_RX | 4 _FLCO_RX | 5..7 zero
+ *   | 8..11 _srcId_RX, 12..15 _dstId_RX, little endian
+ *   | 16 FLCO of the embedded LC, 17..25 its nine getRawData bytes (with _EMBEDDED, else zero)
+ *   | 26 talker-alias format (0 7-bit, 1 ISO 8-bit, 2 UTF-8, 3 UTF-16BE), 27 its length field, 28 the number of bytes collected (at most 68:
+ *   blocks are only appended to an incomplete alias, and the largest need is 2 x 31), 32..99 those bytes: the header's six (format 0: first
+ *   the low bit of its options byte, as a byte), then seven per block (with _TALKER_ALIAS, else zero) | 29..31, 100..127 zero.
+ * Turning the alias bytes into text, the GPS arithmetic of CUtils::extractGPSPosition and the signals' HTML strings stay host work
+ * (host/dmr_frame_hip.h), as do repeater mode / CACH and the data messages of dmrmessagehandler.
+ * qrl_dmr_rx_create: config = colour code 0..15 and promiscuous 0 / 1, anything else QRL_ERR_ARG.  _set_config: from the next
+ * qrl_dmr_rx_process on.  _reset: every stream back to a fresh handle's state, asynchronous on hip_stream.  _process: out 16-byte aligned;
+ * a null pointer or cap_frames == 0 is QRL_ERR_ARG before any device work.  _get_state: the public 12 bytes per stream (0 receiver state,
+ * 1 _color_code_RX, 2 _FLCO_RX, 3 zero, 4..7 source, 8..11 destination, little endian), out 4-byte aligned, asynchronous on hip_stream. */
+#define QRL_DMR_RX_RECORD_BYTES 128
+#define QRL_DMR_RX_STATE_BYTES 12
+#define QRL_DMR_RX_VALID 0x0001
+#define QRL_DMR_RX_PROCESSED 0x0002
+#define QRL_DMR_RX_HEADER_VOICE 0x0004
+#define QRL_DMR_RX_HEADER_DATA 0x0008
+#define QRL_DMR_RX_TERMINATOR 0x0010
+#define QRL_DMR_RX_END_BEEP 0x0020
+#define QRL_DMR_RX_AUDIO 0x0040
+#define QRL_DMR_RX_EMBEDDED 0x0080
+#define QRL_DMR_RX_TALKER_ALIAS 0x0100
+#define QRL_DMR_RX_GPS 0x0200
+#define QRL_DMR_RX_UNKNOWN_FLCO 0x0400
+typedef struct qrl_dmr_rx qrl_dmr_rx;
+typedef struct qrl_dmr_rx_config { int color_code; int promiscuous; } qrl_dmr_rx_config;
+int qrl_dmr_rx_create(qrl_ctx* ctx, size_t batch, const qrl_dmr_rx_config* config, qrl_dmr_rx** out);
+void qrl_dmr_rx_destroy(qrl_dmr_rx* h);
+int qrl_dmr_rx_reset(qrl_dmr_rx* h, void* hip_stream);
+int qrl_dmr_rx_set_config(qrl_dmr_rx* h, const qrl_dmr_rx_config* config);
+int qrl_dmr_rx_process(qrl_dmr_rx* h, void* hip_stream, const uint8_t* l2_records /* [batch][cap_frames][80] */, const uint32_t* counts /* [batch] or NULL */,
+                       size_t cap_frames, uint8_t* out /* [batch][cap_frames][128] */);
+int qrl_dmr_rx_get_state(qrl_dmr_rx* h, void* hip_stream, uint8_t* out /* [batch][12], device */);
 
 /* ---- developer aids (NOT part of the drop-in surface; tools/prof_phases.py): shader-clock phase profile of k_decim_mfma ---- */
 void qrl_debug_decim_prof(unsigned long long* out8);

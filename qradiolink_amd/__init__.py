@@ -68,6 +68,10 @@ class _AModConfig(C.Structure):
                 ("device_samp_rate", C.c_int), ("carrier_offset_hz", C.c_double)]
 
 
+class _DmrRxConfig(C.Structure):
+    _fields_ = [("color_code", C.c_int), ("promiscuous", C.c_int)]
+
+
 class _Out(C.Structure):
     _fields_ = [("filtered", C.c_void_p), ("filtered_cap", C.c_size_t), ("constellation", C.c_void_p),
                 ("constellation_cap", C.c_size_t), ("bits_a", C.c_void_p), ("bits_cap", C.c_size_t),
@@ -130,6 +134,13 @@ def load_library():
     lib.qrl_dmr_trellis34_encode.argtypes = [vp, vp, vp, sz, vp]
     lib.qrl_dmr_l2_encode.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, sz]
     lib.qrl_dmr_voice_call_encode.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, sz]
+    lib.qrl_dmr_rx_create.argtypes = [vp, sz, C.POINTER(_DmrRxConfig), C.POINTER(vp)]
+    lib.qrl_dmr_rx_destroy.argtypes = [vp]
+    lib.qrl_dmr_rx_destroy.restype = None
+    lib.qrl_dmr_rx_reset.argtypes = [vp, vp]
+    lib.qrl_dmr_rx_set_config.argtypes = [vp, C.POINTER(_DmrRxConfig)]
+    lib.qrl_dmr_rx_process.argtypes = [vp, vp, vp, vp, sz, vp]
+    lib.qrl_dmr_rx_get_state.argtypes = [vp, vp, vp]
     lib.qrl_demod_set_squelch.argtypes = [vp, C.c_double]
     lib.qrl_demod_set_agc.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_set_filter_width.argtypes = [vp, C.c_int]
@@ -255,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
     "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode", "qrl_dmr_l2_encode", "qrl_dmr_voice_call_encode",
+    "qrl_dmr_rx_create", "qrl_dmr_rx_destroy", "qrl_dmr_rx_reset", "qrl_dmr_rx_set_config", "qrl_dmr_rx_process", "qrl_dmr_rx_get_state",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
@@ -503,6 +515,8 @@ class Demod:
 
     def reset(self):
         _check(self.lib.qrl_demod_reset(self.h), "qrl_demod_reset")
+        if getattr(self, "dmo_call_rx", None) is not None:
+            self.dmo_call_rx.reset(stream=self.stream)
 
     def enable_dmo_sink(self, cap_frames=64):
         """QRL_MODEM_DMR: gr_dmr_dmo_sink on the device; after every process() self.dmo_frames uint8 [batch, cap, 40] /
@@ -525,6 +539,18 @@ class Demod:
         t.cuda.current_stream().synchronize()   # the zero fill is done before the handle's stream writes the buffer
         self._dmo_l2_fec = 1 if audio_fec else 0
 
+    def enable_dmo_call(self, colour_code=1, promiscuous=False):
+        """DMR receive call layer behind layer 2 (enable_dmo_l2 first): every process() also fills self.dmo_call uint8 [batch, cap, 128], what
+        the reference's DMRControl::addFrames makes of each burst of the call and the stream's call state afterwards (qrl_dmr_rx_process, the
+        record of include/qrl_hip.h), queued on the handle's stream right behind layer 2 with no host synchronisation in between; slots at or
+        past dmo_counts[b] are zero.  The tracker, self.dmo_call_rx (a DmrRx), carries its state from call to call; reset() resets it too."""
+        if getattr(self, "dmo_l2", None) is None:
+            raise RuntimeError("enable_dmo_call: enable_dmo_l2() first")
+        t = self.torch
+        self.dmo_call_rx = DmrRx(self.ctx, self.batch, colour_code=colour_code, promiscuous=promiscuous)
+        self.dmo_call = t.zeros((self.batch, self.dmo_frames.shape[1], DMR_RX_RECORD_BYTES), dtype=t.uint8, device=self.dmo_frames.device)
+        t.cuda.current_stream().synchronize()
+
     def _dmo_l2_async(self):
         if getattr(self, "dmo_l2", None) is None:
             return
@@ -532,6 +558,8 @@ class Demod:
         self.stream_wait(s)   # the slicer may run on another of the handle's streams: an on-device wait, the host goes on
         _check(self.lib.qrl_dmr_l2_decode(self.ctx.h, C.c_void_p(s), self.dmo_frames.data_ptr(), self.dmo_counts.data_ptr(), self.batch,
                                           self.dmo_frames.shape[1], self._dmo_l2_fec, self.dmo_l2.data_ptr()), "qrl_dmr_l2_decode")
+        if getattr(self, "dmo_call", None) is not None:
+            self.dmo_call_rx.process(self.dmo_l2, self.dmo_counts, out=self.dmo_call, stream=s)
 
     def dmo_records(self):
         """host copy of the last call's records: per stream a list of (type, fn, colour code, 33 bytes)"""
@@ -553,6 +581,8 @@ class Demod:
         if self.h:
             self.lib.qrl_demod_destroy(self.h)
             self.h = C.c_void_p()
+        if getattr(self, "dmo_call_rx", None) is not None:
+            self.dmo_call_rx.close()
 
 
 class Channelizer:
@@ -1179,6 +1209,65 @@ def dmr_l2_decode(ctx, frames, counts=None, audio_fec=True):
                                      frames.shape[1], 1 if audio_fec else 0, out.data_ptr()), "qrl_dmr_l2_decode")
     torch.cuda.synchronize()
     return out
+
+
+DMR_RX_RECORD_BYTES, DMR_RX_STATE_BYTES = 128, 12
+(DMR_RX_VALID, DMR_RX_PROCESSED, DMR_RX_HEADER_VOICE, DMR_RX_HEADER_DATA, DMR_RX_TERMINATOR, DMR_RX_END_BEEP, DMR_RX_AUDIO, DMR_RX_EMBEDDED,
+ DMR_RX_TALKER_ALIAS, DMR_RX_GPS, DMR_RX_UNKNOWN_FLCO) = (1 << _i for _i in range(11))
+
+
+class DmrRx:
+    """DMR receive call layer (qrl_dmr_rx_*): per stream the receive half of the reference's DMRControl in DMO mode, kept on the device
+    between calls.  process() takes the [batch, cap, 80] records of dmr_l2_decode and returns [batch, cap, 128] call records; state() the
+    public [batch, 12] bytes (receiver state, _color_code_RX, _FLCO_RX, 0, source, destination little endian).  stream: a HIP stream
+    handle (int) or None for the null stream; the calls of one tracker must be ordered by the caller."""
+
+    def __init__(self, ctx, batch, colour_code=1, promiscuous=False):
+        self.ctx, self.lib, self.batch = ctx, ctx.lib, batch
+        self.h = C.c_void_p()
+        cfg = _DmrRxConfig(int(colour_code), int(promiscuous))
+        _check(self.lib.qrl_dmr_rx_create(ctx.h, batch, C.byref(cfg), C.byref(self.h)), "qrl_dmr_rx_create")
+
+    def set_config(self, colour_code, promiscuous):
+        """from the next process() on"""
+        cfg = _DmrRxConfig(int(colour_code), int(promiscuous))
+        _check(self.lib.qrl_dmr_rx_set_config(self.h, C.byref(cfg)), "qrl_dmr_rx_set_config")
+
+    def reset(self, stream=None):
+        """every stream back to a fresh tracker's state"""
+        _check(self.lib.qrl_dmr_rx_reset(self.h, C.c_void_p(stream)), "qrl_dmr_rx_reset")
+
+    def process(self, l2, counts=None, out=None, stream=None):
+        import torch
+        assert l2.is_cuda and l2.dtype == torch.uint8 and l2.dim() == 3 and l2.shape[0] == self.batch and l2.shape[2] == 80 and l2.is_contiguous()
+        if counts is not None:
+            assert counts.is_cuda and counts.dtype in (torch.int32, torch.uint32) and counts.shape == (self.batch,) and counts.is_contiguous()
+        cap = l2.shape[1]
+        if out is None:
+            out = torch.empty((self.batch, cap, DMR_RX_RECORD_BYTES), dtype=torch.uint8, device=l2.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.shape == (self.batch, cap, DMR_RX_RECORD_BYTES) and out.is_contiguous()
+        if stream is None:
+            torch.cuda.current_stream().synchronize()   # the call runs on the null stream, not torch's: what made l2 must be done
+        _check(self.lib.qrl_dmr_rx_process(self.h, C.c_void_p(stream), l2.data_ptr(), counts.data_ptr() if counts is not None else None, cap,
+                                           out.data_ptr()), "qrl_dmr_rx_process")
+        if stream is None:
+            torch.cuda.synchronize()
+        return out
+
+    def state(self, stream=None):
+        import torch
+        out = torch.empty((self.batch, DMR_RX_STATE_BYTES), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_dmr_rx_get_state(self.h, C.c_void_p(stream), out.data_ptr()), "qrl_dmr_rx_get_state")
+        if stream is None:
+            torch.cuda.synchronize()
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.qrl_dmr_rx_destroy(self.h)
+            self.h = C.c_void_p()
 
 
 def dmr_trellis34_decode(ctx, bursts):

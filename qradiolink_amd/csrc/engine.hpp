@@ -435,6 +435,12 @@ void launch_dmr_tx(const uint8_t* records, const uint32_t* counts, size_t batch,
                    hipStream_t s);
 void launch_dmr_tx_call(const uint8_t* calls, const uint8_t* voice, const uint32_t* first, size_t batch, size_t n_bursts, uint8_t* out,
                         size_t out_stride, size_t slot_bytes, hipStream_t s);
+// ---- DMR receive call layer (kernels_dmr_rx.hip): layer-2 records [batch][cap][80] -> call records [batch][cap][128] through the per-stream
+//      states [batch] (dmr_rx_core.hpp's dmr_rx_state); the public 12 bytes of every state ----
+constexpr size_t DMR_RX_RECORD_BYTES = 128, DMR_RX_STATE_BYTES = 128, DMR_RX_PUBLIC_BYTES = 12;   // kernels_dmr_rx.hip holds them to the core
+void launch_dmr_rx(const uint8_t* l2, const uint32_t* counts, size_t batch, size_t cap, int color_code, int promiscuous, void* states, uint8_t* out,
+                   hipStream_t s);
+void launch_dmr_rx_state(const void* states, size_t batch, uint8_t* out, hipStream_t s);
 
 // ---- side outputs (kernels_side.hip): rssi_block on port 0, rx_fft_c on the device-rate IQ ----
 constexpr uint32_t RSSI_RING = 4096;   // |x|^2 look-back ring per stream (moving_average_ff(2000) reads 1999 items back)

@@ -1,10 +1,11 @@
 // dmr_frame_hip.h — an 80-byte record of qrl_dmr_l2_decode (include/qrl_hip.h) behind the getters of the reference's DMRFrame
 // (src/DMR/dmrframe.h:50-88) as they read after DMRFrame(bytes, type), validate() and runAudioFEC(): what DMRControl::addFrames /
 // processAudio (src/DMR/dmrcontrol.cpp:225-260, :625-700) look at.  The work is done on the device; this class only reads bytes.
-// Below it the transmit side: dmr_tx_record and dmr_call_descriptor write the two records of qrl_dmr_l2_encode / qrl_dmr_voice_call_encode.
+// Below it dmr_call_event_hip reads a 128-byte record of qrl_dmr_rx_process and dmr_alias_text turns collected alias bytes into text; then the transmit side: dmr_tx_record and dmr_call_descriptor write the two records of qrl_dmr_l2_encode / qrl_dmr_voice_call_encode.
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "qrl_hip.h"
 
@@ -40,6 +41,90 @@ private:
     uint32_t le32(int o) const { return (uint32_t)_r[o] | ((uint32_t)_r[o + 1] << 8) | ((uint32_t)_r[o + 2] << 16) | ((uint32_t)_r[o + 3] << 24); }
     unsigned char _r[QRL_DMR_L2_RECORD_BYTES];
 };
+
+// ---- the receive call layer: a 128-byte record of qrl_dmr_rx_process (include/qrl_hip.h), what DMRControl::addFrames did with one burst
+// (which of its signals fired) and the stream's call state afterwards (src/DMR/dmrcontrol.cpp:225-665).  The state lives on the device.
+class dmr_call_event_hip {
+public:
+    enum receiver_state : uint8_t { Idle = 0, LateEntry = 1, Audio = 2, Data = 3 };   // RECEIVER_STATE
+    explicit dmr_call_event_hip(const unsigned char* record128) { std::memcpy(_r, record128, QRL_DMR_RX_RECORD_BYTES); }
+    explicit dmr_call_event_hip(const std::vector<unsigned char>& record128) { std::memcpy(_r, record128.data(), QRL_DMR_RX_RECORD_BYTES); }
+    unsigned flags() const { return (unsigned)_r[0] | ((unsigned)_r[1] << 8); }
+    bool validated() const { return flags() & QRL_DMR_RX_VALID; }
+    bool processed() const { return flags() & QRL_DMR_RX_PROCESSED; }                 // its process* call returned true
+    bool voiceHeaderReceived() const { return flags() & QRL_DMR_RX_HEADER_VOICE; }    // headerReceived, from processVoiceHeader
+    bool dataHeaderReceived() const { return flags() & QRL_DMR_RX_HEADER_DATA; }      // headerReceived, from processDataHeader
+    bool terminatorReceived() const { return flags() & QRL_DMR_RX_TERMINATOR; }
+    bool endBeep() const { return flags() & QRL_DMR_RX_END_BEEP; }
+    bool digitalAudio() const { return flags() & QRL_DMR_RX_AUDIO; }                  // the codec bytes: dmr_frame_hip::getVoice of the same slot
+    bool embeddedData() const { return flags() & QRL_DMR_RX_EMBEDDED; }               // an embedded LC completed: processEmbeddedData ran
+    bool talkerAlias() const { return flags() & QRL_DMR_RX_TALKER_ALIAS; }
+    bool gpsInfo() const { return flags() & QRL_DMR_RX_GPS; }
+    bool unknownEmbeddedFLCO() const { return flags() & QRL_DMR_RX_UNKNOWN_FLCO; }
+    uint8_t receiverState() const { return _r[2]; }
+    uint8_t colorCodeRX() const { return _r[3]; }
+    uint8_t FLCO_RX() const { return _r[4]; }
+    uint32_t srcIdRX() const { return le32(8); }
+    uint32_t dstIdRX() const { return le32(12); }
+    uint8_t embeddedFLCO() const { return _r[16]; }
+    void getEmbeddedRawData(unsigned char* data9) const { std::memcpy(data9, _r + 17, 9); }   // CDMREmbeddedData::getRawData
+    uint8_t aliasFormat() const { return _r[26]; }
+    uint8_t aliasLength() const { return _r[27]; }
+    std::vector<unsigned char> aliasBytes() const { return std::vector<unsigned char>(_r + 32, _r + 32 + (_r[28] <= 68 ? _r[28] : 68)); }
+
+private:
+    uint32_t le32(int o) const { return (uint32_t)_r[o] | ((uint32_t)_r[o + 1] << 8) | ((uint32_t)_r[o + 2] << 16) | ((uint32_t)_r[o + 3] << 24); }
+    unsigned char _r[QRL_DMR_RX_RECORD_BYTES];
+};
+
+// The collected alias bytes as UTF-8 text, what DMRControl::processTalkerAlias puts into its signal (src/DMR/dmrcontrol.cpp:578-623):
+//   format 1, 2   the bytes as they are (the reference reads both as UTF-8)
+//   format 0      the 7-bit characters unpacked as DMRUtils::parseISO7bitToISO8bit unpacks them (src/DMR/dmrutils.cpp:102-123: the first byte holds the
+//                 top bit of the first character), the first unpacked character dropped, as the reference drops it, white space trimmed at both ends
+//   format 3      UTF-16, high byte first (DMRUtils::parseUTF16, :81-100), surrogate pairs joined
+// Bytes that are no valid UTF-8 (formats 1, 2) or lone surrogates (format 3) are passed on / replaced by U+FFFD; nothing here fails.
+inline void dmr_utf8_append(std::string& out, uint32_t c)
+{
+    if (c < 0x80) out += (char)c;
+    else if (c < 0x800) { out += (char)(0xC0 | (c >> 6)); out += (char)(0x80 | (c & 0x3F)); }
+    else if (c < 0x10000) { out += (char)(0xE0 | (c >> 12)); out += (char)(0x80 | ((c >> 6) & 0x3F)); out += (char)(0x80 | (c & 0x3F)); }
+    else { out += (char)(0xF0 | (c >> 18)); out += (char)(0x80 | ((c >> 12) & 0x3F)); out += (char)(0x80 | ((c >> 6) & 0x3F)); out += (char)(0x80 | (c & 0x3F)); }
+}
+inline std::string dmr_alias_text(unsigned format, const std::vector<unsigned char>& bytes)
+{
+    std::string out;
+    const size_t size = bytes.size();
+    if (format == 1 || format == 2) return std::string(bytes.begin(), bytes.end());
+    if (format == 3) {
+        for (size_t i = 0; i + 1 < size; i += 2) {
+            uint32_t c = ((uint32_t)bytes[i] << 8) | bytes[i + 1];
+            if (c >= 0xD800 && c < 0xDC00 && i + 3 < size) {
+                const uint32_t lo = ((uint32_t)bytes[i + 2] << 8) | bytes[i + 3];
+                if (lo >= 0xDC00 && lo < 0xE000) { c = 0x10000 + ((c - 0xD800) << 10) + (lo - 0xDC00); i += 2; }
+            }
+            if (c >= 0xD800 && c < 0xE000) c = 0xFFFD;
+            dmr_utf8_append(out, c);
+        }
+        return out;
+    }
+    // format 0
+    const size_t bit7_size = 8 * size / 7;
+    std::vector<unsigned char> conv(bit7_size + 1, 0);
+    unsigned remainder = 0;
+    for (size_t i = 0, j = 1, k = 0; k < bit7_size && i < size; ++i, ++j, ++k) {
+        if (j > 7) j = 1;
+        conv[k] = (unsigned char)((remainder << (8 - j)) | (bytes[i] >> j));
+        const unsigned mask = (1u << j) - 1u;
+        remainder = bytes[i] & mask;
+        if (mask == 0x7F) { ++k; conv[k] = (unsigned char)(remainder & 0x7F); remainder = 0; }
+    }
+    size_t a = bit7_size ? 1 : 0, b = bit7_size;
+    auto space = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13); };
+    while (a < b && space(conv[a])) ++a;
+    while (b > a && space(conv[b - 1])) --b;
+    for (size_t k = a; k < b; ++k) dmr_utf8_append(out, conv[k]);
+    return out;
+}
 
 // ---- the transmit side: writers of the two records of qrl_dmr_l2_encode / qrl_dmr_voice_call_encode (include/qrl_hip.h) ----
 // A 48-byte TX record: what DMRFrame(type) and its setters / constructLCFrame / constructCSBKFrame take in the reference (src/DMR/dmrframe.h).

@@ -73,13 +73,14 @@ struct gr_demod_base_hip::slot {
     uint8_t *d_fr[2] = {nullptr, nullptr}, *h_fr[2] = {nullptr, nullptr}; uint32_t *d_frcnt[2] = {nullptr, nullptr}, *h_frcnt[2] = {nullptr, nullptr};   // framed records of bits A / B
     bool framed = false, bits_copied = true;
     uint8_t *d_l2 = nullptr, *h_l2 = nullptr; bool l2 = false;   // DMR layer 2 records of the call's bursts (set_dmr_l2; device / pinned)
+    uint8_t *d_call = nullptr, *h_call = nullptr; bool call = false;   // DMR call records of the same bursts (set_dmr_call)
     hipEvent_t done = nullptr;
 };
 static constexpr size_t kDmoCap = 16;
 
 gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_chunk)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_chunk(max_chunk & ~(size_t)1),
-      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams), d_boxl(streams)
+      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams), d_boxl(streams), d_boxe(streams)
 {
     d_boxf[0].resize(streams); d_boxf[1].resize(streams); d_boxs.resize(streams);
     for (int k = 0; k < 2; ++k) { d_fbits[k].assign(streams, 0); d_fact[k].assign(streams, 0); }
@@ -96,6 +97,7 @@ gr_demod_base_hip::~gr_demod_base_hip()
 {
     try { flush(); } catch (...) {}
     close();
+    if (d_call_rx) qrl_dmr_rx_destroy(d_call_rx);
     if (d_copy) (void)hipStreamDestroy(static_cast<hipStream_t>(d_copy));
 }
 void gr_demod_base_hip::close()
@@ -127,6 +129,8 @@ void gr_demod_base_hip::close()
             if (p) (void)hipHostFree(p);
         if (sp->d_l2) (void)hipFree(sp->d_l2);
         if (sp->h_l2) (void)hipHostFree(sp->h_l2);
+        if (sp->d_call) (void)hipFree(sp->d_call);
+        if (sp->h_call) (void)hipHostFree(sp->h_call);
         if (sp->done) (void)hipEventDestroy(sp->done);
         delete sp;
         sp = nullptr;
@@ -201,10 +205,26 @@ void gr_demod_base_hip::open()
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_dmocnt), N * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
             hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES), "hipMalloc");
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES), "hipMalloc");
+            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
         }
         hchk(hipEventCreateWithFlags(&sp->done, hipEventDisableTiming), "hipEventCreate");
     }
     d_calls = 0;
+    if (d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // the receiver starts afresh, and so does the call state behind it
+}
+void gr_demod_base_hip::set_dmr_call(bool on, int colour_code, bool promiscuous)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    const qrl_dmr_rx_config c = {colour_code, promiscuous ? 1 : 0};
+    if (!d_call_rx) {
+        if (!on) return;
+        chk(qrl_dmr_rx_create(d_rt.ctx(), (size_t)d_n, &c, &d_call_rx), "qrl_dmr_rx_create");
+    } else {
+        chk(qrl_dmr_rx_set_config(d_call_rx, &c), "qrl_dmr_rx_set_config");
+        if (on && !d_call_on) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // switched back on: nothing of the calls it missed
+    }
+    d_call_on = on;
 }
 void gr_demod_base_hip::set_mode(int mode)   // gr_demod_base::set_mode (src/gr/gr_demod_base.cpp:460-1090): swap the graph, drop what was queued
 {
@@ -219,7 +239,7 @@ void gr_demod_base_hip::set_mode(int mode)   // gr_demod_base::set_mode (src/gr/
         throw std::invalid_argument(std::string("gr_demod_base_hip::set_mode: time-domain settings rejected and reset to the defaults (the mode is open): ") + e.what());
     }
     std::lock_guard<std::mutex> g(d_mutex);
-    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxl[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
+    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxl[s].clear(); d_boxe[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
 }
 void gr_demod_base_hip::enable_device_framing(bool value)
 {
@@ -357,6 +377,11 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
             chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, sl.d_dmo, sl.d_dmocnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.d_l2), "qrl_dmr_l2_decode");
             hchk(hipMemcpyAsync(sl.h_l2, sl.d_l2, N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
         }
+        sl.call = sl.l2 && d_call_on && d_call_rx;
+        if (sl.call) {   // the call layer behind layer 2 on the same stream: every call of this handle goes through the copy stream, so the per-stream state is carried in order
+            chk(qrl_dmr_rx_process(d_call_rx, cs, sl.d_l2, sl.d_dmocnt, kDmoCap, sl.d_call), "qrl_dmr_rx_process");
+            hchk(hipMemcpyAsync(sl.h_call, sl.d_call, N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        }
     }
     sl.rssi_valid = d_rssi_on;
     if (d_rssi_on) {   // rssi_valve open: port 0 of this call through rssi_block, the probe keeps the latest value
@@ -425,6 +450,10 @@ void gr_demod_base_hip::harvest(int which)
                 if (sl.l2) {
                     const uint8_t* r2 = sl.h_l2 + ((size_t)s * kDmoCap + i) * QRL_DMR_L2_RECORD_BYTES;
                     d_boxl[s].emplace_back(r2, r2 + QRL_DMR_L2_RECORD_BYTES);
+                }
+                if (sl.call) {
+                    const uint8_t* r3 = sl.h_call + ((size_t)s * kDmoCap + i) * QRL_DMR_RX_RECORD_BYTES;
+                    d_boxe[s].emplace_back(r3, r3 + QRL_DMR_RX_RECORD_BYTES);
                 }
             }
         }
@@ -617,6 +646,13 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRDecoded(int str
     std::lock_guard<std::mutex> g(d_mutex);
     std::vector<std::vector<unsigned char>> out;
     out.swap(d_boxl[stream]);
+    return out;
+}
+std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRCallEvents(int stream)
+{
+    std::lock_guard<std::mutex> g(d_mutex);
+    std::vector<std::vector<unsigned char>> out;
+    out.swap(d_boxe[stream]);
     return out;
 }
 
@@ -1099,6 +1135,8 @@ bool gr_modem_hip::demodulate(int stream)   // gr_modem.cpp:1019-1117
         if (_ev.dmrFrames) _ev.dmrFrames(stream, frames);
         auto decoded = _gr_demod_base->getDMRDecoded(stream);   // set_dmr_l2: the same bursts validated and FEC'd on the device (DMRFrame::validate / runAudioFEC)
         if (!decoded.empty() && _ev.dmrFramesDecoded) _ev.dmrFramesDecoded(stream, decoded);
+        auto events = _gr_demod_base->getDMRCallEvents(stream);   // set_dmr_call: what DMRControl::addFrames makes of each of them, per-stream state on the device
+        if (!events.empty() && _ev.dmrCallEvents) _ev.dmrCallEvents(stream, events);
         return true;
     }
     const bool two = modem_two_branches(_modem_type_rx);

@@ -81,6 +81,13 @@ public:
     // host/dmr_frame_hip.h reads it) -- what DMRFrame::validate / runAudioFEC and CDMREMB::putData make of it (reference src/DMR/dmrcontrol.cpp:233-248, :630)
     void set_dmr_l2(bool on, bool audio_fec = true) { std::lock_guard<std::recursive_mutex> hg(d_hmutex); d_l2_on = on; d_l2_fec = audio_fec; }
     std::vector<std::vector<unsigned char>> getDMRDecoded(int stream = 0);
+    // DMR receive call layer (qrl_dmr_rx_process), off by default and only while set_dmr_l2 is on: every burst of getDMRData also arrives as a
+    // 128-byte call record (QRL_DMR_RX_RECORD_BYTES; dmr_call_event_hip in host/dmr_frame_hip.h reads it) -- what DMRControl::addFrames does with it
+    // and the stream's call state afterwards (reference src/DMR/dmrcontrol.cpp:225-665).  The state lives on the device and is carried from work()
+    // to work(); set_mode and switching the layer back on start it afresh.  Throws std::runtime_error for a colour code
+    // outside 0..15 (the C ABI's QRL_ERR_ARG).
+    void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false);
+    std::vector<std::vector<unsigned char>> getDMRCallEvents(int stream = 0);
     uint64_t dmr_bursts_dropped() const { return d_dmo_dropped; }        // bursts beyond the 16-per-call record buffer (a call longer than 0.48 s of signal)
     // analogue voice modes (NBFM2500 / NBFM5000 / AM5000 / WBFM): port 1 = audio at 8 ksps (gr_demod_base::getAudio :968-976; caller deletes)
     std::vector<float>* getAudio(int stream = 0);
@@ -155,6 +162,8 @@ private:
     std::vector<std::vector<std::vector<unsigned char>>> d_boxd;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxl;   // layer 2 records, one per record of d_boxd while set_dmr_l2 is on
     bool d_l2_on = false, d_l2_fec = true;
+    std::vector<std::vector<std::vector<unsigned char>>> d_boxe;   // call records, one per record of d_boxd while set_dmr_call is on
+    qrl_dmr_rx* d_call_rx = nullptr; bool d_call_on = false;
     uint64_t d_dmo_dropped = 0;   // DMR bursts found beyond the per-call record buffer (16 per stream and call): not delivered
 };
 
@@ -253,6 +262,7 @@ struct gr_modem_events {
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records)> dmrFrames;     // DMO slicer bursts
     std::function<void(int stream, std::vector<float>* pcm)> pcmAudio;   // analogue modes (gr_modem::pcmAudio); the slot owns pcm
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records80)> dmrFramesDecoded;   // the same bursts through DMR layer 2 (set_dmr_l2)
+    std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records128)> dmrCallEvents;     // and through the call layer (set_dmr_call)
 };
 
 class gr_modem_hip {
@@ -280,6 +290,8 @@ public:
     void set_burst_ip_modem(bool v) { _burst_ip_modem = v; }
     // DMR layer 2 on the device, off by default: dmrFramesDecoded(stream, records80) fires beside dmrFrames (the demodulator's set_dmr_l2)
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
+    // the DMR receive call layer on the device, off by default, behind set_dmr_l2: dmrCallEvents(stream, records128) fires beside dmrFramesDecoded
+    void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false) { if (_gr_demod_base) _gr_demod_base->set_dmr_call(on, colour_code, promiscuous); }
     // DMR voice bursts built on the device from a call descriptor and codec bytes (the modulator's setDMRCall / txDMRVoice): what
     // gr_modem::transmitDMR does through DMRControl::getTxAudio and setDMRData (src/gr_modem.cpp:766-802)
     void setDMRCall(const uint8_t* descriptor40, int stream = 0) { if (_gr_mod_base) _gr_mod_base->setDMRCall(descriptor40, stream); }
