@@ -135,7 +135,7 @@ int qrl_demod_set_dmo_output(qrl_demod* d, uint8_t* frames, size_t cap_frames, u
  * (the history kept for the next call, the edge scratch of this one) then read it on a fourth internal stream beside the front end of the
  * call before instead of in line with it; qrl_demod_sync / qrl_demod_stream_wait cover that stream too.  With value 0 everything that reads
  * the caller's buffer is ordered behind the handle's stream, as qrl_demod_process documents. */
-enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5 };
+enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups; for 2FSK-1k / -2k also the FLL and the FIR stages as the two kernels k_fll + k_2fsk_ff instead of k_2fsk_tail (same results) */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5 };
 int qrl_demod_set_option(qrl_demod* d, int option, int value);
 int qrl_demod_out_caps(const qrl_demod* d, size_t n, size_t* filtered_cap, size_t* constellation_cap, size_t* bits_cap);
 /* analogue voice receivers (QRL_MODEM_NBFM2500 / NBFM5000 / AM5000 / WBFM / USB2500 / LSB2500; replace make_gr_demod_nbfm / _am /

@@ -446,17 +446,20 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         return QRL_OK;
     }
     RingC filt_in = r2;
+    const bool fused_2fsk = fam == F_2FSK && !fm && filt_nt <= 41 && disc_nt <= 41 && symf_nt <= 25;
+    // the FLL and the three FIR stages in one kernel (k_2fsk_tail): gr_demod_2fsk's 41 + 41 + 25 designs; QRL_OPT_FLL_SLIM = 1 keeps the pair of kernels
+    const bool tail_fused = fsk2_tail_eligible(fused_2fsk, 16, fsk2_ff_padded(filt_nt), fsk2_ff_padded(disc_nt), fsk2_ff_padded(symf_nt), fll_slim);
+    FllParams fllp{};
     if (fam == F_2FSK || fam == F_BPSK || (fam == F_QPSK && qpsk_fll)) {
-        FllParams f{};
+        FllParams& f = fllp;
         f.in = r2; f.out = r2l; f.q0 = n2_0; f.count = c2; f.st = fll_st.p;
         f.lower = fll_lo.p; f.upper = fll_up.p; f.nt = fam == F_2FSK ? 16 : 32; f.alpha = fll_alpha; f.beta = fll_beta; f.max_freq = fll_maxf;
         // (slim single-wave FLL workgroups under an 8-wave-workgroup front end were measured in round 3: the front end alone slows from
         //  6.57 to 7.24 ms with 8-wave workgroups and stretches to 8.4 - 9.1 ms when it shares the SIMDs; 9.47 ms per step against 9.29)
         f.slim = fll_slim ? 1 : 0;
-        if (!(QRL_DEV_SKIP & 1)) launch_fll(f, B, cs);
+        if (!(QRL_DEV_SKIP & 1) && !tail_fused) launch_fll(f, B, cs);
         filt_in = r2l;
     }
-    const bool fused_2fsk = fam == F_2FSK && !fm && filt_nt <= 41 && disc_nt <= 41 && symf_nt <= 25;
     if (fam == F_DMR) {
         RingC dem_in = r2;
         if (m17) {   // gr_demod_m17.cpp:60-61,89-90: channel filter behind the resampler, its output is port 0
@@ -479,7 +482,10 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         f.tf = ff_tf.p; f.nf = fsk2_ff_padded(filt_nt); f.up = ff_up.p; f.lo = ff_lo.p; f.nb = fsk2_ff_padded(disc_nt);
         f.ts = ff_ts.p; f.ns = fsk2_ff_padded(symf_nt);
         f.port = fport.p; f.port_cap = fport.cap; f.counts = counts;
-        if (!(QRL_DEV_SKIP & 2)) launch_2fsk_ff(f, B, cs);
+        if (tail_fused) {   // r2l keeps only the call's last windows of y: the history both forms start from
+            Fsk2TailParams t{}; t.fll = fllp; t.ff = f;
+            if (!(QRL_DEV_SKIP & 3)) launch_2fsk_tail(t, B, cs);
+        } else if (!(QRL_DEV_SKIP & 2)) launch_2fsk_ff(f, B, cs);
         if (!overlap) { HIPCHK(hipEventRecord(ev_ff, stream)); HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0)); }
     } else {
         if (!d2f) {

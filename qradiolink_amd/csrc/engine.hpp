@@ -8,6 +8,7 @@
 #include <vector>
 #include "zero_runs.hpp"   // struct ZeroRun
 #include "decim_plan.hpp"  // which decimator a geometry gets, its sizes, the split of a call: host arithmetic free of HIP
+#include "fsk2_tail_geo.hpp"   // k_2fsk_tail: which calls get it, its windows, rings and LDS size (HIP-free as well)
 
 namespace qrl {
 
@@ -175,6 +176,11 @@ struct FllParams { RingC in; RingC out; uint64_t q0; uint32_t count; FllState* s
                    const float2* lower; const float2* upper; int nt; float alpha, beta, max_freq;
                    int slim; };   // 1: single-wave workgroups with a 16-sample window (3 KB LDS): fits beside a CU full of front-end workgroups (overlapped mode)
 void launch_fll(const FllParams& p, int batch, hipStream_t s);
+// k_fll<16> + k_2fsk_ff<11, 11, 7> as one wave-specialised kernel (kernels_2fsk_tail.hip; which calls get it: fsk2_tail_eligible).  fll.out is
+// unused; ff.in is the r2l ring, of which the kernel reads the 104 items in front of q0 and writes the call's last windows of y
+struct Fsk2TailParams { FllParams fll; Fsk2FfParams ff; };
+void launch_2fsk_tail(const Fsk2TailParams& p, int batch, hipStream_t s);
+size_t fsk2_tail_lds_bytes();
 
 struct SymSyncState { uint64_t ii; uint64_t oo; float mu, avg, inst; float x0, x1, x2, d0, d1, d2; };
 struct SymSyncParams {
