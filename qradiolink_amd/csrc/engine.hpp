@@ -29,6 +29,17 @@ int create_role_stream(hipStream_t* s, int priority, const char* role);
 struct RingC { float2* p; uint32_t mask; };   // complex ring, stream stride = mask+1 items
 struct RingF { float* p; uint32_t mask; };
 struct RingB { uint8_t* p; uint32_t mask; };
+// item i of stream b; an item in front of the stream start is zero
+__device__ __forceinline__ float2 ringc_at(const RingC& r, int b, int64_t i)
+{
+    if (i < 0) return make_float2(0.f, 0.f);
+    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
+}
+__device__ __forceinline__ float ringf_at(const RingF& r, int b, int64_t i)
+{
+    if (i < 0) return 0.f;
+    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
+}
 
 // ---- per-stream rotator (qrl_*_set_carrier_offsets) ----
 // A parameter block with rot_acc_s != nullptr carries one NCO per stream: stream b's (acc, inc) are rot_acc_s[b], rot_inc_s[b] and its fine

@@ -1,10 +1,10 @@
 // kernels_2fsk_tail.hip — k_2fsk_tail: fll_band_edge_cc and the three FIR stages behind it (gr_demod_2fsk.cpp:90-104,140-152) in ONE
 // wave-specialised kernel.  The arithmetic is that of k_fll (kernels_loops.hip) and of k_2fsk_ff<11, 11, 7> (kernels_ff.hip), chain for
-// chain; what changes is who runs when and where the hand-off lives:
-//   FLL waves   k_fll's loop body, four lanes per stream, 16 streams per wave.  y goes into the stream's LDS ring instead of an LDS
+// chain -- both take it from fsk2_steps.hpp, as this kernel does; what changes is who runs when and where the hand-off lives:
+//   FLL waves   QRL_FLL_STEP, four lanes per stream, 16 streams per wave.  y goes into the stream's LDS ring instead of an LDS
 //               window that is flushed to the r2l ring in HBM.
 //   FIR waves   one per 16 streams, four threads per stream, each thread four consecutive outputs of a stage (the register window of
-//               ff_window4).  While the FLL waves work on window j they run _filter -> band-pass pair / divide / rail -> _symbol_filter on
+//               window4).  While the FLL waves work on window j they run _filter -> band-pass pair / divide / rail -> _symbol_filter on
 //               window j - 1; a stream's three stages hand over through LDS inside one wave.
 // One __syncthreads() per window (the FLL -> FIR hand-off and the reuse of the y ring); trip counts come from P.count alone.
 // Between calls the chain lives in the r2l ring as before: a call stores its last windows of y there (>= the 104 samples the first
@@ -14,44 +14,16 @@
 #include "devmath.hpp"
 #include "engine.hpp"
 #include "fsk2_tail_geo.hpp"
+#include "fsk2_steps.hpp"
 
 namespace qrl {
 
-template <int CTRL> __device__ __forceinline__ float tl_dpp_quad(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 // LDS hand-over inside one wave: the writes of all lanes in front of the reads behind (LDS operations of a wave complete in order)
 __device__ __forceinline__ void tl_wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ff_window4 on a ring of NW words: acc[r] += sum_k taps[k] * item[4 w + r - k], k = 0 .. 4 NQ - 1, fmaf chain k ascending.  rows: the
-// stream's four rows of NW words; w: the word of this thread's four outputs.  The taps are read from LDS (a 16-byte broadcast read per quad) and the
-// loop is unrolled completely: a FIR wave is alone on its SIMD beside one FLL wave, nothing hides a wait, and scalar tap loads, which share their
-// counter with the LDS reads, cost a full wait per four quads (2.52 ms for the kernel alone against 2.08: docs/KERNELS.md section 28).
-template <int NW, int NQ, typename TapT, typename ItemT, typename Fma>
-__device__ __forceinline__ void tl_window4(const ItemT* __restrict__ rows, int w, const TapT* __restrict__ taps, Fma&& fma4)
-{
-    ItemT cur[4], nxt[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) cur[s] = rows[s * NW + w];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        w = (w == 0 ? NW : w) - 1;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) nxt[s] = rows[s * NW + w];
-        const TapT h0 = taps[4 * q], h1 = taps[4 * q + 1], h2 = taps[4 * q + 2], h3 = taps[4 * q + 3];
-        fma4(h0, cur[0], cur[1], cur[2], cur[3]);
-        fma4(h1, nxt[3], cur[0], cur[1], cur[2]);
-        fma4(h2, nxt[2], nxt[3], cur[0], cur[1]);
-        fma4(h3, nxt[1], nxt[2], nxt[3], cur[0]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) cur[s] = nxt[s];
-    }
 }
 
 template <int NS>
@@ -166,39 +138,8 @@ __global__ __launch_bounds__(Fsk2TailGeo::threads(NS)) void k_2fsk_tail(const Fs
                     float2* const yr = Y + sl * YP + 4 * ys_w;
                     for (int k = 0; k < len; ++k) {
                         const float2 x = xw[k];
-                        // k_fll's sample step: see the comments there
-                        const float2 nco = sincos_rad(phase);  // (cos, sin)
-                        float2 carry;
-                        carry.x = tl_dpp_quad<0x90>(dl[GL - 1].x);
-                        carry.y = tl_dpp_quad<0x90>(dl[GL - 1].y);
-#pragma unroll
-                        for (int t = GL - 1; t > 0; --t) dl[t] = dl[t - 1];
-                        float ur = 0.f, ui = 0.f, lr = 0.f, li = 0.f;
-#pragma unroll
-                        for (int t = GL - 1; t >= 1; --t) {
-                            const float2 v = dl[t];
-                            ur = fmaf(hu[t].x, v.x, ur); ur = fmaf(-hu[t].y, v.y, ur);
-                            ui = fmaf(hu[t].x, v.y, ui); ui = fmaf(hu[t].y, v.x, ui);
-                            lr = fmaf(hl[t].x, v.x, lr); lr = fmaf(-hl[t].y, v.y, lr);
-                            li = fmaf(hl[t].x, v.y, li); li = fmaf(hl[t].y, v.x, li);
-                        }
-                        const float2 y = cmul(x, nco);
-                        *(g == 0 ? &yr[(k & 3) * YW + (k >> 2)] : &dump[tid]) = y;   // item k of the window: row k & 3, word k >> 2
-                        dl[0] = g == 0 ? y : carry;
-                        {
-                            const float2 v = dl[0];
-                            ur = fmaf(hu[0].x, v.x, ur); ur = fmaf(-hu[0].y, v.y, ur);
-                            ui = fmaf(hu[0].x, v.y, ui); ui = fmaf(hu[0].y, v.x, ui);
-                            lr = fmaf(hl[0].x, v.x, lr); lr = fmaf(-hl[0].y, v.y, lr);
-                            li = fmaf(hl[0].x, v.y, li); li = fmaf(hl[0].y, v.x, li);
-                        }
-                        ur = ur + tl_dpp_quad<0xB1>(ur); ui = ui + tl_dpp_quad<0xB1>(ui); lr = lr + tl_dpp_quad<0xB1>(lr); li = li + tl_dpp_quad<0xB1>(li);
-                        ur = ur + tl_dpp_quad<0x4E>(ur); ui = ui + tl_dpp_quad<0x4E>(ui); lr = lr + tl_dpp_quad<0x4E>(lr); li = li + tl_dpp_quad<0x4E>(li);
-                        const float error = (lr * lr + li * li) - (ur * ur + ui * ui);
-                        freq = freq + P.fll.beta * error;
-                        phase = phase + freq + P.fll.alpha * error;
-                        phase = phase_wrap(phase);
-                        freq = __builtin_fminf(__builtin_fmaxf(freq, -P.fll.max_freq), P.fll.max_freq);
+                        // item k of the window: row k & 3, word k >> 2
+                        QRL_FLL_STEP(GL, P.fll, x, g, g == 0 ? &yr[(k & 3) * YW + (k >> 2)] : &dump[tid], phase, freq, dl, hu, hl)
                     }
                 }
                 ys_w = ys_w == G::YWIN - 1 ? 0 : ys_w + 1;
@@ -234,14 +175,9 @@ __global__ __launch_bounds__(Fsk2TailGeo::threads(NS)) void k_2fsk_tail(const Fs
                 }
             }
             {   // stage 1: f[n] = sum tf[k] y[n - k]
-                float2 a[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-                tl_window4<YW, G::QF>(Ys, 4 * ys_r + ft, tap_f,
-                                      [&](float h, const float2& x0, const float2& x1, const float2& x2, const float2& x3) {
-                                          a[0].x = fmaf(h, x0.x, a[0].x); a[0].y = fmaf(h, x0.y, a[0].y);
-                                          a[1].x = fmaf(h, x1.x, a[1].x); a[1].y = fmaf(h, x1.y, a[1].y);
-                                          a[2].x = fmaf(h, x2.x, a[2].x); a[2].y = fmaf(h, x2.y, a[2].y);
-                                          a[3].x = fmaf(h, x3.x, a[3].x); a[3].y = fmaf(h, x3.y, a[3].y);
-                                      });
+                AccRealCplx acc;
+                window4<YW, true, G::QF, true>(Ys, 4 * ys_r + ft, 0, tap_f, acc);
+                float2 (&a)[4] = acc.a;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (n0 + r < 0) a[r] = make_float2(0.f, 0.f);
@@ -254,35 +190,20 @@ __global__ __launch_bounds__(Fsk2TailGeo::threads(NS)) void k_2fsk_tail(const Fs
                 }
             }
             tl_wave_sync();
-            if (jw >= -2) {   // stage 2: conjugate tap pair (k_disc_2fsk): A = sum a f, B = sum b f; d = rail(|u| / |l|) - 1
-                float ar[4] = {0.f, 0.f, 0.f, 0.f}, ai[4] = {0.f, 0.f, 0.f, 0.f}, br[4] = {0.f, 0.f, 0.f, 0.f}, bi[4] = {0.f, 0.f, 0.f, 0.f};
-                tl_window4<FW, G::QB>(Fs, 4 * fs_r + ft, tap_b,
-                                      [&](const float2 h, const float2& x0, const float2& x1, const float2& x2, const float2& x3) {
-                                          const float2 xs[4] = {x0, x1, x2, x3};
-#pragma unroll
-                                          for (int r = 0; r < 4; ++r) {
-                                              ar[r] = fmaf(h.x, xs[r].x, ar[r]); ai[r] = fmaf(h.x, xs[r].y, ai[r]);
-                                              br[r] = fmaf(h.y, xs[r].x, br[r]); bi[r] = fmaf(h.y, xs[r].y, bi[r]);
-                                          }
-                                      });
+            if (jw >= -2) {   // stage 2: conjugate tap pair (AccConjPair): A = sum a f, B = sum b f; d = rail(|u| / |l|) - 1
+                AccConjPair<4> acc;
+                window4<FW, true, G::QB, true>(Fs, 4 * fs_r + ft, 0, tap_b, acc);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float ur = ar[r] - bi[r], ui = ai[r] + br[r], lr = ar[r] + bi[r], li = ai[r] - br[r];
-                    const float mu = sqrtf(ur * ur + ui * ui);
-                    const float ml = sqrtf(lr * lr + li * li);
-                    float v = mu / ml;
-                    if (!(v >= 0.0f)) v = 0.0f;   // rail_ff lower bound; NaN (0/0) -> 0
-                    if (v > 2.0f) v = 2.0f;
-                    Ds[r * DW + 4 * fs_r + ft] = (n0 + r < 0) ? 0.f : v + (-1.0f);
+                    const float d = acc.disc(r);   // unconditional: a select, not a branch
+                    Ds[r * DW + 4 * fs_r + ft] = (n0 + r < 0) ? 0.f : d;
                 }
                 tl_wave_sync();
             }
             if (jw >= 0) {    // stage 3: o[n] = sum ts[k] d[n - k]
-                float a[4] = {0.f, 0.f, 0.f, 0.f};
-                tl_window4<DW, G::QS>(Ds, 4 * fs_r + ft, tap_s,
-                                      [&](float h, float x0, float x1, float x2, float x3) {
-                                          a[0] = fmaf(h, x0, a[0]); a[1] = fmaf(h, x1, a[1]); a[2] = fmaf(h, x2, a[2]); a[3] = fmaf(h, x3, a[3]);
-                                      });
+                AccRealReal acc;
+                window4<DW, true, G::QS, true>(Ds, 4 * fs_r + ft, 0, tap_s, acc);
+                const float (&a)[4] = acc.a;
                 if ((jw & 1) == 0 && jw != nwin - 1) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hold[r] = a[r];

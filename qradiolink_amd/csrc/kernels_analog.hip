@@ -13,16 +13,6 @@
 
 namespace qrl {
 
-__device__ __forceinline__ float2 an_ringc_at(const RingC& r, int b, int64_t i)
-{
-    if (i < 0) return make_float2(0.f, 0.f);
-    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
-}
-__device__ __forceinline__ float an_ringf_at(const RingF& r, int b, int64_t i)
-{
-    if (i < 0) return 0.f;
-    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
-}
 // items the stage behind the gate has produced once g items passed it: rational resampler I:D, or (I == 0) the cessb stretcher,
 // which emits whole chunks of 1024 and reads two items ahead
 __device__ __forceinline__ uint64_t an_decim_count(uint64_t n, int I, int D)
@@ -48,7 +38,7 @@ __global__ __launch_bounds__(256) void k_an_fir_ccc(const FirCccParams P)
     const int kmax = n + 1 < (int64_t)P.nt ? (int)(n + 1) : P.nt;
     for (int k = 0; k < kmax; ++k) {
         const float2 h = an_taps[k];
-        const float2 x = an_ringc_at(P.in, b, n - k);
+        const float2 x = ringc_at(P.in, b, n - k);
         ar = fmaf(h.x, x.x, ar);
         ar = fmaf(-h.y, x.y, ar);
         ai = fmaf(h.x, x.y, ai);
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(64) void k_an_gate(const AnGateParams P, int batch)
     constexpr int AN_PF = 16;
     for (uint32_t t0 = 0; t0 < P.count; t0 += AN_PF) {
 #pragma unroll
-    for (int k = 0; k < AN_PF; ++k) xq[k][threadIdx.x] = an_ringc_at(P.in, b, (int64_t)(P.q0 + t0 + k));   // (ring reads are in bounds for any index; a lane only reads back its own column)
+    for (int k = 0; k < AN_PF; ++k) xq[k][threadIdx.x] = ringc_at(P.in, b, (int64_t)(P.q0 + t0 + k));   // (ring reads are in bounds for any index; a lane only reads back its own column)
     for (int k = 0; k < AN_PF; ++k) {
         if (t0 + k >= P.count) break;
         const float2 x = xq[k][threadIdx.x];
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(256) void k_an_resamp(const AnResampParams P)
     float a = 0.f;
     for (int j = 0; ph + j * P.I < P.nt; ++j) {
         if (c - j < 0) break;
-        a = fmaf(an_rt[ph + j * P.I], an_ringf_at(P.in, b, c - j), a);
+        a = fmaf(an_rt[ph + j * P.I], ringf_at(P.in, b, c - j), a);
     }
     P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)q & P.out.mask)] = a;
     if (P.port && t < P.port_cap) P.port[(size_t)b * P.port_cap + t] = a;
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(256) void k_an_fir(const AnFirParams P)
     if (q >= q1) return;
     float a = 0.f;
     const int kmax = q + 1 < (uint64_t)P.nt ? (int)(q + 1) : P.nt;
-    for (int k = 0; k < kmax; ++k) a = fmaf(an_ft[k], an_ringf_at(P.in, b, (int64_t)q - k), a);
+    for (int k = 0; k < kmax; ++k) a = fmaf(an_ft[k], ringf_at(P.in, b, (int64_t)q - k), a);
     if (P.out.p) P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)q & P.out.mask)] = a;
     if (P.port && t < P.port_cap) P.port[(size_t)b * P.port_cap + t] = a;
 }
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(256) void k_an_stretch(const AnStretchParams P)
     float e = 0.0f;
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
-        const float2 x = an_ringc_at(P.in, b, (int64_t)q + j);
+        const float2 x = ringc_at(P.in, b, (int64_t)q + j);
         const float m = sqrtf(x.x * x.x + x.y * x.y);
         e = m > e ? m : e;
     }
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(256) void k_an_stretch(const AnStretchParams P)
     h = h - 1.0f;
     h = h * 2.0f;
     h = h + 1.0f;
-    const float2 x = an_ringc_at(P.in, b, (int64_t)q);
+    const float2 x = ringc_at(P.in, b, (int64_t)q);
     P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)q & P.out.mask)] = (x.x / h) * P.level;
 }
 void launch_an_stretch(const AnStretchParams& p, uint32_t max_out, int batch, hipStream_t s)
@@ -267,7 +257,7 @@ __global__ __launch_bounds__(64) void k_an_ctcss(const CtcssParams P, int batch)
     c.g2_prev = c.g2;
     float* out = P.out.p + (size_t)b * (P.out.mask + 1u);
     for (uint64_t q = q0; q < q1; ++q) {
-        const float x = an_ringf_at(P.in, b, (int64_t)q);
+        const float x = ringf_at(P.in, b, (int64_t)q);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             float y = x + P.wr[k] * c.d1[k];
@@ -317,7 +307,7 @@ __global__ __launch_bounds__(64) void k_an_deemph(const AnDeemphParams P, int ba
     if (P.cs) { q0 = P.cs[b].g2_prev; q1 = P.cs[b].g2; }
     float x1 = st.de_x; double y1 = st.de_y;
     for (uint64_t q = q0; q < q1; ++q) {
-        const float x = an_ringf_at(P.in, b, (int64_t)q);
+        const float x = ringf_at(P.in, b, (int64_t)q);
         double acc = P.ff0 * (double)x;
         acc += P.ff1 * (double)x1;
         acc += P.fb1 * y1;
@@ -474,7 +464,7 @@ __global__ __launch_bounds__(256) void k_am_stretch(const AmStretchParams P)
     float e = 0.0f;
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
-        const float2 x = an_ringc_at(P.in, b, (int64_t)q + j);
+        const float2 x = ringc_at(P.in, b, (int64_t)q + j);
         const float m = sqrtf(x.x * x.x + x.y * x.y);
         e = m > e ? m : e;
     }
@@ -483,7 +473,7 @@ __global__ __launch_bounds__(256) void k_am_stretch(const AmStretchParams P)
     h = h - 1.0f;
     h = h * 2.0f;
     h = h + 1.0f;
-    const float2 x = an_ringc_at(P.in, b, (int64_t)q);
+    const float2 x = ringc_at(P.in, b, (int64_t)q);
     P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)q & P.out.mask)] = make_float2(x.x / h, x.y / h);
 }
 void launch_am_stretch(const AmStretchParams& p, int batch, hipStream_t s)

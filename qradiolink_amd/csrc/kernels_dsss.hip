@@ -12,12 +12,6 @@
 
 namespace qrl {
 
-__device__ __forceinline__ float2 ring_at(const RingC& r, int b, int64_t i)
-{
-    if (i < 0) return make_float2(0.f, 0.f);
-    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
-}
-
 template <int MODE>
 __global__ __launch_bounds__(64) void k_dsss_loop(const DsssLoopParams P, int batch)
 {
@@ -30,7 +24,7 @@ __global__ __launch_bounds__(64) void k_dsss_loop(const DsssLoopParams P, int ba
     float2* out = P.out.p + (size_t)b * (P.out.mask + 1u);
     for (uint32_t t = 0; t < P.count; ++t) {
         const uint64_t n = P.q0 + t;
-        const float2 x = ring_at(P.in, b, (int64_t)n);
+        const float2 x = ringc_at(P.in, b, (int64_t)n);
         float2 o;
         if (MODE == 0) {   // costas_loop_cc, order 2, SNR-weighted error (contract: oracle orc_costas)
             const float2 nco = sincos_rad(-st.phase);
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(64) void k_dsss_mf(const DsssMfParams P)
     const uint64_t I = P.i0 + blockIdx.x;
     for (int k = lane; k < DS_NT; k += 64) taps[k] = P.taps[k];
     const int64_t P0 = (int64_t)DS_L * ((int64_t)I - 2) + 1;      // window j covers x[P0 + j .. P0 + j + 600): history 325 = 324 old items + the new one
-    for (int i = lane; i < DS_L + DS_NT - 1; i += 64) xs[i] = ring_at(P.in, b, P0 + i);
+    for (int i = lane; i < DS_L + DS_NT - 1; i += 64) xs[i] = ringc_at(P.in, b, P0 + i);
     __syncthreads();
     float best = 0.0f; float2 bv = make_float2(0.f, 0.f); int bj = 0x7fffffff;
     for (int j = lane; j < DS_L; j += 64) {
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(64) void k_dsss_tail(const DsssTailParams P, int ba
         float2 y = make_float2(0.f, 0.f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const float2 x = ring_at(P.in, b, (int64_t)(st.ii + k));
+            const float2 x = ringc_at(P.in, b, (int64_t)(st.ii + k));
             y.x = fmaf(t[7 - k], x.x, y.x);
             y.y = fmaf(t[7 - k], x.y, y.y);
         }

@@ -7,20 +7,10 @@
 //   k_disc_2fsk  2x fft_filter_ccc + complex_to_mag + divide + rail(0,2) + add(-1) (gr_demod_2fsk.cpp:94-102,140-149)
 #include "devmath.hpp"
 #include "engine.hpp"
+#include "fsk2_steps.hpp"
 #include <cstdlib>
 
 namespace qrl {
-
-__device__ __forceinline__ float2 ringc_at(const RingC& r, int b, int64_t i)
-{
-    if (i < 0) return make_float2(0.f, 0.f);
-    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
-}
-__device__ __forceinline__ float ringf_at(const RingF& r, int b, int64_t i)
-{
-    if (i < 0) return 0.f;
-    return r.p[(size_t)b * (r.mask + 1u) + ((uint32_t)i & r.mask)];
-}
 
 __global__ __launch_bounds__(256) void k_fir_ccf(const FirCcfParams P)
 {
@@ -176,22 +166,13 @@ __global__ __launch_bounds__(256) void k_disc_2fsk(const Disc2fskParams P)
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= P.count) return;
     const int64_t n = (int64_t)(P.q0 + t);
-    // the two filters are a conjugate pair (the engine checks it bit for bit): h = a + j b, A = sum a x, B = sum b x (real taps, k
-    // ascending), upper = (A.re - B.im, A.im + B.re), lower = (A.re + B.im, A.im - B.re) -- oracle orc_fir_ccc_conj_pair
-    float ar = 0.f, ai = 0.f, br = 0.f, bi = 0.f;
+    // the conjugate tap pair of AccConjPair (fsk2_steps.hpp), one output per thread
+    AccConjPair<1> acc;
     for (int k = 0; k < P.nt; ++k) {
         const float2 x = ringc_at(P.in, b, n - k);
-        const float2 h = P.up[k];
-        ar = fmaf(h.x, x.x, ar); ai = fmaf(h.x, x.y, ai);
-        br = fmaf(h.y, x.x, br); bi = fmaf(h.y, x.y, bi);
+        acc.tap(P.up[k], x, 0);
     }
-    const float ur = ar - bi, ui = ai + br, lr = ar + bi, li = ai - br;
-    const float mu = sqrtf(ur * ur + ui * ui);
-    const float ml = sqrtf(lr * lr + li * li);
-    float r = mu / ml;
-    if (!(r >= 0.0f)) r = 0.0f;   // rail_ff lower bound; NaN (0/0) -> 0
-    if (r > 2.0f) r = 2.0f;
-    P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)n & P.out.mask)] = r + (-1.0f);
+    P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)n & P.out.mask)] = acc.disc(0);
 }
 // gr_demod_4fsk non-FM branch (gr_demod_4fsk.cpp:110-127,165-176 + gr_4fsk_discriminator::work, gr_4fsk_discriminator.cpp:17-44):
 // four complex band-pass filters -> complex_to_mag -> strict arg-max -> one of (+-0.707107, +-0.707107), else 0
@@ -237,44 +218,10 @@ void launch_disc_2fsk(const Disc2fskParams& p, int batch, hipStream_t s)
 //   _filter (fft_filter_ccf) -> {_upper_filter, _lower_filter} (fft_filter_ccc) -> complex_to_mag x2 -> divide ->
 //   rail(0,2) -> add_const(-1) -> _symbol_filter (fft_filter_fff)
 // One workgroup = FF_T consecutive outputs of one stream; the three FIR stages run out of LDS with the intermediate
-// halos recomputed (6 % extra MACs).  Every thread owns FOUR consecutive outputs of a stage and slides a register
-// window over the taps (one 8-byte LDS read per tap for four outputs instead of four); tiles are stored TRANSPOSED
-// by 4 (item i at row i & 3, word (i >> 2) + 1) so that the lanes of a wave read consecutive LDS words.  Taps are
-// wave-uniform (scalar loads) and zero padded to 4A + 1 entries: every output is the same fmaf chain (k ascending) as
-// the unfused kernels followed by zero taps, which leave the value untouched.  Items at negative absolute index are
-// zero, exactly as a ring read in front of the stream start returns zero.
+// halos recomputed (6 % extra MACs).  Every thread owns FOUR consecutive outputs of a stage (window4, fsk2_steps.hpp); tiles are
+// stored TRANSPOSED by 4 (item i at row i & 3, word (i >> 2) + 1).  Taps are wave-uniform (scalar loads) and zero padded to 4A + 1
+// entries.  Items at negative absolute index are zero, exactly as a ring read in front of the stream start returns zero.
 constexpr int FF_PL = 280, FF_PF = 264, FF_PD = 264;   // row pitches (words); 8-byte rows: pitch = 8 or 24 (mod 32)
-
-// acc[r] += sum_k taps[k] * tile[4 t + r + 4 A - k], k = 0 .. 4 nq - 1, fmaf chain k ascending (CPLX: complex taps)
-// NQ > 0: the number of tap quads is a compile-time constant and the loop is unrolled by four -- the (wave-uniform, scalar) tap loads of four
-// quads are issued together, one wait per sixteen taps; NQ = 0: run-time count, one scalar load and one wait per quad.  The scalar loads share
-// their counter with the LDS reads, so they cannot be prefetched across a quad's LDS wait: at C1's geometry (41 + 41 + 25 taps) the per-quad
-// form waits 29 times per thread, 1 011 us alone against 855 (a complete unroll: 914 us and 105 VGPRs).  profiles/r06_c1_helper_stream.log
-template <int PITCH, int NQ, typename TapT, typename ItemT, typename Fma>
-__device__ __forceinline__ void ff_window4(const ItemT* __restrict__ tile, int w, int nq_rt, const TapT* __restrict__ taps, Fma&& fma4)
-{
-    ItemT cur[4], nxt[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) cur[s] = tile[s * PITCH + w];
-    auto quad = [&](int q) {
-        --w;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) nxt[s] = tile[s * PITCH + w];   // word w - 1: subs 1..3 are this step's u < 0 samples
-        const TapT h0 = taps[4 * q], h1 = taps[4 * q + 1], h2 = taps[4 * q + 2], h3 = taps[4 * q + 3];
-        fma4(h0, cur[0], cur[1], cur[2], cur[3]);     // e = 0: output r takes sample u = r
-        fma4(h1, nxt[3], cur[0], cur[1], cur[2]);     // e = 1: u = r - 1
-        fma4(h2, nxt[2], nxt[3], cur[0], cur[1]);     // e = 2: u = r - 2
-        fma4(h3, nxt[1], nxt[2], nxt[3], cur[0]);     // e = 3: u = r - 3
-#pragma unroll
-        for (int s = 0; s < 4; ++s) cur[s] = nxt[s];
-    };
-    if constexpr (NQ > 0) {
-#pragma unroll 4
-        for (int q = 0; q < NQ; ++q) quad(q);
-    } else {
-        for (int q = 0; q < nq_rt; ++q) quad(q);
-    }
-}
 
 template <int NQF, int NQB, int NQS>   // tap quads of the three filters ((padded taps - 1) / 4 + 1), or 0, 0, 0 = run-time counts
 __global__ __launch_bounds__(256) void k_2fsk_ff(const Fsk2FfParams P)
@@ -304,72 +251,28 @@ __global__ __launch_bounds__(256) void k_2fsk_ff(const Fsk2FfParams P)
     }
     __syncthreads();
     {   // stage 1: f[j] = sum tf[k] l[j + hf - k], j = 4 tid + r
-        float2 a[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-        ff_window4<FF_PL, NQF>(lt, tid + (hf >> 2) + 1, (hf >> 2) + 1, P.tf,
-                          [&](float h, const float2& x0, const float2& x1, const float2& x2, const float2& x3) {
-                              a[0].x = fmaf(h, x0.x, a[0].x); a[0].y = fmaf(h, x0.y, a[0].y);
-                              a[1].x = fmaf(h, x1.x, a[1].x); a[1].y = fmaf(h, x1.y, a[1].y);
-                              a[2].x = fmaf(h, x2.x, a[2].x); a[2].y = fmaf(h, x2.y, a[2].y);
-                              a[3].x = fmaf(h, x3.x, a[3].x); a[3].y = fmaf(h, x3.y, a[3].y);
-                          });
+        AccRealCplx acc;
+        window4<FF_PL, false, NQF, false>(lt, tid + (hf >> 2) + 1, (hf >> 2) + 1, P.tf, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const bool neg = n0t - (hb + hs) + 4 * tid + r < 0;
-            ft[r * FF_PF + tid + 1] = neg ? make_float2(0.f, 0.f) : a[r];
+            ft[r * FF_PF + tid + 1] = neg ? make_float2(0.f, 0.f) : acc.a[r];
         }
     }
     __syncthreads();
     if (4 * tid < nd) {   // stage 2: u/l[j] = sum up/lo[k] f[j + hb - k]; d = rail(|u| / |l|) - 1
-        // conjugate tap pair (see k_disc_2fsk): A = sum a x, B = sum b x with the real and imaginary parts of the UPPER filter's taps
-        float ar[4] = {0.f, 0.f, 0.f, 0.f}, ai[4] = {0.f, 0.f, 0.f, 0.f}, br[4] = {0.f, 0.f, 0.f, 0.f}, bi[4] = {0.f, 0.f, 0.f, 0.f};
-        const int nq = NQB > 0 ? NQB : (hb >> 2) + 1;
-        int w = tid + (hb >> 2) + 1;
-        float2 cur[4], nxt[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) cur[s] = ft[s * FF_PF + w];
-        auto step = [&](const float2 h, const float2& x0, const float2& x1, const float2& x2, const float2& x3) {
-            const float2 xs[4] = {x0, x1, x2, x3};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                ar[r] = fmaf(h.x, xs[r].x, ar[r]); ai[r] = fmaf(h.x, xs[r].y, ai[r]);
-                br[r] = fmaf(h.y, xs[r].x, br[r]); bi[r] = fmaf(h.y, xs[r].y, bi[r]);
-            }
-        };
-        auto quad = [&](int q) {
-            --w;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) nxt[s] = ft[s * FF_PF + w];
-            step(P.up[4 * q], cur[0], cur[1], cur[2], cur[3]);
-            step(P.up[4 * q + 1], nxt[3], cur[0], cur[1], cur[2]);
-            step(P.up[4 * q + 2], nxt[2], nxt[3], cur[0], cur[1]);
-            step(P.up[4 * q + 3], nxt[1], nxt[2], nxt[3], cur[0]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) cur[s] = nxt[s];
-        };
-        if constexpr (NQB > 0) {
-#pragma unroll 4
-            for (int q = 0; q < NQB; ++q) quad(q);
-        } else {
-            for (int q = 0; q < nq; ++q) quad(q);
-        }
+        AccConjPair<4> acc;
+        window4<FF_PF, false, NQB, false>(ft, tid + (hb >> 2) + 1, (hb >> 2) + 1, P.up, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float ur = ar[r] - bi[r], ui = ai[r] + br[r], lr = ar[r] + bi[r], li = ai[r] - br[r];
-            const float mu = sqrtf(ur * ur + ui * ui);
-            const float ml = sqrtf(lr * lr + li * li);
-            float v = mu / ml;
-            if (!(v >= 0.0f)) v = 0.0f;   // rail_ff lower bound; NaN (0/0) -> 0
-            if (v > 2.0f) v = 2.0f;
-            dt[r * FF_PD + tid + 1] = (n0t - hs + 4 * tid + r < 0) ? 0.f : v + (-1.0f);
+            const float d = acc.disc(r);   // unconditional: a select, not a branch
+            dt[r * FF_PD + tid + 1] = (n0t - hs + 4 * tid + r < 0) ? 0.f : d;
         }
     }
     __syncthreads();
     if (4 * tid < T) {   // stage 3: y[o] = sum ts[k] d[o + hs - k]
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        ff_window4<FF_PD, NQS>(dt, tid + (hs >> 2) + 1, (hs >> 2) + 1, P.ts,
-                          [&](float h, float x0, float x1, float x2, float x3) {
-                              a[0] = fmaf(h, x0, a[0]); a[1] = fmaf(h, x1, a[1]); a[2] = fmaf(h, x2, a[2]); a[3] = fmaf(h, x3, a[3]);
-                          });
+        AccRealReal acc;
+        window4<FF_PD, false, NQS, false>(dt, tid + (hs >> 2) + 1, (hs >> 2) + 1, P.ts, acc);
         const uint32_t t0 = blockIdx.x * (uint32_t)T + 4u * tid;   // output index inside this call
         if (t0 == 0 && P.counts) P.counts[b * 4 + 0] = P.count;
         const int wf = tid + ((hb + hs) >> 2) + 1;
@@ -378,7 +281,7 @@ __global__ __launch_bounds__(256) void k_2fsk_ff(const Fsk2FfParams P)
             const uint32_t t = t0 + r;
             if (t < P.count) {
                 const int64_t n = n0t + 4 * tid + r;
-                P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)n & P.out.mask)] = a[r];
+                P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)n & P.out.mask)] = acc.a[r];
                 if (P.port && t < P.port_cap) P.port[(size_t)b * P.port_cap + t] = ft[r * FF_PF + wf];
             }
         }

@@ -8,6 +8,7 @@
 //                 gr_demod_gmsk.cpp:89-101): TED (mod-)M&M, MMSE 8-tap interpolator, PI clock loop
 #include "devmath.hpp"
 #include "engine.hpp"
+#include "fsk2_steps.hpp"
 
 namespace qrl {
 
@@ -36,18 +37,7 @@ namespace qrl {
 #ifndef QRL_FLL_TH
 #define QRL_FLL_TH 256   // threads per workgroup of the default geometry (4 lanes per stream): 256 = one wave per SIMD and CU at 16 k streams
 #endif
-template <int CTRL> __device__ __forceinline__ float dpp_quad(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-// FOUR LANES PER STREAM.  The two NT-tap band-edge filters are the bulk of the arithmetic but only their newest link sits on
-// the recursion's critical path, so the delay line is cut into 4 groups of NT/4 samples, one per lane of a quad: every lane
-// runs the short oldest-first fmaf chains of its group, the delay line shifts through the quad with one DPP move, and the
-// partial sums meet by two DPP butterflies as (p0 + p1) + (p2 + p3) -- the summation contract of oracle orc_fll_band_edge.
-// The NCO / loop update is computed redundantly by the four lanes (bit-identical inputs, bit-identical results).  Compared with
-// the lane-per-stream kernel there are 4x more waves (one per SIMD instead of one per CU at 16k streams) with ~3x shorter
-// instruction streams.
+// FOUR LANES PER STREAM, the sample step and its summation contract: QRL_FLL_STEP (fsk2_steps.hpp)
 template <int NT, int FLL_TH, int FLL_CH>
 __global__ __launch_bounds__(FLL_TH) void k_fll(const FllParams P, int batch)
 {
@@ -102,45 +92,8 @@ __global__ __launch_bounds__(FLL_TH) void k_fll(const FllParams P, int batch)
         if (active) {
             for (int k = 0; k < len; ++k) {
                 const float2 x = win[sl][k];
-                // critical path: NCO -> derotated sample -> newest link of lane 0 -> butterflies -> loop update.  The body is ONE
-                // basic block (no lane-dependent branch: lanes 1-3 of a quad send their copy of y to a dump slot), so the scheduler
-                // can fill the dependency gaps of this chain with the independent work below.
-                const float2 nco = sincos_rad(phase);  // (cos, sin)
-                // independent of this sample's NCO: shift the delay line through the quad -- lane g takes the oldest entry of lane
-                // g - 1 -- and run the oldest-first chains over everything but the newest slot
-                float2 carry;
-                carry.x = dpp_quad<0x90>(dl[GL - 1].x);
-                carry.y = dpp_quad<0x90>(dl[GL - 1].y);
-#pragma unroll
-                for (int t = GL - 1; t > 0; --t) dl[t] = dl[t - 1];
-                float ur = 0.f, ui = 0.f, lr = 0.f, li = 0.f;
-#pragma unroll
-                for (int t = GL - 1; t >= 1; --t) {
-                    const float2 v = dl[t];
-                    ur = fmaf(hu[t].x, v.x, ur); ur = fmaf(-hu[t].y, v.y, ur);
-                    ui = fmaf(hu[t].x, v.y, ui); ui = fmaf(hu[t].y, v.x, ui);
-                    lr = fmaf(hl[t].x, v.x, lr); lr = fmaf(-hl[t].y, v.y, lr);
-                    li = fmaf(hl[t].x, v.y, li); li = fmaf(hl[t].y, v.x, li);
-                }
-                const float2 y = cmul(x, nco);
-                *(g == 0 ? &win[sl][k] : &dump[tid]) = y;   // output staged in place (lane 0 of the quad), flushed coalesced below
-                dl[0] = g == 0 ? y : carry;
-                {
-                    const float2 v = dl[0];
-                    ur = fmaf(hu[0].x, v.x, ur); ur = fmaf(-hu[0].y, v.y, ur);
-                    ui = fmaf(hu[0].x, v.y, ui); ui = fmaf(hu[0].y, v.x, ui);
-                    lr = fmaf(hl[0].x, v.x, lr); lr = fmaf(-hl[0].y, v.y, lr);
-                    li = fmaf(hl[0].x, v.y, li); li = fmaf(hl[0].y, v.x, li);
-                }
-                // (p0 + p1) + (p2 + p3): quad butterflies (lane ^ 1, then lane ^ 2); float addition commutes, so all four
-                // lanes end up with the same bits
-                ur = ur + dpp_quad<0xB1>(ur); ui = ui + dpp_quad<0xB1>(ui); lr = lr + dpp_quad<0xB1>(lr); li = li + dpp_quad<0xB1>(li);
-                ur = ur + dpp_quad<0x4E>(ur); ui = ui + dpp_quad<0x4E>(ui); lr = lr + dpp_quad<0x4E>(lr); li = li + dpp_quad<0x4E>(li);
-                const float error = (lr * lr + li * li) - (ur * ur + ui * ui);
-                freq = freq + P.beta * error;
-                phase = phase + freq + P.alpha * error;
-                phase = phase_wrap(phase);
-                freq = __builtin_fminf(__builtin_fmaxf(freq, -P.max_freq), P.max_freq);   // == the two-sided clamp for finite freq
+                // output staged in place (lane 0 of the quad), flushed coalesced below
+                QRL_FLL_STEP(GL, P, x, g, g == 0 ? &win[sl][k] : &dump[tid], phase, freq, dl, hu, hl)
             }
         }
         __syncthreads();
