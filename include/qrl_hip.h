@@ -717,18 +717,30 @@ int qrl_dmr_voice_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* cal
  *   endBeep | _AUDIO digitalAudio: the 27 codec bytes are bytes 53..79 of the layer-2 record of the same slot | _EMBEDDED an embedded LC
  *   completed and was valid, processEmbeddedData ran | _TALKER_ALIAS talkerAlias fired | _GPS gpsInfo fired | _UNKNOWN_FLCO an embedded FLCO
  *   the reference only logs
- *   | 2 receiver state after the burst (RECEIVER_STATE: 0 idle, 1 late entry, 2 audio, 3 data) | 3 _color_code_RX | 4 _FLCO_RX | 5..7 zero
+ *   | 2 receiver state after the burst (RECEIVER_STATE: 0 idle, 1 late entry, 2 audio, 3 data) | 3 _color_code_RX | 4 _FLCO_RX | 5 _timeslot_RX | 6..7 zero
  *   | 8..11 _srcId_RX, 12..15 _dstId_RX, little endian
  *   | 16 FLCO of the embedded LC, 17..25 its nine getRawData bytes (with _EMBEDDED, else zero)
  *   | 26 talker-alias format (0 7-bit, 1 ISO 8-bit, 2 UTF-8, 3 UTF-16BE), 27 its length field, 28 the number of bytes collected (at most 68:
  *   blocks are only appended to an incomplete alias, and the largest need is 2 x 31), 32..99 those bytes: the header's six (format 0: first
  *   the low bit of its options byte, as a byte), then seven per block (with _TALKER_ALIAS, else zero) | 29..31, 100..127 zero.
  * Turning the alias bytes into text, the GPS arithmetic of CUtils::extractGPSPosition and the signals' HTML strings stay host work
- * (host/dmr_frame_hip.h), as do repeater mode / CACH and the data messages of dmrmessagehandler.
+ * (host/dmr_frame_hip.h), as do the data messages of dmrmessagehandler, the short LC of the CACH (CDMRShortLC has no user in the
+ * reference) and trunked mode.
+ * Repeater mode (dmr_mode != DMR_MODE_DMO): qrl_dmr_rx_set_mode(h, QRL_DMR_MODE_REPEATER, timeslot 1 or 2) from the next process call on; a
+ * fresh handle is in DMO mode.  qrl_dmr_rx_process_slots takes, beside the layer-2 records, the slot records [batch][cap_frames][16] of
+ * qrl_dmr_sink_process for the same slots and adds what dmrcontrol.cpp does outside DMO mode: addFrames passes over a burst whose CACH
+ * was not decoded (:636-640) and one of the other timeslot unless promiscuous (:641-644); every process* call runs processTimeslot
+ * (:444-462), which in promiscuous mode locks _timeslot_RX to the first slot seen until processTerminator releases it (:373).  The order
+ * of the checks is the reference's: processAudio asks the timeslot before the colour code (:227-230), the other calls the colour code
+ * first (:275-278 ...), and each check takes its lock before the other refuses the burst.  qrl_dmr_rx_process works in either mode: with
+ * no slot records every burst reads as cachDecoded() == false, slot 0.  Byte 5 of the output record and byte 3 of the public state carry
+ * _timeslot_RX (0 in DMO mode); QRL_DMR_RX_SLOT_REFUSED: the burst was dropped by one of the CACH or timeslot rules (then _PROCESSED is not set).
+ * qrl_dmr_rx_set_mode: mode outside 0..1, or a repeater-mode timeslot outside 1..2, is QRL_ERR_ARG; the timeslot is ignored in DMO mode.
+ * qrl_dmr_rx_process_slots: batch must be the handle's.  The transmitter stays idle.
  * qrl_dmr_rx_create: config = colour code 0..15 and promiscuous 0 / 1, anything else QRL_ERR_ARG.  _set_config: from the next
  * qrl_dmr_rx_process on.  _reset: every stream back to a fresh handle's state, asynchronous on hip_stream.  _process: out 16-byte aligned;
  * a null pointer or cap_frames == 0 is QRL_ERR_ARG before any device work.  _get_state: the public 12 bytes per stream (0 receiver state,
- * 1 _color_code_RX, 2 _FLCO_RX, 3 zero, 4..7 source, 8..11 destination, little endian), out 4-byte aligned, asynchronous on hip_stream. */
+ * 1 _color_code_RX, 2 _FLCO_RX, 3 _timeslot_RX, 4..7 source, 8..11 destination, little endian), out 4-byte aligned, asynchronous on hip_stream. */
 #define QRL_DMR_RX_RECORD_BYTES 128
 #define QRL_DMR_RX_STATE_BYTES 12
 #define QRL_DMR_RX_VALID 0x0001
@@ -742,6 +754,9 @@ int qrl_dmr_voice_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* cal
 #define QRL_DMR_RX_TALKER_ALIAS 0x0100
 #define QRL_DMR_RX_GPS 0x0200
 #define QRL_DMR_RX_UNKNOWN_FLCO 0x0400
+#define QRL_DMR_RX_SLOT_REFUSED 0x0800
+#define QRL_DMR_MODE_REPEATER 0
+#define QRL_DMR_MODE_DMO 1
 typedef struct qrl_dmr_rx qrl_dmr_rx;
 typedef struct qrl_dmr_rx_config { int color_code; int promiscuous; } qrl_dmr_rx_config;
 int qrl_dmr_rx_create(qrl_ctx* ctx, size_t batch, const qrl_dmr_rx_config* config, qrl_dmr_rx** out);
@@ -751,6 +766,50 @@ int qrl_dmr_rx_set_config(qrl_dmr_rx* h, const qrl_dmr_rx_config* config);
 int qrl_dmr_rx_process(qrl_dmr_rx* h, void* hip_stream, const uint8_t* l2_records /* [batch][cap_frames][80] */, const uint32_t* counts /* [batch] or NULL */,
                        size_t cap_frames, uint8_t* out /* [batch][cap_frames][128] */);
 int qrl_dmr_rx_get_state(qrl_dmr_rx* h, void* hip_stream, uint8_t* out /* [batch][12], device */);
+int qrl_dmr_rx_set_mode(qrl_dmr_rx* h, int mode, int timeslot /* 1 or 2; ignored in DMO mode */);
+int qrl_dmr_rx_process_slots(qrl_dmr_rx* h, void* hip_stream, const uint8_t* l2_records, const uint8_t* slot_info /* [batch][cap_frames][16] */,
+                             const uint32_t* counts, size_t batch, size_t cap_frames, uint8_t* out);
+
+/* ---- DMR repeater-mode burst sink (reference src/gr/gr_dmr_sink.cpp; gr_demod_base connects it to port 2 of gr_demod_dmr, src/gr/gr_demod_base.cpp:814,
+ * and getDMRData(false) returns its frames, :947-966) -------------------------------------------------------------------------------------
+ * The sink behind a repeater's downlink: BS- and MS-sourced sync on the hard bits, the 24-bit CACH in front of every burst, two
+ * alternating slot contexts.  A handle shaped like qrl_deframer_*: qrl_dmr_sink_process consumes the unpacked bits of one demodulator
+ * port (bits[b*stride + i]; i < n, or i < min(n, counts[b*count_stride]) when counts != NULL: the demodulator's counts + 2 with count_stride 4
+ * for port 2) and the state is carried from call to call on the device.  gr_dmr_sink::work / processBits / findSync (:79-260) as they
+ * stand: a bit goes only to the context _next_slot, which changes hands after each burst emitted (a context waiting for sync keeps the
+ * other one's voice call waiting); the four 48-bit sync words of src/DMR/constants.h:9-12 match on equality only (errs < 1, :207-218);
+ * a sync found with fewer than DATA_AND_SYNC_BITS = 180 buffered bits clears the context (:238-245); 108 more bits make a data or
+ * voice-sync burst (:88-110), and the five 288-bit bursts behind a voice sync get FN 1..5 (setFN(6 - frames_to_receive), :113-131).
+ * The erase at work()'s entry (:163-169) cannot change a result and is not run (qradiolink_amd/csrc/dmr_sink_core.hpp says why).
+ * frames [batch][cap_frames][40]: the DMO sink's record, so qrl_dmr_l2_decode takes the array as it is: 0 DMRFrameType (0 data, 1 voice,
+ *   2 voice sync) | 1 FN | 2, 3 zero | 4..36 the 33 frame bytes, DMRFrame::packFrame of bits 24..287 (src/DMR/dmrframe.cpp:58-63, :370-384)
+ *   | 37..39 zero.
+ * slot_info [batch][cap_frames][16]: what DMRFrame(bits, type) + setDownlink() leave (src/DMR/dmrframe.cpp:255-288): 0 downlink (a BS-sourced
+ *   sync) | 1 cachDecoded() | 2 getSlotNo() 0, 1, 2 | 3 LCSS | 4 AT | 5..7 the three CACH bytes | 8..15 end_bit, u64 little endian: the
+ *   number of bits the stream has consumed since creation or reset, up to and including the bit that completed the burst.  The TACT
+ *   bits sit at CACH bits 0 (AT), 4 (TC), 8, 12 (LCSS), the Hamming (7,4) parity at 14, 18, 22; a parity mismatch or an MS-sourced sync
+ *   leaves cachDecoded 0, slot 0, LCSS 0, AT 0.
+ * out_counts[b]: the number of bursts the call found; nothing is written past cap_frames, so out_counts[b] > cap_frames says that bursts
+ * were dropped, as with the DMO mailbox.  Slots behind the count are left as they were.
+ * _reset: a fresh handle's state.  _flush: gr_dmr_sink::flush() (:55-60): only the two bit buffers, the state machines untouched; in the
+ * middle of a data burst the reference then reads past the end of its buffer, here the missing bits read as zero.
+ * _process: frames 8-byte aligned, slot_info 16-byte aligned, n <= stride (whatever the batch), else QRL_ERR_ARG; n > 2^32 - 129 is QRL_ERR_TOO_BIG;
+ * a null pointer or cap_frames == 0 is QRL_ERR_ARG before any device work.
+ * All pointers are device pointers; asynchronous on the handle's stream (give it the demodulator's stream to chain).
+ * Python hands the slot records to the call layer through DmrRx.process_slots(l2, slot_info, ...), a method of its own beside DmrRx.process(),
+ * whose parameter list stays what it was.
+ * Still host work: the short LC carried by the CACH payload (CDMRShortLC has no user in the reference), dmrmessagehandler, trunked mode. */
+#define QRL_DMR_SINK_FRAME_BYTES 40
+#define QRL_DMR_SINK_INFO_BYTES 16
+typedef struct qrl_dmr_sink qrl_dmr_sink;
+int qrl_dmr_sink_create(qrl_ctx* ctx, int batch, void* hip_stream, qrl_dmr_sink** out);
+void qrl_dmr_sink_destroy(qrl_dmr_sink* h);
+int qrl_dmr_sink_reset(qrl_dmr_sink* h);
+int qrl_dmr_sink_flush(qrl_dmr_sink* h);
+int qrl_dmr_sink_process(qrl_dmr_sink* h, const uint8_t* bits, size_t stride, size_t n, const uint32_t* counts, size_t count_stride,
+                         uint8_t* frames /* [batch][cap_frames][40] */, uint8_t* slot_info /* [batch][cap_frames][16] */, size_t cap_frames,
+                         uint32_t* out_counts /* [batch] */);
+int qrl_dmr_sink_sync(qrl_dmr_sink* h);
 
 /* ---- developer aids (NOT part of the drop-in surface; tools/prof_phases.py): shader-clock phase profile of k_decim_mfma ---- */
 void qrl_debug_decim_prof(unsigned long long* out8);

@@ -141,6 +141,8 @@ def load_library():
     lib.qrl_dmr_rx_set_config.argtypes = [vp, C.POINTER(_DmrRxConfig)]
     lib.qrl_dmr_rx_process.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.qrl_dmr_rx_get_state.argtypes = [vp, vp, vp]
+    lib.qrl_dmr_rx_set_mode.argtypes = [vp, C.c_int, C.c_int]
+    lib.qrl_dmr_rx_process_slots.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]
     lib.qrl_demod_set_squelch.argtypes = [vp, C.c_double]
     lib.qrl_demod_set_agc.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_set_filter_width.argtypes = [vp, C.c_int]
@@ -241,6 +243,13 @@ def load_library():
     lib.qrl_deframer_reset.argtypes = [vp]
     lib.qrl_deframer_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, vp]
     lib.qrl_deframer_sync.argtypes = [vp]
+    lib.qrl_dmr_sink_create.argtypes = [vp, C.c_int, vp, C.POINTER(vp)]
+    lib.qrl_dmr_sink_destroy.argtypes = [vp]
+    lib.qrl_dmr_sink_destroy.restype = None
+    lib.qrl_dmr_sink_reset.argtypes = [vp]
+    lib.qrl_dmr_sink_flush.argtypes = [vp]
+    lib.qrl_dmr_sink_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    lib.qrl_dmr_sink_sync.argtypes = [vp]
     lib.qrl_framesync_create.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.qrl_framesync_destroy.argtypes = [vp]
     lib.qrl_framesync_reset.argtypes = [vp]
@@ -266,7 +275,8 @@ EXPORTED_SYMBOLS = [
     "qrl_demod_audio_cap", "qrl_demod_set_squelch", "qrl_demod_set_agc", "qrl_demod_set_filter_width", "qrl_demod_set_gain", "qrl_demod_set_ctcss", "qrl_demod_time_domain_cap", "qrl_demod_set_time_domain_output",
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
     "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode", "qrl_dmr_l2_encode", "qrl_dmr_voice_call_encode",
-    "qrl_dmr_rx_create", "qrl_dmr_rx_destroy", "qrl_dmr_rx_reset", "qrl_dmr_rx_set_config", "qrl_dmr_rx_process", "qrl_dmr_rx_get_state",
+    "qrl_dmr_rx_create", "qrl_dmr_rx_destroy", "qrl_dmr_rx_reset", "qrl_dmr_rx_set_config", "qrl_dmr_rx_process", "qrl_dmr_rx_get_state", "qrl_dmr_rx_set_mode", "qrl_dmr_rx_process_slots",
+    "qrl_dmr_sink_create", "qrl_dmr_sink_destroy", "qrl_dmr_sink_reset", "qrl_dmr_sink_flush", "qrl_dmr_sink_process", "qrl_dmr_sink_sync",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
@@ -431,6 +441,7 @@ class Demod:
         _check(self.lib.qrl_demod_process(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1], C.byref(self._out)),
                "qrl_demod_process")
         self._dmo_l2_async()
+        self._dmr_sink_async()
 
     def sync(self):
         _check(self.lib.qrl_demod_sync(self.h), "qrl_demod_sync")
@@ -449,6 +460,7 @@ class Demod:
         _check(self.lib.qrl_demod_process_sc16(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2, C.byref(self._out)),
                "qrl_demod_process_sc16")
         self._dmo_l2_async()
+        self._dmr_sink_async()
 
     def process_sc16(self, iq):
         self.process_sc16_async(iq)
@@ -517,6 +529,10 @@ class Demod:
         _check(self.lib.qrl_demod_reset(self.h), "qrl_demod_reset")
         if getattr(self, "dmo_call_rx", None) is not None:
             self.dmo_call_rx.reset(stream=self.stream)
+        if getattr(self, "dmr_sink", None) is not None:
+            self.dmr_sink.reset()
+        if getattr(self, "dmr_call_rx", None) is not None:
+            self.dmr_call_rx.reset(stream=self.stream)
 
     def enable_dmo_sink(self, cap_frames=64):
         """QRL_MODEM_DMR: gr_dmr_dmo_sink on the device; after every process() self.dmo_frames uint8 [batch, cap, 40] /
@@ -561,6 +577,49 @@ class Demod:
         if getattr(self, "dmo_call", None) is not None:
             self.dmo_call_rx.process(self.dmo_l2, self.dmo_counts, out=self.dmo_call, stream=s)
 
+    def enable_dmr_sink(self, cap_frames=64):
+        """QRL_MODEM_DMR: the repeater-mode sink, gr_dmr_sink, on the device behind port 2 (reference src/gr/gr_demod_base.cpp:814).  Every
+        process() also runs it over the call's hard bits on the handle's stream with no host synchronisation; afterwards self.dmr_frames
+        uint8 [batch, cap, 40], self.dmr_slot_info uint8 [batch, cap, 16] and self.dmr_counts int32 [batch] hold the call's bursts
+        (qrl_dmr_sink_process).  The sink, self.dmr_sink (a DmrSink), carries its two slot contexts from call to call; reset() resets it too."""
+        self.dmr_sink = DmrSink(self.ctx, self.batch, cap_frames=cap_frames, stream=self.stream)
+        self.dmr_frames, self.dmr_slot_info, self.dmr_counts = self.dmr_sink.frames, self.dmr_sink.slot_info, self.dmr_sink.counts
+        self.torch.cuda.current_stream().synchronize()   # the zero fills are done before the handle's stream writes the buffers
+
+    def enable_dmr_sink_l2(self, audio_fec=True):
+        """DMR layer 2 behind the repeater-mode sink (enable_dmr_sink first): every process() also fills self.dmr_l2 uint8 [batch, cap, 80]
+        (qrl_dmr_l2_decode), queued right behind the sink; mirrors enable_dmo_l2."""
+        if getattr(self, "dmr_sink", None) is None:
+            raise RuntimeError("enable_dmr_sink_l2: enable_dmr_sink() first")
+        t = self.torch
+        self.dmr_l2 = t.zeros((self.batch, self.dmr_frames.shape[1], 80), dtype=t.uint8, device=self.dmr_frames.device)
+        t.cuda.current_stream().synchronize()
+        self._dmr_l2_fec = 1 if audio_fec else 0
+
+    def enable_dmr_sink_call(self, colour_code=1, promiscuous=False, timeslot=1):
+        """the receive call layer in repeater mode behind layer 2 (enable_dmr_sink_l2 first): every process() also fills self.dmr_call uint8
+        [batch, cap, 128] (qrl_dmr_rx_process_slots with the sink's slot records); mirrors enable_dmo_call.  The tracker, self.dmr_call_rx,
+        carries its state from call to call; reset() resets it too."""
+        if getattr(self, "dmr_l2", None) is None:
+            raise RuntimeError("enable_dmr_sink_call: enable_dmr_sink_l2() first")
+        t = self.torch
+        self.dmr_call_rx = _repeater_tracker(self.ctx, self.batch, colour_code, promiscuous, timeslot)
+        self.dmr_call = t.zeros((self.batch, self.dmr_frames.shape[1], DMR_RX_RECORD_BYTES), dtype=t.uint8, device=self.dmr_frames.device)
+        t.cuda.current_stream().synchronize()
+
+    def _dmr_sink_async(self):
+        if getattr(self, "dmr_sink", None) is None:
+            return
+        s = self.stream
+        self.stream_wait(s)   # the bits may be written on another of the handle's streams: an on-device wait, the host goes on
+        self.dmr_sink.process(self.bits_a, self.counts[:, 2], count_stride=4, sync=False)
+        if getattr(self, "dmr_l2", None) is None:
+            return
+        _check(self.lib.qrl_dmr_l2_decode(self.ctx.h, C.c_void_p(s), self.dmr_frames.data_ptr(), self.dmr_counts.data_ptr(), self.batch,
+                                          self.dmr_frames.shape[1], self._dmr_l2_fec, self.dmr_l2.data_ptr()), "qrl_dmr_l2_decode")
+        if getattr(self, "dmr_call", None) is not None:
+            self.dmr_call_rx.process_slots(self.dmr_l2, self.dmr_slot_info, self.dmr_counts, out=self.dmr_call, stream=s)
+
     def dmo_records(self):
         """host copy of the last call's records: per stream a list of (type, fn, colour code, 33 bytes)"""
         f, c = self.dmo_frames.cpu().numpy(), self.dmo_counts.cpu().numpy()
@@ -578,6 +637,10 @@ class Demod:
         _check(self.lib.qrl_demod_set_carrier_offsets(self.h, arr), "qrl_demod_set_carrier_offsets")
 
     def close(self):
+        if getattr(self, "dmr_sink", None) is not None:
+            self.dmr_sink.close()    # it works on this handle's stream: before the stream goes
+        if getattr(self, "dmr_call_rx", None) is not None:
+            self.dmr_call_rx.close()
         if self.h:
             self.lib.qrl_demod_destroy(self.h)
             self.h = C.c_void_p()
@@ -1214,6 +1277,8 @@ def dmr_l2_decode(ctx, frames, counts=None, audio_fec=True):
 DMR_RX_RECORD_BYTES, DMR_RX_STATE_BYTES = 128, 12
 (DMR_RX_VALID, DMR_RX_PROCESSED, DMR_RX_HEADER_VOICE, DMR_RX_HEADER_DATA, DMR_RX_TERMINATOR, DMR_RX_END_BEEP, DMR_RX_AUDIO, DMR_RX_EMBEDDED,
  DMR_RX_TALKER_ALIAS, DMR_RX_GPS, DMR_RX_UNKNOWN_FLCO) = (1 << _i for _i in range(11))
+DMR_RX_SLOT_REFUSED = 1 << 11
+DMR_MODE_REPEATER, DMR_MODE_DMO = 0, 1
 
 
 class DmrRx:
@@ -1233,11 +1298,26 @@ class DmrRx:
         cfg = _DmrRxConfig(int(colour_code), int(promiscuous))
         _check(self.lib.qrl_dmr_rx_set_config(self.h, C.byref(cfg)), "qrl_dmr_rx_set_config")
 
+    def set_mode(self, mode, timeslot=1):
+        """DMR_MODE_REPEATER with the timeslot 1 or 2, or DMR_MODE_DMO (a fresh tracker's); from the next process() on, the state is carried"""
+        _check(self.lib.qrl_dmr_rx_set_mode(self.h, int(mode), int(timeslot)), "qrl_dmr_rx_set_mode")
+
     def reset(self, stream=None):
         """every stream back to a fresh tracker's state"""
         _check(self.lib.qrl_dmr_rx_reset(self.h, C.c_void_p(stream)), "qrl_dmr_rx_reset")
 
     def process(self, l2, counts=None, out=None, stream=None):
+        """without slot records: every burst reads as cachDecoded() false, slot 0 (qrl_dmr_rx_process)"""
+        return self._process(l2, None, counts, out, stream)
+
+    def process_slots(self, l2, slot_info, counts=None, out=None, stream=None):
+        """process() with the [batch, cap, 16] slot records of DmrSink for the same slots (qrl_dmr_rx_process_slots): in repeater mode the
+        CACH and timeslot rules of the reference's DMRControl apply"""
+        import torch
+        assert slot_info.is_cuda and slot_info.dtype == torch.uint8 and slot_info.shape == (self.batch, l2.shape[1], 16) and slot_info.is_contiguous()
+        return self._process(l2, slot_info, counts, out, stream)
+
+    def _process(self, l2, slot_info, counts, out, stream):
         import torch
         assert l2.is_cuda and l2.dtype == torch.uint8 and l2.dim() == 3 and l2.shape[0] == self.batch and l2.shape[2] == 80 and l2.is_contiguous()
         if counts is not None:
@@ -1248,8 +1328,12 @@ class DmrRx:
         assert out.is_cuda and out.dtype == torch.uint8 and out.shape == (self.batch, cap, DMR_RX_RECORD_BYTES) and out.is_contiguous()
         if stream is None:
             torch.cuda.current_stream().synchronize()   # the call runs on the null stream, not torch's: what made l2 must be done
-        _check(self.lib.qrl_dmr_rx_process(self.h, C.c_void_p(stream), l2.data_ptr(), counts.data_ptr() if counts is not None else None, cap,
-                                           out.data_ptr()), "qrl_dmr_rx_process")
+        cnt = counts.data_ptr() if counts is not None else None
+        if slot_info is not None:
+            _check(self.lib.qrl_dmr_rx_process_slots(self.h, C.c_void_p(stream), l2.data_ptr(), slot_info.data_ptr(), cnt, self.batch, cap,
+                                                     out.data_ptr()), "qrl_dmr_rx_process_slots")
+        else:
+            _check(self.lib.qrl_dmr_rx_process(self.h, C.c_void_p(stream), l2.data_ptr(), cnt, cap, out.data_ptr()), "qrl_dmr_rx_process")
         if stream is None:
             torch.cuda.synchronize()
         return out
@@ -1268,6 +1352,67 @@ class DmrRx:
         if self.h:
             self.lib.qrl_dmr_rx_destroy(self.h)
             self.h = C.c_void_p()
+
+
+DMR_SINK_FRAME_BYTES, DMR_SINK_INFO_BYTES = 40, 16
+
+
+class DmrSink:
+    """gr_dmr_sink on the device (qrl_dmr_sink_*, reference src/gr/gr_dmr_sink.cpp): the repeater-mode burst sink on the hard bits of port 2
+    of a QRL_MODEM_DMR demodulator.  process(bits, counts) takes the uint8 cuda tensor [batch, cap] of unpacked bits plus the per-stream
+    valid counts (int32 cuda view, stride in elements, or None) and returns (frames uint8 cuda [batch, cap_frames, 40], the DMO sink's
+    records, which dmr_l2_decode takes as they are; slot_info uint8 cuda [batch, cap_frames, 16]; counts int32 cuda [batch] = bursts
+    found, above cap_frames when bursts were dropped).  The two slot contexts are carried from call to call.  The same three tensors are
+    written by every call; copy what must outlive the next one."""
+
+    def __init__(self, ctx, batch, cap_frames=64, stream=None):
+        import torch
+        self.torch = torch
+        self.ctx, self.lib, self.batch, self.cap_frames = ctx, ctx.lib, batch, int(cap_frames)
+        self.h = C.c_void_p()
+        _check(self.lib.qrl_dmr_sink_create(ctx.h, batch, stream, C.byref(self.h)), "qrl_dmr_sink_create")
+        dev = "cuda:%d" % ctx.device
+        self.frames = torch.zeros((batch, self.cap_frames, DMR_SINK_FRAME_BYTES), dtype=torch.uint8, device=dev)
+        self.slot_info = torch.zeros((batch, self.cap_frames, DMR_SINK_INFO_BYTES), dtype=torch.uint8, device=dev)
+        self.counts = torch.zeros((batch,), dtype=torch.int32, device=dev)
+
+    def process(self, bits, counts=None, count_stride=1, n=None, sync=True):
+        """sync=False: neither waits for torch's stream nor for the handle's (the caller orders the work, e.g. on one shared HIP stream)"""
+        t = self.torch
+        assert bits.is_cuda and bits.dtype == t.uint8 and bits.dim() == 2 and bits.shape[0] == self.batch and bits.stride(1) == 1
+        n = bits.shape[1] if n is None else n
+        assert 0 <= n <= bits.shape[1]
+        if sync:
+            t.cuda.current_stream().synchronize()   # the handle has its own HIP stream: the producer of `bits` must be done
+        _check(self.lib.qrl_dmr_sink_process(self.h, bits.data_ptr(), bits.stride(0), n, counts.data_ptr() if counts is not None else None,
+                                             count_stride, self.frames.data_ptr(), self.slot_info.data_ptr(), self.cap_frames,
+                                             self.counts.data_ptr()), "qrl_dmr_sink_process")
+        if sync:
+            _check(self.lib.qrl_dmr_sink_sync(self.h), "qrl_dmr_sink_sync")
+        return self.frames, self.slot_info, self.counts
+
+    def reset(self):
+        """every stream back to a fresh sink's state"""
+        _check(self.lib.qrl_dmr_sink_reset(self.h), "qrl_dmr_sink_reset")
+
+    def flush(self):
+        """gr_dmr_sink::flush(): the two bit buffers of every stream emptied, the state machines left alone"""
+        _check(self.lib.qrl_dmr_sink_flush(self.h), "qrl_dmr_sink_flush")
+
+    def sync(self):
+        _check(self.lib.qrl_dmr_sink_sync(self.h), "qrl_dmr_sink_sync")
+
+    def close(self):
+        if self.h:
+            self.lib.qrl_dmr_sink_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def _repeater_tracker(ctx, batch, colour_code, promiscuous, timeslot):
+    """a DmrRx in repeater mode on the given timeslot (Demod.enable_dmr_sink_call)"""
+    rx = DmrRx(ctx, batch, colour_code=colour_code, promiscuous=promiscuous)
+    rx.set_mode(DMR_MODE_REPEATER, timeslot)
+    return rx
 
 
 def dmr_trellis34_decode(ctx, bursts):

@@ -10,6 +10,7 @@ struct qrl_dmr_rx {
     qrl_ctx* ctx = nullptr;
     size_t batch = 0;
     int color_code = 0, promiscuous = 0;
+    int mode = QRL_DMR_MODE_DMO, timeslot = 1;   // Settings::dmr_mode, dmr_timeslot; a fresh handle is in DMO mode
     DevBuf<uint8_t> states;             // DMR_RX_STATE_BYTES per stream (dmr_rx_core.hpp's dmr_rx_state); all zero bytes = a fresh DMRControl
 };
 
@@ -59,12 +60,37 @@ int qrl_dmr_rx_set_config(qrl_dmr_rx* h, const qrl_dmr_rx_config* config)
     return QRL_OK;
 }
 
+int qrl_dmr_rx_set_mode(qrl_dmr_rx* h, int mode, int timeslot)
+{
+    if (!h) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_set_mode: null handle");
+    if (mode != QRL_DMR_MODE_REPEATER && mode != QRL_DMR_MODE_DMO) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_set_mode: mode outside 0..1");
+    if (mode == QRL_DMR_MODE_REPEATER && (timeslot < 1 || timeslot > 2)) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_set_mode: timeslot outside 1..2");
+    h->mode = mode;
+    if (mode == QRL_DMR_MODE_REPEATER) h->timeslot = timeslot;
+    return QRL_OK;
+}
+
+// without slot records every burst reads as cachDecoded() == false, slot 0
 int qrl_dmr_rx_process(qrl_dmr_rx* h, void* hip_stream, const uint8_t* l2_records, const uint32_t* counts, size_t cap_frames, uint8_t* out)
 {
     if (!h || !l2_records || !out || !cap_frames) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_process: null argument or cap_frames 0");
     if (reinterpret_cast<uintptr_t>(out) & 15u) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_process: out is not 16-byte aligned");
     HIPCHK(hipSetDevice(h->ctx->device));
-    launch_dmr_rx(l2_records, counts, h->batch, cap_frames, h->color_code, h->promiscuous, h->states.p, out, static_cast<hipStream_t>(hip_stream));
+    launch_dmr_rx(l2_records, counts, h->batch, cap_frames, h->color_code, h->promiscuous, h->states.p, out, static_cast<hipStream_t>(hip_stream),
+                  nullptr, h->mode == QRL_DMR_MODE_REPEATER, h->timeslot);
+    HIPCHK(hipGetLastError());
+    return QRL_OK;
+}
+
+int qrl_dmr_rx_process_slots(qrl_dmr_rx* h, void* hip_stream, const uint8_t* l2_records, const uint8_t* slot_info, const uint32_t* counts, size_t batch,
+                             size_t cap_frames, uint8_t* out)
+{
+    if (!h || !l2_records || !slot_info || !out || !cap_frames) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_process_slots: null argument or cap_frames 0");
+    if (batch != h->batch) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_process_slots: batch is not the handle's");
+    if (reinterpret_cast<uintptr_t>(out) & 15u) return qrl_set_error(QRL_ERR_ARG, "qrl_dmr_rx_process_slots: out is not 16-byte aligned");
+    HIPCHK(hipSetDevice(h->ctx->device));
+    launch_dmr_rx(l2_records, counts, h->batch, cap_frames, h->color_code, h->promiscuous, h->states.p, out, static_cast<hipStream_t>(hip_stream),
+                  slot_info, h->mode == QRL_DMR_MODE_REPEATER, h->timeslot);
     HIPCHK(hipGetLastError());
     return QRL_OK;
 }

@@ -2,7 +2,8 @@
 // receive half of DMRControl in DMO mode with an idle transmitter (reference src/DMR/dmrcontrol.cpp).
 //   one burst                addFrames' loop body                              src/DMR/dmrcontrol.cpp:625-665
 //   by data type             processCSBK / processDataHeader / processVoiceHeader / processTerminator / processAudio   :225-402
-//   colour code              processColorCode (processTimeslot is true in DMO) :415-442
+//   colour code              processColorCode                                  :415-442
+//   timeslot (repeater mode) processTimeslot, the CACH and timeslot filters of addFrames   :444-462, :636-644
 //   embedded LC              CDMREmbeddedData::addData / decodeEmbeddedData / reset / getLC / getRawData   src/MMDVM/DMREmbeddedData.cpp:47-109, :213-322
 //                            CHamming::decode16114, CCRC::checkFiveBit         src/MMDVM/Hamming.cpp:231-277, CRC.cpp:122-146
 //   what the LC says         processEmbeddedData, the completion rule of processTalkerAlias   src/DMR/dmrcontrol.cpp:464-623
@@ -12,6 +13,10 @@
 // any burst of another colour code is refused; a voice burst is checked with _color_code_RX in place of its own colour code; a terminator
 // with source and destination 0 is passed over; nothing but reset() and an LCSS 1 fragment clears the embedded data, and a terminator
 // leaves a half-collected alias where it is.  The two fields the reference never initialises (_ta_df, _ta_dl) start at 0.
+// In repeater mode (dmr_mode != DMR_MODE_DMO) addFrames passes over a burst whose CACH was not decoded, and one of the other timeslot unless
+// promiscuous; every process* call then runs processTimeslot, which in promiscuous mode locks _timeslot_RX to the first slot seen until a
+// terminator releases it.  processAudio asks the timeslot before the colour code, the other calls the colour code first, and each check
+// takes its lock before the other refuses the burst; that order is kept.  The transmitter is idle.
 //
 // The 128 bits of an embedded LC are kept as the four fragments, first bit highest.  The matrix is sent by columns, so byte c of those 16
 // is column c with row 0 in its top bit, and the de-interleave (b += 16 mod 127) is the transpose 16 columns x 8 rows -> 8 row words,
@@ -21,13 +26,13 @@
 // Output record, DMR_RX_REC = 128 bytes (QRL_DMR_RX_RECORD_BYTES):
 //   0..1     flags, little endian (F_*)
 //   2        receiver state after the burst (RECEIVER_STATE: 0 idle, 1 late entry, 2 audio, 3 data)   3   _color_code_RX   4   _FLCO_RX
-//   5..7     zero
+//   5        _timeslot_RX after the burst (0 in DMO mode)   6..7   zero
 //   8..11    _srcId_RX, 12..15 _dstId_RX, little endian
 //   16       FLCO of the embedded LC, 17..25 its nine getRawData bytes (F_EMBEDDED only, else zero)
 //   26       talker-alias format, 27 its length field, 28 the number of bytes collected, 32..99 those bytes (F_TALKER_ALIAS only, else zero)
 //   29..31, 100..127   zero
 // Per-stream state, DMR_RX_STATE_SIZE = 128 bytes; its first 12 bytes are the public part (QRL_DMR_RX_STATE_BYTES):
-//   0 receiver state, 1 _color_code_RX, 2 _FLCO_RX, 3 zero, 4..7 source, 8..11 destination (little endian)
+//   0 receiver state, 1 _color_code_RX, 2 _FLCO_RX, 3 _timeslot_RX, 4..7 source, 8..11 destination (little endian)
 // A state of all zero bytes is a fresh DMRControl.
 #pragma once
 #include "dmr_l2_core.hpp"
@@ -37,17 +42,20 @@ namespace dmr {
 
 enum { DMR_RX_REC = 128, DMR_RX_STATE_SIZE = 128, DMR_RX_STATE_PUBLIC = 12, TA_MAX = 68 };
 enum { F_VALID = 1 << 0, F_PROCESSED = 1 << 1, F_HEADER_VOICE = 1 << 2, F_HEADER_DATA = 1 << 3, F_TERMINATOR = 1 << 4, F_END_BEEP = 1 << 5,
-       F_AUDIO = 1 << 6, F_EMBEDDED = 1 << 7, F_TALKER_ALIAS = 1 << 8, F_GPS = 1 << 9, F_UNKNOWN_FLCO = 1 << 10 };
-enum { X_FLAGS = 0, X_STATE = 2, X_CC = 3, X_FLCO = 4, X_SRC = 8, X_DST = 12, X_EMB_FLCO = 16, X_EMB_RAW = 17, X_TA_FORMAT = 26, X_TA_LENGTH = 27,
+       F_AUDIO = 1 << 6, F_EMBEDDED = 1 << 7, F_TALKER_ALIAS = 1 << 8, F_GPS = 1 << 9, F_UNKNOWN_FLCO = 1 << 10, F_SLOT_REFUSED = 1 << 11 };
+enum { X_FLAGS = 0, X_STATE = 2, X_CC = 3, X_FLCO = 4, X_TS = 5, X_SRC = 8, X_DST = 12, X_EMB_FLCO = 16, X_EMB_RAW = 17, X_TA_FORMAT = 26, X_TA_LENGTH = 27,
        X_TA_COUNT = 28, X_TA = 32 };
 enum { RX_IDLE = 0, RX_LATE_ENTRY = 1, RX_AUDIO = 2, RX_DATA = 3 };
 enum { LCS_NONE = 0, LCS_FIRST = 1, LCS_SECOND = 2, LCS_THIRD = 3 };
 enum { FLCO_GROUP = 0, FLCO_USER_USER = 3, FLCO_TA_HEADER = 4, FLCO_TA_BLOCK1 = 5, FLCO_TA_BLOCK3 = 7, FLCO_GPS_INFO = 8 };
 
-struct dmr_rx_config { int color_code; int promiscuous; };
+// repeater: 0 = DMR_MODE_DMO (what two initialisers give), 1 = repeater mode with the timeslot 1 or 2 of Settings::dmr_timeslot
+struct dmr_rx_config { int color_code; int promiscuous; int repeater; int timeslot; };
+// the two bytes of a slot record (dmr_sink_core.hpp) the call layer reads
+enum { SLOT_CACH_DECODED = 1, SLOT_NO = 2, SLOT_REC = 16 };
 
 struct dmr_rx_state {
-    uint8_t rx_state, cc_rx, flco_rx, pad0;
+    uint8_t rx_state, cc_rx, flco_rx, ts_rx;   // ts_rx: _timeslot_RX
     uint32_t src, dst;
     uint8_t lcs, emb_valid, emb_flco, ta_received;   // CDMREmbeddedData: m_state, m_valid, m_FLCO
     uint8_t ta_df, ta_dl, ta_size, pad1;
@@ -239,9 +247,31 @@ QRL_HD inline bool colour_code_ok(const dmr_rx_config& cfg, dmr_rx_state& st, un
     return true;
 }
 
-// one iteration of addFrames' loop.  rec: the burst's 80-byte layer-2 record; out: the DMR_RX_REC bytes as 32 little-endian words, all written.
-QRL_HD inline void dmr_rx_step(const dmr_rx_config& cfg, dmr_rx_state& st, const uint8_t* rec, uint32_t* out)
+// DMRControl::processTimeslot
+QRL_HD inline bool timeslot_ok(const dmr_rx_config& cfg, dmr_rx_state& st, unsigned slot)
 {
+    if (!cfg.repeater) return true;
+    if (slot != (unsigned)cfg.timeslot && !cfg.promiscuous) return false;
+    if (cfg.promiscuous) {
+        if (slot != st.ts_rx && st.ts_rx != 0u) return false;
+        if (st.ts_rx == 0u) st.ts_rx = (uint8_t)slot;
+    }
+    return true;
+}
+// a process* call's two checks: the colour code first, as everywhere but in processAudio.  slot_refused: it was the timeslot that said no
+QRL_HD inline bool colour_then_slot(const dmr_rx_config& cfg, dmr_rx_state& st, unsigned cc, unsigned slot, bool& slot_refused)
+{
+    if (!colour_code_ok(cfg, st, cc)) return false;
+    if (!timeslot_ok(cfg, st, slot)) { slot_refused = true; return false; }
+    return true;
+}
+
+// one iteration of addFrames' loop.  rec: the burst's 80-byte layer-2 record; slot: its 16-byte slot record, or null (cachDecoded() false, slot
+// 0: a burst of the DMO sink); out: the DMR_RX_REC bytes as 32 little-endian words, all written.
+QRL_HD inline void dmr_rx_step_slots(const dmr_rx_config& cfg, dmr_rx_state& st, const uint8_t* rec, const uint8_t* slot, uint32_t* out)
+{
+    const bool cach_decoded = slot && slot[SLOT_CACH_DECODED];
+    const unsigned slot_no = slot ? slot[SLOT_NO] : 0u;
 #pragma GCC unroll 32
     for (int i = 0; i < DMR_RX_REC / 4; ++i) out[i] = 0;
     unsigned flags = 0;
@@ -249,19 +279,21 @@ QRL_HD inline void dmr_rx_step(const dmr_rx_config& cfg, dmr_rx_state& st, const
         const unsigned dt = rec[R_DTYPE], cc = rec[R_CC];
         const uint32_t src = (uint32_t)rec[R_SRC] | ((uint32_t)rec[R_SRC + 1] << 8) | ((uint32_t)rec[R_SRC + 2] << 16) | ((uint32_t)rec[R_SRC + 3] << 24);
         const uint32_t dst = (uint32_t)rec[R_DST] | ((uint32_t)rec[R_DST + 1] << 8) | ((uint32_t)rec[R_DST + 2] << 16) | ((uint32_t)rec[R_DST + 3] << 24);
-        bool ok = true;
+        bool ok = true, slot_refused = false;
         flags = F_VALID;
-        if (dt == DT_CSBK || dt == DT_MBC_HEADER || dt == DT_MBC_CONTINUATION) {
-            ok = colour_code_ok(cfg, st, cc);
+        if (cfg.repeater && (!cach_decoded || (slot_no != (unsigned)cfg.timeslot && !cfg.promiscuous))) {
+            ok = false; slot_refused = true;   // addFrames goes on to the next burst
+        } else if (dt == DT_CSBK || dt == DT_MBC_HEADER || dt == DT_MBC_CONTINUATION) {
+            ok = colour_then_slot(cfg, st, cc, slot_no, slot_refused);
         } else if (dt == DT_DATA_HEADER) {
-            ok = colour_code_ok(cfg, st, cc);
+            ok = colour_then_slot(cfg, st, cc, slot_no, slot_refused);
             if (ok) {
                 st.cc_rx = (uint8_t)cc; st.src = src; st.dst = dst; st.flco_rx = rec[R_FLCO];
                 st.rx_state = RX_DATA;
                 flags |= F_HEADER_DATA;
             }
         } else if (dt == DT_VOICE_LC_HEADER) {
-            ok = colour_code_ok(cfg, st, cc);
+            ok = colour_then_slot(cfg, st, cc, slot_no, slot_refused);
             if (ok) {
                 st.cc_rx = (uint8_t)cc;
                 if (st.rx_state == RX_IDLE) flags |= F_END_BEEP;
@@ -271,14 +303,16 @@ QRL_HD inline void dmr_rx_step(const dmr_rx_config& cfg, dmr_rx_state& st, const
             }
         } else if (dt == DT_TERMINATOR_WITH_LC) {
             if (dst != 0u || src != 0u) {   // one with neither ID comes from a trunking site and is passed over
-                ok = colour_code_ok(cfg, st, cc);
+                ok = colour_then_slot(cfg, st, cc, slot_no, slot_refused);
                 if (ok) {
                     if (st.rx_state != RX_IDLE) flags |= F_TERMINATOR | F_END_BEEP;
-                    st.src = 0; st.dst = 0; st.flco_rx = 0; st.rx_state = RX_IDLE; st.ta_received = 0; st.cc_rx = 0;
+                    st.src = 0; st.dst = 0; st.flco_rx = 0; st.rx_state = RX_IDLE; st.ta_received = 0; st.cc_rx = 0; st.ts_rx = 0;
                 }
             }
         } else if (dt == DT_VOICE_SYNC || dt == DT_VOICE) {
-            ok = colour_code_ok(cfg, st, st.cc_rx);   // addFrames has put _color_code_RX into the frame
+            ok = timeslot_ok(cfg, st, slot_no);       // processAudio asks the timeslot first
+            if (!ok) slot_refused = true;
+            else ok = colour_code_ok(cfg, st, st.cc_rx);   // addFrames has put _color_code_RX into the frame
             if (ok) {
                 if (dt == DT_VOICE_SYNC) {
                     st.lcs = LCS_NONE; st.emb_valid = 0;
@@ -293,12 +327,20 @@ QRL_HD inline void dmr_rx_step(const dmr_rx_config& cfg, dmr_rx_state& st, const
             }
         }
         if (ok) flags |= F_PROCESSED;
+        if (slot_refused) flags |= F_SLOT_REFUSED;
     }
     out[0] = flags | ((uint32_t)st.rx_state << 16) | ((uint32_t)st.cc_rx << 24);
-    out[X_FLCO / 4] = st.flco_rx;
+    out[X_FLCO / 4] = st.flco_rx | ((uint32_t)st.ts_rx << 8);
     out[X_SRC / 4] = st.src; out[X_DST / 4] = st.dst;
 }
+QRL_HD inline void dmr_rx_step(const dmr_rx_config& cfg, dmr_rx_state& st, const uint8_t* rec, uint32_t* out) { dmr_rx_step_slots(cfg, st, rec, nullptr, out); }
 // the same, the record as bytes
+QRL_HD inline void dmr_rx_step_slots_bytes(const dmr_rx_config& cfg, dmr_rx_state& st, const uint8_t* rec, const uint8_t* slot, uint8_t* out)
+{
+    uint32_t w[DMR_RX_REC / 4];
+    dmr_rx_step_slots(cfg, st, rec, slot, w);
+    for (int i = 0; i < DMR_RX_REC / 4; ++i) put32(out + 4 * i, w[i]);
+}
 QRL_HD inline void dmr_rx_step_bytes(const dmr_rx_config& cfg, dmr_rx_state& st, const uint8_t* rec, uint8_t* out)
 {
     uint32_t w[DMR_RX_REC / 4];

@@ -455,9 +455,19 @@ void launch_dmr_tx_call(const uint8_t* calls, const uint8_t* voice, const uint32
 // ---- DMR receive call layer (kernels_dmr_rx.hip): layer-2 records [batch][cap][80] -> call records [batch][cap][128] through the per-stream
 //      states [batch] (dmr_rx_core.hpp's dmr_rx_state); the public 12 bytes of every state ----
 constexpr size_t DMR_RX_RECORD_BYTES = 128, DMR_RX_STATE_BYTES = 128, DMR_RX_PUBLIC_BYTES = 12;   // kernels_dmr_rx.hip holds them to the core
+//      slot_info: the slot records [batch][cap][16] of the repeater-mode sink, or null; repeater 1: DMRControl outside DMO mode, on `timeslot`
 void launch_dmr_rx(const uint8_t* l2, const uint32_t* counts, size_t batch, size_t cap, int color_code, int promiscuous, void* states, uint8_t* out,
-                   hipStream_t s);
+                   hipStream_t s, const uint8_t* slot_info = nullptr, int repeater = 0, int timeslot = 1);
 void launch_dmr_rx_state(const void* states, size_t batch, uint8_t* out, hipStream_t s);
+// ---- DMR repeater-mode burst sink (kernels_dmr_sink.hip): unpacked bits bits[b * stride + i], i < min(n, counts[b * count_stride]), -> frame
+//      records [batch][cap][40] and slot records [batch][cap][16] through the per-stream states [batch] (dmr_sink_core.hpp's dmr_sink_state) ----
+constexpr size_t DMR_SINK_STATE_BYTES = 160;   // kernels_dmr_sink.hip holds it to the core
+struct DmrSinkParams {
+    const uint8_t* bits; size_t stride; uint32_t n; const uint32_t* counts; size_t count_stride;
+    void* st; uint8_t* frames; uint8_t* info; uint32_t cap; uint32_t* out_counts;
+};
+void launch_dmr_sink(const DmrSinkParams& p, int batch, hipStream_t s);
+void launch_dmr_sink_flush(void* states, int batch, hipStream_t s);
 
 // ---- side outputs (kernels_side.hip): rssi_block on port 0, rx_fft_c on the device-rate IQ ----
 constexpr uint32_t RSSI_RING = 4096;   // |x|^2 look-back ring per stream (moving_average_ff(2000) reads 1999 items back)

@@ -3,6 +3,8 @@
 // processAudio (src/DMR/dmrcontrol.cpp:225-260, :625-700) look at.  The work is done on the device; this class only reads bytes.
 // Below it dmr_call_event_hip reads a 128-byte record of qrl_dmr_rx_process and dmr_alias_text turns collected alias bytes into text; then the transmit side: dmr_tx_record and dmr_call_descriptor write the two records of qrl_dmr_l2_encode / qrl_dmr_voice_call_encode.
 #pragma once
+#include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -15,6 +17,12 @@ class dmr_frame_hip {
 public:
     explicit dmr_frame_hip(const unsigned char* record80) { std::memcpy(_r, record80, QRL_DMR_L2_RECORD_BYTES); }
     explicit dmr_frame_hip(const std::vector<unsigned char>& record80) { std::memcpy(_r, record80.data(), QRL_DMR_L2_RECORD_BYTES); }
+    // a burst of the repeater-mode sink: the layer-2 record and the 16-byte slot record of qrl_dmr_sink_process for the same slot
+    dmr_frame_hip(const unsigned char* record80, const unsigned char* slot_info16)
+    {
+        std::memcpy(_r, record80, QRL_DMR_L2_RECORD_BYTES);
+        std::memcpy(_s, slot_info16, QRL_DMR_SINK_INFO_BYTES);
+    }
     bool validate() const { return _r[4] != 0; }
     uint8_t getFrameType() const { return _r[0]; }
     uint8_t getFN() const { return _r[1]; }
@@ -36,11 +44,44 @@ public:
     }
     // the decoded payload: 12 bytes of a BPTC burst, 18 of a rate 3/4 burst, 27 of a voice burst; length 0 for a refused or rate 1 burst
     void getDataPayload(unsigned char* data, uint8_t& length) const { length = _r[8]; std::memcpy(data, _r + 53, length); }
+    // what DMRFrame(bits, type) + setDownlink() left (src/DMR/dmrframe.cpp:255-298); all zero for a burst of the DMO sink
+    bool getDownlink() const { return _s[0] != 0; }
+    bool cachDecoded() const { return _s[1] != 0; }
+    uint8_t getSlotNo() const { return _s[2]; }
+    uint8_t getCachLCSS() const { return _s[3]; }               // the TACT's LCSS; getLCSS() above is the EMB's
+    uint8_t getAT() const { return _s[4]; }
+    void getCACH(unsigned char* cach_data) const { std::memcpy(cach_data, _s + 5, 3); }
+    uint64_t endBit() const { uint64_t v = 0; for (int i = 7; i >= 0; --i) v = (v << 8) | _s[8 + i]; return v; }
 
 private:
     uint32_t le32(int o) const { return (uint32_t)_r[o] | ((uint32_t)_r[o + 1] << 8) | ((uint32_t)_r[o + 2] << 16) | ((uint32_t)_r[o + 3] << 24); }
     unsigned char _r[QRL_DMR_L2_RECORD_BYTES];
+    unsigned char _s[QRL_DMR_SINK_INFO_BYTES] = {};
 };
+
+// ---- slot timing of the repeater-mode sink (src/gr/gr_dmr_sink.cpp:171-197, src/DMR/dmrtiming.cpp:54-82).  While it walks the bits the reference
+// keeps DMRTiming's sample counter: every second bit of the stream (_symbol_bits back at 0) adds SYMBOL_LENGTH_SAMPLES = 5 samples, and a bit
+// that carries an rx_time tag zeroes the counter, sets the time base to the tag's time and adds nothing.  For a burst with downlink, a decoded
+// CACH and slot 1 or 2 it then calls set_slot_times(slot), which stores get_sample_counter() = time base + counter * time per sample.  From
+// a slot record's end_bit and the tags the host gets that value without seeing the bit stream.
+struct dmr_time_tag { uint64_t bit; uint64_t ns; };      // the tag's absolute bit offset (counted like end_bit, from 0) and its time in nanoseconds
+constexpr uint64_t DMR_TIME_PER_SAMPLE_NS = 41667;         // TIME_PER_SAMPLE, src/bursttimer.h:31
+// rx_time's (whole seconds, fraction) as work() turns it into nanoseconds (:182-185)
+inline uint64_t dmr_tag_ns(uint64_t secs, double fracs) { return (uint64_t)llround((double)(secs * 1000000000ull) + fracs * 1000000000.0); }
+// whether set_slot_times is called for the burst (:105, :121)
+inline bool dmr_slot_time_set(const unsigned char* slot_info16) { return slot_info16[0] && slot_info16[1] && slot_info16[2] >= 1 && slot_info16[2] <= 2; }
+// the value it stores; tags in any order, the last one at or before the burst's last bit counts
+inline uint64_t dmr_slot_time(uint64_t end_bit, const dmr_time_tag* tags, size_t ntags, uint64_t time_per_sample = DMR_TIME_PER_SAMPLE_NS)
+{
+    uint64_t base = 0, first = 0;   // the counter adds at odd bit indices first <= j < end_bit
+    bool have = false;
+    uint64_t at = 0;
+    for (size_t k = 0; k < ntags; ++k)
+        if (tags[k].bit < end_bit && (!have || tags[k].bit >= at)) { have = true; at = tags[k].bit; base = tags[k].ns; }
+    if (have) first = at + 1;
+    const uint64_t adds = end_bit / 2 - first / 2;   // odd j in [first, end_bit): floor(end_bit / 2) - floor(first / 2)
+    return base + adds * 5u * time_per_sample;
+}
 
 // ---- the receive call layer: a 128-byte record of qrl_dmr_rx_process (include/qrl_hip.h), what DMRControl::addFrames did with one burst
 // (which of its signals fired) and the stream's call state afterwards (src/DMR/dmrcontrol.cpp:225-665).  The state lives on the device.

@@ -74,13 +74,14 @@ struct gr_demod_base_hip::slot {
     bool framed = false, bits_copied = true;
     uint8_t *d_l2 = nullptr, *h_l2 = nullptr; bool l2 = false;   // DMR layer 2 records of the call's bursts (set_dmr_l2; device / pinned)
     uint8_t *d_call = nullptr, *h_call = nullptr; bool call = false;   // DMR call records of the same bursts (set_dmr_call)
+    uint8_t *d_rep = nullptr, *d_info = nullptr, *h_info = nullptr; uint32_t* d_repcnt = nullptr; bool rep = false;   // the repeater-mode sink's bursts, their slot records (set_dmr_repeater)
     hipEvent_t done = nullptr;
 };
 static constexpr size_t kDmoCap = 16;
 
 gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_chunk)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_chunk(max_chunk & ~(size_t)1),
-      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams), d_boxl(streams), d_boxe(streams)
+      d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_boxa(streams), d_box1(streams), d_box2(streams), d_boxc(streams), d_boxd(streams), d_boxl(streams), d_boxe(streams), d_boxi(streams)
 {
     d_boxf[0].resize(streams); d_boxf[1].resize(streams); d_boxs.resize(streams);
     for (int k = 0; k < 2; ++k) { d_fbits[k].assign(streams, 0); d_fact[k].assign(streams, 0); }
@@ -98,6 +99,7 @@ gr_demod_base_hip::~gr_demod_base_hip()
     try { flush(); } catch (...) {}
     close();
     if (d_call_rx) qrl_dmr_rx_destroy(d_call_rx);
+    if (d_sink) qrl_dmr_sink_destroy(d_sink);   // it works on the copy stream: before the stream goes
     if (d_copy) (void)hipStreamDestroy(static_cast<hipStream_t>(d_copy));
 }
 void gr_demod_base_hip::close()
@@ -130,6 +132,8 @@ void gr_demod_base_hip::close()
         if (sp->d_l2) (void)hipFree(sp->d_l2);
         if (sp->h_l2) (void)hipHostFree(sp->h_l2);
         if (sp->d_call) (void)hipFree(sp->d_call);
+        for (void* p : {(void*)sp->d_rep, (void*)sp->d_info, (void*)sp->d_repcnt}) if (p) (void)hipFree(p);
+        if (sp->h_info) (void)hipHostFree(sp->h_info);
         if (sp->h_call) (void)hipHostFree(sp->h_call);
         if (sp->done) (void)hipEventDestroy(sp->done);
         delete sp;
@@ -207,11 +211,33 @@ void gr_demod_base_hip::open()
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
             hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES), "hipMalloc");
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_rep), N * kDmoCap * QRL_DMR_SINK_FRAME_BYTES), "hipMalloc");
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_info), N * kDmoCap * QRL_DMR_SINK_INFO_BYTES), "hipMalloc");
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_repcnt), N * sizeof(uint32_t)), "hipMalloc");
+            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_info), N * kDmoCap * QRL_DMR_SINK_INFO_BYTES, hipHostMallocDefault), "hipHostMalloc");
         }
         hchk(hipEventCreateWithFlags(&sp->done, hipEventDisableTiming), "hipEventCreate");
     }
     d_calls = 0;
     if (d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // the receiver starts afresh, and so does the call state behind it
+    if (d_sink) chk(qrl_dmr_sink_reset(d_sink), "qrl_dmr_sink_reset");
+}
+void gr_demod_base_hip::apply_call_mode()
+{
+    if (d_call_rx) chk(qrl_dmr_rx_set_mode(d_call_rx, d_rep_on ? QRL_DMR_MODE_REPEATER : QRL_DMR_MODE_DMO, d_rep_slot), "qrl_dmr_rx_set_mode");
+}
+void gr_demod_base_hip::set_dmr_repeater(bool on, int timeslot)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (on && (timeslot < 1 || timeslot > 2)) throw std::runtime_error("gr_demod_base_hip::set_dmr_repeater: timeslot outside 1..2");
+    if (on) {
+        if (!d_sink) chk(qrl_dmr_sink_create(d_rt.ctx(), d_n, d_copy, &d_sink), "qrl_dmr_sink_create");
+        else if (!d_rep_on) chk(qrl_dmr_sink_reset(d_sink), "qrl_dmr_sink_reset");   // switched back on: nothing of the bits it missed
+        d_rep_slot = timeslot;
+    }
+    if (on != d_rep_on && d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // another sink's bursts: no call goes on across the switch
+    d_rep_on = on;
+    apply_call_mode();
 }
 void gr_demod_base_hip::set_dmr_call(bool on, int colour_code, bool promiscuous)
 {
@@ -220,6 +246,7 @@ void gr_demod_base_hip::set_dmr_call(bool on, int colour_code, bool promiscuous)
     if (!d_call_rx) {
         if (!on) return;
         chk(qrl_dmr_rx_create(d_rt.ctx(), (size_t)d_n, &c, &d_call_rx), "qrl_dmr_rx_create");
+        apply_call_mode();
     } else {
         chk(qrl_dmr_rx_set_config(d_call_rx, &c), "qrl_dmr_rx_set_config");
         if (on && !d_call_on) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // switched back on: nothing of the calls it missed
@@ -239,7 +266,7 @@ void gr_demod_base_hip::set_mode(int mode)   // gr_demod_base::set_mode (src/gr/
         throw std::invalid_argument(std::string("gr_demod_base_hip::set_mode: time-domain settings rejected and reset to the defaults (the mode is open): ") + e.what());
     }
     std::lock_guard<std::mutex> g(d_mutex);
-    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxl[s].clear(); d_boxe[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
+    for (int s = 0; s < d_n; ++s) { d_box1[s].clear(); d_box2[s].clear(); d_boxc[s].clear(); d_boxd[s].clear(); d_boxl[s].clear(); d_boxe[s].clear(); d_boxi[s].clear(); d_boxa[s].clear(); d_boxf[0][s].clear(); d_boxf[1][s].clear(); d_boxs[s].clear(); d_fbits[0][s] = d_fbits[1][s] = d_fact[0][s] = d_fact[1][s] = 0; }
 }
 void gr_demod_base_hip::enable_device_framing(bool value)
 {
@@ -370,16 +397,26 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     sl.const_copied = d_const_on;
     if (d_const_on) hchk(hipMemcpyAsync(sl.h_const, sl.d_const, N * d_ccap * sizeof(gr_complex), hipMemcpyDeviceToHost, cs), "D2H");
     if (d_mode == QRL_MODEM_DMR) {
-        hchk(hipMemcpyAsync(sl.h_dmocnt, sl.d_dmocnt, N * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
-        hchk(hipMemcpyAsync(sl.h_dmo, sl.d_dmo, N * kDmoCap * QRL_DMO_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        sl.rep = d_rep_on && d_sink;
+        // getDMRData(bool dmo): the bursts of the DMO slicer, or those the repeater-mode sink finds in port 2 of this call (on the copy stream, which
+        // waits for the demodulator on the device); the same record either way, so everything behind it takes frames / fcnt
+        const uint8_t* frames = sl.rep ? sl.d_rep : sl.d_dmo;
+        const uint32_t* fcnt = sl.rep ? sl.d_repcnt : sl.d_dmocnt;
+        if (sl.rep) {
+            chk(qrl_dmr_sink_process(d_sink, sl.d_a, d_bcap, d_bcap, sl.d_cnt + 2, 4, sl.d_rep, sl.d_info, kDmoCap, sl.d_repcnt), "qrl_dmr_sink_process");
+            hchk(hipMemcpyAsync(sl.h_info, sl.d_info, N * kDmoCap * QRL_DMR_SINK_INFO_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        }
+        hchk(hipMemcpyAsync(sl.h_dmocnt, fcnt, N * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
+        hchk(hipMemcpyAsync(sl.h_dmo, frames, N * kDmoCap * QRL_DMO_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
         sl.l2 = d_l2_on;
         if (sl.l2) {   // layer 2 on the copy stream, which waits for the slicer on the device: validate / FEC of the call's bursts, no host synchronisation
-            chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, sl.d_dmo, sl.d_dmocnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.d_l2), "qrl_dmr_l2_decode");
+            chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, frames, fcnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.d_l2), "qrl_dmr_l2_decode");
             hchk(hipMemcpyAsync(sl.h_l2, sl.d_l2, N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
         }
         sl.call = sl.l2 && d_call_on && d_call_rx;
         if (sl.call) {   // the call layer behind layer 2 on the same stream: every call of this handle goes through the copy stream, so the per-stream state is carried in order
-            chk(qrl_dmr_rx_process(d_call_rx, cs, sl.d_l2, sl.d_dmocnt, kDmoCap, sl.d_call), "qrl_dmr_rx_process");
+            if (sl.rep) chk(qrl_dmr_rx_process_slots(d_call_rx, cs, sl.d_l2, sl.d_info, fcnt, N, kDmoCap, sl.d_call), "qrl_dmr_rx_process_slots");
+            else chk(qrl_dmr_rx_process(d_call_rx, cs, sl.d_l2, fcnt, kDmoCap, sl.d_call), "qrl_dmr_rx_process");
             hchk(hipMemcpyAsync(sl.h_call, sl.d_call, N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
         }
     }
@@ -450,6 +487,10 @@ void gr_demod_base_hip::harvest(int which)
                 if (sl.l2) {
                     const uint8_t* r2 = sl.h_l2 + ((size_t)s * kDmoCap + i) * QRL_DMR_L2_RECORD_BYTES;
                     d_boxl[s].emplace_back(r2, r2 + QRL_DMR_L2_RECORD_BYTES);
+                }
+                if (sl.rep) {
+                    const uint8_t* r4 = sl.h_info + ((size_t)s * kDmoCap + i) * QRL_DMR_SINK_INFO_BYTES;
+                    d_boxi[s].emplace_back(r4, r4 + QRL_DMR_SINK_INFO_BYTES);
                 }
                 if (sl.call) {
                     const uint8_t* r3 = sl.h_call + ((size_t)s * kDmoCap + i) * QRL_DMR_RX_RECORD_BYTES;
@@ -646,6 +687,14 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRDecoded(int str
     std::lock_guard<std::mutex> g(d_mutex);
     std::vector<std::vector<unsigned char>> out;
     out.swap(d_boxl[stream]);
+    return out;
+}
+std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRSlotInfo(int stream)
+{
+    std::lock_guard<std::mutex> g(d_mutex);
+    std::vector<std::vector<unsigned char>> out;
+    if (stream < 0 || stream >= d_n) return out;
+    out.swap(d_boxi[stream]);
     return out;
 }
 std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRCallEvents(int stream)
@@ -1137,6 +1186,8 @@ bool gr_modem_hip::demodulate(int stream)   // gr_modem.cpp:1019-1117
         if (!decoded.empty() && _ev.dmrFramesDecoded) _ev.dmrFramesDecoded(stream, decoded);
         auto events = _gr_demod_base->getDMRCallEvents(stream);   // set_dmr_call: what DMRControl::addFrames makes of each of them, per-stream state on the device
         if (!events.empty() && _ev.dmrCallEvents) _ev.dmrCallEvents(stream, events);
+        auto info = _gr_demod_base->getDMRSlotInfo(stream);       // set_dmr_repeater: the slot record of each of them (CACH, timeslot, end_bit)
+        if (!info.empty() && _ev.dmrSlotInfo) _ev.dmrSlotInfo(stream, info);
         return true;
     }
     const bool two = modem_two_branches(_modem_type_rx);

@@ -88,6 +88,14 @@ public:
     // outside 0..15 (the C ABI's QRL_ERR_ARG).
     void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false);
     std::vector<std::vector<unsigned char>> getDMRCallEvents(int stream = 0);
+    // The reference's getDMRData(bool dmo) choice (src/gr/gr_demod_base.cpp:947-966): off (the default) getDMRData returns the bursts of the DMO
+    // slicer, gr_dmr_dmo_sink; on, those of the repeater-mode sink gr_dmr_sink on port 2 (qrl_dmr_sink_process: BS / MS sync on the hard bits, the
+    // CACH, two slot contexts), in the same 40-byte record, and set_dmr_l2 / set_dmr_call work on them: sink -> layer 2 -> qrl_dmr_rx_process_slots
+    // in repeater mode on `timeslot`, queued on the copy stream with no host synchronisation.  Every burst then also has a 16-byte slot record
+    // (QRL_DMR_SINK_INFO_BYTES; dmr_frame_hip(record80, slot_info16) reads it): getDMRSlotInfo.  The sink's state lives on the device and is
+    // carried from work() to work(); set_mode and switching it on start it afresh.  Throws std::runtime_error for a timeslot outside 1..2.
+    void set_dmr_repeater(bool on, int timeslot = 1);
+    std::vector<std::vector<unsigned char>> getDMRSlotInfo(int stream = 0);
     uint64_t dmr_bursts_dropped() const { return d_dmo_dropped; }        // bursts beyond the 16-per-call record buffer (a call longer than 0.48 s of signal)
     // analogue voice modes (NBFM2500 / NBFM5000 / AM5000 / WBFM): port 1 = audio at 8 ksps (gr_demod_base::getAudio :968-976; caller deletes)
     std::vector<float>* getAudio(int stream = 0);
@@ -164,6 +172,9 @@ private:
     bool d_l2_on = false, d_l2_fec = true;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxe;   // call records, one per record of d_boxd while set_dmr_call is on
     qrl_dmr_rx* d_call_rx = nullptr; bool d_call_on = false;
+    std::vector<std::vector<std::vector<unsigned char>>> d_boxi;   // slot records, one per record of d_boxd while set_dmr_repeater is on
+    qrl_dmr_sink* d_sink = nullptr; bool d_rep_on = false; int d_rep_slot = 1;
+    void apply_call_mode();                                        // the tracker's mode follows set_dmr_repeater
     uint64_t d_dmo_dropped = 0;   // DMR bursts found beyond the per-call record buffer (16 per stream and call): not delivered
 };
 
@@ -263,6 +274,7 @@ struct gr_modem_events {
     std::function<void(int stream, std::vector<float>* pcm)> pcmAudio;   // analogue modes (gr_modem::pcmAudio); the slot owns pcm
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records80)> dmrFramesDecoded;   // the same bursts through DMR layer 2 (set_dmr_l2)
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records128)> dmrCallEvents;     // and through the call layer (set_dmr_call)
+    std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records16)> dmrSlotInfo;        // their slot records (set_dmr_repeater)
 };
 
 class gr_modem_hip {
@@ -292,6 +304,9 @@ public:
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
     // the DMR receive call layer on the device, off by default, behind set_dmr_l2: dmrCallEvents(stream, records128) fires beside dmrFramesDecoded
     void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false) { if (_gr_demod_base) _gr_demod_base->set_dmr_call(on, colour_code, promiscuous); }
+    // the reference's getDMRData(bool dmo) choice: on, dmrFrames / dmrFramesDecoded / dmrCallEvents deliver the bursts of the repeater-mode sink
+    // (gr_dmr_sink on port 2) and dmrSlotInfo(stream, records16) fires beside them; off by default (the demodulator's set_dmr_repeater)
+    void set_dmr_repeater(bool on, int timeslot = 1) { if (_gr_demod_base) _gr_demod_base->set_dmr_repeater(on, timeslot); }
     // DMR voice bursts built on the device from a call descriptor and codec bytes (the modulator's setDMRCall / txDMRVoice): what
     // gr_modem::transmitDMR does through DMRControl::getTxAudio and setDMRData (src/gr_modem.cpp:766-802)
     void setDMRCall(const uint8_t* descriptor40, int stream = 0) { if (_gr_mod_base) _gr_mod_base->setDMRCall(descriptor40, stream); }
