@@ -271,11 +271,19 @@ class Cluster:
         self.front = q.Channelizer(ctx, num_channels, batch=streams_local, max_chunk=max_chunk, _handle=self.L.qrl_cluster_front(self.h))
         self.tail = q.Channelizer(ctx, 1, batch=self.rows, max_chunk=max_chunk // num_channels, form=3, _handle=self.L.qrl_cluster_tail(self.h))
 
+    def _behind_torch(self, iq):
+        """iq is a torch tensor: whatever produced it (a .contiguous() copy, an upload) is queued on torch's current stream, which the channelizer's
+        own non-blocking stream does not follow by itself.  The channelizer waits for it ON THE DEVICE (an event, no host synchronisation)."""
+        import torch
+        self.front.wait_for(torch.cuda.current_stream(iq.device).cuda_stream)
+
     def step_async(self, iq):
         t = self.tail
+        self._behind_torch(iq)
         _ck(self.L.qrl_cluster_step(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1], t.out.data_ptr(), t.cap, t.counts.data_ptr()), "qrl_cluster_step")
 
     def channelize(self, iq):
+        self._behind_torch(iq)
         _ck(self.L.qrl_cluster_channelize(self.h, iq.data_ptr(), iq.stride(0), iq.shape[1]), "qrl_cluster_channelize")
 
     def exchange(self):

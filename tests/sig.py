@@ -35,6 +35,12 @@ MODES = {
     "4fsk100k": (orc.mod_4fsk, dict(sps=2, filter_width=125000, fm=True), bytes([0xDE, 0x98, 0xAA]), 1516, 300.0, 16.0),
     "bpsk1k": (orc.mod_bpsk, dict(sps=500, filter_width=1500), bytes([0xB5]), 4, 3.0, -6.0),
     "bpsk2k": (orc.mod_bpsk, dict(sps=250, filter_width=2800), bytes([0xED, 0x89, 0xAA]), 7, 3.0, -4.0),
+    # the 40 ksps 2FSK / GMSK receivers and 2FSK-10k FM (2/25 resampler in front of the FLL): the modulator arguments of csrc/tx.cpp's mode
+    # table; the SNRs are levels at which the oracle alone returns the frames (tests/test_oracle.py::test_loopback_2fsk_gmsk_40k_and_10kfm)
+    "2fsk2k": (orc.mod_2fsk, dict(sps=25, filter_width=4000, fm=False), bytes([0xED, 0x89, 0xAA]), 7, 137.0, -5.0),
+    "2fsk2kfm": (orc.mod_2fsk, dict(sps=25, filter_width=4000, fm=True), bytes([0xED, 0x89, 0xAA]), 7, 137.0, -5.0),
+    "2fsk10kfm": (orc.mod_2fsk, dict(sps=5, filter_width=25000, fm=True), bytes([0xED, 0x89, 0xAA]), 47, 137.0, 4.0),
+    "gmsk2k": (orc.mod_gmsk, dict(sps=50, filter_width=4000), bytes([0xED, 0x89, 0xAA]), 7, 137.0, -5.0),
 }
 
 
@@ -63,11 +69,17 @@ SPEC_CLEAN = Impair(0.37, 20.0, None, name="survey8d_modesnr")   # same timing, 
 # (orc.loop_clamp_hits, tests/test_channel_8d.py): whether a loop reaches its clamp depends on its bandwidth and on the stream's length
 # (symbol_sync_cc of QPSK-250k: max_dev 8e-4 sample behind a loop bandwidth of 2 pi / 25000 needs > 1e5 symbols; clock_recovery_mm_cc of the
 # BPSK chains: gain_omega 2.5e-5 against a limit of 1e-3 omega needs thousands), so the table carries the frame count too.
+# The 40 ksps receivers (symbol_sync_ff max_dev 200 / symbol rate = 0.05 of 10 samples: 5000 ppm) measured on seed 8, two frames: 2FSK-2k 142 hits at
+# +5000 ppm (97 at -5000, none at +-2000, +-10000, +-15000: past twice the limit the loop no longer follows and slips instead), 2FSK-2k FM 191 at +10000
+# (111 at -10000, 15 / 18 at +-5000), GMSK-2k 367 at +10000 (268 at -10000, 46 / 55 at +-5000).  2FSK-10k FM (max_dev 0.01 of 4 samples behind a loop
+# bandwidth of 2 pi / 2000) reaches its limiter in NO two-frame stream up to +-30000 ppm, though the symbol count moves (1802 .. 1912); from three frames on
+# it does at +5000 ppm: 466 hits in 3 frames, 1184 in 4, 1948 in 5 -- hence 4 frames.
 # (sig mode, clock error in ppm, frames per stream, minimum limiter hits of one stream in the oracle)
 CLAMP_CASES = {
     "2fsk1k": (15000.0, 2, 100), "gmsk10k": (-15000.0, 2, 300), "4fsk2kfm": (-5000.0, 2, 5), "4fsk100k": (-15000.0, 2, 10000),
     "4fsk2k": (5000.0, 2, 10), "qpsk20k": (15000.0, 2, 30), "qpsk250k": (1000.0, 12, 50000), "bpsk2k": (3000.0, 30, 500),
     "bpsk1k": (3000.0, 30, 200),
+    "2fsk2k": (5000.0, 2, 70), "2fsk2kfm": (10000.0, 2, 95), "gmsk2k": (10000.0, 2, 180), "2fsk10kfm": (5000.0, 4, 600),
 }
 
 

@@ -46,6 +46,8 @@ DEMODS = {
     "2fsk1k": (orc.demod_2fsk, dict(sps=10, filter_width=2000, fm=False)), "gmsk10k": (orc.demod_gmsk, dict(sps=1, filter_width=20000)),
     "4fsk2kfm": (orc.demod_4fsk, dict(sps=5, filter_width=3000, fm=True)), "4fsk100k": (orc.demod_4fsk, dict(sps=2, filter_width=125000, fm=True)),
     "4fsk2k": (orc.demod_4fsk, dict(sps=5, filter_width=4000, fm=False)), "bpsk1k": (orc.demod_bpsk, dict(sps=10)), "bpsk2k": (orc.demod_bpsk, dict(sps=5)),
+    "2fsk2k": (orc.demod_2fsk, dict(sps=5, filter_width=4000, fm=False)), "2fsk2kfm": (orc.demod_2fsk, dict(sps=5, filter_width=4000, fm=True)),
+    "2fsk10kfm": (orc.demod_2fsk, dict(sps=1, filter_width=25000, fm=True)), "gmsk2k": (orc.demod_gmsk, dict(sps=5, filter_width=4000)),
 }
 
 

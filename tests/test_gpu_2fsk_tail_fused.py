@@ -3,7 +3,8 @@ bit: call sizes around the kernel's 16-sample window and its 104-sample history 
 decimated samples per call), a full workgroup beside a nearly empty one, switching between the fused kernel and the unfused pair
 (QRL_OPT_FLL_SLIM) from call to call -- both find their history in the r2l ring -- and the serial order of a call.
 
-2FSK-2k (QRL_MODEM_2FSK2K, 40 ksps, the same tap counts) is not here: tests/sig.py has no modulator entry for that mode."""
+Both modes that run the kernel: 2FSK-1k (20 ksps behind the 1:50 first decimator, 10 samples per symbol) and 2FSK-2k (40 ksps behind the 1:25 one, the
+same 41 / 41 / 25 tap counts with other taps, FLL band edges and clock-loop gains), the second with call sizes that give the same decimated counts."""
 import numpy as np
 import pytest
 
@@ -12,26 +13,42 @@ import sig
 
 pytestmark = pytest.mark.gpu
 
-RATE, OFFSET, MODEM_2FSK1K = 1000000, 1200.0, 18
-# samples per call at 1 Msps, decimation 50
-CALLS = (50, 750, 800, 850, 5150, 5200, 5250, 2, 20000, 33334)
+RATE, OFFSET = 1000000, 1200.0
 NS = 64   # streams per workgroup of k_2fsk_tail (QRL_TAIL_NS in kernels_2fsk_tail.hip)
 
 
+class Case:
+    """one mode that runs k_2fsk_tail: sig.MODES name, modem type, the oracle receiver's arguments, samples per call at 1 Msps"""
+
+    def __init__(self, mode, modem, sps, filter_width, calls):
+        self.mode, self.modem, self.sps, self.filter_width, self.calls = mode, modem, sps, filter_width, calls
+
+
+CASES = [
+    Case("2fsk1k", 18, 10, 2000, (50, 750, 800, 850, 5150, 5200, 5250, 2, 20000, 33334)),    # decimation 50
+    Case("2fsk2k", 17, 5, 4000, (25, 375, 400, 425, 2575, 2600, 2625, 2, 10000, 16668)),     # decimation 25: the same decimated counts
+]
+
+
+@pytest.fixture(scope="module", params=CASES, ids=[c.mode for c in CASES])
+def case(request):
+    return request.param
+
+
 @pytest.fixture(scope="module")
-def stream():
-    x, _ = sig.make_stream("2fsk1k", nframes=2, device_rate=RATE, rx_offset_hz=OFFSET, impair=sig.SPEC)
+def stream(case):
+    x, _ = sig.make_stream(case.mode, nframes=2, device_rate=RATE, rx_offset_hz=OFFSET, impair=sig.SPEC)
     return x[:x.size & ~1].astype(np.complex64)
 
 
 @pytest.fixture(scope="module")
-def refs(stream):
+def refs(case, stream):
     """oracle output of stream b (the base stream shifted circularly by 3001 b samples), computed once per b"""
     cache = {}
 
     def get(b):
         if b not in cache:
-            cache[b] = orc.demod_2fsk(orc.frontend(np.roll(stream, 3001 * b), RATE, OFFSET), sps=10, filter_width=2000, fm=False)
+            cache[b] = orc.demod_2fsk(orc.frontend(np.roll(stream, 3001 * b), RATE, OFFSET), sps=case.sps, filter_width=case.filter_width, fm=False)
         return cache[b]
     return get
 
@@ -40,12 +57,13 @@ def _batch(stream, B):
     return np.stack([np.roll(stream, 3001 * b) for b in range(B)])
 
 
-def _run_calls(qrl_ctx, iq, options=(), slim_pattern=None):
-    """iq [B, N] through one handle in calls of CALLS (cycled); slim_pattern: QRL_OPT_FLL_SLIM values set before successive calls"""
+def _run_calls(qrl_ctx, case, iq, options=(), slim_pattern=None):
+    """iq [B, N] through one handle in calls of case.calls (cycled); slim_pattern: QRL_OPT_FLL_SLIM values set before successive calls"""
     import torch
     import qradiolink_amd as q
+    CALLS = case.calls
     B, N = iq.shape
-    dem = q.Demod(qrl_ctx, MODEM_2FSK1K, batch=B, max_chunk=max(CALLS), device_samp_rate=RATE, carrier_offset_hz=OFFSET)
+    dem = q.Demod(qrl_ctx, case.modem, batch=B, max_chunk=max(CALLS), device_samp_rate=RATE, carrier_offset_hz=OFFSET)
     for opt, val in options:
         dem.set_option(opt, val)
     dev = torch.from_numpy(iq).cuda()
@@ -86,17 +104,17 @@ def _compare(out, refs, B):
 
 
 @pytest.mark.parametrize("B", [1, 3, NS + 1])
-def test_call_edges(qrl_ctx, stream, refs, B):
-    out = _run_calls(qrl_ctx, _batch(stream, B))
+def test_call_edges(qrl_ctx, case, stream, refs, B):
+    out = _run_calls(qrl_ctx, case, _batch(stream, B))
     _compare(out, refs, B)
 
 
-def test_switching_between_fused_and_unfused_kernels(qrl_ctx, stream, refs):
-    out = _run_calls(qrl_ctx, _batch(stream, 3), slim_pattern=(1, 0))
+def test_switching_between_fused_and_unfused_kernels(qrl_ctx, case, stream, refs):
+    out = _run_calls(qrl_ctx, case, _batch(stream, 3), slim_pattern=(1, 0))
     _compare(out, refs, 3)
 
 
-def test_serial_order(qrl_ctx, stream, refs):
+def test_serial_order(qrl_ctx, case, stream, refs):
     import qradiolink_amd as q
-    out = _run_calls(qrl_ctx, _batch(stream, 3), options=[(q.OPT_OVERLAP, 0)])
+    out = _run_calls(qrl_ctx, case, _batch(stream, 3), options=[(q.OPT_OVERLAP, 0)])
     _compare(out, refs, 3)

@@ -109,7 +109,7 @@ def _bits_with_frames(rng, modem, nframes, noise_bits=200):
     return np.concatenate(parts)
 
 
-@pytest.mark.parametrize("modem", [18, 22, 17, 26, 27, 5, 40])
+@pytest.mark.parametrize("modem", [18, 22, 17, 26, 27, 5, 40, 2])
 @pytest.mark.parametrize("ncuts", [1, 7])
 def test_framesync_bit_exact(qrl_ctx, modem, ncuts):
     import torch
@@ -183,7 +183,7 @@ def _call_sizes(kind, n, first_sync, frame_bits):
     return [c for c in sizes if c > 0]
 
 
-@pytest.mark.parametrize("modem", [18, 22, 17, 26, 27, 5, 40])
+@pytest.mark.parametrize("modem", [18, 22, 17, 26, 27, 5, 40, 2])
 @pytest.mark.parametrize("kind", ["129s", "mixed", "tiny"])
 def test_framesync_across_many_launches(qrl_ctx, modem, kind):
     """an open frame's bits wait in bitbuf (carry / fstart of k_framesync) across MANY launches, not two: calls far shorter than a frame, down

@@ -5,7 +5,9 @@ max_chunk 40000), the values of qrl_demod_out_caps, qrl_demod_audio_cap and qrl_
 literals were recorded from the build BEFORE the two modem_type switches became one table and the five derivations of the counts one
 function, so they pin the function and the table's family, kind and sps columns against the old code, not against themselves.  The caps do
 not depend on filter_width, fm, m17 or lsb (2FSK2KFM and 2FSK2K, DMR and M17, USB and LSB have equal rows): those four columns are pinned by the
-per-mode output tests (test_gpu_parity.py and its neighbours), not here.  No kernel is launched."""
+per-mode output tests, not here: every row's receiver runs against the oracle's chain with the row's literals in test_gpu_parity.py (the digital
+modes, QRL_MODEM_QPSKVIDEO against QPSK250K's chain and handle; NBFM, AM, WBFM, SSB, DMR, M17 and BPSK8 in tests of their own there).  No kernel is
+launched."""
 import ctypes as C
 
 import pytest

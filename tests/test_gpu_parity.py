@@ -24,6 +24,12 @@ def _run(qrl_ctx, mode_name, modem, device_rate, offset, B, chunk, nframes=3, se
 
 def _oracle(mode_name, x, device_rate, offset):
     fe = orc.frontend(x, device_rate, offset)
+    if mode_name in ("2fsk2k", "2fsk2kfm"):
+        return orc.demod_2fsk(fe, sps=5, filter_width=4000, fm=mode_name.endswith("fm"))
+    if mode_name == "2fsk10kfm":
+        return orc.demod_2fsk(fe, sps=1, filter_width=25000, fm=True)
+    if mode_name == "gmsk2k":
+        return orc.demod_gmsk(fe, sps=5, filter_width=4000)
     if mode_name.startswith("2fsk"):
         return orc.demod_2fsk(fe, sps=10, filter_width=2500 if mode_name.endswith("fm") else 2000, fm=mode_name.endswith("fm"))
     if mode_name == "gmsk10k":
@@ -86,6 +92,12 @@ PARITY_LIST = [
     ("4fsk100k", 27, 1000000, 1 << 20),     # 1:2 decimation to 500 ksps, 5 samples per symbol
     ("bpsk1k", 24, 1000000, 1 << 21),       # gr_demod_bpsk: FLL(32 taps) -> RRC -> agc2 -> clock_recovery_mm_cc -> costas(2)
     ("bpsk2k", 0, 2000000, 1 << 22),
+    ("2fsk2k", 17, 1000000, 1 << 21),       # k_2fsk_tail at 40 ksps behind the 1:25 first decimator (sps 5: other taps and clock-loop gains than 2FSK-1k)
+    ("2fsk2k", 17, 2000000, 1 << 22),       # the 1:25 plan reading the front-end ring
+    ("2fsk2kfm", 15, 1000000, 1 << 21),     # FM branch at 40 ksps: FLL, filter, quadrature demodulator, 351-tap RRC
+    ("2fsk10kfm", 19, 1000000, 1 << 20),    # 2/25 resampler to 80 ksps IN FRONT OF THE FLL (no other mode), 13-tap filter, 501-tap RRC
+    ("2fsk10kfm", 19, 4000000, 1 << 22),    # the same behind the 4:1 front end
+    ("gmsk2k", 20, 1000000, 1 << 21),       # GMSK tail at 40 ksps behind the 1:25 first decimator
 ]
 
 
@@ -112,6 +124,10 @@ def test_chain_bit_exact_survey_8d_channel(qrl_ctx, mode_name, modem, rate, chun
     ("gmsk1k", 21, 2000000, 100002), ("qpsk250k", 26, 1000000, 33334), ("qpsk250k", 26, 100000000, 3000000), ("qpsk2k", 7, 1000000, 60000),
     ("qpsk20k", 1, 2000000, 100002), ("4fsk2k", 3, 1000000, 50000), ("4fsk2kfm", 5, 1000000, 50000), ("4fsk10kfm", 4, 4000000, 200000),
     ("4fsk100k", 27, 1000000, 30000), ("bpsk1k", 24, 1000000, 65536), ("bpsk2k", 0, 2000000, 100002),
+    ("2fsk2k", 17, 1000000, 33334), ("2fsk2kfm", 15, 1000000, 12502), ("gmsk2k", 20, 1000000, 50000),
+    ("2fsk10kfm", 19, 1000000, 6400),       # 512 outputs per call at 80 ksps: the first size at which k_fir_fff runs its tiled form
+    ("2fsk10kfm", 19, 1000000, 6250),       # 500 outputs per call: the per-thread form
+    ("2fsk10kfm", 19, 4000000, 100002),
 ])
 def test_chain_bit_exact_survey_8d_channel_cut_into_calls(qrl_ctx, mode_name, modem, rate, chunk):
     offset = 25000.0 if rate >= 2000000 else 1200.0
@@ -130,6 +146,7 @@ def test_chain_bit_exact_survey_8d_channel_cut_into_calls(qrl_ctx, mode_name, mo
     ("gmsk10k", 22, 1000000, 30000), ("gmsk10k", 22, 25000000, 750000),
     ("4fsk2kfm", 5, 1000000, 50000), ("4fsk100k", 27, 1000000, 30000),
     ("bpsk1k", 24, 1000000, 1 << 21), ("bpsk2k", 0, 1000000, 200000),
+    ("2fsk2k", 17, 1000000, 33334), ("2fsk2kfm", 15, 1000000, 12502), ("gmsk2k", 20, 1000000, 50000), ("2fsk10kfm", 19, 1000000, 6400),
 ])
 def test_chain_bit_exact_clock_error_past_the_loop_clamp(qrl_ctx, mode_name, modem, rate, chunk):
     offset = 25000.0 if rate >= 2000000 else 1200.0
@@ -401,6 +418,75 @@ def test_loopback_frames_recovered(qrl_ctx):
     dem.close()
     got = [sum((bytes([0xAA]) + p) in sig.find_frames(out[k][0], bytes([0xED, 0x89]), 384) for p in payloads) for k in ("bits_a", "bits_b")]
     assert max(got) == len(payloads), got
+
+
+# the frames the ORACLE alone returns from the same streams (tests/test_oracle.py::test_loopback_2fsk_gmsk_40k_and_10kfm): all five, or all but the
+# first where the 351- / 501-tap RRC and the loops are still settling behind the 8-byte preamble
+@pytest.mark.parametrize("mode_name,modem,want", [("2fsk2k", 17, 5), ("2fsk2kfm", 15, 4), ("2fsk10kfm", 19, 4), ("gmsk2k", 20, 5)])
+def test_loopback_frames_recovered_40k_and_10kfm(qrl_ctx, mode_name, modem, want):
+    """mod -> channel -> HIP demod returns the transmitted frames of the 40 ksps 2FSK / GMSK modes and of 2FSK-10k FM through the gr_modem-style
+    sync search: a check of the device chain that does not go through the oracle's demodulator."""
+    import torch
+    import qradiolink_amd as q
+    y, payloads = sig.make_stream(mode_name, nframes=5, device_rate=1000000, seed=5)
+    y = y[: y.size & ~1]
+    dem = q.Demod(qrl_ctx, modem, batch=1, max_chunk=y.size)
+    out = q.collect(dem, torch.from_numpy(y[None, :]).cuda(), y.size)
+    dem.close()
+    nbits = (sig.MODES[mode_name][3] + 1) * 8
+    got = [sum((bytes([0xAA]) + p) in sig.find_frames(out[k][0], bytes([0xED, 0x89]), nbits) for p in payloads) for k in ("bits_a", "bits_b")]
+    assert max(got) >= want, got
+
+
+MIXED_CALLS_2FSK10KFM = (50, 6250, 6400, 6500, 2, 12502, 33334, 24)   # samples per call at 1 Msps; 2 / 25 of them come out at 80 ksps
+
+
+@pytest.mark.parametrize("overlap", [1, 0])
+def test_2fsk10kfm_mixed_call_sizes_through_one_handle(qrl_ctx, overlap):
+    """2FSK-10k FM (2/25 resampler -> FLL -> 13-tap filter -> quadrature demodulator -> 501-tap RRC) through ONE handle in calls of changing size: calls
+    far shorter than the RRC's history (50 samples = 4 outputs, 24 = 2, 2 = 0 or 1), k_fir_fff's per-thread form (500 outputs) and its tiled form (512,
+    520 and more) alternating on the same ring, and the resampler's phase carried across sizes that are no multiple of 25.  The whole stream
+    equals the oracle's, in the overlapped order of the 2FSK family and in the serial one."""
+    import torch
+    import qradiolink_amd as q
+    B, rate, offset = 2, 1000000, 1200.0
+    iq = sig.make_batch("2fsk10kfm", B, nframes=3, device_rate=rate, rx_offset_hz=offset, seed=14, impair=sig.SPEC)
+    N = iq.shape[1]
+    dem = q.Demod(qrl_ctx, 19, batch=B, max_chunk=max(MIXED_CALLS_2FSK10KFM), device_samp_rate=rate, carrier_offset_hz=offset)
+    dem.set_option(q.OPT_OVERLAP, overlap)
+    dev = torch.from_numpy(iq).cuda()
+    names = ("filtered", "constellation", "bits_a", "bits_b")
+    parts = {k: [[] for _ in range(B)] for k in names}
+    s = k = 0
+    while s < N:
+        n = min(MIXED_CALLS_2FSK10KFM[k % len(MIXED_CALLS_2FSK10KFM)], N - s)
+        part = torch.zeros((B, n + 2), dtype=dev.dtype, device=dev.device)   # a buffer of its own: even pitch, 16-byte aligned rows
+        part[:, :n] = dev[:, s:s + n]
+        out = dem.process(part[:, :n])
+        cnt = out["counts"].cpu().numpy()
+        for j, name in enumerate(names):
+            host = out[name].cpu().numpy()
+            for b in range(B):
+                parts[name][b].append(host[b, :cnt[b, j]].copy())
+        s += n
+        k += 1
+    dem.close()
+    assert k >= 2 * len(MIXED_CALLS_2FSK10KFM)   # every call size came up twice
+    _compare(iq, {name: [np.concatenate(v) for v in parts[name]] for name in names}, "2fsk10kfm", rate, offset)
+
+
+def test_qpskvideo_is_the_qpsk250k_chain(qrl_ctx):
+    """QRL_MODEM_QPSKVIDEO (2) has a mode row of its own with QPSK-250k's literals (gr_demod_base.cpp:223-224): on the same input it gives the oracle's
+    QPSK-250k output, and its four ports and counts are those of modem 26."""
+    offset = 1200.0
+    outs = {}
+    for modem in (2, 26):
+        iq, outs[modem] = _run(qrl_ctx, "qpsk250k", modem, 1000000, offset, B=3, chunk=1 << 20, nframes=2)
+    _compare(iq, outs[2], "qpsk250k", 1000000, offset)
+    for port in ("filtered", "constellation", "bits_a", "bits_b"):
+        for b in range(3):
+            got, want = outs[2][port][b], outs[26][port][b]
+            assert got.size == want.size and np.array_equal(got.view(np.uint8), want.view(np.uint8)), (port, b)
 
 
 # ---- DMR / 4FSK symbol demodulator (gr_demod_dmr, the in-tree "4FSK demod" of BASELINE config 4)

@@ -207,6 +207,34 @@ def test_cluster_with_the_rccl_transport_on_one_rank_equals_the_plain_receiver(q
         ex.close()
 
 
+def test_cluster_input_is_ordered_behind_torchs_stream(qrl_ctx):
+    """sharding.Cluster takes a torch tensor and runs the channelizer on a non-blocking stream of its own: the step must wait, on the device, for what
+    torch's current stream still has queued to produce that tensor.  The input is filled in (from zeros) behind a few milliseconds of other work on
+    torch's stream and handed over at once, as the tests above hand over a fresh .contiguous() copy; a channelizer that started early would read zeros."""
+    import torch
+    import test_gpu_chan as tg
+    M, B, n = 64, 2, 64 * 600
+    iq = tg._wideband(M, n, seed=94, nstreams=B)
+    d = torch.from_numpy(iq).cuda()
+    ref = _unsharded(qrl_ctx, d, M, [n], 0.5)
+    ex = sharding.Exchange.self_()
+    cl = sharding.Cluster(qrl_ctx, ex, M, B, n)
+    cl.tail.calibrate_rssi(0.5)
+    cl.tail.enable_4fsk()
+    buf = torch.zeros_like(d)
+    busy = torch.ones(1 << 26, dtype=torch.float32, device=d.device)
+    torch.cuda.synchronize()
+    for _ in range(20):
+        busy.mul_(1.0001)            # 20 passes over 256 MB on torch's stream in front of the copy
+    buf.copy_(d)
+    cl.step_async(buf)
+    cl.sync()
+    _compare_rank(cl.tail, ref[0], 0, 1, B, M)
+    assert np.abs(ref[0][0]).max() > 1000
+    cl.close()
+    ex.close()
+
+
 @pytest.mark.parametrize("world,Bl", [(8, 1), (4, 2)])
 def test_emulated_ranks_with_the_local_group_transport_equal_the_unsharded_receiver(qrl_ctx, world, Bl):
     """the multi-GPU step at the 8-rank SHAPE on one device.  `world` chan_cluster objects of one process behind qrl_host::local_group -- a

@@ -473,6 +473,31 @@ def test_loopback_4fsk_bpsk(mode):
     assert r["filtered"].size > 0 and r["constellation"].size > 0
 
 
+MODES_40K_10KFM = {
+    # mode: (oracle receiver, frames that may be lost)
+    "2fsk2k": (lambda fe: orc.demod_2fsk(fe, sps=5, filter_width=4000, fm=False), 0),
+    "gmsk2k": (lambda fe: orc.demod_gmsk(fe, sps=5, filter_width=4000), 0),
+    # the FM variants: the 351- / 501-tap RRC and the loops are still settling behind the 8-byte preamble, the first frame is lost
+    "2fsk2kfm": (lambda fe: orc.demod_2fsk(fe, sps=5, filter_width=4000, fm=True), 1),
+    "2fsk10kfm": (lambda fe: orc.demod_2fsk(fe, sps=1, filter_width=25000, fm=True), 1),
+}
+
+
+@pytest.mark.parametrize("impair", [None, sig.SPEC], ids=["default", "survey8d"])
+@pytest.mark.parametrize("seed,nframes", [(3, 3), (5, 5), (104, 3)])
+@pytest.mark.parametrize("mode", sorted(MODES_40K_10KFM))
+def test_loopback_2fsk_gmsk_40k_and_10kfm(mode, seed, nframes, impair):
+    """The stimulus of the 40 ksps 2FSK / GMSK receivers and of 2FSK-10k FM (sig.MODES) is one the oracle alone decodes, in the default channel and
+    in SURVEY 8(d)'s: what makes the device loopback of tests/test_gpu_parity.py::test_loopback_frames_recovered_40k_and_10kfm a statement"""
+    dem, may_lose = MODES_40K_10KFM[mode]
+    y, payloads = sig.make_stream(mode, nframes, device_rate=1000000, rx_offset_hz=0.0, seed=seed, impair=impair)
+    r = dem(orc.frontend(y, 1000000, 0.0))
+    nbits = (sig.MODES[mode][3] + 1) * 8
+    got = max(sum((b"\xAA" + p) in sig.find_frames(r[k], b"\xED\x89", nbits) for p in payloads) for k in ("bits_a", "bits_b"))
+    assert got >= nframes - may_lose, (mode, seed, got)
+    assert r["filtered"].size > 0 and r["constellation"].size > 0
+
+
 def test_4level_slicer_follows_constellation_rect_sectors():
     """symbol_sync_ff on a constant input: the decision is the sector (int)(x + 2) clamped to [0, 3], so exact zeros
     (the start-up transient) slice to +0.5, not -0.5"""
