@@ -488,7 +488,7 @@ int qrl_deframer_sync(qrl_deframer* d);
  * dropped (out_cap >= n/8 + qrl_framesync_frame_bytes() + 96 + 16 per frame never overflows: a frame begun in earlier calls may
  * complete in this one).  Search state, a partial frame
  * and the _modem_sync counter carry across calls.  QRL_MODEM_M17: the M17 sync words (LSF 0x55F7, stream 0xFF5D, EOT
- * 0x555D555D, :1186-1210) and 46-byte frames (:309-313); the M17 frame decoder itself stays on the host. */
+ * 0x555D555D, :1186-1210) and 46-byte frames (:309-313); qrl_m17_rx_process takes these records as they are. */
 typedef struct qrl_framesync qrl_framesync;
 int qrl_framesync_create(qrl_ctx* ctx, int modem_type, int batch, void* hip_stream, qrl_framesync** out);
 void qrl_framesync_destroy(qrl_framesync* f);
@@ -638,14 +638,84 @@ int qrl_bptc19696_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* payloads
  * frames: [n][48] (sync word + 46 bytes, as the frame synchroniser delivers them).  records: [n][QRL_M17_RECORD_BYTES] =
  * {type (M17FrameType: 0 preamble, 1 link setup, 2 stream, 4 unknown), LICH ok, payload[30] (30 LSF bytes | 18 stream-frame bytes),
  * LICH segment[6] (5 LSF bytes + segment number), 0, 0}.  The LSF reassembly from LICH segments (:130-147, per-stream state + CRC)
- * is host work: host/m17_frame_decoder_hip. */
+ * is qrl_m17_rx_process's on the device, or host/m17_frame_decoder_hip's above this call. */
 #define QRL_M17_RECORD_BYTES 40
 int qrl_m17_decode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* frames, size_t n, uint8_t* records);
 /* the inverse: replaces the per-frame work of M17FrameEncoder::encodeLsf / encodeStreamFrame (reference
  * src/M17/M17/M17FrameEncoder.cpp:52-118): records of the same layout (type 1: the 30 LSF bytes with their CRC; type 2: the 18
  * stream-frame bytes = frame number (EOS bit in its top bit) + 16 payload bytes, and the 6-byte LICH segment = 5 LSF bytes +
- * segment number) -> 48-byte frames.  Frame numbering, the LICH round robin and the LSF CRC are per-stream state: host work. */
+ * segment number) -> 48-byte frames.  Frame numbering, the LICH round robin and the LSF CRC are a function of the frame's index in its
+ * call: qrl_m17_call_start / _encode / _end below. */
 int qrl_m17_encode_frames(qrl_ctx* ctx, void* hip_stream, const uint8_t* records, size_t n, uint8_t* frames);
+
+/* ---- M17 link layer, receive: what gr_modem::processReceivedData does with the M17 frames of a stream (reference src/gr_modem.cpp:1370-1439)
+ * and what M17FrameDecoder keeps between them (src/M17/M17/M17FrameDecoder.cpp:37-43 reset, :111-117 decodeLSF, :119-159 decodeStream), per
+ * stream, on the device between calls: lsf[30], lsfFromLich[30], lsfSegmentMap, _m17_decoder_locked.  A fresh or reset handle is the decoder
+ * after reset() with the lock clear (the reference leaves lsfSegmentMap uninitialised before the first reset()).
+ * config: Settings::m17_can_rx 0..15, m17_decode_all_can 0 / 1 (src/gr_modem.cpp:1406, :1432); set_config holds from the next process on.
+ * qrl_m17_rx_process consumes the output of a QRL_MODEM_M17 frame synchroniser as qrl_framesync_process wrote it: record i of stream b at
+ * frames + b * frame_stride + 56 i = {u32 frame type, u32 nbytes | _modem_sync << 16, 46 payload bytes padded to 48}, i <
+ * min(counts[2 b + 1], cap_frames) (counts: the synchroniser's out_counts).  Asynchronous on hip_stream, two kernels: the per-frame decode
+ * of qrl_m17_decode_frames on every LSF / stream frame where it lies (an EOT frame is never decoded), then one lane per stream through the
+ * frames in order.  out: [batch][cap_frames][QRL_M17_RX_RECORD_BYTES], 16-byte aligned, one record per slot, zeros behind the count:
+ *   0..1   flags, little endian (QRL_M17_RX_*)      2  M17FrameType (1 link setup, 2 stream, EOT: 0xFF)      3  CAN
+ *   4..5   frame number of a stream frame, EOS bit 0x8000 included, little endian      6  LICH segment number      7  segment map after the frame
+ *   8..13  encoded source (M17LinkSetupFrame.cpp:49-52)      14..19  encoded destination
+ *   20     source text length, 21..30 the text of getSource() (decode_callsign, src/M17/M17/M17Callsign.cpp:70-105)
+ *   31     destination text length, 32..41 the text of getDestination() (src/M17/M17/M17LinkSetupFrame.cpp:83-97)
+ *   42..47 zero      48..63  the 16 payload bytes with QRL_M17_RX_AUDIO, else zero
+ * Bytes 3 and 8..41 are filled where the reference reads them: where lsf.valid().  A record whose nbytes is not 46, or whose frame type is
+ * none of the three M17 words, is passed over: its output record is zero and the state untouched.
+ * QRL_ERR_ARG before any device work: a null pointer, cap_frames 0, 56 * cap_frames > frame_stride, frames / frame_stride not multiples of
+ * 4 bytes, out not 16-byte aligned.  The calls of one handle share its state and its scratch array: the caller orders them (one stream, or
+ * events between streams).  The scratch array grows with the first call of a larger batch x cap_frames than any before: a hipFree and a
+ * hipMalloc, which wait for the device; every other call is asynchronous.
+ * qrl_m17_rx_get_state: asynchronous, out [batch][QRL_M17_RX_STATE_BYTES], 16-byte aligned = {_m17_decoder_locked, lsf.valid(), CAN, segment
+ * map, encoded source[6], encoded destination[6]}, the last three as the LSF holds them, valid or not. */
+#define QRL_M17_RX_RECORD_BYTES 64
+#define QRL_M17_RX_STATE_BYTES 16
+#define QRL_M17_FRAMESYNC_RECORD_BYTES 56
+#define QRL_M17_RX_FRAME 0x0001          /* an M17 frame went through processReceivedData */
+#define QRL_M17_RX_LSF_VALID 0x0002      /* lsf.valid() after the frame */
+#define QRL_M17_RX_INFO 0x0004           /* m17FrameInfoReceived(source, destination, CAN) */
+#define QRL_M17_RX_AUDIO 0x0008          /* digitalAudio(payload, 16) */
+#define QRL_M17_RX_END 0x0010            /* endAudioTransmission() + receiveEnd() */
+#define QRL_M17_RX_LICH_OK 0x0020        /* the four Golay words of the LICH decoded */
+#define QRL_M17_RX_LSF_FROM_LICH 0x0040  /* a LICH round completed with a good CRC and replaced the LSF */
+#define QRL_M17_RX_LOCKED 0x0080         /* _m17_decoder_locked after the frame */
+typedef struct qrl_m17_rx qrl_m17_rx;
+typedef struct { int can_rx; int decode_all_can; } qrl_m17_rx_config;
+int qrl_m17_rx_create(qrl_ctx* ctx, size_t batch, const qrl_m17_rx_config* config, qrl_m17_rx** out);
+void qrl_m17_rx_destroy(qrl_m17_rx* h);
+int qrl_m17_rx_reset(qrl_m17_rx* h, void* hip_stream);                               /* M17FrameDecoder::reset + the lock clear */
+int qrl_m17_rx_set_config(qrl_m17_rx* h, const qrl_m17_rx_config* config);
+int qrl_m17_rx_process(qrl_m17_rx* h, void* hip_stream, const uint8_t* frames, size_t frame_stride, const uint32_t* counts, size_t cap_frames,
+                       uint8_t* out);
+int qrl_m17_rx_get_state(qrl_m17_rx* h, void* hip_stream, uint8_t* out);
+/* the HIP stream of a frame synchroniser, to queue qrl_m17_rx_process behind qrl_framesync_process */
+void* qrl_framesync_stream(qrl_framesync* f);
+
+/* ---- M17 link layer, transmit: a call as a function of the frame index.  Stateless; device pointers; asynchronous on hip_stream.
+ * calls: [batch][QRL_M17_CALL_BYTES] descriptors = {0..8 source characters, 9 their number (10: more than nine), 10..18 destination
+ * characters, 19 their number, 20 CAN, 21 destination_type 0..4, zeros}.  The LSF is M17Transmitter::start's (reference
+ * src/M17/M17/M17Transmitter.cpp:46-72): encode_callsign as it stands (src/M17/M17/M17Callsign.cpp:26-68, not strict: an unknown character is
+ * digit 0, more than nine characters give the zero address), an empty destination with type 0 keeps the cleared LSF's 0xFF bytes, types 1..4
+ * the byte strings of setDestination(int) (src/M17/M17/M17LinkSetupFrame.cpp:59-81), type field stream 1, dataType 2, encType 0, CAN, the CRC.
+ * qrl_m17_call_start (gr_modem::startTransmission, src/gr_modem.cpp:687-697; M17Transmitter.cpp:74-105): out[b * out_stride ...] = 48 preamble
+ *   bytes 0x77, the LSF frame; 96 bytes.
+ * qrl_m17_call_encode (gr_modem::transmitM17Audio, src/gr_modem.cpp:868-884; M17Transmitter::send, M17Transmitter.cpp:108-143): slot i of stream b,
+ *   out[b * out_stride + i * slot_bytes ...], = stream frame k = first[b] + i (first NULL: 0) with payloads[b][i][16]: frame number k & 0x7FF,
+ *   LICH segment k % 6 of the call's LSF; 48 bytes and zeros up to slot_bytes >= 48.  A call can be cut anywhere.
+ * qrl_m17_call_end (gr_modem::endTransmission, src/gr_modem.cpp:718-729): out[b * out_stride ...] = the last frame (index first[b], zero
+ *   payload, EOS bit), the sixteen EOT bytes 0x55 0x5D; 64 bytes.
+ * Rows are whole multiples of the modulator's 3-byte block: qrl_mod_process (QRL_MODEM_M17) takes them as they are. */
+#define QRL_M17_CALL_BYTES 32
+#define QRL_M17_CALL_START_BYTES 96
+#define QRL_M17_CALL_END_BYTES 64
+int qrl_m17_call_start(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls, size_t batch, uint8_t* out, size_t out_stride);
+int qrl_m17_call_encode(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls, const uint8_t* payloads, const uint32_t* first, size_t batch, size_t n,
+                        uint8_t* out, size_t out_stride, size_t slot_bytes);
+int qrl_m17_call_end(qrl_ctx* ctx, void* hip_stream, const uint8_t* calls, const uint32_t* first, size_t batch, uint8_t* out, size_t out_stride);
 /* DMR layer 2, the stateless per-burst work behind the DMO slicer's mailbox (qrl_demod_set_dmo_output): what the reference does to every
  * burst gr_dmr_dmo_sink::get_data() returns -- DMRFrame::DMRFrame (slot type, Golay(20,8)), DMRFrame::validate (reference
  * src/DMR/dmrframe.cpp:115-246: BPTC(196,96) + RS(12,9) or CRC-CCITT per data type, the rate 3/4 trellis, the burst re-encoded from the

@@ -72,6 +72,10 @@ class _DmrRxConfig(C.Structure):
     _fields_ = [("color_code", C.c_int), ("promiscuous", C.c_int)]
 
 
+class _M17RxConfig(C.Structure):
+    _fields_ = [("can_rx", C.c_int), ("decode_all_can", C.c_int)]
+
+
 class _Out(C.Structure):
     _fields_ = [("filtered", C.c_void_p), ("filtered_cap", C.c_size_t), ("constellation", C.c_void_p),
                 ("constellation_cap", C.c_size_t), ("bits_a", C.c_void_p), ("bits_cap", C.c_size_t),
@@ -143,6 +147,16 @@ def load_library():
     lib.qrl_dmr_rx_get_state.argtypes = [vp, vp, vp]
     lib.qrl_dmr_rx_set_mode.argtypes = [vp, C.c_int, C.c_int]
     lib.qrl_dmr_rx_process_slots.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp]
+    lib.qrl_m17_rx_create.argtypes = [vp, sz, C.POINTER(_M17RxConfig), C.POINTER(vp)]
+    lib.qrl_m17_rx_destroy.argtypes = [vp]
+    lib.qrl_m17_rx_destroy.restype = None
+    lib.qrl_m17_rx_reset.argtypes = [vp, vp]
+    lib.qrl_m17_rx_set_config.argtypes = [vp, C.POINTER(_M17RxConfig)]
+    lib.qrl_m17_rx_process.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+    lib.qrl_m17_rx_get_state.argtypes = [vp, vp, vp]
+    lib.qrl_m17_call_start.argtypes = [vp, vp, vp, sz, vp, sz]
+    lib.qrl_m17_call_encode.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, sz]
+    lib.qrl_m17_call_end.argtypes = [vp, vp, vp, vp, sz, vp, sz]
     lib.qrl_demod_set_squelch.argtypes = [vp, C.c_double]
     lib.qrl_demod_set_agc.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_set_filter_width.argtypes = [vp, C.c_int]
@@ -257,6 +271,8 @@ def load_library():
     lib.qrl_framesync_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, vp]
     lib.qrl_framesync_sync.argtypes = [vp]
     lib.qrl_framesync_set_activity_output.argtypes = [vp, vp]
+    lib.qrl_framesync_stream.argtypes = [vp]
+    lib.qrl_framesync_stream.restype = vp
     lib.qrl_firdes_low_pass.argtypes = [C.c_double] * 4 + [C.c_int, vp]
     lib.qrl_firdes_low_pass_2.argtypes = [C.c_double] * 5 + [C.c_int, vp]
     lib.qrl_firdes_complex_band_pass.argtypes = [C.c_double] * 5 + [C.c_int, vp]
@@ -276,6 +292,8 @@ EXPORTED_SYMBOLS = [
     "qrl_bptc19696_decode", "qrl_bptc19696_encode", "qrl_m17_decode_frames", "qrl_m17_encode_frames",
     "qrl_dmr_l2_decode", "qrl_dmr_trellis34_decode", "qrl_dmr_trellis34_encode", "qrl_dmr_l2_encode", "qrl_dmr_voice_call_encode",
     "qrl_dmr_rx_create", "qrl_dmr_rx_destroy", "qrl_dmr_rx_reset", "qrl_dmr_rx_set_config", "qrl_dmr_rx_process", "qrl_dmr_rx_get_state", "qrl_dmr_rx_set_mode", "qrl_dmr_rx_process_slots",
+    "qrl_m17_rx_create", "qrl_m17_rx_destroy", "qrl_m17_rx_reset", "qrl_m17_rx_set_config", "qrl_m17_rx_process", "qrl_m17_rx_get_state",
+    "qrl_m17_call_start", "qrl_m17_call_encode", "qrl_m17_call_end",
     "qrl_dmr_sink_create", "qrl_dmr_sink_destroy", "qrl_dmr_sink_reset", "qrl_dmr_sink_flush", "qrl_dmr_sink_process", "qrl_dmr_sink_sync",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
@@ -289,7 +307,7 @@ EXPORTED_SYMBOLS = [
     "qrl_fft_get_window_type", "qrl_fft_process", "qrl_fft_process_sc16", "qrl_fft_set_sc16_scale", "qrl_fft_get_fft_data", "qrl_fft_sync", "qrl_fft_stream",
     "qrl_deframer_create", "qrl_deframer_destroy", "qrl_deframer_reset", "qrl_deframer_process", "qrl_deframer_sync",
     "qrl_framesync_create", "qrl_framesync_destroy", "qrl_framesync_reset", "qrl_framesync_frame_bytes", "qrl_framesync_process",
-    "qrl_framesync_sync", "qrl_framesync_set_activity_output",
+    "qrl_framesync_sync", "qrl_framesync_set_activity_output", "qrl_framesync_stream",
     "qrl_firdes_low_pass",
     "qrl_firdes_low_pass_2", "qrl_firdes_complex_band_pass", "qrl_firdes_root_raised_cosine", "qrl_table_mmse",
     "qrl_table_atan", "qrl_table_tanh", "qrl_phase_inc_to_turn",
@@ -1043,6 +1061,17 @@ class FrameSync:
         # bits collected into a frame while a sync was held, per call: > 0 <=> gr_modem::synchronize's data_to_process (src/gr_modem.cpp:1121-1175)
         self.activity = torch.zeros((batch,), dtype=torch.int32, device="cuda:%d" % ctx.device)
         _check(self.lib.qrl_framesync_set_activity_output(self.h, self.activity.data_ptr()), "qrl_framesync_set_activity_output")
+        self.m17_rx = self.m17_events = None
+
+    def enable_m17_link(self, can_rx=0, decode_all_can=True):
+        """QRL_MODEM_M17: queue the M17 link layer (M17Rx, qrl_m17_rx_process) behind every process() on the handle's stream, with no host
+        copy between the stages.  After a process() self.m17_events is the [batch, slots, 64] record tensor of that call, one record per
+        frame of out_counts[:, 1]; self.m17_rx the tracker (set_config, reset, state)."""
+        assert self.frame_bytes == 46, "the M17 link layer follows a QRL_MODEM_M17 synchroniser"
+        if self.m17_rx is None:
+            self.m17_rx = M17Rx(self.ctx, self.batch, can_rx, decode_all_can)
+        else:
+            self.m17_rx.set_config(can_rx, decode_all_can)
 
     def process(self, bits, counts=None, count_stride=1, n=None):
         t = self.torch
@@ -1056,14 +1085,25 @@ class FrameSync:
         _check(self.lib.qrl_framesync_process(self.h, bits.data_ptr(), bits.stride(0), n, counts.data_ptr() if counts is not None else None,
                                               count_stride, self.out.data_ptr(), self.out.shape[1], self.out_counts.data_ptr()),
                "qrl_framesync_process")
+        if self.m17_rx is not None:
+            slots = self.out.shape[1] // M17_FRAMESYNC_RECORD_BYTES
+            if self.m17_events is None or self.m17_events.shape[1] != slots:
+                # empty, not zeros: a fill would be queued on torch's stream, unordered against the synchroniser's; k_m17_rx writes every slot
+                self.m17_events = t.empty((self.batch, slots, M17_RX_RECORD_BYTES), dtype=t.uint8, device=bits.device)
+            self.m17_rx.process(self.out, self.out_counts, out=self.m17_events, stream=self.lib.qrl_framesync_stream(self.h) or 0)
         _check(self.lib.qrl_framesync_sync(self.h), "qrl_framesync_sync")
         return self.out, self.out_counts
 
     def reset(self):
         _check(self.lib.qrl_framesync_reset(self.h), "qrl_framesync_reset")
+        if self.m17_rx is not None:
+            self.m17_rx.reset(stream=self.lib.qrl_framesync_stream(self.h) or 0)
 
     def close(self):
         if self.h:
+            if self.m17_rx is not None:
+                _check(self.lib.qrl_framesync_sync(self.h), "qrl_framesync_sync")   # the link layer's kernels run on this handle's stream
+                self.m17_rx.close()
             self.lib.qrl_framesync_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -1580,6 +1620,139 @@ def m17_encode_frames(ctx, records):
     _check(ctx.lib.qrl_m17_encode_frames(ctx.h, None, records.data_ptr(), records.shape[0], out.data_ptr()), "qrl_m17_encode_frames")
     torch.cuda.synchronize()
     return out
+
+
+M17_RX_RECORD_BYTES, M17_RX_STATE_BYTES, M17_FRAMESYNC_RECORD_BYTES = 64, 16, 56
+M17_RX_FRAME, M17_RX_LSF_VALID, M17_RX_INFO, M17_RX_AUDIO, M17_RX_END, M17_RX_LICH_OK, M17_RX_LSF_FROM_LICH, M17_RX_LOCKED = (1 << i for i in range(8))
+M17_CALL_BYTES, M17_CALL_START_BYTES, M17_CALL_END_BYTES = 32, 96, 64
+
+
+class M17Rx:
+    """M17 link layer on receive (qrl_m17_rx_*): per stream what the reference's M17FrameDecoder and gr_modem keep between frames (the LSF, its
+    reassembly from LICH segments, the lock), kept on the device between calls.  process() takes the [batch, out_cap] record rows and the
+    [batch, 2] counts of a QRL_MODEM_M17 FrameSync as they are and returns [batch, slots, 64] link records; state() the public [batch, 16]
+    bytes (locked, lsf.valid(), CAN, segment map, encoded source, encoded destination).  stream: a HIP stream handle (int) or None for the
+    null stream, in which case the call is synchronous; the calls of one tracker must be ordered by the caller."""
+
+    def __init__(self, ctx, batch, can_rx=0, decode_all_can=True):
+        self.ctx, self.lib, self.batch = ctx, ctx.lib, batch
+        self.h = C.c_void_p()
+        cfg = _M17RxConfig(int(can_rx), int(bool(decode_all_can)))
+        _check(self.lib.qrl_m17_rx_create(ctx.h, batch, C.byref(cfg), C.byref(self.h)), "qrl_m17_rx_create")
+
+    def set_config(self, can_rx, decode_all_can):
+        """from the next process() on"""
+        cfg = _M17RxConfig(int(can_rx), int(bool(decode_all_can)))
+        _check(self.lib.qrl_m17_rx_set_config(self.h, C.byref(cfg)), "qrl_m17_rx_set_config")
+
+    def reset(self, stream=None):
+        """every stream back to a fresh tracker's state"""
+        _check(self.lib.qrl_m17_rx_reset(self.h, C.c_void_p(stream)), "qrl_m17_rx_reset")
+
+    def process(self, frames, counts, cap_frames=None, out=None, stream=None):
+        import torch
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 2 and frames.shape[0] == self.batch and frames.stride(1) == 1
+        assert counts.is_cuda and counts.dtype in (torch.int32, torch.uint32) and counts.shape == (self.batch, 2) and counts.is_contiguous()
+        cap = frames.shape[1] // M17_FRAMESYNC_RECORD_BYTES if cap_frames is None else int(cap_frames)
+        if out is None:
+            out = torch.empty((self.batch, cap, M17_RX_RECORD_BYTES), dtype=torch.uint8, device=frames.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.shape == (self.batch, cap, M17_RX_RECORD_BYTES) and out.is_contiguous()
+        if stream is None:
+            torch.cuda.current_stream().synchronize()   # the call runs on the null stream, not torch's: what made frames must be done
+        _check(self.lib.qrl_m17_rx_process(self.h, C.c_void_p(stream), frames.data_ptr(), frames.stride(0) if self.batch > 1 else frames.shape[1],
+                                           counts.data_ptr(), cap, out.data_ptr()), "qrl_m17_rx_process")
+        if stream is None:
+            torch.cuda.synchronize()
+        return out
+
+    def state(self, stream=None):
+        import torch
+        out = torch.empty((self.batch, M17_RX_STATE_BYTES), dtype=torch.uint8, device="cuda:%d" % self.ctx.device)
+        if stream is None:
+            torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_m17_rx_get_state(self.h, C.c_void_p(stream), out.data_ptr()), "qrl_m17_rx_get_state")
+        if stream is None:
+            torch.cuda.synchronize()
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.qrl_m17_rx_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def m17_call_descriptor(source, destination="", can=0, destination_type=0):
+    """the 32-byte call descriptor of qrl_m17_call_* as a numpy array: the characters of the two callsigns as M17Transmitter::start is given
+    them (nine are kept; a length above nine reads as the reference's "more than nine": the zero address), the CAN, Settings::m17_destination_type"""
+    d = np.zeros(M17_CALL_BYTES, np.uint8)
+    for at, text in ((0, source), (10, destination)):
+        raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        d[at:at + min(len(raw), 9)] = np.frombuffer(raw[:9], np.uint8)
+        d[at + 9] = min(len(raw), 10)
+    d[20], d[21] = int(can) & 15, int(destination_type) & 255
+    return d
+
+
+def _m17_calls(calls):
+    import torch
+    assert calls.is_cuda and calls.dtype == torch.uint8 and calls.dim() == 2 and calls.shape[1] == M17_CALL_BYTES and calls.is_contiguous()
+    return calls.shape[0]
+
+
+def m17_call_start(ctx, calls):
+    """calls [batch, 32] cuda uint8 -> [batch, 96]: the preamble and the LSF frame (qrl_m17_call_start)"""
+    import torch
+    batch = _m17_calls(calls)
+    out = torch.zeros((batch, M17_CALL_START_BYTES), dtype=torch.uint8, device=calls.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_m17_call_start(ctx.h, None, calls.data_ptr(), batch, out.data_ptr(), M17_CALL_START_BYTES), "qrl_m17_call_start")
+    torch.cuda.synchronize()
+    return out
+
+
+def m17_call_encode(ctx, calls, payloads, first=None, slot_bytes=48):
+    """calls [batch, 32], payloads [batch, n, 16], first [batch] int32 / uint32: the index of payloads[b][0] within its call (None = 0)
+    -> [batch, n, slot_bytes] stream frames (qrl_m17_call_encode).  All cuda tensors."""
+    import torch
+    batch = _m17_calls(calls)
+    assert payloads.is_cuda and payloads.dtype == torch.uint8 and payloads.dim() == 3 and payloads.shape[0] == batch and payloads.shape[2] == 16
+    assert payloads.is_contiguous() and slot_bytes >= 48
+    n = payloads.shape[1]
+    if first is not None:
+        assert first.is_cuda and first.dtype in (torch.int32, torch.uint32) and first.shape == (batch,) and first.is_contiguous()
+    out = torch.zeros((batch, n, slot_bytes), dtype=torch.uint8, device=calls.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_m17_call_encode(ctx.h, None, calls.data_ptr(), payloads.data_ptr(), first.data_ptr() if first is not None else None, batch, n,
+                                       out.data_ptr(), n * slot_bytes, slot_bytes), "qrl_m17_call_encode")
+    torch.cuda.synchronize()
+    return out
+
+
+def m17_call_end(ctx, calls, first):
+    """calls [batch, 32], first [batch]: the index of the last frame -> [batch, 64]: that frame and the EOT bytes (qrl_m17_call_end)"""
+    import torch
+    batch = _m17_calls(calls)
+    assert first.is_cuda and first.dtype in (torch.int32, torch.uint32) and first.shape == (batch,) and first.is_contiguous()
+    out = torch.zeros((batch, M17_CALL_END_BYTES), dtype=torch.uint8, device=calls.device)
+    torch.cuda.current_stream().synchronize()
+    _check(ctx.lib.qrl_m17_call_end(ctx.h, None, calls.data_ptr(), first.data_ptr(), batch, out.data_ptr(), M17_CALL_END_BYTES), "qrl_m17_call_end")
+    torch.cuda.synchronize()
+    return out
+
+
+def m17_call_bytes(ctx, call, payloads):
+    """One whole transmission as the reference emits it: startTransmission's preamble and LSF frame, one stream frame per row of payloads
+    [n, 16], endTransmission's last frame and EOT bytes -> numpy uint8 [96 + 48 n + 64], ready for Mod(QRL_MODEM_M17)."""
+    import torch
+    dev = "cuda:%d" % ctx.device
+    calls = torch.from_numpy(np.asarray(call, np.uint8).reshape(1, M17_CALL_BYTES)).to(dev)
+    payloads = np.ascontiguousarray(payloads, np.uint8).reshape(-1, 16)
+    n = payloads.shape[0]
+    parts = [m17_call_start(ctx, calls).cpu().numpy().reshape(-1)]
+    if n:
+        parts.append(m17_call_encode(ctx, calls, torch.from_numpy(payloads.reshape(1, n, 16)).to(dev)).cpu().numpy().reshape(-1))
+    parts.append(m17_call_end(ctx, calls, torch.tensor([n], dtype=torch.int32, device=dev)).cpu().numpy().reshape(-1))
+    return np.concatenate(parts)
 
 
 def collect(dem, iq, chunk):

@@ -127,6 +127,7 @@ int qrl_framesync_set_activity_output(qrl_framesync* h, uint32_t* activity)
     h->activity = activity;
     return QRL_OK;
 }
+void* qrl_framesync_stream(qrl_framesync* h) { return h ? static_cast<void*>(static_cast<hipStream_t>(h->stream)) : nullptr; }
 int qrl_framesync_sync(qrl_framesync* h)
 {
     if (!h) return QRL_ERR_ARG;

@@ -468,6 +468,19 @@ struct DmrSinkParams {
 };
 void launch_dmr_sink(const DmrSinkParams& p, int batch, hipStream_t s);
 void launch_dmr_sink_flush(void* states, int batch, hipStream_t s);
+// ---- M17 link layer (kernels_m17_link.hip): the frame synchroniser's records frames[b * frame_stride + 56 i], i < min(counts[2 b + 1], cap), ->
+//      decode records scratch [batch][cap][40] -> link records [batch][cap][64] through the per-stream states [batch] (m17_link_core.hpp's
+//      m17_rx_state); the public 16 bytes of every state; every state to a fresh decoder's ----
+constexpr size_t M17_RX_RECORD_BYTES = 64, M17_RX_STATE_BYTES = 64, M17_RX_PUBLIC_BYTES = 16, M17_FS_RECORD_BYTES = 56,
+                 M17_DEC_RECORD_BYTES = 40;   // kernels_m17_link.hip holds them to the core
+void launch_m17_rx(const uint8_t* frames, size_t frame_stride, const uint32_t* counts, size_t batch, size_t cap, int can_rx, int decode_all_can,
+                   uint8_t* scratch, void* states, uint8_t* out, hipStream_t s);
+void launch_m17_rx_state(const void* states, size_t batch, uint8_t* out, hipStream_t s);
+void launch_m17_rx_reset(void* states, size_t batch, hipStream_t s);
+//      transmit: call descriptors [batch][32] -> kind 0: preamble + LSF frame (96 bytes a row), 1: stream frames first[b] + i with payloads
+//      [batch][n][16] at out[b * out_stride + i * slot_bytes], 2: the last frame + the EOT bytes (64 bytes a row)
+void launch_m17_call(int kind, const uint8_t* calls, const uint8_t* payloads, const uint32_t* first, size_t batch, size_t n, uint8_t* out,
+                     size_t out_stride, size_t slot_bytes, hipStream_t s);
 
 // ---- side outputs (kernels_side.hip): rssi_block on port 0, rx_fft_c on the device-rate IQ ----
 constexpr uint32_t RSSI_RING = 4096;   // |x|^2 look-back ring per stream (moving_average_ff(2000) reads 1999 items back)

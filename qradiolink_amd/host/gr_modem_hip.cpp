@@ -73,6 +73,7 @@ struct gr_demod_base_hip::slot {
     uint8_t *d_fr[2] = {nullptr, nullptr}, *h_fr[2] = {nullptr, nullptr}; uint32_t *d_frcnt[2] = {nullptr, nullptr}, *h_frcnt[2] = {nullptr, nullptr};   // framed records of bits A / B
     bool framed = false, bits_copied = true;
     uint8_t *d_l2 = nullptr, *h_l2 = nullptr; bool l2 = false;   // DMR layer 2 records of the call's bursts (set_dmr_l2; device / pinned)
+    uint8_t *d_m17ev = nullptr, *h_m17ev = nullptr; bool m17 = false;   // M17 link records of the frames of bits A (set_m17_link)
     uint8_t *d_call = nullptr, *h_call = nullptr; bool call = false;   // DMR call records of the same bursts (set_dmr_call)
     uint8_t *d_rep = nullptr, *d_info = nullptr, *h_info = nullptr; uint32_t* d_repcnt = nullptr; bool rep = false;   // the repeater-mode sink's bursts, their slot records (set_dmr_repeater)
     hipEvent_t done = nullptr;
@@ -99,6 +100,7 @@ gr_demod_base_hip::~gr_demod_base_hip()
     try { flush(); } catch (...) {}
     close();
     if (d_call_rx) qrl_dmr_rx_destroy(d_call_rx);
+    if (d_m17_rx) qrl_m17_rx_destroy(d_m17_rx);
     if (d_sink) qrl_dmr_sink_destroy(d_sink);   // it works on the copy stream: before the stream goes
     if (d_copy) (void)hipStreamDestroy(static_cast<hipStream_t>(d_copy));
 }
@@ -121,6 +123,8 @@ void gr_demod_base_hip::close()
             if (sp->h_fr[k]) (void)hipHostFree(sp->h_fr[k]);
             if (sp->h_frcnt[k]) (void)hipHostFree(sp->h_frcnt[k]);
         }
+        if (sp->d_m17ev) (void)hipFree(sp->d_m17ev);
+        if (sp->h_m17ev) (void)hipHostFree(sp->h_m17ev);
         if (sp->d_rssi) (void)hipFree(sp->d_rssi);
         if (sp->h_rssi) (void)hipHostFree(sp->h_rssi);
         if (sp->d_audio) (void)hipFree(sp->d_audio);
@@ -185,6 +189,11 @@ void gr_demod_base_hip::open()
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_fr[k]), N * d_frcap, hipHostMallocDefault), "hipHostMalloc");
             hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_frcnt[k]), N * 3 * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
         }
+        if (fs_on && d_mode == QRL_MODEM_M17) {   // one link record per frame the row can hold
+            const size_t ev = N * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) * QRL_M17_RX_RECORD_BYTES;
+            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_m17ev), ev), "hipMalloc");
+            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_m17ev), ev, hipHostMallocDefault), "hipHostMalloc");
+        }
         hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_rssi), N * sizeof(float)), "hipMalloc");
         hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_rssi), N * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
         hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_iq), N * d_chunk * sizeof(gr_complex), hipHostMallocDefault), "hipHostMalloc");
@@ -221,6 +230,7 @@ void gr_demod_base_hip::open()
     d_calls = 0;
     if (d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // the receiver starts afresh, and so does the call state behind it
     if (d_sink) chk(qrl_dmr_sink_reset(d_sink), "qrl_dmr_sink_reset");
+    if (d_m17_rx) chk(qrl_m17_rx_reset(d_m17_rx, d_copy), "qrl_m17_rx_reset");
 }
 void gr_demod_base_hip::apply_call_mode()
 {
@@ -252,6 +262,19 @@ void gr_demod_base_hip::set_dmr_call(bool on, int colour_code, bool promiscuous)
         if (on && !d_call_on) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // switched back on: nothing of the calls it missed
     }
     d_call_on = on;
+}
+void gr_demod_base_hip::set_m17_link(bool on, int can_rx, bool decode_all_can)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    const qrl_m17_rx_config c = {can_rx, decode_all_can ? 1 : 0};
+    if (!d_m17_rx) {
+        if (!on) return;
+        chk(qrl_m17_rx_create(d_rt.ctx(), (size_t)d_n, &c, &d_m17_rx), "qrl_m17_rx_create");
+    } else {
+        chk(qrl_m17_rx_set_config(d_m17_rx, &c), "qrl_m17_rx_set_config");
+        if (on && !d_m17_on) chk(qrl_m17_rx_reset(d_m17_rx, d_copy), "qrl_m17_rx_reset");   // switched back on: nothing of the frames it missed
+    }
+    d_m17_on = on;
 }
 void gr_demod_base_hip::set_mode(int mode)   // gr_demod_base::set_mode (src/gr/gr_demod_base.cpp:460-1090): swap the graph, drop what was queued
 {
@@ -378,6 +401,7 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         hchk(hipMemcpyAsync(sl.h_scope, sl.d_scope, N * d_scap * sizeof(gr_complex), hipMemcpyDeviceToHost, cs), "D2H");
     }
     sl.framed = d_fs[0] != nullptr;
+    sl.m17 = false;
     sl.bits_copied = !sl.framed || d_keep_bits;
     if (sl.framed) {
         // the frame synchronisers run on the copy stream behind the demodulator (no host synchronisation in between): bits A / B of
@@ -388,6 +412,12 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         for (int k = 0; k < 2; ++k) {
             hchk(hipMemcpyAsync(sl.h_frcnt[k], sl.d_frcnt[k], N * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
             hchk(hipMemcpyAsync(sl.h_fr[k], sl.d_fr[k], N * d_frcap, hipMemcpyDeviceToHost, cs), "D2H");
+        }
+        sl.m17 = d_m17_on && d_m17_rx && sl.d_m17ev;
+        if (sl.m17) {   // the link layer behind the synchroniser of bits A, on the same stream: the records of this call's frames
+            const size_t cap = d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES;
+            chk(qrl_m17_rx_process(d_m17_rx, cs, sl.d_fr[0], d_frcap, sl.d_frcnt[0], cap, sl.d_m17ev), "qrl_m17_rx_process");
+            hchk(hipMemcpyAsync(sl.h_m17ev, sl.d_m17ev, N * cap * QRL_M17_RX_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
         }
     }
     if (sl.bits_copied) {
@@ -465,7 +495,8 @@ void gr_demod_base_hip::harvest(int which)
             d_fact[k][s] += sl.h_frcnt[k][2 * (size_t)d_n + s];
             const uint8_t* p = sl.h_fr[k] + (size_t)s * d_frcap;
             const uint32_t nbytes = std::min<uint32_t>(sl.h_frcnt[k][2 * s], (uint32_t)d_frcap);
-            for (uint32_t pos = 0; pos + 8 <= nbytes;) {
+            uint32_t index = 0;   // of the record within the row: where its M17 link record lies
+            for (uint32_t pos = 0; pos + 8 <= nbytes; ++index) {
                 uint32_t hdr[2];
                 std::memcpy(hdr, p + pos, 8);
                 const uint32_t nb = hdr[1] & 0xFFFFu, padded = (nb + 3u) & ~3u;
@@ -474,6 +505,10 @@ void gr_demod_base_hip::harvest(int which)
                 r.type = hdr[0]; r.modem_sync = hdr[1] >> 16;
                 r.payload.assign(p + pos + 8, p + pos + 8 + padded);
                 r.payload.resize((size_t)padded + 4, 0);   // processReceivedData reads frame_length + 1 bytes
+                if (k == 0 && sl.m17) {
+                    const uint8_t* e = sl.h_m17ev + ((size_t)s * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) + index) * QRL_M17_RX_RECORD_BYTES;
+                    r.m17_event.assign(e, e + QRL_M17_RX_RECORD_BYTES);
+                }
                 d_boxf[k][s].push_back(std::move(r));
                 pos += 8 + padded;
             }
@@ -708,7 +743,8 @@ std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRCallEvents(int 
 // ================================================================================================ gr_mod_base_hip
 gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_bytes)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_max(max_bytes), d_offsets((size_t)std::max(streams, 0), carrier_offset_hz), d_queue(streams), d_aqueue(streams), d_sent(streams, 0), d_clipped((size_t)std::max(streams, 0), 0),
-      d_dmr_jobs((size_t)std::max(streams, 0)), d_dmr_call((size_t)std::max(streams, 0)), d_dmr_next((size_t)std::max(streams, 0), 0)
+      d_dmr_jobs((size_t)std::max(streams, 0)), d_dmr_call((size_t)std::max(streams, 0)), d_dmr_next((size_t)std::max(streams, 0), 0),
+      d_m17_call((size_t)std::max(streams, 0)), d_m17_next((size_t)std::max(streams, 0), 0)
 {
     d_cw_n = std::min<size_t>(1024, d_max);   // a facade built for fewer than 1024 items per call must still key CW
 }
@@ -838,6 +874,53 @@ void gr_mod_base_hip::setDMRCall(const uint8_t* descriptor40, int stream)   // t
     d_dmr_call.at((size_t)stream).assign(descriptor40, descriptor40 + QRL_DMR_CALL_BYTES);
     d_dmr_next[(size_t)stream] = 0;
 }
+// one qrl_m17_call_* launch on the null stream and a blocking copy of its bytes, which then take the byte path
+void gr_mod_base_hip::queue_m17(int kind, const uint8_t* payloads, size_t n, int stream)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (d_mode != QRL_MODEM_M17 || !d_h) throw std::runtime_error("gr_mod_base_hip: an M17 call outside M17 mode");
+    if (d_m17_call.at((size_t)stream).empty()) throw std::runtime_error("gr_mod_base_hip: txM17Audio / endM17Call before setM17Call");
+    const size_t bytes = kind == 0 ? QRL_M17_CALL_START_BYTES : kind == 2 ? QRL_M17_CALL_END_BYTES : n * 48;
+    const size_t in = QRL_M17_CALL_BYTES + 4 + (kind == 1 ? n * 16 : 0);
+    uint8_t* dev = nullptr;
+    hchk(hipMalloc(reinterpret_cast<void**>(&dev), in + bytes), "hipMalloc");
+    std::vector<uint8_t> h(in);
+    std::memcpy(h.data(), d_m17_call[(size_t)stream].data(), QRL_M17_CALL_BYTES);
+    std::memcpy(h.data() + QRL_M17_CALL_BYTES, &d_m17_next[(size_t)stream], 4);
+    if (kind == 1) std::memcpy(h.data() + QRL_M17_CALL_BYTES + 4, payloads, n * 16);
+    std::vector<uint8_t>* out = new std::vector<uint8_t>(bytes);
+    int rc = QRL_OK;
+    hipError_t e = hipMemcpy(dev, h.data(), in, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const uint32_t* first = reinterpret_cast<const uint32_t*>(dev + QRL_M17_CALL_BYTES);
+        uint8_t* o = dev + in;
+        if (kind == 0) rc = qrl_m17_call_start(d_rt.ctx(), nullptr, dev, 1, o, bytes);
+        else if (kind == 1) rc = qrl_m17_call_encode(d_rt.ctx(), nullptr, dev, dev + QRL_M17_CALL_BYTES + 4, first, 1, n, o, bytes, 48);
+        else rc = qrl_m17_call_end(d_rt.ctx(), nullptr, dev, first, 1, o, bytes);
+        if (rc == QRL_OK) e = hipMemcpy(out->data(), o, bytes, hipMemcpyDeviceToHost);   // (waits for the null stream)
+    }
+    (void)hipFree(dev);
+    if (rc != QRL_OK || e != hipSuccess) { delete out; if (rc != QRL_OK) chk(rc, "qrl_m17_call"); hchk(e, "hipMemcpy"); }
+    if (kind == 1) d_m17_next[(size_t)stream] += (uint32_t)n;
+    set_data(out, stream);
+}
+void gr_mod_base_hip::setM17Call(const uint8_t* descriptor32, int stream)   // M17Transmitter::start: the counters to 0, preamble and LSF frame
+{
+    {
+        std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+        if (d_mode != QRL_MODEM_M17 || !d_h) throw std::runtime_error("gr_mod_base_hip::setM17Call outside M17 mode");
+        d_m17_call.at((size_t)stream).assign(descriptor32, descriptor32 + QRL_M17_CALL_BYTES);
+        d_m17_next[(size_t)stream] = 0;
+    }
+    queue_m17(0, nullptr, 0, stream);
+}
+int gr_mod_base_hip::txM17Audio(const uint8_t* payloads, size_t n, int stream)
+{
+    if (!n) return 0;
+    queue_m17(1, payloads, n, stream);
+    return (int)n;
+}
+void gr_mod_base_hip::endM17Call(int stream) { queue_m17(2, nullptr, 0, stream); }
 int gr_mod_base_hip::txDMRVoice(const uint8_t* voice, size_t n, int stream)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // as in setDMRData: slots and their zero runs become visible to a pass together
@@ -1213,6 +1296,11 @@ bool gr_modem_hip::demodulate(int stream)   // gr_modem.cpp:1019-1117
                 r.current_frame_type = f.type;
                 processReceivedData(f.payload.data(), f.type, r, stream);
             }
+            if (k == 0 && _ev.m17LinkEvents) {   // set_m17_link: the same frames through the link layer on the device
+                std::vector<std::vector<unsigned char>> events;
+                for (auto& f : recs) if (!f.m17_event.empty()) events.push_back(std::move(f.m17_event));
+                if (!events.empty()) _ev.m17LinkEvents(stream, events);
+            }
         }
         return data_to_process;
     }
@@ -1362,7 +1450,7 @@ void gr_modem_hip::processReceivedData(unsigned char* received_data, uint64_t cu
         r.last_frame_type = FrameTypeIP;
         if (_ev.netData) _ev.netData(stream, received_data, L);
     } else if (current_frame_type == FrameTypeM17Stream || current_frame_type == FrameTypeM17LSF || current_frame_type == FrameTypeM17EOT) {
-        if (_ev.m17Frame) _ev.m17Frame(stream, current_frame_type, received_data, L);   // the M17 decoder itself is out of scope
+        if (_ev.m17Frame) _ev.m17Frame(stream, current_frame_type, received_data, L);   // raw; the link layer's records of the same frames: m17LinkEvents (set_m17_link)
     }
 }
 void gr_modem_hip::handleStreamEnd(rx_state& r, int stream)   // gr_modem.cpp:1443-1451

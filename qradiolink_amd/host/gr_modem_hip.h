@@ -65,7 +65,8 @@ public:
     // src/gr_modem.cpp:1119-1282): when enabled (gr_modem_hip does it in toggleRxMode) every work() call runs it behind the demodulator
     // on both bit ports and only the framed records come back to the host -- no raw bits over PCIe, no per-bit host loop.
     // keep_bits(true) still copies the raw bit ports into the getData() mailboxes (tests that replay them into the reference).
-    struct frame_record { uint32_t type = 0, modem_sync = 0; std::vector<unsigned char> payload; };
+    // m17_event: while set_m17_link is on, the frame's 64-byte link record (QRL_M17_RX_RECORD_BYTES), else empty
+    struct frame_record { uint32_t type = 0, modem_sync = 0; std::vector<unsigned char> payload, m17_event; };
     void enable_device_framing(bool value);                    // takes effect at the next set_mode (toggleRxMode calls it first)
     bool device_framing() const { return d_fs[0] != nullptr; }
     void keep_bits(bool value) { d_keep_bits = value; }
@@ -88,6 +89,12 @@ public:
     // outside 0..15 (the C ABI's QRL_ERR_ARG).
     void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false);
     std::vector<std::vector<unsigned char>> getDMRCallEvents(int stream = 0);
+    // M17 link layer (qrl_m17_rx_process), off by default, QRL_MODEM_M17 with the device frame synchroniser: every frame record of bits A then carries
+    // its 64-byte link record (frame_record::m17_event; m17_link_event_hip in host/m17_link_hip.h reads it) -- what gr_modem::processReceivedData does
+    // with the frame (reference src/gr_modem.cpp:1370-1439) and the stream's state afterwards.  Queued on the copy stream behind the synchroniser, with
+    // no host synchronisation; the state lives on the device and is carried from work() to work(); set_mode and switching the layer back on start it
+    // afresh.  Throws std::runtime_error for a CAN outside 0..15 (the C ABI's QRL_ERR_ARG).
+    void set_m17_link(bool on, int can_rx = 0, bool decode_all_can = true);
     // The reference's getDMRData(bool dmo) choice (src/gr/gr_demod_base.cpp:947-966): off (the default) getDMRData returns the bursts of the DMO
     // slicer, gr_dmr_dmo_sink; on, those of the repeater-mode sink gr_dmr_sink on port 2 (qrl_dmr_sink_process: BS / MS sync on the hard bits, the
     // CACH, two slot contexts), in the same 40-byte record, and set_dmr_l2 / set_dmr_call work on them: sink -> layer 2 -> qrl_dmr_rx_process_slots
@@ -172,6 +179,7 @@ private:
     bool d_l2_on = false, d_l2_fec = true;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxe;   // call records, one per record of d_boxd while set_dmr_call is on
     qrl_dmr_rx* d_call_rx = nullptr; bool d_call_on = false;
+    qrl_m17_rx* d_m17_rx = nullptr; bool d_m17_on = false;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxi;   // slot records, one per record of d_boxd while set_dmr_repeater is on
     qrl_dmr_sink* d_sink = nullptr; bool d_rep_on = false; int d_rep_slot = 1;
     void apply_call_mode();                                        // the tracker's mode follows set_dmr_repeater
@@ -197,6 +205,14 @@ public:
     // them and however the passes cut the slots.  Returns the number of bursts queued.  QRL_MODEM_DMR mode only.
     void setDMRCall(const uint8_t* descriptor40, int stream = 0);
     int txDMRVoice(const uint8_t* voice, size_t n, int stream = 0);
+    // An M17 call framed on the device (qrl_m17_call_start / _encode / _end) beside the byte path: what gr_modem::startTransmission, transmitM17Audio
+    // and endTransmission do through M17Transmitter (reference src/gr_modem.cpp:687-697, 868-884, 718-729).  setM17Call takes the 32-byte call
+    // descriptor (host/m17_link_hip.h: m17_call_descriptor), starts the frame count at 0 and queues the preamble and the LSF frame; txM17Audio queues n
+    // stream frames (payloads = n x 16 bytes) and returns n; endM17Call queues the last frame and the EOT bytes.  The bytes go through set_data like any
+    // others.  Each call launches one small kernel and waits for its bytes: the side is launch-bound.  QRL_MODEM_M17 mode only.
+    void setM17Call(const uint8_t* descriptor32, int stream = 0);
+    int txM17Audio(const uint8_t* payloads, size_t n, int stream = 0);
+    void endM17Call(int stream = 0);
     void set_bb_gain(float value);
     void set_carrier_offset(double hz);                        // every stream
     void set_carrier_offset(double hz, int stream);            // one radio (gr_modem::setTxCarrierOffset of radio `stream`); kept across set_mode / set_samp_rate
@@ -259,6 +275,8 @@ private:
     std::vector<std::vector<uint8_t>> d_dmr_call; std::vector<uint32_t> d_dmr_next;   // per stream: descriptor, index of the next voice burst
     uint8_t* d_dmr_dev = nullptr; size_t d_dmr_cap = 0;   // device staging of a pass: descriptors, first indices, codec bytes, straddling slots
     void encode_dmr_jobs(const std::vector<uint64_t>& window0, size_t nb, void* stream);
+    std::vector<std::vector<uint8_t>> d_m17_call; std::vector<uint32_t> d_m17_next;   // per stream: descriptor, index of the next stream frame
+    void queue_m17(int kind, const uint8_t* payloads, size_t n, int stream);          // 0 start, 1 frames, 2 end
 };
 
 // the Qt signals of gr_modem that the RX / TX paths emit (src/gr_modem.h:118-139); unset callbacks are skipped.  Buffers are only
@@ -275,6 +293,7 @@ struct gr_modem_events {
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records80)> dmrFramesDecoded;   // the same bursts through DMR layer 2 (set_dmr_l2)
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records128)> dmrCallEvents;     // and through the call layer (set_dmr_call)
     std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records16)> dmrSlotInfo;        // their slot records (set_dmr_repeater)
+    std::function<void(int stream, const std::vector<std::vector<unsigned char>>& records64)> m17LinkEvents;      // the M17 frames through the link layer (set_m17_link), beside m17Frame
 };
 
 class gr_modem_hip {
@@ -311,6 +330,13 @@ public:
     // gr_modem::transmitDMR does through DMRControl::getTxAudio and setDMRData (src/gr_modem.cpp:766-802)
     void setDMRCall(const uint8_t* descriptor40, int stream = 0) { if (_gr_mod_base) _gr_mod_base->setDMRCall(descriptor40, stream); }
     int txDMRVoice(const uint8_t* voice, size_t n, int stream = 0) { return _gr_mod_base ? _gr_mod_base->txDMRVoice(voice, n, stream) : 0; }
+    // the M17 link layer on the device, off by default: m17LinkEvents(stream, records64) fires beside the unchanged m17Frame, one record per frame of
+    // the same demodulate() (the demodulator's set_m17_link; needs the device frame synchroniser)
+    void set_m17_link(bool on, int can_rx = 0, bool decode_all_can = true) { if (_gr_demod_base) _gr_demod_base->set_m17_link(on, can_rx, decode_all_can); }
+    // an M17 call framed on the device (the modulator's setM17Call / txM17Audio / endM17Call) beside startTransmission / transmit / endTransmission
+    void setM17Call(const uint8_t* descriptor32, int stream = 0) { if (_gr_mod_base) _gr_mod_base->setM17Call(descriptor32, stream); }
+    int txM17Audio(const uint8_t* payloads, size_t n, int stream = 0) { return _gr_mod_base ? _gr_mod_base->txM17Audio(payloads, n, stream) : 0; }
+    void endM17Call(int stream = 0) { if (_gr_mod_base) _gr_mod_base->endM17Call(stream); }
     // two-branch modes (both Viterbi alignments decoded): BranchRuleBoth (default) runs the frame synchroniser on both
     // branches, BranchRuleReference applies gr_modem.cpp:1080-1090 literally (see demodulate())
     enum branch_rule { BranchRuleBoth = 0, BranchRuleReference = 1 };
