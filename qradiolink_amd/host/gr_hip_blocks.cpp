@@ -6,14 +6,8 @@
 #include <cstring>
 #include <string>
 
-static void chk(int rc, const char* what)
-{
-    if (rc != QRL_OK) throw std::runtime_error(std::string(what) + ": " + qrl_strerror(rc) + " (" + qrl_last_error() + ")");
-}
-static void hchk(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
+using qrl_host::chk;
+using qrl_host::hchk;
 
 qrl_runtime::qrl_runtime(int device) { chk(qrl_init(device, &d_ctx), "qrl_init"); }
 qrl_runtime::~qrl_runtime() { qrl_shutdown(d_ctx); }
@@ -63,101 +57,89 @@ gr_demod_hip::gr_demod_hip(qrl_runtime& rt, int fam, int sps, int samp_rate, int
 }
 void gr_demod_hip::open()
 {
-    if (d_h) { qrl_demod_destroy(d_h); d_h = nullptr; }
-    chk(qrl_demod_create(d_rt.ctx(), &d_cfg, &d_h), "qrl_demod_create");
-    chk(qrl_demod_out_caps(d_h, kChunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
-    if (!d_iq) {
-        hchk(hipMalloc(reinterpret_cast<void**>(&d_iq), kChunk * sizeof(gr_complex)), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&d_cnt), 4 * sizeof(uint32_t)), "hipMalloc");
-        hipStream_t cs;
-        // lowest priority -- not for the scheduling: streams of one priority share a few hardware queues, and a wait queued on this
-        // stream would otherwise hold back the kernels of a handle stream that happens to sit on the same queue (csrc/engine.cpp, stream creation)
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        hchk(hipStreamCreateWithPriority(&cs, hipStreamNonBlocking, prio_lo), "hipStreamCreate");
-        d_cs = cs;
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&d_hcnt), 6 * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+    d_h.reset();
+    qrl_demod* h = nullptr;
+    chk(qrl_demod_create(d_rt.ctx(), &d_cfg, &h), "qrl_demod_create");
+    d_h.reset(h);
+    chk(qrl_demod_out_caps(d_h.get(), kChunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
+    if (!d_iq.get()) {   // once, for the life of the block (interleaved cf32)
+        d_iq.alloc(2 * kChunk);
+        d_cnt.alloc(4);
+        d_hcnt.alloc(6);
     }
-    for (void* p : {(void*)d_const, (void*)d_a, (void*)d_b}) if (p) (void)hipFree(p);
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_const), d_ccap * sizeof(gr_complex)), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_a), d_bcap), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_b), d_bcap), "hipMalloc");
+    d_const.alloc(2 * d_ccap);
+    d_a.alloc(d_bcap);
+    d_b.alloc(d_bcap);
     d_ha.resize(d_bcap); d_hb.resize(d_bcap); d_hc.resize(d_ccap);
-    chk(qrl_demod_audio_cap(d_h, kChunk, &d_acap), "qrl_demod_audio_cap");
-    if (d_audio) { (void)hipFree(d_audio); d_audio = nullptr; }
-    if (d_acap) hchk(hipMalloc(reinterpret_cast<void**>(&d_audio), d_acap * sizeof(float)), "hipMalloc");
+    chk(qrl_demod_audio_cap(d_h.get(), kChunk, &d_acap), "qrl_demod_audio_cap");
+    d_audio.reset();
+    if (d_acap) d_audio.alloc(d_acap);
     d_hau.resize(d_acap);
     if (d_df1) attach_deframer(d_df_type);   // the deframer buffers follow the (possibly new) bit capacity
 }
-gr_demod_hip::~gr_demod_hip()
-{
-    if (d_h) qrl_demod_destroy(d_h);
-    if (d_df1) qrl_deframer_destroy(d_df1);
-    if (d_df2) qrl_deframer_destroy(d_df2);
-    for (void* p : {(void*)d_iq, (void*)d_const, (void*)d_a, (void*)d_b, (void*)d_cnt, (void*)d_fa, (void*)d_fb, (void*)d_fcnt, (void*)d_audio}) if (p) (void)hipFree(p);
-    if (d_hcnt) (void)hipHostFree(d_hcnt);
-    if (d_cs) (void)hipStreamDestroy(static_cast<hipStream_t>(d_cs));
-}
 void gr_demod_hip::attach_deframer(int type)
 {
-    if (d_df1) { qrl_deframer_destroy(d_df1); qrl_deframer_destroy(d_df2); d_df1 = d_df2 = nullptr; }
+    d_df1.reset(); d_df2.reset();
     d_df_type = type;
-    chk(qrl_deframer_create(d_rt.ctx(), type, 1, d_cs, &d_df1), "qrl_deframer_create");   // on the copy stream, behind the demodulator
-    chk(qrl_deframer_create(d_rt.ctx(), type, 1, d_cs, &d_df2), "qrl_deframer_create");
+    qrl_deframer *f1 = nullptr, *f2 = nullptr;
+    chk(qrl_deframer_create(d_rt.ctx(), type, 1, d_cs.get(), &f1), "qrl_deframer_create");   // on the copy stream, behind the demodulator
+    d_df1.reset(f1);
+    chk(qrl_deframer_create(d_rt.ctx(), type, 1, d_cs.get(), &f2), "qrl_deframer_create");
+    d_df2.reset(f2);
     d_dfcap = 2 * d_bcap + 24;
-    for (void* p : {(void*)d_fa, (void*)d_fb, (void*)d_fcnt}) if (p) (void)hipFree(p);
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_fa), d_dfcap), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_fb), d_dfcap), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_fcnt), 2 * sizeof(uint32_t)), "hipMalloc");
+    d_fa.alloc(d_dfcap);
+    d_fb.alloc(d_dfcap);
+    d_fcnt.alloc(2);
     d_ha.resize(d_dfcap); d_hb.resize(d_dfcap);
 }
 void gr_demod_hip::set_device_samp_rate(int r) { d_cfg.device_samp_rate = r; open(); }
-void gr_demod_hip::set_carrier_offset(double hz) { d_cfg.carrier_offset_hz = hz; chk(qrl_demod_set_carrier_offset(d_h, hz), "qrl_demod_set_carrier_offset"); }
+void gr_demod_hip::set_carrier_offset(double hz) { d_cfg.carrier_offset_hz = hz; chk(qrl_demod_set_carrier_offset(d_h.get(), hz), "qrl_demod_set_carrier_offset"); }
 void gr_demod_hip::flush()
 {
-    chk(qrl_demod_reset(d_h), "qrl_demod_reset");
+    chk(qrl_demod_reset(d_h.get()), "qrl_demod_reset");
     gr::thread::scoped_lock g(d_mutex);
     d_box1.clear(); d_box2.clear(); d_boxc.clear(); d_boxa.clear(); d_carry.clear();
 }
 
 void gr_demod_hip::run(const gr_complex* x, size_t n)   // n even, <= kChunk
 {
-    hipStream_t s = static_cast<hipStream_t>(qrl_demod_stream(d_h));
-    hchk(hipMemcpyAsync(d_iq, x, n * sizeof(gr_complex), hipMemcpyHostToDevice, s), "H2D");
+    hipStream_t s = static_cast<hipStream_t>(qrl_demod_stream(d_h.get()));
+    hchk(hipMemcpyAsync(d_iq.get(), x, n * sizeof(gr_complex), hipMemcpyHostToDevice, s), "H2D");
     qrl_demod_out o{};
-    o.constellation = d_const; o.constellation_cap = d_ccap;
-    o.bits_a = d_a; o.bits_b = d_b; o.bits_cap = d_bcap; o.counts = d_cnt;
-    o.audio = d_audio; o.audio_cap = d_acap;
-    chk(qrl_demod_process(d_h, d_iq, kChunk, n, &o), "qrl_demod_process");
+    o.constellation = d_const.get(); o.constellation_cap = d_ccap;
+    o.bits_a = d_a.get(); o.bits_b = d_b.get(); o.bits_cap = d_bcap; o.counts = d_cnt.get();
+    o.audio = d_audio.get(); o.audio_cap = d_acap;
+    chk(qrl_demod_process(d_h.get(), d_iq.get(), kChunk, n, &o), "qrl_demod_process");
     // everything behind the demodulator is chained on the copy stream with a device-side wait: the deframers (ports 2 / 3 ->
     // gr_deframer_bb on the device; the mailboxes then hold sync + frame bits) and the copy of the counts -- ONE host synchronisation
     // per call, after which the copies below move exactly the bytes the call produced
-    hipStream_t cs = static_cast<hipStream_t>(d_cs);
-    chk(qrl_demod_stream_wait(d_h, cs), "qrl_demod_stream_wait");
+    hipStream_t cs = d_cs.get();
+    chk(qrl_demod_stream_wait(d_h.get(), cs), "qrl_demod_stream_wait");
     if (d_df1) {
-        chk(qrl_deframer_process(d_df1, d_a, d_bcap, d_bcap, d_cnt + 2, 4, d_fa, d_dfcap, d_fcnt), "qrl_deframer_process");
-        chk(qrl_deframer_process(d_df2, d_b, d_bcap, d_bcap, d_cnt + 3, 4, d_fb, d_dfcap, d_fcnt + 1), "qrl_deframer_process");
-        hchk(hipMemcpyAsync(d_hcnt + 4, d_fcnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
+        chk(qrl_deframer_process(d_df1.get(), d_a.get(), d_bcap, d_bcap, d_cnt.get() + 2, 4, d_fa.get(), d_dfcap, d_fcnt.get()), "qrl_deframer_process");
+        chk(qrl_deframer_process(d_df2.get(), d_b.get(), d_bcap, d_bcap, d_cnt.get() + 3, 4, d_fb.get(), d_dfcap, d_fcnt.get() + 1), "qrl_deframer_process");
+        hchk(hipMemcpyAsync(d_hcnt.get() + 4, d_fcnt.get(), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
     }
-    hchk(hipMemcpyAsync(d_hcnt, d_cnt, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
+    hchk(hipMemcpyAsync(d_hcnt.get(), d_cnt.get(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
     hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");
-    uint32_t cnt[4] = {d_hcnt[0], d_hcnt[1], d_hcnt[2], d_hcnt[3]};
+    const uint32_t* hc = d_hcnt.get();
+    uint32_t cnt[4] = {hc[0], hc[1], hc[2], hc[3]};
     if (d_df1) {
-        cnt[2] = d_hcnt[4]; cnt[3] = d_hcnt[5];
-        if (cnt[2]) hchk(hipMemcpy(d_ha.data(), d_fa, cnt[2], hipMemcpyDeviceToHost), "D2H");
-        if (cnt[3]) hchk(hipMemcpy(d_hb.data(), d_fb, cnt[3], hipMemcpyDeviceToHost), "D2H");
+        cnt[2] = hc[4]; cnt[3] = hc[5];
+        if (cnt[2]) hchk(hipMemcpy(d_ha.data(), d_fa.get(), cnt[2], hipMemcpyDeviceToHost), "D2H");
+        if (cnt[3]) hchk(hipMemcpy(d_hb.data(), d_fb.get(), cnt[3], hipMemcpyDeviceToHost), "D2H");
     } else {
-        if (cnt[2]) hchk(hipMemcpy(d_ha.data(), d_a, cnt[2], hipMemcpyDeviceToHost), "D2H");
-        if (cnt[3]) hchk(hipMemcpy(d_hb.data(), d_b, cnt[3], hipMemcpyDeviceToHost), "D2H");
+        if (cnt[2]) hchk(hipMemcpy(d_ha.data(), d_a.get(), cnt[2], hipMemcpyDeviceToHost), "D2H");
+        if (cnt[3]) hchk(hipMemcpy(d_hb.data(), d_b.get(), cnt[3], hipMemcpyDeviceToHost), "D2H");
     }
     if (d_acap) {   // analogue modes: port 1 is audio
-        if (cnt[1]) hchk(hipMemcpy(d_hau.data(), d_audio, cnt[1] * sizeof(float), hipMemcpyDeviceToHost), "D2H");
+        if (cnt[1]) hchk(hipMemcpy(d_hau.data(), d_audio.get(), cnt[1] * sizeof(float), hipMemcpyDeviceToHost), "D2H");
         gr::thread::scoped_lock g(d_mutex);
         if (d_boxa.size() > 8000) d_boxa.clear();      // gr_audio_sink::work: a backlog of more than one second is dropped (gr_audio_sink.cpp:79-85)
         else d_boxa.insert(d_boxa.end(), d_hau.begin(), d_hau.begin() + cnt[1]);
         return;
     }
-    if (cnt[1]) hchk(hipMemcpy(d_hc.data(), d_const, cnt[1] * sizeof(gr_complex), hipMemcpyDeviceToHost), "D2H");
+    if (cnt[1]) hchk(hipMemcpy(d_hc.data(), d_const.get(), cnt[1] * sizeof(gr_complex), hipMemcpyDeviceToHost), "D2H");
     gr::thread::scoped_lock g(d_mutex);
     if (d_box1.size() <= 1048576) d_box1.insert(d_box1.end(), d_ha.begin(), d_ha.begin() + cnt[2]);   // drop rule of gr_bit_sink.cpp:71-76
     if (d_box2.size() <= 1048576) d_box2.insert(d_box2.end(), d_hb.begin(), d_hb.begin() + cnt[3]);
@@ -188,9 +170,9 @@ std::vector<float>* gr_demod_hip::get_audio_data()
     d_boxa.erase(d_boxa.begin(), d_boxa.begin() + 640);
     return v;
 }
-void gr_demod_hip::set_squelch(int value) { chk(qrl_demod_set_squelch(d_h, (double)value), "qrl_demod_set_squelch"); }
-void gr_demod_hip::set_agc_attack(float value) { d_attack = value; chk(qrl_demod_set_agc(d_h, d_attack, d_decay), "qrl_demod_set_agc"); }
-void gr_demod_hip::set_agc_decay(float value) { d_decay = value; chk(qrl_demod_set_agc(d_h, d_attack, d_decay), "qrl_demod_set_agc"); }
+void gr_demod_hip::set_squelch(int value) { chk(qrl_demod_set_squelch(d_h.get(), (double)value), "qrl_demod_set_squelch"); }
+void gr_demod_hip::set_agc_attack(float value) { d_attack = value; chk(qrl_demod_set_agc(d_h.get(), d_attack, d_decay), "qrl_demod_set_agc"); }
+void gr_demod_hip::set_agc_decay(float value) { d_decay = value; chk(qrl_demod_set_agc(d_h.get(), d_attack, d_decay), "qrl_demod_set_agc"); }
 std::vector<unsigned char>* gr_demod_hip::get_data(int nr)
 {
     gr::thread::scoped_lock g(d_mutex);
@@ -234,16 +216,10 @@ gr_mod_hip::gr_mod_hip(qrl_mod* handle)
     : gr::sync_interpolator("gr_mod_hip", gr::io_signature::make(1, 1, sizeof(unsigned char)),
                             gr::io_signature::make(1, 1, sizeof(gr_complex)), (unsigned)qrl_mod_samples_per_byte(handle)), d_h(handle)
 {
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_bytes), kMaxBytes), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_iq), kMaxBytes * qrl_mod_samples_per_byte(d_h) * sizeof(gr_complex)), "hipMalloc");
+    d_bytes.alloc(kMaxBytes);
+    d_iq.alloc(2 * kMaxBytes * qrl_mod_samples_per_byte(d_h.get()));   // interleaved cf32
 }
-gr_mod_hip::~gr_mod_hip()
-{
-    if (d_h) qrl_mod_destroy(d_h);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_iq) (void)hipFree(d_iq);
-}
-void gr_mod_hip::set_bb_gain(float v) { chk(qrl_mod_set_bb_gain(d_h, v), "qrl_mod_set_bb_gain"); }
+void gr_mod_hip::set_bb_gain(float v) { chk(qrl_mod_set_bb_gain(d_h.get(), v), "qrl_mod_set_bb_gain"); }
 gr_amod_hip_sptr make_gr_mod_nbfm_hip(qrl_runtime& rt, int sps, int samp_rate, int carrier_freq, int filter_width)
 {
     (void)carrier_freq;
@@ -264,17 +240,13 @@ gr_amod_hip::gr_amod_hip(qrl_runtime& rt, int filter_width, int modem_type)
     qrl_amod_config c{};
     c.modem_type = modem_type >= 0 ? modem_type : filter_width == 2500 ? QRL_MODEM_NBFM2500 : QRL_MODEM_NBFM5000;
     c.batch = 1; c.max_samples = kMaxAudio; c.bb_gain = 1.0f;
-    chk(qrl_amod_create(rt.ctx(), &c, &d_h), "qrl_amod_create");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_audio), kMaxAudio * sizeof(float)), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_iq), kMaxAudio * 125 * sizeof(gr_complex)), "hipMalloc");
+    qrl_amod* h = nullptr;
+    chk(qrl_amod_create(rt.ctx(), &c, &h), "qrl_amod_create");
+    d_h.reset(h);
+    d_audio.alloc(kMaxAudio);
+    d_iq.alloc(2 * kMaxAudio * 125);   // interleaved cf32
 }
-gr_amod_hip::~gr_amod_hip()
-{
-    if (d_h) qrl_amod_destroy(d_h);
-    if (d_audio) (void)hipFree(d_audio);
-    if (d_iq) (void)hipFree(d_iq);
-}
-void gr_amod_hip::set_bb_gain(float value) { chk(qrl_amod_set_bb_gain(d_h, value), "qrl_amod_set_bb_gain"); }
+void gr_amod_hip::set_bb_gain(float value) { chk(qrl_amod_set_bb_gain(d_h.get(), value), "qrl_amod_set_bb_gain"); }
 // noutput_items = 125 x the audio items offered; audio that does not fill a group of 4 waits in d_carry (its 125 x output items are
 // handed out with the group that completes it: the block then returns fewer items than asked, as a GNU Radio block may)
 int gr_amod_hip::work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items)
@@ -283,14 +255,14 @@ int gr_amod_hip::work(int noutput_items, gr_vector_const_void_star& input_items,
     gr_complex* out = static_cast<gr_complex*>(output_items[0]);
     d_carry.insert(d_carry.end(), in, in + (size_t)noutput_items / 125);
     const size_t usable = d_carry.size() & ~(size_t)3;
-    hipStream_t s = static_cast<hipStream_t>(qrl_amod_stream(d_h));
+    hipStream_t s = static_cast<hipStream_t>(qrl_amod_stream(d_h.get()));
     size_t done = 0;
     while (done < usable) {
         const size_t take = std::min(usable - done, kMaxAudio);
-        hchk(hipMemcpyAsync(d_audio, d_carry.data() + done, take * sizeof(float), hipMemcpyHostToDevice, s), "H2D");
-        chk(qrl_amod_process(d_h, d_audio, kMaxAudio, take, d_iq, kMaxAudio * 125), "qrl_amod_process");
-        hchk(hipMemcpyAsync(out + done * 125, d_iq, take * 125 * sizeof(gr_complex), hipMemcpyDeviceToHost, s), "D2H");
-        chk(qrl_amod_sync(d_h), "qrl_amod_sync");
+        hchk(hipMemcpyAsync(d_audio.get(), d_carry.data() + done, take * sizeof(float), hipMemcpyHostToDevice, s), "H2D");
+        chk(qrl_amod_process(d_h.get(), d_audio.get(), kMaxAudio, take, d_iq.get(), kMaxAudio * 125), "qrl_amod_process");
+        hchk(hipMemcpyAsync(out + done * 125, d_iq.get(), take * 125 * sizeof(gr_complex), hipMemcpyDeviceToHost, s), "D2H");
+        chk(qrl_amod_sync(d_h.get()), "qrl_amod_sync");
         done += take;
     }
     d_carry.erase(d_carry.begin(), d_carry.begin() + (std::ptrdiff_t)usable);
@@ -299,17 +271,17 @@ int gr_amod_hip::work(int noutput_items, gr_vector_const_void_star& input_items,
 
 int gr_mod_hip::work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items)
 {
-    const size_t spb = qrl_mod_samples_per_byte(d_h);
+    const size_t spb = qrl_mod_samples_per_byte(d_h.get());
     const unsigned char* in = static_cast<const unsigned char*>(input_items[0]);
     gr_complex* out = static_cast<gr_complex*>(output_items[0]);
     size_t nbytes = (size_t)noutput_items / spb, done = 0;
-    hipStream_t s = static_cast<hipStream_t>(qrl_mod_stream(d_h));
+    hipStream_t s = static_cast<hipStream_t>(qrl_mod_stream(d_h.get()));
     while (done < nbytes) {
         const size_t take = std::min(nbytes - done, kMaxBytes);
-        hchk(hipMemcpyAsync(d_bytes, in + done, take, hipMemcpyHostToDevice, s), "H2D");
-        chk(qrl_mod_process(d_h, d_bytes, kMaxBytes, take, d_iq, kMaxBytes * spb), "qrl_mod_process");
-        hchk(hipMemcpyAsync(out + done * spb, d_iq, take * spb * sizeof(gr_complex), hipMemcpyDeviceToHost, s), "D2H");
-        chk(qrl_mod_sync(d_h), "qrl_mod_sync");
+        hchk(hipMemcpyAsync(d_bytes.get(), in + done, take, hipMemcpyHostToDevice, s), "H2D");
+        chk(qrl_mod_process(d_h.get(), d_bytes.get(), kMaxBytes, take, d_iq.get(), kMaxBytes * spb), "qrl_mod_process");
+        hchk(hipMemcpyAsync(out + done * spb, d_iq.get(), take * spb * sizeof(gr_complex), hipMemcpyDeviceToHost, s), "D2H");
+        chk(qrl_mod_sync(d_h.get()), "qrl_mod_sync");
         done += take;
     }
     return (int)(nbytes * spb);

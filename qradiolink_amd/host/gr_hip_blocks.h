@@ -6,6 +6,7 @@
 // behaviour as device construction in the reference (std::runtime_error, src/radiocontroller.cpp:1974-1983).
 #pragma once
 #include "gr_compat.h"
+#include "hip_owned.h"
 #include "qrl_hip.h"
 #include <memory>
 #include <stdexcept>
@@ -57,7 +58,6 @@ gr_demod_hip_sptr make_gr_demod_ssb_hip(qrl_runtime& rt, int sps = 125, int samp
 class gr_demod_hip : public gr::sync_block {
 public:
     gr_demod_hip(qrl_runtime& rt, int modem_family, int sps, int samp_rate, int carrier_freq, int filter_width, bool fm);
-    ~gr_demod_hip() override;
     // gr_demod_base::set_samp_rate / set_carrier_offset (src/gr/gr_demod_base.cpp:1303-1362, 1220-1225)
     void set_device_samp_rate(int device_samp_rate);
     void set_carrier_offset(double hz);
@@ -79,16 +79,19 @@ private:
     void run(const gr_complex* x, size_t n);
     qrl_runtime& d_rt;
     qrl_demod_config d_cfg{};
-    qrl_demod* d_h = nullptr;
-    qrl_deframer *d_df1 = nullptr, *d_df2 = nullptr; uint8_t *d_fa = nullptr, *d_fb = nullptr; uint32_t* d_fcnt = nullptr; size_t d_dfcap = 0;
+    // members are released in reverse order of declaration: the handles at the end first, then the buffers they work on, the copy stream last
+    qrl_host::hip_stream d_cs{true};                        // the deframers run on it behind the demodulator
+    qrl_host::dev_buf<uint8_t> d_fa, d_fb; qrl_host::dev_buf<uint32_t> d_fcnt; size_t d_dfcap = 0;
     int d_df_type = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0;
     std::vector<gr_complex> d_carry;                        // at most one sample: the ABI takes even counts
     std::vector<gr_complex> d_buf;
-    float *d_iq = nullptr, *d_const = nullptr; uint8_t *d_a = nullptr, *d_b = nullptr; uint32_t* d_cnt = nullptr;   // device
-    void* d_cs = nullptr; uint32_t* d_hcnt = nullptr;       // copy stream (hipStream_t) the deframers run on behind the demodulator; pinned [6]: port counts + deframed counts
+    qrl_host::dev_buf<float> d_iq, d_const; qrl_host::dev_buf<uint8_t> d_a, d_b; qrl_host::dev_buf<uint32_t> d_cnt;
+    qrl_host::pinned_buf<uint32_t> d_hcnt;                  // [6]: port counts + deframed counts
     std::vector<unsigned char> d_box1, d_box2, d_ha, d_hb; std::vector<gr_complex> d_boxc, d_hc;
-    float* d_audio = nullptr; size_t d_acap = 0; std::vector<float> d_boxa, d_hau; float d_attack = 0.1f, d_decay = 0.1f;
+    qrl_host::dev_buf<float> d_audio; size_t d_acap = 0; std::vector<float> d_boxa, d_hau; float d_attack = 0.1f, d_decay = 0.1f;
+    qrl_host::demod_handle d_h;
+    qrl_host::deframer_handle d_df1, d_df2;
     gr::thread::mutex d_mutex;
     static constexpr size_t kChunk = 1 << 18;
 };
@@ -118,11 +121,10 @@ gr_amod_hip_sptr make_gr_mod_am_hip(qrl_runtime& rt, int sps = 125, int samp_rat
 class gr_amod_hip : public gr::sync_interpolator {
 public:
     gr_amod_hip(qrl_runtime& rt, int filter_width, int modem_type = -1);   // modem_type -1: NBFM by filter width
-    ~gr_amod_hip() override;
     void set_bb_gain(float value);                  // gr_mod_nbfm::set_bb_gain
     int work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items) override;
 private:
-    qrl_amod* d_h = nullptr; float *d_audio = nullptr, *d_iq = nullptr;
+    qrl_host::dev_buf<float> d_audio, d_iq; qrl_host::amod_handle d_h;   // the handle goes first
     std::vector<float> d_carry;                     // the C ABI takes multiples of 4 audio samples (25:4 resampler)
     static constexpr size_t kMaxAudio = 4096;
 };
@@ -130,10 +132,9 @@ private:
 class gr_mod_hip : public gr::sync_interpolator {   // u8 packed bytes in -> cf32 out, qrl_mod_samples_per_byte samples per byte
 public:
     gr_mod_hip(qrl_mod* handle);                    // takes ownership of a handle made by one of the factories
-    ~gr_mod_hip() override;
     void set_bb_gain(float value);                  // gr_mod_qpsk::set_bb_gain
     int work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items) override;
 private:
-    qrl_mod* d_h = nullptr; uint8_t* d_bytes = nullptr; float* d_iq = nullptr;
+    qrl_host::dev_buf<uint8_t> d_bytes; qrl_host::dev_buf<float> d_iq; qrl_host::mod_handle d_h;   // the handle goes first
     static constexpr size_t kMaxBytes = 8192;
 };

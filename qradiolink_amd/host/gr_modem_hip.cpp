@@ -1,8 +1,6 @@
 // gr_modem_hip.cpp — see gr_modem_hip.h.  Every function cites the reference lines it restates.
 #include "gr_modem_hip.h"
 
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -11,14 +9,6 @@
 namespace qrl_host {
 
 namespace {
-void chk(int rc, const char* what)
-{
-    if (rc != QRL_OK) throw std::runtime_error(std::string(what) + ": " + qrl_strerror(rc) + " (" + qrl_last_error() + ")");
-}
-void hchk(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 enum {   // gr_modem_types (src/modem_types.h:5-50); the modes without a QRL_MODEM_* constant
     ModemTypeBPSK8 = 25, ModemTypeM17 = 40
 };
@@ -62,23 +52,37 @@ bool modem_two_branches(int m)   // gr_modem.cpp:1048-1058
 
 // ================================================================================================ gr_demod_base_hip
 struct gr_demod_base_hip::slot {
-    gr_complex* h_iq = nullptr;                           // pinned [streams][chunk]
-    float* d_iq = nullptr;                                // device [streams][chunk] cf32 (an int16 call uses the first half of every buffer: 4-byte samples at the same pitch)
-    bool const_copied = true;
-    float *d_filt = nullptr, *d_const = nullptr; uint8_t *d_a = nullptr, *d_b = nullptr, *d_dmo = nullptr; uint32_t *d_cnt = nullptr, *d_dmocnt = nullptr;
-    gr_complex* h_const = nullptr; uint8_t *h_a = nullptr, *h_b = nullptr, *h_dmo = nullptr; uint32_t *h_cnt = nullptr, *h_dmocnt = nullptr;   // pinned
-    float *d_rssi = nullptr, *h_rssi = nullptr; bool rssi_valid = false;   // latest rssi_block value per stream (device / pinned)
-    float *d_audio = nullptr, *h_audio = nullptr;         // analogue modes: port 1 (device / pinned)
-    float *d_scope = nullptr; gr_complex* h_scope = nullptr; uint32_t *d_scnt = nullptr, *h_scnt = nullptr; bool scoped = false;   // time-domain scope items of the call
-    uint8_t *d_fr[2] = {nullptr, nullptr}, *h_fr[2] = {nullptr, nullptr}; uint32_t *d_frcnt[2] = {nullptr, nullptr}, *h_frcnt[2] = {nullptr, nullptr};   // framed records of bits A / B
+    pinned_buf<gr_complex> h_iq;                          // [streams][chunk]
+    dev_buf<float> d_iq;                                  // [streams][chunk] cf32 (an int16 call uses the first half of every buffer: 4-byte samples at the same pitch)
+    dev_buf<float> d_filt;                                // port 0, cf32
+    mirror<gr_complex> konst; bool const_copied = true;   // port 1
+    mirror<uint8_t> a, b, dmo; mirror<uint32_t> cnt, dmocnt;   // dmo / dmocnt: the pinned side takes the DMO slicer's bursts or the repeater sink's
+    mirror<float> rssi; bool rssi_valid = false;          // latest rssi_block value per stream
+    mirror<float> audio;                                  // analogue modes: port 1
+    mirror<gr_complex> scope; mirror<uint32_t> scnt; bool scoped = false;   // time-domain scope items of the call
+    mirror<uint8_t> fr[2]; mirror<uint32_t> frcnt[2];     // framed records of bits A / B; counts [2 N]: bytes, frames; [N]: bits collected under a sync
     bool framed = false, bits_copied = true;
-    uint8_t *d_l2 = nullptr, *h_l2 = nullptr; bool l2 = false;   // DMR layer 2 records of the call's bursts (set_dmr_l2; device / pinned)
-    uint8_t *d_m17ev = nullptr, *h_m17ev = nullptr; bool m17 = false;   // M17 link records of the frames of bits A (set_m17_link)
-    uint8_t *d_call = nullptr, *h_call = nullptr; bool call = false;   // DMR call records of the same bursts (set_dmr_call)
-    uint8_t *d_rep = nullptr, *d_info = nullptr, *h_info = nullptr; uint32_t* d_repcnt = nullptr; bool rep = false;   // the repeater-mode sink's bursts, their slot records (set_dmr_repeater)
-    hipEvent_t done = nullptr;
+    mirror<uint8_t> rec_l2; bool l2 = false;              // DMR layer 2 records of the call's bursts (set_dmr_l2)
+    mirror<uint8_t> rec_m17; bool m17 = false;            // M17 link records of the frames of bits A (set_m17_link)
+    mirror<uint8_t> rec_call; bool call = false;          // DMR call records of the same bursts (set_dmr_call)
+    dev_buf<uint8_t> d_rep; mirror<uint8_t> rec_info; dev_buf<uint32_t> d_repcnt; bool rep = false;   // the repeater-mode sink's bursts, their slot records (set_dmr_repeater)
+    hip_event done;
 };
 static constexpr size_t kDmoCap = 16;
+using records = std::vector<std::vector<unsigned char>>;
+// record i of stream s, `bytes` long, of a pinned array of kDmoCap records per stream: appended to the stream's mailbox
+static void append_record(records& box, const uint8_t* h, size_t s, size_t i, size_t bytes)
+{
+    const uint8_t* r = h + (s * kDmoCap + i) * bytes;
+    box.emplace_back(r, r + bytes);
+}
+static records take_box(std::mutex& m, records& box)
+{
+    std::lock_guard<std::mutex> g(m);
+    records out;
+    out.swap(box);
+    return out;
+}
 
 gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_chunk)
     : d_rt(rt), d_n(streams), d_rate(device_samp_rate), d_offset(carrier_offset_hz), d_chunk(max_chunk & ~(size_t)1),
@@ -87,165 +91,110 @@ gr_demod_base_hip::gr_demod_base_hip(qrl_runtime& rt, int streams, int device_sa
     d_boxf[0].resize(streams); d_boxf[1].resize(streams); d_boxs.resize(streams);
     for (int k = 0; k < 2; ++k) { d_fbits[k].assign(streams, 0); d_fact[k].assign(streams, 0); }
     if (streams < 1 || d_chunk < 2) throw std::invalid_argument("gr_demod_base_hip: streams >= 1, max_chunk >= 2");
-    hipStream_t s;
-    // lowest priority -- not for the scheduling: streams of one priority share a few hardware queues, and a wait queued on this
-    // stream would otherwise hold back the kernels of a handle stream that happens to sit on the same queue (csrc/engine.cpp, stream creation)
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    hchk(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_lo), "hipStreamCreate");
-    d_copy = s;
 }
 gr_demod_base_hip::~gr_demod_base_hip()
 {
     try { flush(); } catch (...) {}
-    close();
-    if (d_call_rx) qrl_dmr_rx_destroy(d_call_rx);
-    if (d_m17_rx) qrl_m17_rx_destroy(d_m17_rx);
-    if (d_sink) qrl_dmr_sink_destroy(d_sink);   // it works on the copy stream: before the stream goes
-    if (d_copy) (void)hipStreamDestroy(static_cast<hipStream_t>(d_copy));
+    close();   // then the members, in reverse order of declaration (gr_modem_hip.h)
 }
 void gr_demod_base_hip::close()
 {
-    if (d_h) { qrl_demod_destroy(d_h); d_h = nullptr; }
-    if (d_rssi) { qrl_rssi_destroy(d_rssi); d_rssi = nullptr; }
-    if (d_fft) { qrl_fft_destroy(d_fft); d_fft = nullptr; }
-    if (d_fftout) { (void)hipFree(d_fftout); d_fftout = nullptr; }
-    for (auto& f : d_fs) if (f) { qrl_framesync_destroy(f); f = nullptr; }
-    for (auto& sp : d_slot) {
-        if (!sp) continue;
-        if (sp->d_scope) (void)hipFree(sp->d_scope);
-        if (sp->d_scnt) (void)hipFree(sp->d_scnt);
-        if (sp->h_scope) (void)hipHostFree(sp->h_scope);
-        if (sp->h_scnt) (void)hipHostFree(sp->h_scnt);
-        for (int k = 0; k < 2; ++k) {
-            if (sp->d_fr[k]) (void)hipFree(sp->d_fr[k]);
-            if (sp->d_frcnt[k]) (void)hipFree(sp->d_frcnt[k]);
-            if (sp->h_fr[k]) (void)hipHostFree(sp->h_fr[k]);
-            if (sp->h_frcnt[k]) (void)hipHostFree(sp->h_frcnt[k]);
-        }
-        if (sp->d_m17ev) (void)hipFree(sp->d_m17ev);
-        if (sp->h_m17ev) (void)hipHostFree(sp->h_m17ev);
-        if (sp->d_rssi) (void)hipFree(sp->d_rssi);
-        if (sp->h_rssi) (void)hipHostFree(sp->h_rssi);
-        if (sp->d_audio) (void)hipFree(sp->d_audio);
-        if (sp->h_audio) (void)hipHostFree(sp->h_audio);
-        for (void* p : {(void*)sp->d_iq, (void*)sp->d_filt, (void*)sp->d_const, (void*)sp->d_a, (void*)sp->d_b, (void*)sp->d_dmo, (void*)sp->d_cnt, (void*)sp->d_dmocnt})
-            if (p) (void)hipFree(p);
-        for (void* p : {(void*)sp->h_iq, (void*)sp->h_const, (void*)sp->h_a, (void*)sp->h_b, (void*)sp->h_dmo, (void*)sp->h_cnt, (void*)sp->h_dmocnt})
-            if (p) (void)hipHostFree(p);
-        if (sp->d_l2) (void)hipFree(sp->d_l2);
-        if (sp->h_l2) (void)hipHostFree(sp->h_l2);
-        if (sp->d_call) (void)hipFree(sp->d_call);
-        for (void* p : {(void*)sp->d_rep, (void*)sp->d_info, (void*)sp->d_repcnt}) if (p) (void)hipFree(p);
-        if (sp->h_info) (void)hipHostFree(sp->h_info);
-        if (sp->h_call) (void)hipHostFree(sp->h_call);
-        if (sp->done) (void)hipEventDestroy(sp->done);
-        delete sp;
-        sp = nullptr;
-    }
+    d_h.reset(); d_rssi.reset(); d_fft.reset(); d_fftout.reset();
+    for (auto& f : d_fs) f.reset();
+    for (auto& sp : d_slot) sp.reset();
     d_inflight = -1;
 }
-void gr_demod_base_hip::open()
-{
+void gr_demod_base_hip::open()   // a failed open leaves the facade closed
+try {
     close();
     qrl_demod_config c{};
     c.modem_type = d_mode; c.use_mode_defaults = 1; c.device_samp_rate = d_rate; c.carrier_offset_hz = d_offset;
     c.batch = d_n; c.max_chunk = d_chunk; c.enable_side_outputs = 1;
     c.time_domain_samp_rate = d_scope_rate; c.time_domain_filter_width = d_scope_fw;
-    chk(qrl_demod_create(d_rt.ctx(), &c, &d_h), "qrl_demod_create");
-    chk(qrl_demod_set_sc16_scale(d_h, d_sc16_scale), "qrl_demod_set_sc16_scale");
-    if (d_per_stream) chk(qrl_demod_set_carrier_offsets(d_h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
-    chk(qrl_demod_out_caps(d_h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
-    chk(qrl_demod_audio_cap(d_h, d_chunk, &d_acap), "qrl_demod_audio_cap");
-    if (d_acap) chk(qrl_demod_set_squelch(d_h, (double)d_squelch), "qrl_demod_set_squelch");
-    if (d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");   // the reference's _am, _usb and _lsb instances all keep the rates
-    if (d_acap && d_ctcss != 0.0f && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_demod_set_ctcss(d_h, d_ctcss), "qrl_demod_set_ctcss");   // the reference's instances keep their tone across mode changes
-    if (d_acap && d_width.count(d_mode)) chk(qrl_demod_set_filter_width(d_h, d_width[d_mode]), "qrl_demod_set_filter_width");   // ... and their set_filter_width designs
-    if (d_acap && d_if_gain >= 0.0f && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(d_h, d_if_gain), "qrl_demod_set_gain");
+    qrl_demod* h = nullptr;
+    chk(qrl_demod_create(d_rt.ctx(), &c, &h), "qrl_demod_create");
+    d_h.reset(h);
+    chk(qrl_demod_set_sc16_scale(h, d_sc16_scale), "qrl_demod_set_sc16_scale");
+    if (d_per_stream) chk(qrl_demod_set_carrier_offsets(h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
+    chk(qrl_demod_out_caps(h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
+    chk(qrl_demod_audio_cap(h, d_chunk, &d_acap), "qrl_demod_audio_cap");
+    if (d_acap) chk(qrl_demod_set_squelch(h, (double)d_squelch), "qrl_demod_set_squelch");
+    if (d_acap && has_agc()) chk(qrl_demod_set_agc(h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");   // the reference's _am, _usb and _lsb instances all keep the rates
+    if (d_acap && d_ctcss != 0.0f && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_demod_set_ctcss(h, d_ctcss), "qrl_demod_set_ctcss");   // the reference's instances keep their tone across mode changes
+    if (d_acap && d_width.count(d_mode)) chk(qrl_demod_set_filter_width(h, d_width[d_mode]), "qrl_demod_set_filter_width");   // ... and their set_filter_width designs
+    if (d_acap && d_if_gain >= 0.0f && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(h, d_if_gain), "qrl_demod_set_gain");
     const size_t N = (size_t)d_n;
     // side outputs on the copy stream: rssi_block behind port 0, rx_fft_c on the device-rate IQ (gr_demod_base.cpp:166,185,199-200)
-    chk(qrl_rssi_create(d_rt.ctx(), d_n, d_rssi_cal, d_copy, &d_rssi), "qrl_rssi_create");
-    chk(qrl_fft_create(d_rt.ctx(), d_n, d_fftsize, 5 /* WIN_BLACKMAN_HARRIS */, d_copy, &d_fft), "qrl_fft_create");
-    chk(qrl_fft_set_enabled(d_fft, d_fft_on ? 1 : 0), "qrl_fft_set_enabled");
-    chk(qrl_fft_set_sc16_scale(d_fft, d_sc16_scale), "qrl_fft_set_sc16_scale");
+    qrl_rssi* rssi = nullptr; qrl_fft* fft = nullptr;
+    chk(qrl_rssi_create(d_rt.ctx(), d_n, d_rssi_cal, d_copy.get(), &rssi), "qrl_rssi_create");
+    d_rssi.reset(rssi);
+    chk(qrl_fft_create(d_rt.ctx(), d_n, d_fftsize, 5 /* WIN_BLACKMAN_HARRIS */, d_copy.get(), &fft), "qrl_fft_create");
+    d_fft.reset(fft);
+    chk(qrl_fft_set_enabled(fft, d_fft_on ? 1 : 0), "qrl_fft_set_enabled");
+    chk(qrl_fft_set_sc16_scale(fft, d_sc16_scale), "qrl_fft_set_sc16_scale");
     d_level.assign(N, 0.0f);
     // L1 frame synchronisers on the copy stream, behind the demodulator (digital modes with gr_modem framing: not DMR, not analogue)
     const bool fs_on = d_want_fs && !d_acap && d_mode != QRL_MODEM_DMR;
     if (fs_on) {
-        for (auto& f : d_fs) chk(qrl_framesync_create(d_rt.ctx(), d_mode, d_n, d_copy, &f), "qrl_framesync_create");
-        const size_t fb = (size_t)qrl_framesync_frame_bytes(d_fs[0]);
+        for (auto& f : d_fs) {
+            qrl_framesync* fs = nullptr;
+            chk(qrl_framesync_create(d_rt.ctx(), d_mode, d_n, d_copy.get(), &fs), "qrl_framesync_create");
+            f.reset(fs);
+        }
+        const size_t fb = (size_t)qrl_framesync_frame_bytes(d_fs[0].get());
         d_frcap = (d_bcap / 8 + fb + 96 + 16 * (d_bcap / std::max<size_t>(8 * fb, 8) + 2) + 3) & ~(size_t)3;   // never overflows (include/qrl_hip.h)
     }
-    chk(qrl_demod_time_domain_cap(d_h, d_chunk, &d_scap), "qrl_demod_time_domain_cap");
+    chk(qrl_demod_time_domain_cap(h, d_chunk, &d_scap), "qrl_demod_time_domain_cap");
     for (auto& sp : d_slot) {
-        sp = new slot;
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_scope), N * d_scap * sizeof(gr_complex)), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_scnt), N * sizeof(uint32_t)), "hipMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_scope), N * d_scap * sizeof(gr_complex), hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_scnt), N * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+        sp = std::make_unique<slot>();
+        sp->scope.alloc(N * d_scap);
+        sp->scnt.alloc(N);
         if (fs_on) for (int k = 0; k < 2; ++k) {
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_fr[k]), N * d_frcap), "hipMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_frcnt[k]), N * 3 * sizeof(uint32_t)), "hipMalloc");   // [2 N]: bytes, frames; [N]: bits collected under a sync
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_fr[k]), N * d_frcap, hipHostMallocDefault), "hipHostMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_frcnt[k]), N * 3 * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+            sp->fr[k].alloc(N * d_frcap);
+            sp->frcnt[k].alloc(N * 3);
         }
-        if (fs_on && d_mode == QRL_MODEM_M17) {   // one link record per frame the row can hold
-            const size_t ev = N * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) * QRL_M17_RX_RECORD_BYTES;
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_m17ev), ev), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_m17ev), ev, hipHostMallocDefault), "hipHostMalloc");
-        }
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_rssi), N * sizeof(float)), "hipMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_rssi), N * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_iq), N * d_chunk * sizeof(gr_complex), hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_iq), N * d_chunk * sizeof(gr_complex)), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_filt), N * d_fcap * sizeof(gr_complex)), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_const), N * d_ccap * sizeof(gr_complex)), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_a), N * d_bcap), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_b), N * d_bcap), "hipMalloc");
-        hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_cnt), N * 4 * sizeof(uint32_t)), "hipMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_const), N * d_ccap * sizeof(gr_complex), hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_a), N * d_bcap, hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_b), N * d_bcap, hipHostMallocDefault), "hipHostMalloc");
-        hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_cnt), N * 4 * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
-        if (d_acap) {
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_audio), N * d_acap * sizeof(float)), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_audio), N * d_acap * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-        }
+        if (fs_on && d_mode == QRL_MODEM_M17) sp->rec_m17.alloc(N * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) * QRL_M17_RX_RECORD_BYTES);   // one link record per frame the row can hold
+        sp->rssi.alloc(N);
+        sp->h_iq.alloc(N * d_chunk);
+        sp->d_iq.alloc(2 * N * d_chunk);
+        sp->d_filt.alloc(2 * N * d_fcap);
+        sp->konst.alloc(N * d_ccap);
+        sp->a.alloc(N * d_bcap);
+        sp->b.alloc(N * d_bcap);
+        sp->cnt.alloc(N * 4);
+        if (d_acap) sp->audio.alloc(N * d_acap);
         if (d_mode == QRL_MODEM_DMR) {
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_dmo), N * kDmoCap * QRL_DMO_RECORD_BYTES), "hipMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_dmocnt), N * sizeof(uint32_t)), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_dmo), N * kDmoCap * QRL_DMO_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_dmocnt), N * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_l2), N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_call), N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipHostMallocDefault), "hipHostMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_rep), N * kDmoCap * QRL_DMR_SINK_FRAME_BYTES), "hipMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_info), N * kDmoCap * QRL_DMR_SINK_INFO_BYTES), "hipMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&sp->d_repcnt), N * sizeof(uint32_t)), "hipMalloc");
-            hchk(hipHostMalloc(reinterpret_cast<void**>(&sp->h_info), N * kDmoCap * QRL_DMR_SINK_INFO_BYTES, hipHostMallocDefault), "hipHostMalloc");
+            sp->dmo.alloc(N * kDmoCap * QRL_DMO_RECORD_BYTES);
+            sp->dmocnt.alloc(N);
+            sp->rec_l2.alloc(N * kDmoCap * QRL_DMR_L2_RECORD_BYTES);
+            sp->rec_call.alloc(N * kDmoCap * QRL_DMR_RX_RECORD_BYTES);
+            sp->d_rep.alloc(N * kDmoCap * QRL_DMR_SINK_FRAME_BYTES);
+            sp->rec_info.alloc(N * kDmoCap * QRL_DMR_SINK_INFO_BYTES);
+            sp->d_repcnt.alloc(N);
         }
-        hchk(hipEventCreateWithFlags(&sp->done, hipEventDisableTiming), "hipEventCreate");
     }
     d_calls = 0;
-    if (d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // the receiver starts afresh, and so does the call state behind it
-    if (d_sink) chk(qrl_dmr_sink_reset(d_sink), "qrl_dmr_sink_reset");
-    if (d_m17_rx) chk(qrl_m17_rx_reset(d_m17_rx, d_copy), "qrl_m17_rx_reset");
+    if (d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx.get(), d_copy.get()), "qrl_dmr_rx_reset");   // the receiver starts afresh, and so does the call state behind it
+    if (d_sink) chk(qrl_dmr_sink_reset(d_sink.get()), "qrl_dmr_sink_reset");
+    if (d_m17_rx) chk(qrl_m17_rx_reset(d_m17_rx.get(), d_copy.get()), "qrl_m17_rx_reset");
+} catch (...) {
+    close();
+    throw;
 }
 void gr_demod_base_hip::apply_call_mode()
 {
-    if (d_call_rx) chk(qrl_dmr_rx_set_mode(d_call_rx, d_rep_on ? QRL_DMR_MODE_REPEATER : QRL_DMR_MODE_DMO, d_rep_slot), "qrl_dmr_rx_set_mode");
+    if (d_call_rx.get()) chk(qrl_dmr_rx_set_mode(d_call_rx.get(), d_rep_on ? QRL_DMR_MODE_REPEATER : QRL_DMR_MODE_DMO, d_rep_slot), "qrl_dmr_rx_set_mode");
 }
 void gr_demod_base_hip::set_dmr_repeater(bool on, int timeslot)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (on && (timeslot < 1 || timeslot > 2)) throw std::runtime_error("gr_demod_base_hip::set_dmr_repeater: timeslot outside 1..2");
     if (on) {
-        if (!d_sink) chk(qrl_dmr_sink_create(d_rt.ctx(), d_n, d_copy, &d_sink), "qrl_dmr_sink_create");
-        else if (!d_rep_on) chk(qrl_dmr_sink_reset(d_sink), "qrl_dmr_sink_reset");   // switched back on: nothing of the bits it missed
+        if (!d_sink) { qrl_dmr_sink* h = nullptr; chk(qrl_dmr_sink_create(d_rt.ctx(), d_n, d_copy.get(), &h), "qrl_dmr_sink_create"); d_sink.reset(h); }
+        else if (!d_rep_on) chk(qrl_dmr_sink_reset(d_sink.get()), "qrl_dmr_sink_reset");   // switched back on: nothing of the bits it missed
         d_rep_slot = timeslot;
     }
-    if (on != d_rep_on && d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // another sink's bursts: no call goes on across the switch
+    if (on != d_rep_on && d_call_rx) chk(qrl_dmr_rx_reset(d_call_rx.get(), d_copy.get()), "qrl_dmr_rx_reset");   // another sink's bursts: no call goes on across the switch
     d_rep_on = on;
     apply_call_mode();
 }
@@ -255,11 +204,13 @@ void gr_demod_base_hip::set_dmr_call(bool on, int colour_code, bool promiscuous)
     const qrl_dmr_rx_config c = {colour_code, promiscuous ? 1 : 0};
     if (!d_call_rx) {
         if (!on) return;
-        chk(qrl_dmr_rx_create(d_rt.ctx(), (size_t)d_n, &c, &d_call_rx), "qrl_dmr_rx_create");
+        qrl_dmr_rx* h = nullptr;
+        chk(qrl_dmr_rx_create(d_rt.ctx(), (size_t)d_n, &c, &h), "qrl_dmr_rx_create");
+        d_call_rx.reset(h);
         apply_call_mode();
     } else {
-        chk(qrl_dmr_rx_set_config(d_call_rx, &c), "qrl_dmr_rx_set_config");
-        if (on && !d_call_on) chk(qrl_dmr_rx_reset(d_call_rx, d_copy), "qrl_dmr_rx_reset");   // switched back on: nothing of the calls it missed
+        chk(qrl_dmr_rx_set_config(d_call_rx.get(), &c), "qrl_dmr_rx_set_config");
+        if (on && !d_call_on) chk(qrl_dmr_rx_reset(d_call_rx.get(), d_copy.get()), "qrl_dmr_rx_reset");   // switched back on: nothing of the calls it missed
     }
     d_call_on = on;
 }
@@ -269,10 +220,12 @@ void gr_demod_base_hip::set_m17_link(bool on, int can_rx, bool decode_all_can)
     const qrl_m17_rx_config c = {can_rx, decode_all_can ? 1 : 0};
     if (!d_m17_rx) {
         if (!on) return;
-        chk(qrl_m17_rx_create(d_rt.ctx(), (size_t)d_n, &c, &d_m17_rx), "qrl_m17_rx_create");
+        qrl_m17_rx* h = nullptr;
+        chk(qrl_m17_rx_create(d_rt.ctx(), (size_t)d_n, &c, &h), "qrl_m17_rx_create");
+        d_m17_rx.reset(h);
     } else {
-        chk(qrl_m17_rx_set_config(d_m17_rx, &c), "qrl_m17_rx_set_config");
-        if (on && !d_m17_on) chk(qrl_m17_rx_reset(d_m17_rx, d_copy), "qrl_m17_rx_reset");   // switched back on: nothing of the frames it missed
+        chk(qrl_m17_rx_set_config(d_m17_rx.get(), &c), "qrl_m17_rx_set_config");
+        if (on && !d_m17_on) chk(qrl_m17_rx_reset(d_m17_rx.get(), d_copy.get()), "qrl_m17_rx_reset");   // switched back on: nothing of the frames it missed
     }
     d_m17_on = on;
 }
@@ -324,7 +277,7 @@ void gr_demod_base_hip::set_carrier_offset(double hz)   // gr_demod_base.cpp:122
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_offset = hz;
     d_offsets.assign((size_t)d_n, hz);
-    if (d_h) chk(qrl_demod_set_carrier_offset(d_h, hz), "qrl_demod_set_carrier_offset");
+    if (d_h.get()) chk(qrl_demod_set_carrier_offset(d_h.get(), hz), "qrl_demod_set_carrier_offset");
 }
 void gr_demod_base_hip::set_carrier_offset(double hz, int stream)
 {
@@ -332,7 +285,7 @@ void gr_demod_base_hip::set_carrier_offset(double hz, int stream)
     if (stream < 0 || stream >= d_n) throw std::out_of_range("gr_demod_base_hip::set_carrier_offset: stream out of range");
     std::vector<double> v = d_offsets;
     v[(size_t)stream] = hz;
-    if (d_h) chk(qrl_demod_set_carrier_offsets(d_h, v.data()), "qrl_demod_set_carrier_offsets");
+    if (d_h.get()) chk(qrl_demod_set_carrier_offsets(d_h.get(), v.data()), "qrl_demod_set_carrier_offsets");
     d_offsets.swap(v);
     d_per_stream = true;
 }
@@ -352,8 +305,8 @@ void gr_demod_base_hip::set_sc16_scale(float scale)
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_demod_base_hip::set_sc16_scale: finite, non-zero");
     d_sc16_scale = scale;
-    if (d_h) chk(qrl_demod_set_sc16_scale(d_h, scale), "qrl_demod_set_sc16_scale");
-    if (d_fft) chk(qrl_fft_set_sc16_scale(d_fft, scale), "qrl_fft_set_sc16_scale");   // the spectrum tap reads the same int16 slot
+    if (d_h.get()) chk(qrl_demod_set_sc16_scale(d_h.get(), scale), "qrl_demod_set_sc16_scale");
+    if (d_fft.get()) chk(qrl_fft_set_sc16_scale(d_fft.get(), scale), "qrl_fft_set_sc16_scale");   // the spectrum tap reads the same int16 slot
 }
 void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
 {
@@ -371,34 +324,34 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     slot& sl = *d_slot[cur];
     const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the pitch stays d_chunk samples
     // slot `cur` was last used by call k - 2, which work(k - 1) has harvested: its buffers are free
-    for (int s = 0; s < d_n; ++s) std::memcpy(reinterpret_cast<char*>(sl.h_iq) + (size_t)s * d_chunk * sb, iq[s], n * sb);
-    hipStream_t hs = static_cast<hipStream_t>(qrl_demod_stream(d_h)), cs = static_cast<hipStream_t>(d_copy);
+    for (int s = 0; s < d_n; ++s) std::memcpy(reinterpret_cast<char*>(sl.h_iq.get()) + (size_t)s * d_chunk * sb, iq[s], n * sb);
+    hipStream_t hs = static_cast<hipStream_t>(qrl_demod_stream(d_h.get())), cs = d_copy.get();
     if (!d_demod_on) {                                           // _demod_valve closed (gr_demod_base.cpp:1150-1153): only the spectrum tap, which sits in front of it
         // everything of this call on the spectrum block's own stream (d_copy): the upload, the FFT fill behind it, and the host waits for THAT
         // stream before the slot is reused (the upload used to go on the demodulator's stream, which nothing ordered the FFT behind)
-        hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, cs), "H2D");
-        if (sc16) chk(qrl_fft_process_sc16(d_fft, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n), "qrl_fft_process_sc16");
-        else chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
+        hchk(hipMemcpyAsync(sl.d_iq.get(), sl.h_iq.get(), (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, cs), "H2D");
+        if (sc16) chk(qrl_fft_process_sc16(d_fft.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc16");
+        else chk(qrl_fft_process(d_fft.get(), sl.d_iq.get(), d_chunk, n), "qrl_fft_process");
         hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");  // (d_calls does not advance: the next call takes the same slot; no harvest belongs to this call)
         return;
     }
-    hchk(hipMemcpyAsync(sl.d_iq, sl.h_iq, (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, hs), "H2D");
-    if (d_mode == QRL_MODEM_DMR) chk(qrl_demod_set_dmo_output(d_h, sl.d_dmo, kDmoCap, sl.d_dmocnt), "qrl_demod_set_dmo_output");
+    hchk(hipMemcpyAsync(sl.d_iq.get(), sl.h_iq.get(), (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, hs), "H2D");
+    if (d_mode == QRL_MODEM_DMR) chk(qrl_demod_set_dmo_output(d_h.get(), sl.dmo.dev(), kDmoCap, sl.dmocnt.dev()), "qrl_demod_set_dmo_output");
     sl.scoped = d_scope_on;
-    chk(qrl_demod_set_time_domain_output(d_h, d_scope_on ? sl.d_scope : nullptr, d_scap, d_scope_on ? sl.d_scnt : nullptr), "qrl_demod_set_time_domain_output");
+    chk(qrl_demod_set_time_domain_output(d_h.get(), d_scope_on ? reinterpret_cast<float*>(sl.scope.dev()) : nullptr, d_scap, d_scope_on ? sl.scnt.dev() : nullptr), "qrl_demod_set_time_domain_output");
     qrl_demod_out o{};
-    o.filtered = sl.d_filt; o.filtered_cap = d_fcap; o.constellation = sl.d_const; o.constellation_cap = d_ccap;
-    o.bits_a = sl.d_a; o.bits_b = sl.d_b; o.bits_cap = d_bcap; o.counts = sl.d_cnt;
-    o.audio = sl.d_audio; o.audio_cap = d_acap;
-    if (sc16) chk(qrl_demod_process_sc16(d_h, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n, &o), "qrl_demod_process_sc16");
-    else chk(qrl_demod_process(d_h, sl.d_iq, d_chunk, n, &o), "qrl_demod_process");
-    chk(qrl_demod_stream_wait(d_h, cs), "qrl_demod_stream_wait");
+    o.filtered = sl.d_filt.get(); o.filtered_cap = d_fcap; o.constellation = reinterpret_cast<float*>(sl.konst.dev()); o.constellation_cap = d_ccap;
+    o.bits_a = sl.a.dev(); o.bits_b = sl.b.dev(); o.bits_cap = d_bcap; o.counts = sl.cnt.dev();
+    o.audio = sl.audio.dev(); o.audio_cap = d_acap;
+    if (sc16) chk(qrl_demod_process_sc16(d_h.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n, &o), "qrl_demod_process_sc16");
+    else chk(qrl_demod_process(d_h.get(), sl.d_iq.get(), d_chunk, n, &o), "qrl_demod_process");
+    chk(qrl_demod_stream_wait(d_h.get(), cs), "qrl_demod_stream_wait");
     const size_t N = (size_t)d_n;
-    if (d_acap) hchk(hipMemcpyAsync(sl.h_audio, sl.d_audio, N * d_acap * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");
-    hchk(hipMemcpyAsync(sl.h_cnt, sl.d_cnt, N * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
+    if (d_acap) sl.audio.download(cs);
+    sl.cnt.download(cs);
     if (sl.scoped) {
-        hchk(hipMemcpyAsync(sl.h_scnt, sl.d_scnt, N * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
-        hchk(hipMemcpyAsync(sl.h_scope, sl.d_scope, N * d_scap * sizeof(gr_complex), hipMemcpyDeviceToHost, cs), "D2H");
+        sl.scnt.download(cs);
+        sl.scope.download(cs);
     }
     sl.framed = d_fs[0] != nullptr;
     sl.m17 = false;
@@ -406,60 +359,60 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     if (sl.framed) {
         // the frame synchronisers run on the copy stream behind the demodulator (no host synchronisation in between): bits A / B of
         // this call -> records { type, nbytes | _modem_sync << 16, payload }; only those travel to the host
-        for (int k = 0; k < 2; ++k) chk(qrl_framesync_set_activity_output(d_fs[k], sl.d_frcnt[k] + 2 * N), "qrl_framesync_set_activity_output");
-        chk(qrl_framesync_process(d_fs[0], sl.d_a, d_bcap, d_bcap, sl.d_cnt + 2, 4, sl.d_fr[0], d_frcap, sl.d_frcnt[0]), "qrl_framesync_process");
-        chk(qrl_framesync_process(d_fs[1], sl.d_b, d_bcap, d_bcap, sl.d_cnt + 3, 4, sl.d_fr[1], d_frcap, sl.d_frcnt[1]), "qrl_framesync_process");
+        for (int k = 0; k < 2; ++k) chk(qrl_framesync_set_activity_output(d_fs[k].get(), sl.frcnt[k].dev() + 2 * N), "qrl_framesync_set_activity_output");
+        chk(qrl_framesync_process(d_fs[0].get(), sl.a.dev(), d_bcap, d_bcap, sl.cnt.dev() + 2, 4, sl.fr[0].dev(), d_frcap, sl.frcnt[0].dev()), "qrl_framesync_process");
+        chk(qrl_framesync_process(d_fs[1].get(), sl.b.dev(), d_bcap, d_bcap, sl.cnt.dev() + 3, 4, sl.fr[1].dev(), d_frcap, sl.frcnt[1].dev()), "qrl_framesync_process");
         for (int k = 0; k < 2; ++k) {
-            hchk(hipMemcpyAsync(sl.h_frcnt[k], sl.d_frcnt[k], N * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
-            hchk(hipMemcpyAsync(sl.h_fr[k], sl.d_fr[k], N * d_frcap, hipMemcpyDeviceToHost, cs), "D2H");
+            sl.frcnt[k].download(cs);
+            sl.fr[k].download(cs);
         }
-        sl.m17 = d_m17_on && d_m17_rx && sl.d_m17ev;
+        sl.m17 = d_m17_on && d_m17_rx && sl.rec_m17.dev();
         if (sl.m17) {   // the link layer behind the synchroniser of bits A, on the same stream: the records of this call's frames
             const size_t cap = d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES;
-            chk(qrl_m17_rx_process(d_m17_rx, cs, sl.d_fr[0], d_frcap, sl.d_frcnt[0], cap, sl.d_m17ev), "qrl_m17_rx_process");
-            hchk(hipMemcpyAsync(sl.h_m17ev, sl.d_m17ev, N * cap * QRL_M17_RX_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+            chk(qrl_m17_rx_process(d_m17_rx.get(), cs, sl.fr[0].dev(), d_frcap, sl.frcnt[0].dev(), cap, sl.rec_m17.dev()), "qrl_m17_rx_process");
+            sl.rec_m17.download(cs);
         }
     }
     if (sl.bits_copied) {
-        hchk(hipMemcpyAsync(sl.h_a, sl.d_a, N * d_bcap, hipMemcpyDeviceToHost, cs), "D2H");
-        hchk(hipMemcpyAsync(sl.h_b, sl.d_b, N * d_bcap, hipMemcpyDeviceToHost, cs), "D2H");
+        sl.a.download(cs);
+        sl.b.download(cs);
     }
     sl.const_copied = d_const_on;
-    if (d_const_on) hchk(hipMemcpyAsync(sl.h_const, sl.d_const, N * d_ccap * sizeof(gr_complex), hipMemcpyDeviceToHost, cs), "D2H");
+    if (d_const_on) sl.konst.download(cs);
     if (d_mode == QRL_MODEM_DMR) {
         sl.rep = d_rep_on && d_sink;
         // getDMRData(bool dmo): the bursts of the DMO slicer, or those the repeater-mode sink finds in port 2 of this call (on the copy stream, which
         // waits for the demodulator on the device); the same record either way, so everything behind it takes frames / fcnt
-        const uint8_t* frames = sl.rep ? sl.d_rep : sl.d_dmo;
-        const uint32_t* fcnt = sl.rep ? sl.d_repcnt : sl.d_dmocnt;
+        const uint8_t* frames = sl.rep ? sl.d_rep.get() : sl.dmo.dev();
+        const uint32_t* fcnt = sl.rep ? sl.d_repcnt.get() : sl.dmocnt.dev();
         if (sl.rep) {
-            chk(qrl_dmr_sink_process(d_sink, sl.d_a, d_bcap, d_bcap, sl.d_cnt + 2, 4, sl.d_rep, sl.d_info, kDmoCap, sl.d_repcnt), "qrl_dmr_sink_process");
-            hchk(hipMemcpyAsync(sl.h_info, sl.d_info, N * kDmoCap * QRL_DMR_SINK_INFO_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+            chk(qrl_dmr_sink_process(d_sink.get(), sl.a.dev(), d_bcap, d_bcap, sl.cnt.dev() + 2, 4, sl.d_rep.get(), sl.rec_info.dev(), kDmoCap, sl.d_repcnt.get()), "qrl_dmr_sink_process");
+            sl.rec_info.download(cs);
         }
-        hchk(hipMemcpyAsync(sl.h_dmocnt, fcnt, N * sizeof(uint32_t), hipMemcpyDeviceToHost, cs), "D2H");
-        hchk(hipMemcpyAsync(sl.h_dmo, frames, N * kDmoCap * QRL_DMO_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+        sl.dmocnt.download(cs, fcnt);
+        sl.dmo.download(cs, frames);
         sl.l2 = d_l2_on;
         if (sl.l2) {   // layer 2 on the copy stream, which waits for the slicer on the device: validate / FEC of the call's bursts, no host synchronisation
-            chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, frames, fcnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.d_l2), "qrl_dmr_l2_decode");
-            hchk(hipMemcpyAsync(sl.h_l2, sl.d_l2, N * kDmoCap * QRL_DMR_L2_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+            chk(qrl_dmr_l2_decode(d_rt.ctx(), cs, frames, fcnt, N, kDmoCap, d_l2_fec ? 1 : 0, sl.rec_l2.dev()), "qrl_dmr_l2_decode");
+            sl.rec_l2.download(cs);
         }
         sl.call = sl.l2 && d_call_on && d_call_rx;
         if (sl.call) {   // the call layer behind layer 2 on the same stream: every call of this handle goes through the copy stream, so the per-stream state is carried in order
-            if (sl.rep) chk(qrl_dmr_rx_process_slots(d_call_rx, cs, sl.d_l2, sl.d_info, fcnt, N, kDmoCap, sl.d_call), "qrl_dmr_rx_process_slots");
-            else chk(qrl_dmr_rx_process(d_call_rx, cs, sl.d_l2, fcnt, kDmoCap, sl.d_call), "qrl_dmr_rx_process");
-            hchk(hipMemcpyAsync(sl.h_call, sl.d_call, N * kDmoCap * QRL_DMR_RX_RECORD_BYTES, hipMemcpyDeviceToHost, cs), "D2H");
+            if (sl.rep) chk(qrl_dmr_rx_process_slots(d_call_rx.get(), cs, sl.rec_l2.dev(), sl.rec_info.dev(), fcnt, N, kDmoCap, sl.rec_call.dev()), "qrl_dmr_rx_process_slots");
+            else chk(qrl_dmr_rx_process(d_call_rx.get(), cs, sl.rec_l2.dev(), fcnt, kDmoCap, sl.rec_call.dev()), "qrl_dmr_rx_process");
+            sl.rec_call.download(cs);
         }
     }
     sl.rssi_valid = d_rssi_on;
     if (d_rssi_on) {   // rssi_valve open: port 0 of this call through rssi_block, the probe keeps the latest value
-        chk(qrl_rssi_process(d_rssi, sl.d_filt, d_fcap, d_fcap, sl.d_cnt, 4, nullptr, 0, sl.d_rssi, nullptr), "qrl_rssi_process");
-        hchk(hipMemcpyAsync(sl.h_rssi, sl.d_rssi, N * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");
+        chk(qrl_rssi_process(d_rssi.get(), sl.d_filt.get(), d_fcap, d_fcap, sl.cnt.dev(), 4, nullptr, 0, sl.rssi.dev(), nullptr), "qrl_rssi_process");
+        sl.rssi.download(cs);
     }
     if (d_fft_on) {
-        if (sc16) chk(qrl_fft_process_sc16(d_fft, reinterpret_cast<const int16_t*>(sl.d_iq), d_chunk, n), "qrl_fft_process_sc16");
-        else chk(qrl_fft_process(d_fft, sl.d_iq, d_chunk, n), "qrl_fft_process");
+        if (sc16) chk(qrl_fft_process_sc16(d_fft.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc16");
+        else chk(qrl_fft_process(d_fft.get(), sl.d_iq.get(), d_chunk, n), "qrl_fft_process");
     }
-    hchk(hipEventRecord(sl.done, cs), "hipEventRecord");
+    hchk(hipEventRecord(sl.done.get(), cs), "hipEventRecord");
     const int prev = d_inflight;
     d_inflight = cur;
     ++d_calls;
@@ -468,33 +421,33 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
 void gr_demod_base_hip::harvest(int which)
 {
     slot& sl = *d_slot[which];
-    hchk(hipEventSynchronize(sl.done), "hipEventSynchronize");
+    hchk(hipEventSynchronize(sl.done.get()), "hipEventSynchronize");
     std::lock_guard<std::mutex> g(d_mutex);
     for (int s = 0; s < d_n; ++s) {
-        const uint32_t* c = sl.h_cnt + 4 * (size_t)s;
-        if (sl.rssi_valid && c[0]) d_level[s] = sl.h_rssi[s];
+        const uint32_t* c = sl.cnt.host() + 4 * (size_t)s;
+        if (sl.rssi_valid && c[0]) d_level[s] = sl.rssi.host()[s];
         // gr_sample_sink::work (src/gr/gr_sample_sink.cpp:66-89): while more than 524288 items wait, the new ones are dropped
         if (sl.scoped && d_boxs[s].size() <= 524288) {
-            const gr_complex* p = sl.h_scope + (size_t)s * d_scap;
-            d_boxs[s].insert(d_boxs[s].end(), p, p + std::min<size_t>(sl.h_scnt[s], d_scap));
+            const gr_complex* p = sl.scope.host() + (size_t)s * d_scap;
+            d_boxs[s].insert(d_boxs[s].end(), p, p + std::min<size_t>(sl.scnt.host()[s], d_scap));
         }
         if (d_acap) {   // analogue modes: port 1 is audio (gr_audio_sink), no bit / constellation ports
             // gr_audio_sink::work (src/gr/gr_audio_sink.cpp:68-90): more than one second waiting = the reader is too slow: drop it all
             if (d_boxa[s].size() > 8000) d_boxa[s].clear();
-            else d_boxa[s].insert(d_boxa[s].end(), sl.h_audio + (size_t)s * d_acap, sl.h_audio + (size_t)s * d_acap + c[1]);
+            else d_boxa[s].insert(d_boxa[s].end(), sl.audio.host() + (size_t)s * d_acap, sl.audio.host() + (size_t)s * d_acap + c[1]);
             continue;
         }
         // gr_bit_sink::work (src/gr/gr_bit_sink.cpp:61-83): while more than 1 Mi items wait, new ones are not taken (nothing is cleared);
         // gr_const_sink::work (src/gr/gr_const_sink.cpp:64-86): the same at 256 items
         if (sl.bits_copied) {
-            if (d_box1[s].size() <= 1048576) d_box1[s].insert(d_box1[s].end(), sl.h_a + (size_t)s * d_bcap, sl.h_a + (size_t)s * d_bcap + c[2]);
-            if (d_box2[s].size() <= 1048576) d_box2[s].insert(d_box2[s].end(), sl.h_b + (size_t)s * d_bcap, sl.h_b + (size_t)s * d_bcap + c[3]);
+            if (d_box1[s].size() <= 1048576) d_box1[s].insert(d_box1[s].end(), sl.a.host() + (size_t)s * d_bcap, sl.a.host() + (size_t)s * d_bcap + c[2]);
+            if (d_box2[s].size() <= 1048576) d_box2[s].insert(d_box2[s].end(), sl.b.host() + (size_t)s * d_bcap, sl.b.host() + (size_t)s * d_bcap + c[3]);
         }
         if (sl.framed) for (int k = 0; k < 2; ++k) {   // the records of this call, in order
             d_fbits[k][s] += c[2 + k];
-            d_fact[k][s] += sl.h_frcnt[k][2 * (size_t)d_n + s];
-            const uint8_t* p = sl.h_fr[k] + (size_t)s * d_frcap;
-            const uint32_t nbytes = std::min<uint32_t>(sl.h_frcnt[k][2 * s], (uint32_t)d_frcap);
+            d_fact[k][s] += sl.frcnt[k].host()[2 * (size_t)d_n + s];
+            const uint8_t* p = sl.fr[k].host() + (size_t)s * d_frcap;
+            const uint32_t nbytes = std::min<uint32_t>(sl.frcnt[k].host()[2 * s], (uint32_t)d_frcap);
             uint32_t index = 0;   // of the record within the row: where its M17 link record lies
             for (uint32_t pos = 0; pos + 8 <= nbytes; ++index) {
                 uint32_t hdr[2];
@@ -506,31 +459,21 @@ void gr_demod_base_hip::harvest(int which)
                 r.payload.assign(p + pos + 8, p + pos + 8 + padded);
                 r.payload.resize((size_t)padded + 4, 0);   // processReceivedData reads frame_length + 1 bytes
                 if (k == 0 && sl.m17) {
-                    const uint8_t* e = sl.h_m17ev + ((size_t)s * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) + index) * QRL_M17_RX_RECORD_BYTES;
+                    const uint8_t* e = sl.rec_m17.host() + ((size_t)s * (d_frcap / QRL_M17_FRAMESYNC_RECORD_BYTES) + index) * QRL_M17_RX_RECORD_BYTES;
                     r.m17_event.assign(e, e + QRL_M17_RX_RECORD_BYTES);
                 }
                 d_boxf[k][s].push_back(std::move(r));
                 pos += 8 + padded;
             }
         }
-        if (sl.const_copied && d_boxc[s].size() <= 256) d_boxc[s].insert(d_boxc[s].end(), sl.h_const + (size_t)s * d_ccap, sl.h_const + (size_t)s * d_ccap + c[1]);
+        if (sl.const_copied && d_boxc[s].size() <= 256) d_boxc[s].insert(d_boxc[s].end(), sl.konst.host() + (size_t)s * d_ccap, sl.konst.host() + (size_t)s * d_ccap + c[1]);
         if (d_mode == QRL_MODEM_DMR) {
-            if (sl.h_dmocnt[s] > kDmoCap) d_dmo_dropped += sl.h_dmocnt[s] - kDmoCap;   // more bursts in one call than the record buffer holds
-            for (uint32_t i = 0; i < sl.h_dmocnt[s] && i < kDmoCap; ++i) {
-                const uint8_t* r = sl.h_dmo + ((size_t)s * kDmoCap + i) * QRL_DMO_RECORD_BYTES;
-                d_boxd[s].emplace_back(r, r + QRL_DMO_RECORD_BYTES);
-                if (sl.l2) {
-                    const uint8_t* r2 = sl.h_l2 + ((size_t)s * kDmoCap + i) * QRL_DMR_L2_RECORD_BYTES;
-                    d_boxl[s].emplace_back(r2, r2 + QRL_DMR_L2_RECORD_BYTES);
-                }
-                if (sl.rep) {
-                    const uint8_t* r4 = sl.h_info + ((size_t)s * kDmoCap + i) * QRL_DMR_SINK_INFO_BYTES;
-                    d_boxi[s].emplace_back(r4, r4 + QRL_DMR_SINK_INFO_BYTES);
-                }
-                if (sl.call) {
-                    const uint8_t* r3 = sl.h_call + ((size_t)s * kDmoCap + i) * QRL_DMR_RX_RECORD_BYTES;
-                    d_boxe[s].emplace_back(r3, r3 + QRL_DMR_RX_RECORD_BYTES);
-                }
+            if (sl.dmocnt.host()[s] > kDmoCap) d_dmo_dropped += sl.dmocnt.host()[s] - kDmoCap;   // more bursts in one call than the record buffer holds
+            for (uint32_t i = 0; i < sl.dmocnt.host()[s] && i < kDmoCap; ++i) {
+                append_record(d_boxd[s], sl.dmo.host(), (size_t)s, i, QRL_DMO_RECORD_BYTES);
+                if (sl.l2) append_record(d_boxl[s], sl.rec_l2.host(), (size_t)s, i, QRL_DMR_L2_RECORD_BYTES);
+                if (sl.rep) append_record(d_boxi[s], sl.rec_info.host(), (size_t)s, i, QRL_DMR_SINK_INFO_BYTES);
+                if (sl.call) append_record(d_boxe[s], sl.rec_call.host(), (size_t)s, i, QRL_DMR_RX_RECORD_BYTES);
             }
         }
     }
@@ -563,13 +506,13 @@ void gr_demod_base_hip::set_squelch(int value)   // gr_demod_base.cpp:1186-1199
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_squelch = value;
-    if (d_h && d_acap) chk(qrl_demod_set_squelch(d_h, (double)value), "qrl_demod_set_squelch");
+    if (d_h && d_acap) chk(qrl_demod_set_squelch(d_h.get(), (double)value), "qrl_demod_set_squelch");
 }
 void gr_demod_base_hip::set_ctcss(float value)   // gr_demod_base.cpp:1212-1218 -> gr_demod_nbfm::set_ctcss on both NBFM instances (gr_demod_nbfm.cpp:97-123)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_ctcss = value;
-    if (d_h && d_acap && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_demod_set_ctcss(d_h, value), "qrl_demod_set_ctcss");
+    if (d_h && d_acap && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_demod_set_ctcss(d_h.get(), value), "qrl_demod_set_ctcss");
 }
 void gr_demod_base_hip::set_filter_width(int filter_width, int mode)   // gr_demod_base.cpp:1155-1185
 {
@@ -580,7 +523,7 @@ void gr_demod_base_hip::set_filter_width(int filter_width, int mode)   // gr_dem
     }
     if (d_h && d_acap && d_mode == mode) {
         flush();   // the chain restarts: what the running call produced belongs to the old filters (recursive lock)
-        chk(qrl_demod_set_filter_width(d_h, filter_width), "qrl_demod_set_filter_width");
+        chk(qrl_demod_set_filter_width(d_h.get(), filter_width), "qrl_demod_set_filter_width");
     }
     d_width[mode] = filter_width;
 }
@@ -588,7 +531,7 @@ void gr_demod_base_hip::set_gain(float value)   // gr_demod_base.cpp:1206-1210 -
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_if_gain = value;
-    if (d_h && d_acap && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(d_h, value), "qrl_demod_set_gain");
+    if (d_h && d_acap && (d_mode == QRL_MODEM_USB2500 || d_mode == QRL_MODEM_LSB2500)) chk(qrl_demod_set_gain(d_h.get(), value), "qrl_demod_set_gain");
 }
 // gr_demod_base::set_agc_attack(int) / set_agc_decay(int) (gr_demod_base.cpp:1420-1461): the GUI's integer knob becomes a rate here -- 0 -> 1, v < 0 -> 1 / -v,
 // v > 0 -> 20 v (attack) or v (decay) -- and goes to the AM and both SSB receivers (_am, _usb, _lsb)
@@ -597,13 +540,13 @@ void gr_demod_base_hip::set_agc_attack(int value)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_agc_attack = value == 0 ? 1.0f : value < 0 ? 1.0f / (float)-value : (float)value * 20.0f;
-    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
+    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h.get(), d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
 }
 void gr_demod_base_hip::set_agc_decay(int value)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_agc_decay = value == 0 ? 1.0f : value < 0 ? 1.0f / (float)-value : (float)value;
-    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h, d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
+    if (d_h && d_acap && has_agc()) chk(qrl_demod_set_agc(d_h.get(), d_agc_attack, d_agc_decay), "qrl_demod_set_agc");
 }
 std::vector<gr_complex>* gr_demod_base_hip::get_constellation_data(int stream)
 {
@@ -622,7 +565,7 @@ void gr_demod_base_hip::calibrate_rssi(float value)   // :1413-1418
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_rssi_cal = value;
-    if (d_rssi) chk(qrl_rssi_set_level(d_rssi, value), "qrl_rssi_set_level");
+    if (d_rssi.get()) chk(qrl_rssi_set_level(d_rssi.get(), value), "qrl_rssi_set_level");
 }
 void gr_demod_base_hip::enable_time_domain(bool value)   // gr_demod_base.cpp:1115-1147 (+ gr_sample_sink::set_enabled)
 {
@@ -684,61 +627,36 @@ void gr_demod_base_hip::enable_gui_fft(bool value)   // :1110-1113
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_fft_on = value;
-    if (d_fft) chk(qrl_fft_set_enabled(d_fft, value ? 1 : 0), "qrl_fft_set_enabled");
+    if (d_fft.get()) chk(qrl_fft_set_enabled(d_fft.get(), value ? 1 : 0), "qrl_fft_set_enabled");
 }
 void gr_demod_base_hip::set_fft_size(int size)   // :1227-1232
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     flush();
     d_fftsize = (unsigned)size;
-    if (d_fft) chk(qrl_fft_set_fft_size(d_fft, d_fftsize), "qrl_fft_set_fft_size");
-    if (d_fftout) { (void)hipFree(d_fftout); d_fftout = nullptr; }
+    if (d_fft.get()) chk(qrl_fft_set_fft_size(d_fft.get(), d_fftsize), "qrl_fft_set_fft_size");
+    d_fftout.reset();
 }
 void gr_demod_base_hip::get_FFT_data(float* fft_data, unsigned int& fftSize, int stream)   // :978-986 -> rx_fft_c::get_fft_data
 {
     fftSize = 0;
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (!d_fft) return;
-    if (!d_fftout) hchk(hipMalloc(reinterpret_cast<void**>(&d_fftout), (size_t)d_n * d_fftsize * sizeof(float)), "hipMalloc");
+    if (!d_fftout.get()) d_fftout.alloc((size_t)d_n * d_fftsize);
     unsigned got = 0;
-    chk(qrl_fft_get_fft_data(d_fft, d_fftout, d_fftsize, &got), "qrl_fft_get_fft_data");
+    chk(qrl_fft_get_fft_data(d_fft.get(), d_fftout.get(), d_fftsize, &got), "qrl_fft_get_fft_data");
     if (!got) return;
-    hipStream_t cs = static_cast<hipStream_t>(d_copy);
+    hipStream_t cs = d_copy.get();
     d_fftlast.resize((size_t)d_n * got);   // every stream's spectrum of this frame: the other rows stay readable through last_FFT_data()
-    hchk(hipMemcpyAsync(d_fftlast.data(), d_fftout, d_fftlast.size() * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");
+    hchk(hipMemcpyAsync(d_fftlast.data(), d_fftout.get(), d_fftlast.size() * sizeof(float), hipMemcpyDeviceToHost, cs), "D2H");
     hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");
     std::memcpy(fft_data, d_fftlast.data() + (size_t)stream * got, (size_t)got * sizeof(float));
     fftSize = got;
 }
-std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRData(int stream)
-{
-    std::lock_guard<std::mutex> g(d_mutex);
-    std::vector<std::vector<unsigned char>> out;
-    out.swap(d_boxd[stream]);
-    return out;
-}
-std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRDecoded(int stream)
-{
-    std::lock_guard<std::mutex> g(d_mutex);
-    std::vector<std::vector<unsigned char>> out;
-    out.swap(d_boxl[stream]);
-    return out;
-}
-std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRSlotInfo(int stream)
-{
-    std::lock_guard<std::mutex> g(d_mutex);
-    std::vector<std::vector<unsigned char>> out;
-    if (stream < 0 || stream >= d_n) return out;
-    out.swap(d_boxi[stream]);
-    return out;
-}
-std::vector<std::vector<unsigned char>> gr_demod_base_hip::getDMRCallEvents(int stream)
-{
-    std::lock_guard<std::mutex> g(d_mutex);
-    std::vector<std::vector<unsigned char>> out;
-    out.swap(d_boxe[stream]);
-    return out;
-}
+records gr_demod_base_hip::getDMRData(int stream) { return take_box(d_mutex, d_boxd[stream]); }
+records gr_demod_base_hip::getDMRDecoded(int stream) { return take_box(d_mutex, d_boxl[stream]); }
+records gr_demod_base_hip::getDMRSlotInfo(int stream) { return stream < 0 || stream >= d_n ? records() : take_box(d_mutex, d_boxi[stream]); }
+records gr_demod_base_hip::getDMRCallEvents(int stream) { return take_box(d_mutex, d_boxe[stream]); }
 
 // ================================================================================================ gr_mod_base_hip
 gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_rate, double carrier_offset_hz, size_t max_bytes)
@@ -748,16 +666,7 @@ gr_mod_base_hip::gr_mod_base_hip(qrl_runtime& rt, int streams, int device_samp_r
 {
     d_cw_n = std::min<size_t>(1024, d_max);   // a facade built for fewer than 1024 items per call must still key CW
 }
-gr_mod_base_hip::~gr_mod_base_hip()
-{
-    if (d_h) qrl_mod_destroy(d_h);
-    if (d_ah) qrl_amod_destroy(d_ah);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_audio) (void)hipFree(d_audio);
-    if (d_iq) (void)hipFree(d_iq);
-    if (d_clip) (void)hipFree(d_clip);
-    if (d_dmr_dev) (void)hipFree(d_dmr_dev);
-}
+gr_mod_base_hip::~gr_mod_base_hip() = default;
 static bool tx_mode_has_back_end(int mode)   // qrl_mod_create builds the gr_mod_base back end (rotator + interpolator) for every family but these (tx.cpp)
 {
     return !(mode == QRL_MODEM_M17 || mode == QRL_MODEM_BPSK8);
@@ -780,51 +689,42 @@ void gr_mod_base_hip::open()
     // the engine builds the back end at 1 Msps only for a non-zero configured offset: any stream's will do, open() sets each stream's below
     double cfg_offset = d_offset;
     if (d_per_stream && cfg_offset == 0.0) for (double f : d_offsets) if (f != 0.0) { cfg_offset = f; break; }
-    qrl_mod* nh = nullptr; qrl_amod* nah = nullptr; uint8_t* nbytes = nullptr; float* naudio = nullptr; float* niq = nullptr;
+    mod_handle nh; amod_handle nah; dev_buf<uint8_t> nbytes; dev_buf<float> naudio, niq;
     size_t spblock = 0, bpb = 1;
-    if (!d_clip) hchk(hipMalloc(reinterpret_cast<void**>(&d_clip), (size_t)d_n * sizeof(uint32_t)), "hipMalloc");   // one per stream, for the life of the facade
-    try {
-        if (analog_tx_mode(d_mode)) {
-            qrl_amod_config c{};
-            c.modem_type = d_mode; c.batch = d_n; c.max_samples = d_max; c.bb_gain = d_gain;
-            c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
-            chk(qrl_amod_create(d_rt.ctx(), &c, &nah), "qrl_amod_create");
-            if (d_per_stream && backend) chk(qrl_amod_set_carrier_offsets(nah, d_offsets.data()), "qrl_amod_set_carrier_offsets");
-            // the reference's instances keep what their setters did across mode changes
-            if (d_ctcss_touched && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(nah, d_ctcss), "qrl_amod_set_ctcss");
-            if (d_width.count(d_mode)) chk(qrl_amod_set_filter_width(nah, d_width[d_mode]), "qrl_amod_set_filter_width");
-            if (d_mode == QRL_MODEM_CW600USB && d_cw_key) chk(qrl_amod_set_cw_k(nah, 1), "qrl_amod_set_cw_k");
-            chk(qrl_amod_set_sc16_scale(nah, d_sc16_scale), "qrl_amod_set_sc16_scale");
-            chk(qrl_amod_set_sc16_clip_counts(nah, d_clip), "qrl_amod_set_sc16_clip_counts");
-            hchk(hipMalloc(reinterpret_cast<void**>(&naudio), (size_t)d_n * d_max * sizeof(float)), "hipMalloc");
-            hchk(hipMalloc(reinterpret_cast<void**>(&niq), (size_t)d_n * qrl_amod_out_cap(nah, d_max) * sizeof(gr_complex)), "hipMalloc");
-        } else {
-            qrl_mod_config c{};
-            c.modem_type = d_mode; c.use_mode_defaults = 1; c.batch = d_n; c.max_bytes = d_max; c.bb_gain = d_gain;
-            c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
-            chk(qrl_mod_create(d_rt.ctx(), &c, &nh), "qrl_mod_create");
-            chk(qrl_mod_set_sc16_scale(nh, d_sc16_scale), "qrl_mod_set_sc16_scale");
-            chk(qrl_mod_set_sc16_clip_counts(nh, d_clip), "qrl_mod_set_sc16_clip_counts");
-            if (d_per_stream && backend && tx_mode_has_back_end(d_mode)) chk(qrl_mod_set_carrier_offsets(nh, d_offsets.data()), "qrl_mod_set_carrier_offsets");
-            hchk(hipMalloc(reinterpret_cast<void**>(&nbytes), (size_t)d_n * d_max), "hipMalloc");
-            spblock = qrl_mod_samples_per_block(nh, &bpb);     // M17: 2500 samples per 3 bytes; every other mode: samples per byte, 1
-            hchk(hipMalloc(reinterpret_cast<void**>(&niq), (size_t)d_n * (d_max / bpb + 1) * spblock * sizeof(gr_complex)), "hipMalloc");
-        }
-    } catch (...) {
-        if (nh) qrl_mod_destroy(nh);
-        if (nah) qrl_amod_destroy(nah);
-        if (nbytes) (void)hipFree(nbytes);
-        if (naudio) (void)hipFree(naudio);
-        if (niq) (void)hipFree(niq);
-        throw;
+    if (!d_clip.get()) d_clip.alloc((size_t)d_n);   // one per stream, for the life of the facade
+    if (analog_tx_mode(d_mode)) {
+        qrl_amod_config c{};
+        c.modem_type = d_mode; c.batch = d_n; c.max_samples = d_max; c.bb_gain = d_gain;
+        c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
+        qrl_amod* h = nullptr;
+        chk(qrl_amod_create(d_rt.ctx(), &c, &h), "qrl_amod_create");
+        nah.reset(h);
+        if (d_per_stream && backend) chk(qrl_amod_set_carrier_offsets(h, d_offsets.data()), "qrl_amod_set_carrier_offsets");
+        // the reference's instances keep what their setters did across mode changes
+        if (d_ctcss_touched && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(h, d_ctcss), "qrl_amod_set_ctcss");
+        if (d_width.count(d_mode)) chk(qrl_amod_set_filter_width(h, d_width[d_mode]), "qrl_amod_set_filter_width");
+        if (d_mode == QRL_MODEM_CW600USB && d_cw_key) chk(qrl_amod_set_cw_k(h, 1), "qrl_amod_set_cw_k");
+        chk(qrl_amod_set_sc16_scale(h, d_sc16_scale), "qrl_amod_set_sc16_scale");
+        chk(qrl_amod_set_sc16_clip_counts(h, d_clip.get()), "qrl_amod_set_sc16_clip_counts");
+        naudio.alloc((size_t)d_n * d_max);
+        niq.alloc(2 * (size_t)d_n * qrl_amod_out_cap(h, d_max));   // interleaved cf32
+    } else {
+        qrl_mod_config c{};
+        c.modem_type = d_mode; c.use_mode_defaults = 1; c.batch = d_n; c.max_bytes = d_max; c.bb_gain = d_gain;
+        c.device_samp_rate = d_rate; c.carrier_offset_hz = cfg_offset;
+        qrl_mod* h = nullptr;
+        chk(qrl_mod_create(d_rt.ctx(), &c, &h), "qrl_mod_create");
+        nh.reset(h);
+        chk(qrl_mod_set_sc16_scale(h, d_sc16_scale), "qrl_mod_set_sc16_scale");
+        chk(qrl_mod_set_sc16_clip_counts(h, d_clip.get()), "qrl_mod_set_sc16_clip_counts");
+        if (d_per_stream && backend && tx_mode_has_back_end(d_mode)) chk(qrl_mod_set_carrier_offsets(h, d_offsets.data()), "qrl_mod_set_carrier_offsets");
+        nbytes.alloc((size_t)d_n * d_max);
+        spblock = qrl_mod_samples_per_block(h, &bpb);     // M17: 2500 samples per 3 bytes; every other mode: samples per byte, 1
+        niq.alloc(2 * (size_t)d_n * (d_max / bpb + 1) * spblock);   // interleaved cf32
     }
-    if (d_h) qrl_mod_destroy(d_h);
-    if (d_ah) qrl_amod_destroy(d_ah);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_audio) (void)hipFree(d_audio);
-    if (d_iq) (void)hipFree(d_iq);
-    d_h = nh; d_ah = nah; d_bytes = nbytes; d_audio = naudio; d_iq = niq; d_backend = backend;
-    if (nh) { d_spblock = spblock; d_bpb = bpb; }
+    // nothing threw: the new ones move in, the old ones go (the handles now, the buffers with this function's locals)
+    d_h = std::move(nh); d_ah = std::move(nah); d_bytes = std::move(nbytes); d_audio = std::move(naudio); d_iq = std::move(niq); d_backend = backend;
+    if (d_h) { d_spblock = spblock; d_bpb = bpb; }
     d_cw_n = std::min(d_cw_n, d_max);
     // a new handle counts its items from zero: whatever was queued for the old one (and the byte positions of its zero runs) goes with it
     std::lock_guard<std::mutex> g(d_mutex);
@@ -860,7 +760,7 @@ int gr_mod_base_hip::setDMRData(const std::vector<std::vector<uint8_t>>& frames,
         z.stream = stream; z.channel = 0; z.start = first_zero * 20u; z.count = kZeroBytes * 4u * 5u;   // DMR_ZERO_TX_LENGTH_SAMPLES (:25)
         runs.push_back(z);
     }
-    if (!runs.empty() && qrl_mod_add_zero_runs(d_h, runs.data(), runs.size()) != QRL_OK) {
+    if (!runs.empty() && qrl_mod_add_zero_runs(d_h.get(), runs.data(), runs.size()) != QRL_OK) {
         q.resize(q0);   // bytes without their idle zeros would be a different waveform: all or nothing
         throw std::runtime_error(std::string("qrl_mod_add_zero_runs: ") + qrl_last_error());
     }
@@ -882,27 +782,23 @@ void gr_mod_base_hip::queue_m17(int kind, const uint8_t* payloads, size_t n, int
     if (d_m17_call.at((size_t)stream).empty()) throw std::runtime_error("gr_mod_base_hip: txM17Audio / endM17Call before setM17Call");
     const size_t bytes = kind == 0 ? QRL_M17_CALL_START_BYTES : kind == 2 ? QRL_M17_CALL_END_BYTES : n * 48;
     const size_t in = QRL_M17_CALL_BYTES + 4 + (kind == 1 ? n * 16 : 0);
-    uint8_t* dev = nullptr;
-    hchk(hipMalloc(reinterpret_cast<void**>(&dev), in + bytes), "hipMalloc");
+    dev_buf<uint8_t> buf;
+    buf.alloc(in + bytes);
+    uint8_t* dev = buf.get();
     std::vector<uint8_t> h(in);
     std::memcpy(h.data(), d_m17_call[(size_t)stream].data(), QRL_M17_CALL_BYTES);
     std::memcpy(h.data() + QRL_M17_CALL_BYTES, &d_m17_next[(size_t)stream], 4);
     if (kind == 1) std::memcpy(h.data() + QRL_M17_CALL_BYTES + 4, payloads, n * 16);
-    std::vector<uint8_t>* out = new std::vector<uint8_t>(bytes);
-    int rc = QRL_OK;
-    hipError_t e = hipMemcpy(dev, h.data(), in, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const uint32_t* first = reinterpret_cast<const uint32_t*>(dev + QRL_M17_CALL_BYTES);
-        uint8_t* o = dev + in;
-        if (kind == 0) rc = qrl_m17_call_start(d_rt.ctx(), nullptr, dev, 1, o, bytes);
-        else if (kind == 1) rc = qrl_m17_call_encode(d_rt.ctx(), nullptr, dev, dev + QRL_M17_CALL_BYTES + 4, first, 1, n, o, bytes, 48);
-        else rc = qrl_m17_call_end(d_rt.ctx(), nullptr, dev, first, 1, o, bytes);
-        if (rc == QRL_OK) e = hipMemcpy(out->data(), o, bytes, hipMemcpyDeviceToHost);   // (waits for the null stream)
-    }
-    (void)hipFree(dev);
-    if (rc != QRL_OK || e != hipSuccess) { delete out; if (rc != QRL_OK) chk(rc, "qrl_m17_call"); hchk(e, "hipMemcpy"); }
+    auto out = std::make_unique<std::vector<uint8_t>>(bytes);
+    hchk(hipMemcpy(dev, h.data(), in, hipMemcpyHostToDevice), "hipMemcpy");
+    const uint32_t* first = reinterpret_cast<const uint32_t*>(dev + QRL_M17_CALL_BYTES);
+    uint8_t* o = dev + in;
+    if (kind == 0) chk(qrl_m17_call_start(d_rt.ctx(), nullptr, dev, 1, o, bytes), "qrl_m17_call");
+    else if (kind == 1) chk(qrl_m17_call_encode(d_rt.ctx(), nullptr, dev, dev + QRL_M17_CALL_BYTES + 4, first, 1, n, o, bytes, 48), "qrl_m17_call");
+    else chk(qrl_m17_call_end(d_rt.ctx(), nullptr, dev, first, 1, o, bytes), "qrl_m17_call");
+    hchk(hipMemcpy(out->data(), o, bytes, hipMemcpyDeviceToHost), "hipMemcpy");   // (waits for the null stream)
     if (kind == 1) d_m17_next[(size_t)stream] += (uint32_t)n;
-    set_data(out, stream);
+    set_data(out.release(), stream);
 }
 void gr_mod_base_hip::setM17Call(const uint8_t* descriptor32, int stream)   // M17Transmitter::start: the counters to 0, preamble and LSF frame
 {
@@ -941,7 +837,7 @@ int gr_mod_base_hip::txDMRVoice(const uint8_t* voice, size_t n, int stream)
         runs[i] = qrl_zero_run{};
         runs[i].stream = stream; runs[i].start = (job.pos + i * kSlot + 33) * 20u; runs[i].count = kZeroBytes * 4u * 5u;
     }
-    if (qrl_mod_add_zero_runs(d_h, runs.data(), runs.size()) != QRL_OK) throw std::runtime_error(std::string("qrl_mod_add_zero_runs: ") + qrl_last_error());
+    if (qrl_mod_add_zero_runs(d_h.get(), runs.data(), runs.size()) != QRL_OK) throw std::runtime_error(std::string("qrl_mod_add_zero_runs: ") + qrl_last_error());
     q.insert(q.end(), n * kSlot, (uint8_t)0);   // the slots: zeros here, the bursts are written on the device by the pass that sends them
     d_dmr_jobs[(size_t)stream].push_back(std::move(job));
     d_dmr_next[(size_t)stream] += (uint32_t)n;
@@ -996,18 +892,15 @@ void gr_mod_base_hip::encode_dmr_jobs(const std::vector<uint64_t>& window0, size
         }
     }
     if (pieces.empty()) return;
-    if (stage.size() > d_dmr_cap) {   // nothing of an earlier pass is in flight: every pass ends behind qrl_mod_sync
-        if (d_dmr_dev) (void)hipFree(d_dmr_dev);
-        d_dmr_dev = nullptr; d_dmr_cap = 0;
-        hchk(hipMalloc(reinterpret_cast<void**>(&d_dmr_dev), 2 * stage.size()), "hipMalloc");
-        d_dmr_cap = 2 * stage.size();
-    }
-    hchk(hipMemcpyAsync(d_dmr_dev, stage.data(), stage.size(), hipMemcpyHostToDevice, ms), "H2D");
+    if (stage.size() > d_dmr_dev.size()) d_dmr_dev.alloc(2 * stage.size());   // nothing of an earlier pass is in flight: every pass ends behind qrl_mod_sync
+    uint8_t* const dmr_dev = d_dmr_dev.get();
+    uint8_t* const bytes_dev = d_bytes.get();
+    hchk(hipMemcpyAsync(dmr_dev, stage.data(), stage.size(), hipMemcpyHostToDevice, ms), "H2D");
     for (const auto& pc : pieces) {
-        uint8_t* out = pc.cut ? d_dmr_dev + pc.slot : d_bytes + pc.dst;
-        chk(qrl_dmr_voice_call_encode(d_rt.ctx(), ms, d_dmr_dev + pc.call, d_dmr_dev + pc.voice, reinterpret_cast<const uint32_t*>(d_dmr_dev + pc.first), 1,
+        uint8_t* out = pc.cut ? dmr_dev + pc.slot : bytes_dev + pc.dst;
+        chk(qrl_dmr_voice_call_encode(d_rt.ctx(), ms, dmr_dev + pc.call, dmr_dev + pc.voice, reinterpret_cast<const uint32_t*>(dmr_dev + pc.first), 1,
                                       pc.n, out, pc.n * kSlot, kSlot), "qrl_dmr_voice_call_encode");
-        if (pc.cut) hchk(hipMemcpyAsync(d_bytes + pc.dst, d_dmr_dev + pc.slot + pc.skip, pc.len, hipMemcpyDeviceToDevice, ms), "D2D");
+        if (pc.cut) hchk(hipMemcpyAsync(bytes_dev + pc.dst, dmr_dev + pc.slot + pc.skip, pc.len, hipMemcpyDeviceToDevice, ms), "D2D");
     }
     hchk(hipStreamSynchronize(ms), "hipStreamSynchronize");   // the staging bytes are this function's
 }
@@ -1022,19 +915,19 @@ void gr_mod_base_hip::set_cw_k(bool value)   // gr_mod_base.cpp:948-956
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_cw_key = value;
-    if (d_ah && d_mode == QRL_MODEM_CW600USB) chk(qrl_amod_set_cw_k(d_ah, value ? 1 : 0), "qrl_amod_set_cw_k");
+    if (d_ah && d_mode == QRL_MODEM_CW600USB) chk(qrl_amod_set_cw_k(d_ah.get(), value ? 1 : 0), "qrl_amod_set_cw_k");
 }
 void gr_mod_base_hip::set_ctcss(float value)   // gr_mod_base.cpp:872-877
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_ctcss = value; d_ctcss_touched = true;
-    if (d_ah && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(d_ah, value), "qrl_amod_set_ctcss");
+    if (d_ah && (d_mode == QRL_MODEM_NBFM2500 || d_mode == QRL_MODEM_NBFM5000)) chk(qrl_amod_set_ctcss(d_ah.get(), value), "qrl_amod_set_ctcss");
 }
 void gr_mod_base_hip::set_filter_width(int filter_width, int mode)   // gr_mod_base.cpp:878-905
 {
     if (!analog_tx_mode(mode)) return;   // the reference's default branch
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
-    if (d_ah && d_mode == mode) chk(qrl_amod_set_filter_width(d_ah, filter_width), "qrl_amod_set_filter_width");
+    if (d_ah && d_mode == mode) chk(qrl_amod_set_filter_width(d_ah.get(), filter_width), "qrl_amod_set_filter_width");
     d_width[mode] = filter_width;
 }
 int gr_mod_base_hip::set_data(std::vector<uint8_t>* data, int stream)   // gr_mod_base.cpp:783-786 -> gr_byte_source::set_data (:54-62)
@@ -1048,8 +941,8 @@ void gr_mod_base_hip::set_bb_gain(float v)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     d_gain = v;
-    if (d_h) chk(qrl_mod_set_bb_gain(d_h, v), "qrl_mod_set_bb_gain");
-    if (d_ah) chk(qrl_amod_set_bb_gain(d_ah, v), "qrl_amod_set_bb_gain");
+    if (d_h.get()) chk(qrl_mod_set_bb_gain(d_h.get(), v), "qrl_mod_set_bb_gain");
+    if (d_ah.get()) chk(qrl_amod_set_bb_gain(d_ah.get(), v), "qrl_amod_set_bb_gain");
 }
 void gr_mod_base_hip::set_carrier_offset(double hz)
 {
@@ -1071,8 +964,8 @@ void gr_mod_base_hip::set_carrier_offset(double hz)
         }
         return;
     }
-    if (d_h) chk(qrl_mod_set_carrier_offset(d_h, hz), "qrl_mod_set_carrier_offset");
-    if (d_ah) chk(qrl_amod_set_carrier_offset(d_ah, hz), "qrl_amod_set_carrier_offset");
+    if (d_h.get()) chk(qrl_mod_set_carrier_offset(d_h.get(), hz), "qrl_mod_set_carrier_offset");
+    if (d_ah.get()) chk(qrl_amod_set_carrier_offset(d_ah.get(), hz), "qrl_amod_set_carrier_offset");
     d_offset = hz;
     d_offsets.assign((size_t)d_n, hz);
 }
@@ -1099,8 +992,8 @@ void gr_mod_base_hip::set_carrier_offset(double hz, int stream)
         }
         return;
     }
-    if (d_h) chk(qrl_mod_set_carrier_offsets(d_h, v.data()), "qrl_mod_set_carrier_offsets");
-    if (d_ah) chk(qrl_amod_set_carrier_offsets(d_ah, v.data()), "qrl_amod_set_carrier_offsets");
+    if (d_h.get()) chk(qrl_mod_set_carrier_offsets(d_h.get(), v.data()), "qrl_mod_set_carrier_offsets");
+    if (d_ah.get()) chk(qrl_amod_set_carrier_offsets(d_ah.get(), v.data()), "qrl_amod_set_carrier_offsets");
     d_offsets.swap(v);
     d_per_stream = true;
 }
@@ -1124,7 +1017,7 @@ void gr_mod_base_hip::flush_sources()
     for (auto& q : d_aqueue) q.clear();
     for (auto& j : d_dmr_jobs) j.clear();   // their slots went with the queue
 }
-size_t gr_mod_base_hip::samples_per_byte() const { return d_h ? qrl_mod_samples_per_byte(d_h) : 0; }
+size_t gr_mod_base_hip::samples_per_byte() const { return d_h ? qrl_mod_samples_per_byte(d_h.get()) : 0; }
 // int16 I/Q out (out[s] = interleaved int16 I, Q pairs): replaces the SDR driver's fc32 -> sc16 converter.  The modulator's last kernel converts
 // (qrl_mod_process_sc16 / qrl_amod_process_sc16: r = rintf(x * scale), saturated), the download copies 4 bytes per sample, and the per-stream counters of
 // clipped components come back with the samples (clipped()).
@@ -1133,8 +1026,8 @@ void gr_mod_base_hip::set_sc16_scale(float scale)
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_mod_base_hip::set_sc16_scale: finite, non-zero");
     d_sc16_scale = scale;
-    if (d_h) chk(qrl_mod_set_sc16_scale(d_h, scale), "qrl_mod_set_sc16_scale");
-    if (d_ah) chk(qrl_amod_set_sc16_scale(d_ah, scale), "qrl_amod_set_sc16_scale");
+    if (d_h.get()) chk(qrl_mod_set_sc16_scale(d_h.get(), scale), "qrl_mod_set_sc16_scale");
+    if (d_ah.get()) chk(qrl_amod_set_sc16_scale(d_ah.get(), scale), "qrl_amod_set_sc16_scale");
 }
 uint64_t gr_mod_base_hip::clipped(int stream) const
 {
@@ -1148,31 +1041,31 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
     const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the row pitch stays `stride` samples
     // one call of the open analogue handle into d_iq, in the format asked for
     auto amod = [&](const float* audio, size_t astride, size_t n, size_t stride) {
-        if (sc16) chk(qrl_amod_process_sc16(d_ah, audio, astride, n, reinterpret_cast<int16_t*>(d_iq), stride), "qrl_amod_process_sc16");
-        else chk(qrl_amod_process(d_ah, audio, astride, n, d_iq, stride), "qrl_amod_process");
+        if (sc16) chk(qrl_amod_process_sc16(d_ah.get(), audio, astride, n, reinterpret_cast<int16_t*>(d_iq.get()), stride), "qrl_amod_process_sc16");
+        else chk(qrl_amod_process(d_ah.get(), audio, astride, n, d_iq.get(), stride), "qrl_amod_process");
     };
     // the samples of every stream, and for int16 the clip counters of this pass
     auto download = [&](size_t ns, size_t stride) {
         for (int s = 0; s < d_n && ns; ++s)
-            hchk(hipMemcpy(out[s], reinterpret_cast<const char*>(d_iq) + (size_t)s * stride * sb, ns * sb, hipMemcpyDeviceToHost), "D2H");
+            hchk(hipMemcpy(out[s], reinterpret_cast<const char*>(d_iq.get()) + (size_t)s * stride * sb, ns * sb, hipMemcpyDeviceToHost), "D2H");
         if (!sc16) return;
         std::vector<uint32_t> c((size_t)d_n);
-        hchk(hipMemcpy(c.data(), d_clip, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
+        hchk(hipMemcpy(c.data(), d_clip.get(), c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
         for (int s = 0; s < d_n; ++s) d_clipped[(size_t)s] += c[(size_t)s];
     };
-    auto zero_clip = [&](hipStream_t ms) { if (sc16) hchk(hipMemsetAsync(d_clip, 0, (size_t)d_n * sizeof(uint32_t), ms), "hipMemsetAsync"); };
+    auto zero_clip = [&](hipStream_t ms) { if (sc16) hchk(hipMemsetAsync(d_clip.get(), 0, (size_t)d_n * sizeof(uint32_t), ms), "hipMemsetAsync"); };
 
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // the handle and its zero-run list for the whole pass; the byte / audio queues stay under d_mutex
     if (d_ah && d_mode == QRL_MODEM_CW600USB) {   // the tone source lives on the device: nothing to upload
-        const size_t stride = qrl_amod_out_cap(d_ah, d_max);
-        zero_clip(static_cast<hipStream_t>(qrl_amod_stream(d_ah)));
+        const size_t stride = qrl_amod_out_cap(d_ah.get(), d_max);
+        zero_clip(static_cast<hipStream_t>(qrl_amod_stream(d_ah.get())));
         amod(nullptr, 0, d_cw_n, stride);
-        chk(qrl_amod_sync(d_ah), "qrl_amod_sync");
-        const size_t ns = qrl_amod_last_count(d_ah);
+        chk(qrl_amod_sync(d_ah.get()), "qrl_amod_sync");
+        const size_t ns = qrl_amod_last_count(d_ah.get());
         download(ns, stride);
         return ns;
     }
-    if (d_ah) {
+    if (d_ah.get()) {
         size_t na = 0;
         std::vector<float> host((size_t)d_n * d_max, 0.0f);
         {
@@ -1186,13 +1079,13 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
                 d_aqueue[s].erase(d_aqueue[s].begin(), d_aqueue[s].begin() + k);
             }
         }
-        hipStream_t ms = static_cast<hipStream_t>(qrl_amod_stream(d_ah));
-        hchk(hipMemcpyAsync(d_audio, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, ms), "H2D");
-        const size_t stride = qrl_amod_out_cap(d_ah, d_max);
+        hipStream_t ms = static_cast<hipStream_t>(qrl_amod_stream(d_ah.get()));
+        hchk(hipMemcpyAsync(d_audio.get(), host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, ms), "H2D");
+        const size_t stride = qrl_amod_out_cap(d_ah.get(), d_max);
         zero_clip(ms);
-        amod(d_audio, d_max, na, stride);
-        chk(qrl_amod_sync(d_ah), "qrl_amod_sync");
-        const size_t ns = qrl_amod_last_count(d_ah);
+        amod(d_audio.get(), d_max, na, stride);
+        chk(qrl_amod_sync(d_ah.get()), "qrl_amod_sync");
+        const size_t ns = qrl_amod_last_count(d_ah.get());
         download(ns, stride);
         return ns;
     }
@@ -1212,14 +1105,14 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
             d_sent[s] += nb;
         }
     }
-    hipStream_t ms = static_cast<hipStream_t>(qrl_mod_stream(d_h));
-    hchk(hipMemcpyAsync(d_bytes, host.data(), host.size(), hipMemcpyHostToDevice, ms), "H2D");
+    hipStream_t ms = static_cast<hipStream_t>(qrl_mod_stream(d_h.get()));
+    hchk(hipMemcpyAsync(d_bytes.get(), host.data(), host.size(), hipMemcpyHostToDevice, ms), "H2D");
     if (d_mode == QRL_MODEM_DMR) encode_dmr_jobs(window0, nb, ms);
     const size_t ns = nb / d_bpb * d_spblock, stride = (d_max / d_bpb + 1) * d_spblock;
     zero_clip(ms);
-    if (sc16) chk(qrl_mod_process_sc16(d_h, d_bytes, d_max, nb, reinterpret_cast<int16_t*>(d_iq), stride), "qrl_mod_process_sc16");
-    else chk(qrl_mod_process(d_h, d_bytes, d_max, nb, d_iq, stride), "qrl_mod_process");
-    chk(qrl_mod_sync(d_h), "qrl_mod_sync");
+    if (sc16) chk(qrl_mod_process_sc16(d_h.get(), d_bytes.get(), d_max, nb, reinterpret_cast<int16_t*>(d_iq.get()), stride), "qrl_mod_process_sc16");
+    else chk(qrl_mod_process(d_h.get(), d_bytes.get(), d_max, nb, d_iq.get(), stride), "qrl_mod_process");
+    chk(qrl_mod_sync(d_h.get()), "qrl_mod_sync");
     download(ns, stride);
     return ns;
 }

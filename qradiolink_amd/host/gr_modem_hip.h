@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -147,18 +148,21 @@ private:
     qrl_runtime& d_rt;
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_chunk;
     std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
-    qrl_demod* d_h = nullptr;
-    qrl_rssi* d_rssi = nullptr; qrl_fft* d_fft = nullptr; bool d_rssi_on = false, d_fft_on = false; float d_rssi_cal = 0.0f; unsigned d_fftsize = 32768;
+    // Members are released in reverse order of declaration, after the destructor's flush().  The copy stream is declared before, and so
+    // destroyed after, everything that is created on it or reset on it: the rssi and fft handles, the frame synchronisers, the slots with
+    // their events, the repeater sink and the call and M17 trackers further down.
+    hip_stream d_copy{true};                                  // the copy-out
+    demod_handle d_h;
+    rssi_handle d_rssi; fft_handle d_fft; bool d_rssi_on = false, d_fft_on = false; float d_rssi_cal = 0.0f; unsigned d_fftsize = 32768;
     float d_ctcss = 0.0f; bool d_const_on = true, d_demod_on = true;
     void reconfigure_scope(int samp_rate, double filter_width);   // re-open with new scope settings; the old ones come back when the engine rejects them
     int d_scope_rate = 0; double d_scope_fw = 0.0;   // set_time_sink_samp_rate / set_time_domain_filter_width (0: the constructor's 1:10)
     bool d_scope_on = false; size_t d_scap = 0; unsigned d_window = 8096; std::vector<std::vector<gr_complex>> d_boxs;   // scope tap mailboxes
-    qrl_framesync* d_fs[2] = {nullptr, nullptr}; bool d_want_fs = false, d_keep_bits = false; size_t d_frcap = 0;   // device frame synchronisers of bits A / B
+    framesync_handle d_fs[2]; bool d_want_fs = false, d_keep_bits = false; size_t d_frcap = 0;   // device frame synchronisers of bits A / B
     std::vector<std::vector<frame_record>> d_boxf[2];
     std::vector<size_t> d_fbits[2], d_fact[2];   // per branch and stream: bits consumed / bits collected under a sync since the last takeFrames
-    float* d_fftout = nullptr; std::vector<float> d_level, d_fftlast;
-    void* d_copy = nullptr;                                   // hipStream_t for the copy-out
-    slot* d_slot[2] = {nullptr, nullptr};
+    dev_buf<float> d_fftout; std::vector<float> d_level, d_fftlast;
+    std::unique_ptr<slot> d_slot[2];
     void work_any(const void* const* iq, size_t n, bool sc16);   // both work() overloads
     float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
@@ -178,10 +182,10 @@ private:
     std::vector<std::vector<std::vector<unsigned char>>> d_boxl;   // layer 2 records, one per record of d_boxd while set_dmr_l2 is on
     bool d_l2_on = false, d_l2_fec = true;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxe;   // call records, one per record of d_boxd while set_dmr_call is on
-    qrl_dmr_rx* d_call_rx = nullptr; bool d_call_on = false;
-    qrl_m17_rx* d_m17_rx = nullptr; bool d_m17_on = false;
+    dmr_rx_handle d_call_rx; bool d_call_on = false;
+    m17_rx_handle d_m17_rx; bool d_m17_on = false;
     std::vector<std::vector<std::vector<unsigned char>>> d_boxi;   // slot records, one per record of d_boxd while set_dmr_repeater is on
-    qrl_dmr_sink* d_sink = nullptr; bool d_rep_on = false; int d_rep_slot = 1;
+    dmr_sink_handle d_sink; bool d_rep_on = false; int d_rep_slot = 1;
     void apply_call_mode();                                        // the tracker's mode follows set_dmr_repeater
     uint64_t d_dmo_dropped = 0;   // DMR bursts found beyond the per-call record buffer (16 per stream and call): not delivered
 };
@@ -239,8 +243,8 @@ public:
     // (the 25:4 resampler), SSB returns whole chunks of 1024 audio items (the cessb stretcher).  out[s] needs max_audio_out() samples.
     int set_audio(std::vector<float>* data, int stream = 0);
     size_t max_audio() const { return d_max; }
-    size_t max_audio_out() const { return d_ah ? qrl_amod_out_cap(d_ah, d_max) : 0; }
-    size_t samples_per_audio_sample() const { return d_ah ? qrl_amod_samples_per_sample(d_ah) : 0; }   // 125 x device rate / 1e6
+    size_t max_audio_out() const { return d_ah ? qrl_amod_out_cap(d_ah.get(), d_max) : 0; }
+    size_t samples_per_audio_sample() const { return d_ah ? qrl_amod_samples_per_sample(d_ah.get()) : 0; }   // 125 x device rate / 1e6
     bool analog() const { return d_ah != nullptr; }
     // CW600USB (gr_mod_base.cpp:144,180,679-683): the SSB chain fed by the key's tone source; work() produces what cw_samples_per_call() samples of the
     // source give (the reference's source free-runs, paced by the device sink).  set_cw_k = gr_mod_base::set_cw_k (:948-956); the key is kept across mode changes.
@@ -258,8 +262,11 @@ private:
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_max; float d_gain = 1.0f;
     std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
     bool any_offset() const;
-    qrl_mod* d_h = nullptr; uint8_t* d_bytes = nullptr; float* d_iq = nullptr;
-    qrl_amod* d_ah = nullptr; float* d_audio = nullptr; float d_ctcss = 0.0f; bool d_ctcss_touched = false; std::map<int, int> d_width;
+    // the device buffers are declared before the handles that work on them: released after them, as the destructor always did
+    dev_buf<uint8_t> d_bytes; dev_buf<float> d_iq, d_audio;
+    dev_buf<uint32_t> d_clip;      // device counters of one int16 pass (zeroed in front of it), one per stream
+    dev_buf<uint8_t> d_dmr_dev;    // device staging of a pass: descriptors, first indices, codec bytes, straddling slots
+    mod_handle d_h; amod_handle d_ah; float d_ctcss = 0.0f; bool d_ctcss_touched = false; std::map<int, int> d_width;
     bool d_cw_key = false; size_t d_cw_n = 1024;   // clamped to max_bytes by the constructor and by open()
     bool d_backend = false;   // the open handle has the gr_mod_base back end (device rate >= 2 Msps or a non-zero offset at open)
     size_t d_spblock = 0, d_bpb = 1;
@@ -268,12 +275,11 @@ private:
     std::vector<std::vector<uint8_t>> d_queue;
     std::vector<std::vector<float>> d_aqueue;
     std::vector<uint64_t> d_sent;   // bytes per stream handed to the modulator since set_mode (with the zero padding of short queues): positions of the zero runs
-    uint32_t* d_clip = nullptr; std::vector<uint64_t> d_clipped;   // device counters of one int16 pass (zeroed in front of it); totals per stream
+    std::vector<uint64_t> d_clipped;   // totals of d_clip per stream
     // txDMRVoice: bursts whose slots are queued as zeros and encoded on the device by the pass that sends them (under d_mutex, like the queues)
     struct dmr_tx_job { uint64_t pos; uint32_t first; size_t n; std::vector<uint8_t> call, voice; };   // pos: the stream's byte index of slot 0
     std::vector<std::vector<dmr_tx_job>> d_dmr_jobs;
     std::vector<std::vector<uint8_t>> d_dmr_call; std::vector<uint32_t> d_dmr_next;   // per stream: descriptor, index of the next voice burst
-    uint8_t* d_dmr_dev = nullptr; size_t d_dmr_cap = 0;   // device staging of a pass: descriptors, first indices, codec bytes, straddling slots
     void encode_dmr_jobs(const std::vector<uint64_t>& window0, size_t nb, void* stream);
     std::vector<std::vector<uint8_t>> d_m17_call; std::vector<uint32_t> d_m17_next;   // per stream: descriptor, index of the next stream frame
     void queue_m17(int kind, const uint8_t* payloads, size_t n, int stream);          // 0 start, 1 frames, 2 end

@@ -11,23 +11,13 @@
 
 namespace qrl_host {
 
-static void hchk(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
 m17_frame_decoder_hip::m17_frame_decoder_hip(qrl_runtime& rt, int streams, size_t max_frames)
     : d_rt(rt), d_st((size_t)streams), d_cap(max_frames)
 {
     if (streams < 1 || max_frames < 1) throw std::invalid_argument("m17_frame_decoder_hip: streams >= 1, max_frames >= 1");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_frames), d_cap * 48), "hipMalloc");
-    hchk(hipMalloc(reinterpret_cast<void**>(&d_records), d_cap * QRL_M17_RECORD_BYTES), "hipMalloc");
+    d_frames.alloc(d_cap * 48);
+    d_records.alloc(d_cap * QRL_M17_RECORD_BYTES);
     d_host.resize(d_cap * QRL_M17_RECORD_BYTES);
-}
-m17_frame_decoder_hip::~m17_frame_decoder_hip()
-{
-    if (d_frames) (void)hipFree(d_frames);
-    if (d_records) (void)hipFree(d_records);
 }
 void m17_frame_decoder_hip::reset(int stream) { d_st[(size_t)stream] = state(); }
 
@@ -46,9 +36,9 @@ std::vector<M17FrameType> m17_frame_decoder_hip::decodeFrames(const uint8_t* fra
     std::vector<M17FrameType> types(n);
     for (size_t done = 0; done < n;) {
         const size_t m = std::min(n - done, d_cap);
-        hchk(hipMemcpy(d_frames, frames + done * 48, m * 48, hipMemcpyHostToDevice), "H2D");
-        if (qrl_m17_decode_frames(d_rt.ctx(), nullptr, d_frames, m, d_records) != QRL_OK) throw std::runtime_error(std::string("qrl_m17_decode_frames: ") + qrl_last_error());
-        hchk(hipMemcpy(d_host.data(), d_records, m * QRL_M17_RECORD_BYTES, hipMemcpyDeviceToHost), "D2H");   // (synchronises the default stream)
+        hchk(hipMemcpy(d_frames.get(), frames + done * 48, m * 48, hipMemcpyHostToDevice), "H2D");
+        if (qrl_m17_decode_frames(d_rt.ctx(), nullptr, d_frames.get(), m, d_records.get()) != QRL_OK) throw std::runtime_error(std::string("qrl_m17_decode_frames: ") + qrl_last_error());
+        hchk(hipMemcpy(d_host.data(), d_records.get(), m * QRL_M17_RECORD_BYTES, hipMemcpyDeviceToHost), "D2H");   // (synchronises the default stream)
         for (size_t i = 0; i < m; ++i) {
             const uint8_t* r = d_host.data() + i * QRL_M17_RECORD_BYTES;
             state& st = d_st[(size_t)(stream_of ? stream_of[done + i] : 0)];

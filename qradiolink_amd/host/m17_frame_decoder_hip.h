@@ -16,7 +16,6 @@ enum class M17FrameType : uint8_t { PREAMBLE = 0, LINK_SETUP = 1, STREAM = 2, PA
 class m17_frame_decoder_hip {
 public:
     m17_frame_decoder_hip(qrl_runtime& rt, int streams, size_t max_frames = 4096);
-    ~m17_frame_decoder_hip();
     void reset(int stream = 0);                                                  // M17FrameDecoder::reset
     // n frames of 48 bytes (sync word included), frame i belongs to radio stream_of[i] (nullptr: all to stream 0); frames of one
     // stream are applied in the order given.  Returns the frame types (M17FrameDecoder::decodeFrame's return value).
@@ -31,7 +30,7 @@ private:
     qrl_runtime& d_rt;
     std::vector<state> d_st;
     size_t d_cap;
-    uint8_t *d_frames = nullptr, *d_records = nullptr;   // device
+    dev_buf<uint8_t> d_frames, d_records;
     std::vector<uint8_t> d_host;
 };
 

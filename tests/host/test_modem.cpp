@@ -25,6 +25,43 @@ static std::string hex(const unsigned char* d, int n)
     return s;
 }
 
+// The loopback signal: per stream startTransmission, <nframes> voice frames with a known payload, a text message, endTransmission on `modem`
+// (already in its TX mode), everything modulated by `mod`, then the channel: per-stream delay, scale, trailing silence so that the last
+// frames leave the filters / Viterbi.  rx[s] = the samples of stream s, all of one even length.
+static std::vector<std::vector<gr_complex>> loopback_signal(gr_modem_hip& modem, gr_mod_base_hip& mod, int mode, int N, int nframes)
+{
+    const int L = modem_tx_frame_length(mode);
+    for (int s = 0; s < N; ++s) {
+        modem.startTransmission("CALL" + std::to_string(s), s);
+        for (int f = 0; f < nframes; ++f) {
+            unsigned char* d = new unsigned char[L];
+            for (int i = 0; i < L; ++i) d[i] = (unsigned char)(17 * s + 31 * f + 7 * i + 1);
+            modem.transmitDigitalAudio(d, L, s);
+        }
+        modem.transmitTextData("hello from stream " + std::to_string(s), (int)FrameTypeText, s);
+        modem.endTransmission("CALL" + std::to_string(s), s);
+    }
+    // modulate everything that is queued
+    const size_t spb = mod.samples_per_byte();
+    std::vector<std::vector<gr_complex>> tx(N);
+    std::vector<std::vector<gr_complex>> part(N, std::vector<gr_complex>(spb * 4096));
+    for (;;) {
+        std::vector<gr_complex*> outp(N);
+        for (int s = 0; s < N; ++s) outp[s] = part[s].data();
+        const size_t ns = mod.work(outp.data());
+        if (!ns) break;
+        for (int s = 0; s < N; ++s) tx[s].insert(tx[s].end(), part[s].begin(), part[s].begin() + ns);
+    }
+    size_t total = 0;
+    for (int s = 0; s < N; ++s) total = std::max(total, tx[s].size());
+    total += 40000 + 1000 * N;
+    total &= ~(size_t)1;
+    std::vector<std::vector<gr_complex>> rx(N, std::vector<gr_complex>(total, gr_complex(0, 0)));
+    for (int s = 0; s < N; ++s)
+        for (size_t i = 0; i < tx[s].size(); ++i) rx[s][i + 500 * s] = 0.05f * tx[s][i];   // (SDR-like level: the reference's FLL loop gain scales with the input power, there is no AGC in front of it)
+    return rx;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && !strcmp(argv[1], "txpin")) {
@@ -499,6 +536,99 @@ int main(int argc, char** argv)
             return bad ? 3 : 0;
         } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
     }
+    if (argc == 5 && !strcmp(argv[1], "reopen")) {
+        // test_modem reopen <frames> <walked.txt> <fresh.txt>: one receiver of 2 streams walks DMR (repeater sink, layer 2, call layer) -> M17 (device
+        // framing, link layer) -> NBFM5000 -> GMSK10K with one work() in each of the first three, then receives the GMSK10K loopback; a fresh receiver
+        // opened directly in GMSK10K receives the same samples in the same call sizes.  Both logs hold, in order, the bit-port mailboxes ("B stream nr
+        // bits") and the events of every poll: they must be equal.  Then a receiver in DMR mode with all three layers on is destroyed right after a work().
+        const int N = 2, nframes = atoi(argv[2]);
+        try {
+            qrl_runtime rt(0);
+            std::vector<std::vector<gr_complex>> rx;
+            {
+                gr_mod_base_hip mod(rt, N, 1000000, 0.0, 4096);
+                gr_modem_hip txm(nullptr, &mod, gr_modem_events());
+                txm.toggleTxMode(QRL_MODEM_GMSK10K);
+                rx = loopback_signal(txm, mod, QRL_MODEM_GMSK10K, N, nframes);
+            }
+            std::vector<std::vector<gr_complex>> noise(N, std::vector<gr_complex>(4096));   // a fixed pseudo-random signal
+            uint32_t lcg = 12345u;
+            auto rnd = [&]() { lcg = lcg * 1664525u + 1013904223u; return 0.05f * ((float)(lcg >> 8) / 8388608.0f - 1.0f); };
+            for (auto& v : noise) for (auto& x : v) { const float re = rnd(); x = gr_complex(re, rnd()); }
+            std::vector<const gr_complex*> nin(N);
+            for (int s = 0; s < N; ++s) nin[s] = noise[s].data();
+            const size_t chunk = 1 << 17;
+            for (int fresh = 0; fresh < 2; ++fresh) {
+                std::ofstream log(argv[3 + fresh]);
+                gr_modem_events ev;
+                ev.digitalAudio = [&](int s, const unsigned char* d, int n) { log << "E " << s << " audio " << hex(d, n) << "\n"; };
+                ev.textReceived = [&](int s, const std::string& t, bool) { log << "E " << s << " text " << hex(reinterpret_cast<const unsigned char*>(t.data()), (int)t.size()) << "\n"; };
+                ev.callsignReceived = [&](int s, const std::string& c) { log << "E " << s << " callsign " << c << "\n"; };
+                ev.dataFrameReceived = [&](int s) { log << "E " << s << " dataframe\n"; };
+                ev.endAudioTransmission = [&](int s) { log << "E " << s << " endaudio\n"; };
+                ev.receiveEnd = [&](int s) { log << "E " << s << " receiveend\n"; };
+                gr_demod_base_hip demod(rt, N, 1000000, 0.0, chunk);
+                gr_modem_hip modem(&demod, nullptr, ev);
+                demod.keep_bits(true);
+                if (!fresh) {
+                    demod.set_dmr_repeater(true, 1); demod.set_dmr_l2(true); demod.set_dmr_call(true);
+                    demod.set_mode(QRL_MODEM_DMR);
+                    demod.work(nin.data(), 4096);
+                    demod.enable_device_framing(true); demod.set_m17_link(true);
+                    demod.set_mode(QRL_MODEM_M17);
+                    demod.work(nin.data(), 4096);
+                    demod.set_mode(QRL_MODEM_NBFM5000);
+                    demod.work(nin.data(), 4096);
+                }
+                modem.toggleRxMode(QRL_MODEM_GMSK10K);   // set_mode(GMSK10K) with the device frame synchroniser
+                auto poll = [&]() {
+                    for (int s = 0; s < N; ++s) {
+                        for (int nr = 1; nr <= 2; ++nr)
+                            if (std::vector<unsigned char>* v = demod.getData(nr, s)) {
+                                std::string b(v->size(), '0');
+                                for (size_t i = 0; i < v->size(); ++i) b[i] = (char)('0' + ((*v)[i] & 1));
+                                log << "B " << s << " " << nr << " " << b << "\n";
+                                delete v;
+                            }
+                        while (modem.demodulate(s)) {}
+                    }
+                };
+                static const size_t sizes[] = {65536, 10000, 131072, 2, 77778};
+                size_t pos = 0;
+                for (int k = 0; pos < rx[0].size(); ++k) {
+                    const size_t n = std::min(sizes[k % 5], rx[0].size() - pos) & ~(size_t)1;
+                    if (!n) break;
+                    std::vector<const gr_complex*> in(N);
+                    for (int s = 0; s < N; ++s) in[s] = rx[s].data() + pos;
+                    demod.work(in.data(), n);
+                    pos += n;
+                    poll();
+                }
+                demod.flush();
+                poll();
+            }
+            {   // an open() that fails half way (the demodulator exists, the spectrum block rejects its size) leaves the receiver closed, not half open
+                gr_demod_base_hip demod(rt, N, 1000000, 0.0, chunk);
+                demod.set_fft_size(1);
+                int thrown = 0;
+                try { demod.set_mode(QRL_MODEM_GMSK10K); } catch (const std::runtime_error&) { ++thrown; }
+                try { demod.work(nin.data(), 4096); } catch (const std::runtime_error& e) { if (std::strstr(e.what(), "before set_mode")) ++thrown; }
+                if (thrown != 2 || demod.device_framing()) throw std::runtime_error("a failed open did not leave the receiver closed");
+                demod.set_fft_size(4096);
+                demod.set_mode(QRL_MODEM_GMSK10K);   // and the next one opens it
+                demod.work(nin.data(), 4096);
+                demod.flush();
+            }
+            {   // the destructor's order: the slots' events, the sink and the trackers go before the copy stream they work on, with a call in flight
+                gr_demod_base_hip demod(rt, N, 1000000, 0.0, chunk);
+                demod.set_dmr_repeater(true, 1); demod.set_dmr_l2(true); demod.set_dmr_call(true);
+                demod.set_mode(QRL_MODEM_DMR);
+                demod.work(nin.data(), 4096);
+            }
+            std::printf("reopen ok\n");
+            return 0;
+        } catch (const std::exception& e) { std::fprintf(stderr, "error: %s\n", e.what()); return 1; }
+    }
     if (argc != 6 || strcmp(argv[1], "loopback")) { std::fprintf(stderr, "usage: test_modem loopback modem_type streams frames out.txt\n"); return 2; }
     const int mode = atoi(argv[2]), N = atoi(argv[3]), nframes = atoi(argv[4]);
     try {
@@ -572,36 +702,8 @@ int main(int argc, char** argv)
         std::vector<float> spectrum(4096);
         int spectra = 0; float peak_db = -1000.0f; int peak_bin = -1;
         std::vector<float> rssi_max(N, -1000.0f);
-        const int L = modem_tx_frame_length(mode);
-        for (int s = 0; s < N; ++s) {
-            modem.startTransmission("CALL" + std::to_string(s), s);
-            for (int f = 0; f < nframes; ++f) {
-                unsigned char* d = new unsigned char[L];
-                for (int i = 0; i < L; ++i) d[i] = (unsigned char)(17 * s + 31 * f + 7 * i + 1);
-                modem.transmitDigitalAudio(d, L, s);
-            }
-            modem.transmitTextData("hello from stream " + std::to_string(s), (int)FrameTypeText, s);
-            modem.endTransmission("CALL" + std::to_string(s), s);
-        }
-        // modulate everything that is queued
-        const size_t spb = mod.samples_per_byte();
-        std::vector<std::vector<gr_complex>> tx(N);
-        std::vector<std::vector<gr_complex>> part(N, std::vector<gr_complex>(spb * 4096));
-        for (;;) {
-            std::vector<gr_complex*> outp(N);
-            for (int s = 0; s < N; ++s) outp[s] = part[s].data();
-            const size_t ns = mod.work(outp.data());
-            if (!ns) break;
-            for (int s = 0; s < N; ++s) tx[s].insert(tx[s].end(), part[s].begin(), part[s].begin() + ns);
-        }
-        // channel: per-stream delay, scale, trailing silence so that the last frames leave the filters / Viterbi
-        size_t total = 0;
-        for (int s = 0; s < N; ++s) total = std::max(total, tx[s].size());
-        total += 40000 + 1000 * N;
-        total &= ~(size_t)1;
-        std::vector<std::vector<gr_complex>> rx(N, std::vector<gr_complex>(total, gr_complex(0, 0)));
-        for (int s = 0; s < N; ++s)
-            for (size_t i = 0; i < tx[s].size(); ++i) rx[s][i + 500 * s] = 0.05f * tx[s][i];   // (SDR-like level: the reference's FLL loop gain scales with the input power, there is no AGC in front of it)
+        const std::vector<std::vector<gr_complex>> rx = loopback_signal(modem, mod, mode, N, nframes);
+        const size_t total = rx[0].size();
         // feed in ragged, even-sized calls and poll like the radio loop (radiocontroller.cpp:1291-1303)
         size_t pos = 0;
         size_t sizes[] = {65536, 10000, 131072, 2, 77778};
@@ -617,7 +719,7 @@ int main(int argc, char** argv)
             if (getenv("QRL_TEST_DEBUG")) {
                 for (int s = 0; s < N; ++s) {
                     auto* a = demod.getData(1, s); auto* b = demod.getData(2, s);
-                    std::fprintf(stderr, "call %d stream %d: bits A %zu, bits B %zu, tx %zu samples\n", k, s, a ? a->size() : 0, b ? b->size() : 0, tx[s].size());
+                    std::fprintf(stderr, "call %d stream %d: bits A %zu, bits B %zu, %zu samples in all\n", k, s, a ? a->size() : 0, b ? b->size() : 0, total);
                     if (bitlog && s == 0 && a) std::fwrite(a->data(), 1, a->size(), bitlog);
                     delete a; delete b;
                 }

@@ -101,6 +101,27 @@ def test_facade_loopback(tmp_path, mode, L, streams, frames):
         assert int(dict(ev[s])["modem_sync"]) >= 0
 
 
+def test_facade_reopen_equals_a_fresh_facade(tmp_path):
+    """The re-open path: one receiver of 2 streams walks DMR (repeater sink, layer 2, call layer) -> M17 (device framing, link layer)
+    -> NBFM5000 -> GMSK10K with one work() of 4096 pseudo-random samples in each of the first three, then receives the GMSK10K loopback
+    of 2 streams and 3 frames; a fresh receiver opened directly in GMSK10K receives the same samples in the same call sizes.  Nothing
+    of the modes walked through may be left: the events and the bit-port mailboxes of the two are equal.  The driver then lets an open() fail half way
+    (the spectrum block rejects an FFT size of 1 after the demodulator exists): the receiver is closed, work() throws "before set_mode",
+    and the next set_mode opens it.  Last it destroys a receiver in DMR mode with all three layers on right after a work(), without a
+    flush() of its own, and exits 0."""
+    if not os.path.exists(EXE):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "qradiolink_amd", "csrc"), "adaptor"])
+    walked, fresh = tmp_path / "walked.txt", tmp_path / "fresh.txt"
+    r = subprocess.run([EXE, "reopen", "3", str(walked), str(fresh)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "reopen ok" in r.stdout, r.stdout + r.stderr
+    a, b = walked.read_text().splitlines(), fresh.read_text().splitlines()
+    assert [e for e in a if e.startswith("E ")] == [e for e in b if e.startswith("E ")]
+    assert [e for e in a if e.startswith("B ")] == [e for e in b if e.startswith("B ")]
+    assert a == b   # and their order against each other
+    assert any(e.startswith("B 0 1 ") for e in b) and any(e.startswith("B 0 2 ") for e in b)
+    assert any(e.startswith("E 0 callsign ") or e.startswith("E 0 audio ") for e in b)   # not vacuous: the frames arrive
+
+
 def test_facade_side_outputs(tmp_path):
     """enable_rssi / calibrate_rssi / get_rssi and enable_gui_fft / set_fft_size / get_FFT_data of the facade (gr_demod_base.cpp:978-986,
     1105-1113, 1227-1237, 1413-1418): the loopback signal (amplitude ~0.03 at 1 Msps) gives a finite RSSI per stream and spectra
