@@ -57,13 +57,30 @@ double orc_block_timing_get(int i, char* name, size_t cap);
 typedef struct { float re, im; } cf32;
 
 /* ---------- deterministic math ---------- */
-void  orc_sincosf(float x, float* s, float* c);            /* |x| <= ~8 rad */
+void  orc_sincosf(float x, float* s, float* c);            /* within 1.8e-7 of sin / cos for |x| <= 1e5 rad (tests/test_devmath_definition.py) */
 void  orc_sincos_turn(uint64_t angle, float* s, float* c); /* angle in 2^-64 turns */
 float orc_fast_atan2f(float y, float x);                   /* gnuradio fast_atan2f */
 float orc_tanhf_lut(float x);                              /* gnuradio tanhf_lut */
 const float* orc_atan_table(void);  /* 257 entries */
 const float* orc_tanh_table(void);  /* 256 entries */
 const float* orc_mmse_table(void);  /* 129 x 8 */
+/* thin exports of helpers that are static in the file that owns them (orc_blocks.c, orc_chains.c) */
+float   orc_phase_wrap(float phase);                       /* control_loop::phase_wrap */
+float   orc_branchless_clip(float x, float clip);          /* gr::branchless_clip */
+float   orc_ted_error_ff(float u);                         /* QRL_TED_MODMM_ERROR under the variant in force (orc_set_ted_modmm) */
+float   orc_ted_error_cc(float u);
+int16_t orc_f2s(float x, float scale);                     /* float_to_short: rint, saturate, NaN -> 0 */
+/* array loops over the functions above (orc_probe.c): tests/test_gpu_devmath.py, tests/test_devmath_definition.py */
+void orc_probe_sincosf(const float* x, size_t n, float* c, float* s);
+void orc_probe_sincos_turn(const uint64_t* a, size_t n, float* c, float* s);
+void orc_probe_fast_atan2f(const float* y, const float* x, size_t n, float* out);
+void orc_probe_tanhf_lut(const float* x, size_t n, float* out);
+void orc_probe_clip(const float* x, const float* limit, size_t n, float* out);
+void orc_probe_ted_error(const float* u, size_t n, float* ff, float* cc);
+void orc_probe_phase_wrap(const float* x, size_t n, float* out);
+void orc_probe_det_log2f(const float* x, size_t n, float* out);
+void orc_probe_det_log10f(const float* x, size_t n, float* out);
+void orc_probe_f2s(const float* x, const float* scale, size_t n, int16_t* out);
 
 /* ---------- firdes (gr-filter/lib/firdes.cc, gr-fft/lib/window.cc) ---------- */
 enum { ORC_WIN_HAMMING = 0, ORC_WIN_HANN = 1, ORC_WIN_BLACKMAN = 2, ORC_WIN_RECTANGULAR = 3,

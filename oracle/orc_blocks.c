@@ -462,6 +462,9 @@ static inline float branchless_clip(float x, float clip)
     x1 -= x2;
     return 0.5f * x1;
 }
+/* the two helpers above as the loops below call them, for tests that hold them to the device's (orc_probe.c) */
+float orc_phase_wrap(float phase) { return phase_wrap(phase); }
+float orc_branchless_clip(float x, float clip) { return branchless_clip(x, clip); }
 
 /* ------------------------------------------------------------------------------------------
  * fll_band_edge_cc [gr-digital/lib/fll_band_edge_cc_impl.cc]
@@ -601,6 +604,9 @@ void orc_set_ted_modmm(int ff_variant, int cc_variant)
     g_ted_cc = cc_variant < 0 ? QRL_TED_MODMM_CC : cc_variant;
 }
 void orc_get_ted_modmm(int* ff_variant, int* cc_variant) { *ff_variant = g_ted_ff; *cc_variant = g_ted_cc; }
+/* the error the two symbol synchronisers below make of their u, under the variants in force (orc_probe.c) */
+float orc_ted_error_ff(float u) { return QRL_TED_MODMM_ERROR(g_ted_ff, u, branchless_clip); }
+float orc_ted_error_cc(float u) { return QRL_TED_MODMM_ERROR(g_ted_cc, u, branchless_clip); }
 
 static inline float slice_real(int constellation, float x)
 {

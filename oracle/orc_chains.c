@@ -1131,10 +1131,12 @@ size_t orc_pfb_channelizer(const cf32* in, size_t n, const float* taps, int nt, 
 static int16_t f2s(float x, float scale)
 {
     float r = rintf(x * scale);
+    if (r != r) return 0;   /* NaN: 0, as the device's sc16_sat says it (the cast below leaves it undefined) */
     if (r > 32767.0f) r = 32767.0f;
     if (r < -32768.0f) r = -32768.0f;
     return (int16_t)r;
 }
+int16_t orc_f2s(float x, float scale) { return f2s(x, scale); }   /* for orc_probe.c */
 /* whole C4 RX chain; out: [M][cap] int16, returns samples per channel (cap must be >= n/M*24/25 + 2) */
 size_t orc_demod_mmdvm_multi(const cf32* in, size_t n, int M, int16_t* out, size_t cap)
 {

@@ -34,7 +34,8 @@ __device__ __forceinline__ float2 quad_fix(int q, float ps, float pc)
     const uint32_t negc = ((uint32_t)(q + 1) & 2u) << 30, negs = ((uint32_t)q & 2u) << 30;
     return make_float2(__uint_as_float(c0 ^ negc), __uint_as_float(s0 ^ negs));
 }
-// (cos x, sin x) of a float angle in radians, |x| <~ 10
+// (cos x, sin x) of a float angle in radians.  Held to orc_sincosf bit for bit for |x| <= 1e5 (tests/test_gpu_devmath.py), where the oracle stays
+// within 1.8e-7 of sin / cos (tests/test_devmath_definition.py); (int)k needs |x| < 2^31 quarter turns
 __device__ __forceinline__ float2 sincos_rad(float x)
 {
     const float k = rintf(x * 0.636619772367581343f);

@@ -1014,3 +1014,81 @@ def power_spectrum(x, window):
     out = np.zeros(x.size, np.float32)
     lib.orc_power_spectrum(_ptr(x), _ptr(w), x.size, _ptr(out))
     return out
+
+
+# ---- the math primitives over whole arrays (oracle/orc_probe.c): tests/test_gpu_devmath.py, tests/test_devmath_definition.py ----
+_sig("orc_probe_sincosf", None, _p, _sz, _p, _p)
+_sig("orc_probe_sincos_turn", None, _p, _sz, _p, _p)
+_sig("orc_probe_fast_atan2f", None, _p, _p, _sz, _p)
+_sig("orc_probe_tanhf_lut", None, _p, _sz, _p)
+_sig("orc_probe_clip", None, _p, _p, _sz, _p)
+_sig("orc_probe_ted_error", None, _p, _sz, _p, _p)
+_sig("orc_probe_phase_wrap", None, _p, _sz, _p)
+_sig("orc_probe_det_log2f", None, _p, _sz, _p)
+_sig("orc_probe_det_log10f", None, _p, _sz, _p)
+_sig("orc_probe_f2s", None, _p, _p, _sz, _p)
+
+
+def _probe_1(name, x, dtype=np.float32, nout=1):
+    x = np.ascontiguousarray(x, dtype)
+    outs = [np.empty(x.size, np.float32) for _ in range(nout)]
+    getattr(lib, name)(_ptr(x), x.size, *[_ptr(o) for o in outs])
+    return outs[0] if nout == 1 else tuple(outs)
+
+
+def probe_sincosf(x):
+    """(cos, sin) of float32 radians"""
+    return _probe_1("orc_probe_sincosf", x, nout=2)
+
+
+def probe_sincos_turn(a):
+    """(cos, sin) of uint64 angles in 2^-64 turns"""
+    return _probe_1("orc_probe_sincos_turn", a, np.uint64, nout=2)
+
+
+def probe_fast_atan2f(y, x):
+    y = np.ascontiguousarray(y, np.float32)
+    x = np.ascontiguousarray(x, np.float32)
+    assert y.size == x.size
+    out = np.empty(y.size, np.float32)
+    lib.orc_probe_fast_atan2f(_ptr(y), _ptr(x), y.size, _ptr(out))
+    return out
+
+
+def probe_tanhf_lut(x):
+    return _probe_1("orc_probe_tanhf_lut", x)
+
+
+def probe_clip(x, limit):
+    x = np.ascontiguousarray(x, np.float32)
+    limit = np.ascontiguousarray(limit, np.float32)
+    assert x.size == limit.size
+    out = np.empty(x.size, np.float32)
+    lib.orc_probe_clip(_ptr(x), _ptr(limit), x.size, _ptr(out))
+    return out
+
+
+def probe_ted_error(u):
+    """(symbol_sync_ff's error, symbol_sync_cc's error) of u under the variants in force"""
+    return _probe_1("orc_probe_ted_error", u, nout=2)
+
+
+def probe_phase_wrap(x):
+    return _probe_1("orc_probe_phase_wrap", x)
+
+
+def probe_det_log2f(x):
+    return _probe_1("orc_probe_det_log2f", x)
+
+
+def probe_det_log10f(x):
+    return _probe_1("orc_probe_det_log10f", x)
+
+
+def probe_f2s(x, scale):
+    """float_to_short of x[i] * scale[i] (scale: a number or an array of x's size) -> int16"""
+    x = np.ascontiguousarray(x, np.float32)
+    scale = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float32), x.shape))
+    out = np.empty(x.size, np.int16)
+    lib.orc_probe_f2s(_ptr(x), _ptr(scale), x.size, _ptr(out))
+    return out
