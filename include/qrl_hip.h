@@ -134,8 +134,12 @@ int qrl_demod_set_dmo_output(qrl_demod* d, uint8_t* frames, size_t cap_frames, u
  * the product of work the caller has queued on qrl_demod_stream() and not yet waited for.  The two helper kernels of the front end
  * (the history kept for the next call, the edge scratch of this one) then read it on a fourth internal stream beside the front end of the
  * call before instead of in line with it; qrl_demod_sync / qrl_demod_stream_wait cover that stream too.  With value 0 everything that reads
- * the caller's buffer is ordered behind the handle's stream, as qrl_demod_process documents. */
-enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups; for 2FSK-1k / -2k also the FLL and the FIR stages as the two kernels k_fll + k_2fsk_ff instead of k_2fsk_tail (same results) */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5 };
+ * the caller's buffer is ordered behind the handle's stream, as qrl_demod_process documents.  QRL_OPT_SC16_BASEBAND (default 0): value 1
+ * lets a handle WITHOUT a device-rate front end (device_samp_rate 1000000) take int16 IQ through qrl_demod_process_sc16 /
+ * qrl_demod_process_sc16_host; value 0 refuses such calls with QRL_ERR_ARG, as before the option existed.  It allocates nothing and may be
+ * set at any stream position (the format belongs to the call, the carried history is rotated cf32); on a handle with a front end it is
+ * accepted and does nothing. */
+enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups; for 2FSK-1k / -2k also the FLL and the FIR stages as the two kernels k_fll + k_2fsk_ff instead of k_2fsk_tail (same results) */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5, QRL_OPT_SC16_BASEBAND = 6 };
 int qrl_demod_set_option(qrl_demod* d, int option, int value);
 int qrl_demod_out_caps(const qrl_demod* d, size_t n, size_t* filtered_cap, size_t* constellation_cap, size_t* bits_cap);
 /* analogue voice receivers (QRL_MODEM_NBFM2500 / NBFM5000 / AM5000 / WBFM / USB2500 / LSB2500; replace make_gr_demod_nbfm / _am /
@@ -195,9 +199,12 @@ int qrl_demod_process(qrl_demod* d, const float* iq, size_t stride, size_t n, co
  * kernel names) and the scope tap work as with cf32.
  * iq must be 16-byte aligned and stride a multiple of 4 samples, else QRL_ERR_ARG; any n <= max_chunk (the LDS-DMA kernel streams calls
  * with n % 4 == 0, other n take the per-output kernels).
- * Handles with device_samp_rate >= 2000000 only (every modem type, every rate qrl_demod_create accepts): there the device-rate front
- * end and the history keeper are all that read the caller's buffer.  A 1 Msps handle returns QRL_ERR_ARG (qrl_last_error says so),
- * changes nothing and stays usable; widening the per-mode first stages (k_resamp, k_dec2_fir, the analogue loaders) is a later change. */
+ * Handles with device_samp_rate >= 2000000 (every modem type, every rate qrl_demod_create accepts) take it as they are: there the
+ * device-rate front end and the history keeper are all that read the caller's buffer.  A 1 Msps handle takes it once
+ * qrl_demod_set_option(d, QRL_OPT_SC16_BASEBAND, 1) has been called: the per-mode first stage then reads the raw pairs -- the decimators
+ * (the 1:50 matrix-pipe stage streams them with LDS-DMA, 4 bytes per sample), k_resamp, k_dec2_fir, the analogue and DSSS receivers'
+ * first stage and the scope tap -- with the same conversion in front of the rotator, every modem type.  Without the option (the
+ * default) a 1 Msps handle returns QRL_ERR_ARG (qrl_last_error says so), changes nothing and stays usable. */
 int qrl_demod_process_sc16(qrl_demod* d, const int16_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
 int qrl_demod_set_sc16_scale(qrl_demod* d, float scale);
 int qrl_demod_sync(qrl_demod* d);

@@ -25,7 +25,7 @@ MODEM_NBFM2500, MODEM_NBFM5000, MODEM_WBFM, MODEM_AM5000 = 8, 9, 10, 14
 MODEM_USB2500, MODEM_LSB2500, MODEM_CW600USB = 11, 12, 13
 MODEM_M17 = 40
 MODEM_DMR = 41
-OPT_OVERLAP, OPT_UNFUSED_DEC2, OPT_FLL_SLIM, OPT_GROUPED, OPT_INPUT_RESIDENT = 1, 2, 3, 4, 5
+OPT_OVERLAP, OPT_UNFUSED_DEC2, OPT_FLL_SLIM, OPT_GROUPED, OPT_INPUT_RESIDENT, OPT_SC16_BASEBAND = 1, 2, 3, 4, 5, 6
 CHAN_OPT_LEGACY_PFB, CHAN_OPT_LEGACY_TAIL, CHAN_OPT_SERIAL_TAIL = 1, 2, 3
 WIN_HAMMING, WIN_HANN, WIN_BLACKMAN, WIN_RECTANGULAR, WIN_BLACKMAN_HARRIS = 0, 1, 2, 3, 5
 
@@ -471,7 +471,8 @@ class Demod:
 
     def process_sc16_async(self, iq):
         """Queue one pass over 16-bit integer IQ: iq is an int16 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_sc16).
-        Handles with device_samp_rate >= 2 Msps; the row pitch must be a multiple of 4 samples and the base 16-byte aligned."""
+        Handles with device_samp_rate >= 2 Msps take it as they are; a 1 Msps handle takes it after enable_sc16_baseband() (its first stage
+        then reads the raw pairs) and refuses it otherwise.  The row pitch must be a multiple of 4 samples and the base 16-byte aligned."""
         assert iq.is_cuda and iq.dtype == self.torch.int16 and iq.dim() == 2 and iq.shape[0] == self.batch
         assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
         self.torch.cuda.current_stream().synchronize()
@@ -488,6 +489,11 @@ class Demod:
     def set_sc16_scale(self, scale):
         """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_demod_set_sc16_scale)"""
         _check(self.lib.qrl_demod_set_sc16_scale(self.h, C.c_float(scale)), "qrl_demod_set_sc16_scale")
+
+    def enable_sc16_baseband(self, on=True):
+        """A handle without a device-rate front end (1 Msps) takes int16 IQ from the next call on (QRL_OPT_SC16_BASEBAND); off again: such
+        calls are refused as by default.  Changes no result, allocates nothing, any stream position; no effect on a handle with a front end."""
+        _check(self.lib.qrl_demod_set_option(self.h, OPT_SC16_BASEBAND, 1 if on else 0), "qrl_demod_set_option")
 
     def set_squelch(self, db):
         _check(self.lib.qrl_demod_set_squelch(self.h, C.c_double(db)), "qrl_demod_set_squelch")

@@ -175,6 +175,24 @@ inline uint32_t decim_lookback(const DecimChoice& c, int nt, int D)
          : c.cls == DECIM_CLASS_M16 ? (uint32_t)(nt + D) : (uint32_t)(c.Jpad * D);
 }
 
+// ---- can the streaming kernel read this call's buffer? (the `stream_ok` of decim_split) ----
+// What a launcher knows about the call's input: the caller's buffer (in_base = 0: the stage reads an engine ring), whether the rotator runs
+// in this stage, the row pitch and the call's length in samples, the sample format, and the stage's edge scratch (cf32 whatever the format).
+struct CallInput { uint64_t in_base; uint64_t in_stride; uint32_t n; bool sc16; bool rot; uint64_t edge_base; uint32_t edge_stride; };
+// samples per 16-byte piece, minus one: cf32 rows are whole pieces at even sample counts, int16 rows at multiples of FOUR samples
+inline uint32_t pm_piece_mask(bool sc16) { return sc16 ? 3u : 1u; }
+// pm: the matrix kernel streams the rows of the buffer as 16-byte LDS-DMA pieces, so the base, the row pitch and the row length are whole
+// pieces, in EITHER format and at every lag-tile count (one tile: the 1:50 first stages; three: the device-rate front ends); the edge unit of
+// the same launch reads the scratch the same way.  Anything else: one thread per output (k_decim_pm_gen).
+inline bool decim_pm_streamable(const CallInput& c)
+{
+    const uint32_t amask = pm_piece_mask(c.sc16);
+    return c.in_base && c.rot && (c.in_base & 15u) == 0 && (c.in_stride & amask) == 0 && (c.n & amask) == 0 &&
+           c.edge_base && (c.edge_base & 15u) == 0 && (c.edge_stride & 1u) == 0;
+}
+// pl: the register kernel loads per lane (8 or 4 bytes): any caller's buffer that is rotated here
+inline bool decim_pl_streamable(const CallInput& c) { return c.in_base && c.rot; }
+
 // ---- one call of the pm / pl launchers: outputs [m0, m0 + m_count) from the samples [n0, n0 + n) ----
 // Half-open output ranges, in order: per-output kernel, edge unit of the streaming kernel (reads the staged scratch: ROTATED samples
 // edge_i0 .. edge_i0 + edge_len - 1, absolute indices, edge_i0 may be negative), the streaming kernel's segments on the caller's buffer,
@@ -214,6 +232,17 @@ inline DecimSplit decim_pm_split(uint64_t n0, uint32_t n, uint64_t m0, uint32_t 
 inline DecimSplit decim_pl_split(uint64_t n0, uint32_t n, uint64_t m0, uint32_t m_count, int nt, int D, uint32_t edge_cap, bool stream_ok)
 {
     return decim_split(n0, n, m0, m_count, D, pl_geom(nt, D).WU, 1, edge_cap, stream_ok);   // (the register kernel exists for R = 1, D' = D)
+}
+
+// What launch_decim_pm / launch_decim_pl do with one call, whole: the streamability of the call's buffer decides the split, for every geometry of
+// the class (tests/host/test_sc16_baseband_plan.cpp evaluates exactly these two lines for the one-tile stage fed int16)
+inline DecimSplit decim_pm_plan_call(uint64_t n0, uint64_t m0, uint32_t m_count, int nt, int D, uint32_t edge_cap, const CallInput& c)
+{
+    return decim_pm_split(n0, c.n, m0, m_count, nt, D, edge_cap, decim_pm_streamable(c));
+}
+inline DecimSplit decim_pl_plan_call(uint64_t n0, uint64_t m0, uint32_t m_count, int nt, int D, uint32_t edge_cap, const CallInput& c)
+{
+    return decim_pl_split(n0, c.n, m0, m_count, nt, D, edge_cap, decim_pl_streamable(c));
 }
 
 // ---- segments of the streaming kernels: S outputs each, nseg per stream, one wave per unit = (stream, segment) + one edge unit per stream ----

@@ -325,7 +325,7 @@ int qrl_demod::build()
 
 int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt)
 {
-    if (fmt == IN_SC16 && !fe.used)
+    if (fmt == IN_SC16 && !fe.used && !sc16_baseband)
         return qrl_set_error(QRL_ERR_ARG, "qrl_demod_process_sc16: int16 input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps");
     if (n > cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
     if (fmt == IN_SC16) {
@@ -346,7 +346,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     if (grouped && q_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(stream, ev_q[slot ^ 1], 0));   // grouped order: this front end behind the recursion of the call before
     if (pre_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_pre, 0)); pre_pending = false; }   // k_hist of the call before (helper stream)
     const bool use_pre = pre && input_resident;
-    const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16: int16 pairs behind it; only the front end and k_hist read it, both told so)
+    const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16: int16 pairs behind it; only the kernels that read the caller's buffer know: the front end or, without one, what input_source feeds, and k_hist)
     const float2* hist_old = hist_flip ? hist_b.p : hist_a.p;
     const PortC fport = filtered_port(out), cport = constellation_port(out);
     float2* hist_new = hist_flip ? hist_a.p : hist_b.p;
@@ -381,7 +381,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     const uint64_t n2_0 = n2, n2_1 = decim_count(src1, interp, decim);
     if (interp == 1) {
         DecimParams p{};
-        input_source(p, in, stride, hist_old, src0, src1);
+        input_source(p, in, stride, hist_old, src0, src1, fmt);
         p.out = r2; p.m0 = n2_0; p.m_count = (uint32_t)(n2_1 - n2_0);
         p.taps = first.taps.p; p.D = first.D; p.Jpad = first.c.Jpad;
         if (d2f) {   // + _shaping_filter -> port 0 and the filtered ring, in the same kernel
@@ -395,7 +395,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         }
     } else {
         ResampParams p{};
-        input_source(p, in, stride, hist_old, src0, src1);
+        input_source(p, in, stride, hist_old, src0, src1, fmt);
         p.out = r2; p.q0 = n2_0; p.q_count = (uint32_t)(n2_1 - n2_0);
         p.taps = rs_taps.p; p.I = interp; p.D = decim; p.Jp = rs_Jp;
         if (fam == F_DMR && !m17) {   // port 0 of gr_demod_dmr is the resampler output (gr_demod_dmr.cpp:89)
@@ -408,7 +408,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     if (scope_out) {
         const uint64_t ns_1 = decim_count(src1, 1, scope_D);
         DecimParams p{};
-        input_source(p, in, stride, hist_old, src0, src1);
+        input_source(p, in, stride, hist_old, src0, src1, fmt);
         p.out = RingC{s_scope.p, scope_mask}; p.m0 = n_scope; p.m_count = (uint32_t)(ns_1 - n_scope);
         p.taps = scope.taps.p; p.D = scope.D; p.Jpad = scope.c.Jpad;
         if (scope.launch(p, B, stream)) return qrl_set_error(QRL_ERR_HIP, "scope launch: hipFuncSetAttribute failed");
@@ -794,6 +794,9 @@ int qrl_demod_set_option(qrl_demod* d, int option, int value)
         if (d->n_in != 0) return qrl_set_error(QRL_ERR_STATE, "QRL_OPT_UNFUSED_DEC2 can only be set before the first sample (the two forms carry different state)");
         d->d2f = value == 0;
         return QRL_OK;
+    case QRL_OPT_SC16_BASEBAND:
+        d->sc16_baseband = value != 0;   // read by the calls from now on: no state, nothing to wait for (a handle with a front end takes int16 anyway)
+        return QRL_OK;
     default:
         return qrl_set_error(QRL_ERR_ARG, "unknown option");
     }
@@ -904,7 +907,7 @@ static int process_host(qrl_demod* d, const void* iq_host, size_t stride, size_t
     if (!d || !iq_host || !counts_host) return QRL_ERR_ARG;
     HIPCHK(hipSetDevice(d->ctx->device));
     (void)take_launch_error();
-    if (fmt == IN_SC16 && !d->fe.used) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
+    if (fmt == IN_SC16 && !d->fe.used && !d->sc16_baseband) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
     const size_t B = (size_t)d->cfg.batch;
     const size_t st = (n + round - 1) / round * round;
     DevBuf<unsigned char> iq; DevBuf<uint8_t> ba, bb; DevBuf<uint32_t> cnt;

@@ -60,7 +60,8 @@ void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set
 // ---- format of the caller's IQ (qrl_demod_process / qrl_demod_process_sc16) ----
 // IN_SC16: `in` points at interleaved int16 I, Q pairs (4 bytes per sample, in_stride still in samples) and a sample is
 // x = (float)v * in_scale per component: one exact int -> float conversion, one rounded multiply, in front of the rotator.  Only the kernels
-// that read the caller's buffer know the format (the front-end stage and k_hist); history, edge scratch and rings stay rotated cf32.
+// that read the caller's buffer know the format (the front-end stage -- without a front end, under QRL_OPT_SC16_BASEBAND, the mode's first stage and the
+// scope tap -- and k_hist); history, edge scratch and rings stay rotated cf32.
 enum { IN_CF32 = 0, IN_SC16 = 1 };
 __device__ __forceinline__ float2 sc16_to_f2(uint32_t w, float scale)
 {

@@ -765,6 +765,12 @@ __global__ __launch_bounds__(256) void k_pl_edge_stage_sc16(const DecimParams P_
 // produces on the launch stream) and runs the per-output kernel `gen`, `per_wg` outputs per workgroup, on the two ranges left to it.
 // false: nothing for the streaming kernel to do
 typedef void (*DecimGenKernel)(const DecimParams, uint64_t, uint32_t);
+// what decim_plan.hpp's streamability predicates look at
+static CallInput call_input(const DecimParams& p)
+{
+    return CallInput{(uint64_t)reinterpret_cast<uintptr_t>(p.in), (uint64_t)p.in_stride, p.n, p.in_fmt == IN_SC16, p.rot_enable != 0,
+                     (uint64_t)reinterpret_cast<uintptr_t>(p.pl_edge), p.pl_edge_stride};
+}
 static bool launch_split(DecimParams& q, const DecimSplit& sp, DecimGenKernel gen, uint32_t per_wg, int batch, hipStream_t s)
 {
     q.pl_m_begin = sp.main.lo; q.pl_m_end = sp.main.hi;
@@ -870,7 +876,7 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
 {
     if (p.m_count == 0) return 0;
     const PlGeom g = pl_geom(p.nt, p.D);
-    const DecimSplit sp = decim_pl_split(p.n0, p.n, p.m0, p.m_count, p.nt, p.D, p.pl_edge ? p.pl_edge_cap : 0u, p.in && p.rot_enable);
+    const DecimSplit sp = decim_pl_plan_call(p.n0, p.m0, p.m_count, p.nt, p.D, p.pl_edge ? p.pl_edge_cap : 0u, call_input(p));
     const DecimSegments sg = pl_segments(sp.main.count(), (uint32_t)batch, g, !sp.edge.empty());
     DecimParams q = p;
     q.pl_J = g.Upad; q.pl_E = g.E; q.pl_R = g.R;
@@ -955,11 +961,9 @@ static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edg
 template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
 static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
-    // int16 input: the front ends only (three lag tiles); launch_decim_pm keeps the one-tile geometries on the per-output kernel
-    if constexpr (J > 16) {
-        if (q.in_fmt == IN_SC16)
-            return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, true>(q, M, batch, edge_unit, s);
-    }
+    // int16 input: the SC instantiation of the same geometry (front ends: three lag tiles; the first stages of a 1 Msps handle: one)
+    if (q.in_fmt == IN_SC16)
+        return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, true>(q, M, batch, edge_unit, s);
     return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false>(q, M, batch, edge_unit, s);
 }
 int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
@@ -970,15 +974,9 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
     DecimParams q = p;
     q.pl_J = J; q.pl_E = 1; q.pl_R = 1;
     q.pl_hraw = p.pl_taps + (size_t)pm_tiles(J) * NS * 64;
-    // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces: rows 16-byte aligned, even sample counts
-    // (what qrl_demod_process demands; the edge scratch is built that way).  Anything else: one thread per output.
-    // int16 input (4-byte samples): whole pieces per row are multiples of FOUR samples
-    const uint32_t amask = p.in_fmt == IN_SC16 ? 3u : 1u;
-    const bool dma_ok = p.in && p.rot_enable && (reinterpret_cast<uintptr_t>(p.in) & 15u) == 0 && (p.in_stride & amask) == 0 && (p.n & amask) == 0 &&
-                        p.pl_edge && (reinterpret_cast<uintptr_t>(p.pl_edge) & 15u) == 0 && (p.pl_edge_stride & 1u) == 0 &&
-                        !(p.in_fmt == IN_SC16 && J <= 16);   // (not reachable from the front-end stage, whose ~41.8 D taps give J > 16, and int16 input exists
-                                                             //  only there; kept so that a one-tile stage fed int16 would still be exact, through k_decim_pm_gen)
-    const DecimSplit sp = decim_pm_split(p.n0, p.n, p.m0, p.m_count, nt, D, p.pl_edge_cap, dma_ok);
+    // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces (decim_pm_streamable: what qrl_demod_process and
+    // qrl_demod_process_sc16 demand, the latter with n % 4 == 0; the edge scratch is built that way).  Anything else: one thread per output.
+    const DecimSplit sp = decim_pm_plan_call(p.n0, p.m0, p.m_count, nt, D, p.pl_edge_cap, call_input(p));
     if (!launch_split(q, sp, p.rot_acc_s ? k_decim_pm_gen<true> : k_decim_pm_gen<false>, 256, batch, s)) return 0;
     const bool edge_unit = !sp.edge.empty();
     const uint64_t M = sp.main.count();

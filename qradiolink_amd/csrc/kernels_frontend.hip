@@ -352,7 +352,10 @@ constexpr int D2_NTH = 256, D2_R = 8;
 constexpr int D2_W = 261;                        // positions per image: (40 + 2048) / 8
 constexpr int D2_HALO = 24;                      // second-filter taps, padded to a multiple of 8
 constexpr int D2_TY = D2_R * D2_NTH - D2_HALO;   // outputs a workgroup delivers
-template <bool PS>
+// SC: the caller's buffer holds int16 pairs (a 1 Msps handle under QRL_OPT_SC16_BASEBAND): a sample is ONE 32-bit word, converted
+// (sc16_to_f2) in front of the rotator in both staging paths; the carried history and the engine rings stay cf32.  The cf32
+// instantiations keep their code.
+template <bool PS, bool SC = false>
 __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
 {
     const Dec2FirParams& P = P_;
@@ -394,13 +397,30 @@ __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
         } else
 #endif
         if (inb && i_lo >= (int64_t)Q.n0 && i_lo + 2 * 8 * D2_W <= i_end) {   // the whole span lies in the caller's buffer (workgroup uniform)
-            const float2* src = inb + (size_t)(i_lo - (int64_t)Q.n0) + 2 * tid;
+            if constexpr (SC) {
+                const uint32_t* src = reinterpret_cast<const uint32_t*>(Q.in) + (size_t)b * Q.in_stride + (size_t)(i_lo - (int64_t)Q.n0) + 2 * tid;
+                uint32_t w[NK][2];
 #pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                const bool ok = tid + D2_NTH * k < 8 * D2_W;
-                v[k][0] = ok ? src[2 * D2_NTH * k] : make_float2(0.f, 0.f);
-                v[k][1] = ok ? src[2 * D2_NTH * k + 1] : make_float2(0.f, 0.f);
-                fresh[k][0] = fresh[k][1] = Q.rot_enable != 0;
+                for (int k = 0; k < NK; ++k) {
+                    const bool ok = tid + D2_NTH * k < 8 * D2_W;
+                    w[k][0] = ok ? src[2 * D2_NTH * k] : 0u;
+                    w[k][1] = ok ? src[2 * D2_NTH * k + 1] : 0u;
+                }
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    v[k][0] = sc16_to_f2(w[k][0], Q.in_scale);
+                    v[k][1] = sc16_to_f2(w[k][1], Q.in_scale);
+                    fresh[k][0] = fresh[k][1] = Q.rot_enable != 0;
+                }
+            } else {
+                const float2* src = inb + (size_t)(i_lo - (int64_t)Q.n0) + 2 * tid;
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const bool ok = tid + D2_NTH * k < 8 * D2_W;
+                    v[k][0] = ok ? src[2 * D2_NTH * k] : make_float2(0.f, 0.f);
+                    v[k][1] = ok ? src[2 * D2_NTH * k + 1] : make_float2(0.f, 0.f);
+                    fresh[k][0] = fresh[k][1] = Q.rot_enable != 0;
+                }
             }
         } else
 #pragma unroll
@@ -413,7 +433,11 @@ __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
                 fresh[k][e] = false;
                 if (l < 8 * D2_W && i >= 0 && i < i_end) {
                     if (inb) {
-                        if (i >= (int64_t)Q.n0) { src = inb + (size_t)(i - (int64_t)Q.n0); fresh[k][e] = Q.rot_enable != 0; }
+                        if (i >= (int64_t)Q.n0) {
+                            fresh[k][e] = Q.rot_enable != 0;
+                            if constexpr (SC) { v[k][e] = in_load_as<true>(Q, (size_t)b, (size_t)(i - (int64_t)Q.n0)); continue; }   // (the raw word, converted)
+                            else src = inb + (size_t)(i - (int64_t)Q.n0);
+                        }
                         else if ((int64_t)Q.n0 - i <= (int64_t)Q.hist_len) src = hb + (Q.hist_len - (uint32_t)((int64_t)Q.n0 - i));
                     } else src = rb + ((uint32_t)i & Q.in_ring.mask);
                 }
@@ -539,8 +563,12 @@ std::vector<float> dec2_fir_table(const std::vector<float>& h1, const std::vecto
 void launch_dec2_fir(const Dec2FirParams& p, int batch, hipStream_t s)
 {
     if (p.d.m_count == 0) return;
-    if (p.d.rot_acc_s) hipLaunchKernelGGL(k_dec2_fir<true>, dim3((p.d.m_count + D2_TY - 1) / D2_TY, batch), dim3(D2_NTH), 0, s, p);
-    else hipLaunchKernelGGL(k_dec2_fir<false>, dim3((p.d.m_count + D2_TY - 1) / D2_TY, batch), dim3(D2_NTH), 0, s, p);
+    const dim3 grid((p.d.m_count + D2_TY - 1) / D2_TY, batch);
+    if (p.d.in && p.d.in_fmt == IN_SC16) {
+        if (p.d.rot_acc_s) hipLaunchKernelGGL((k_dec2_fir<true, true>), grid, dim3(D2_NTH), 0, s, p);
+        else hipLaunchKernelGGL((k_dec2_fir<false, true>), grid, dim3(D2_NTH), 0, s, p);
+    } else if (p.d.rot_acc_s) hipLaunchKernelGGL(k_dec2_fir<true>, grid, dim3(D2_NTH), 0, s, p);
+    else hipLaunchKernelGGL(k_dec2_fir<false>, grid, dim3(D2_NTH), 0, s, p);
 }
 
 // ---- per-stream rotator state (RotPs, engine.cpp) ----

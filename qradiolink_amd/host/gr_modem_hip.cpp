@@ -115,6 +115,7 @@ try {
     chk(qrl_demod_create(d_rt.ctx(), &c, &h), "qrl_demod_create");
     d_h.reset(h);
     chk(qrl_demod_set_sc16_scale(h, d_sc16_scale), "qrl_demod_set_sc16_scale");
+    chk(qrl_demod_set_option(h, QRL_OPT_SC16_BASEBAND, d_sc16_baseband ? 1 : 0), "qrl_demod_set_option");
     if (d_per_stream) chk(qrl_demod_set_carrier_offsets(h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
     chk(qrl_demod_out_caps(h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
     chk(qrl_demod_audio_cap(h, d_chunk, &d_acap), "qrl_demod_audio_cap");
@@ -298,7 +299,8 @@ void gr_demod_base_hip::set_samp_rate(int device_samp_rate)   // gr_demod_base.c
 }
 void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, false); }
 // 16-bit integer I/Q as the SDR drivers deliver it (interleaved int16 I, Q): 4 bytes per sample are staged in the pinned buffer and uploaded,
-// and the device-rate front end converts (qrl_demod_process_sc16: x = (float)v * scale).  Replaces the driver's sc16 -> fc32 conversion.
+// and the device-rate front end -- at 1 Msps, under set_sc16_baseband, the mode's first stage -- converts (qrl_demod_process_sc16:
+// x = (float)v * scale).  Replaces the driver's sc16 -> fc32 conversion.
 void gr_demod_base_hip::work(const int16_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, true); }
 void gr_demod_base_hip::set_sc16_scale(float scale)
 {
@@ -308,6 +310,12 @@ void gr_demod_base_hip::set_sc16_scale(float scale)
     if (d_h.get()) chk(qrl_demod_set_sc16_scale(d_h.get(), scale), "qrl_demod_set_sc16_scale");
     if (d_fft.get()) chk(qrl_fft_set_sc16_scale(d_fft.get(), scale), "qrl_fft_set_sc16_scale");   // the spectrum tap reads the same int16 slot
 }
+void gr_demod_base_hip::set_sc16_baseband(bool on)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    d_sc16_baseband = on;
+    if (d_h.get()) chk(qrl_demod_set_option(d_h.get(), QRL_OPT_SC16_BASEBAND, on ? 1 : 0), "qrl_demod_set_option");
+}
 void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
@@ -316,7 +324,7 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     if (n > d_chunk || (n & 1)) throw std::invalid_argument("gr_demod_base_hip::work: n must be even and <= max_chunk");
     if (sc16) {
         // the C ABI would refuse the same (QRL_ERR_ARG); checked here before anything is staged or queued
-        if (d_rate < 2000000) throw std::invalid_argument("gr_demod_base_hip::work(int16): needs the device-rate front end (device_samp_rate >= 2000000)");
+        if (d_rate < 2000000 && !d_sc16_baseband) throw std::invalid_argument("gr_demod_base_hip::work(int16): needs the device-rate front end (device_samp_rate >= 2000000)");
         if (d_chunk & 3) throw std::invalid_argument("gr_demod_base_hip::work(int16): max_chunk (the row pitch) must be a multiple of 4 samples");
     }
     if (!d_demod_on && !d_fft_on) return;                        // _demod_valve closed and nobody else listens: the samples are dropped

@@ -54,10 +54,14 @@ public:
     // one scheduler pass: n new samples (even, <= max_chunk) of every stream, iq[s] = host pointer of stream s
     void work(const gr_complex* const* iq, size_t n);
     // the same for 16-bit integer I/Q (iq[s] = n interleaved int16 I, Q pairs): replaces the SDR driver's sc16 -> fc32 conversion.  Handles at
-    // device_samp_rate >= 2 Msps, max_chunk a multiple of 4; x = (float)v * scale, scale 1 / 32768 unless set_sc16_scale.  The spectrum tap
-    // (enable_gui_fft) reads the same uploaded int16 slot (qrl_fft_process_sc16), with the demodulator valve open or closed
+    // device_samp_rate >= 2 Msps, or at 1 Msps after set_sc16_baseband(true); max_chunk a multiple of 4; x = (float)v * scale, scale 1 / 32768
+    // unless set_sc16_scale.  The spectrum tap (enable_gui_fft) reads the same uploaded int16 slot (qrl_fft_process_sc16), with the
+    // demodulator valve open or closed
     void work(const int16_t* const* iq, size_t n);
     void set_sc16_scale(float scale);
+    // a 1 Msps receiver takes work(int16) too: the per-mode first stage reads the raw pairs (QRL_OPT_SC16_BASEBAND).  Default off: work(int16)
+    // at 1 Msps throws std::invalid_argument.  Kept across set_mode / set_samp_rate; no effect at device rates with a front end
+    void set_sc16_baseband(bool on);
     void flush();                                              // waits for the call in flight and harvests it
     std::vector<unsigned char>* getData(int stream = 0) { return getData(1, stream); }
     virtual std::vector<unsigned char>* getData(int nr, int stream);   // nr = 1: bits A (port 2), nr = 2: bits B (port 3); nullptr = nothing yet (virtual: tests tap the bits)
@@ -165,6 +169,7 @@ private:
     std::unique_ptr<slot> d_slot[2];
     void work_any(const void* const* iq, size_t n, bool sc16);   // both work() overloads
     float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
+    bool d_sc16_baseband = false;                                // set_sc16_baseband; re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0, d_acap = 0;
     int d_squelch = -140; float d_agc_attack = 0.1f, d_agc_decay = 0.1f;   // rates, behind the knob mapping (the constructors' 0.1 until a setter is called)
@@ -327,6 +332,8 @@ public:
     void set_burst_ip_modem(bool v) { _burst_ip_modem = v; }
     // DMR layer 2 on the device, off by default: dmrFramesDecoded(stream, records80) fires beside dmrFrames (the demodulator's set_dmr_l2)
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
+    // the receiver at 1 Msps takes work(int16) (gr_demod_base_hip::set_sc16_baseband; default off)
+    void set_sc16_baseband(bool on) { if (_gr_demod_base) _gr_demod_base->set_sc16_baseband(on); }
     // the DMR receive call layer on the device, off by default, behind set_dmr_l2: dmrCallEvents(stream, records128) fires beside dmrFramesDecoded
     void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false) { if (_gr_demod_base) _gr_demod_base->set_dmr_call(on, colour_code, promiscuous); }
     // the reference's getDMRData(bool dmo) choice: on, dmrFrames / dmrFramesDecoded / dmrCallEvents deliver the bursts of the repeater-mode sink
