@@ -207,6 +207,24 @@ int qrl_demod_process(qrl_demod* d, const float* iq, size_t stride, size_t n, co
  * default) a 1 Msps handle returns QRL_ERR_ARG (qrl_last_error says so), changes nothing and stays usable. */
 int qrl_demod_process_sc16(qrl_demod* d, const int16_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
 int qrl_demod_set_sc16_scale(qrl_demod* d, float scale);
+/* like qrl_demod_process_sc16, but iq is interleaved 8-bit I, Q, 2 bytes per sample: stream b at iq + 2*b*stride bytes.
+ *   sc8 (signed: HackRF, cs8):      x = (float)v * scale per component, scale default 1.0f / 128 (qrl_demod_set_sc8_scale);
+ *   cu8 (unsigned: RTL-SDR dongles): x = ((float)u - bias) * scale, defaults bias 127.5f, scale 1.0f / 128 (qrl_demod_set_cu8_scale; the bias is
+ *   a parameter because drivers differ).
+ * One exact conversion, one f32 subtract (cu8), one rounded f32 multiply, in that order and in front of the rotator: the result of a call is
+ * bit for bit what qrl_demod_process gives for those floats.  The front end reads the raw pairs -- a quarter of the cf32 bytes in HBM and on
+ * the upload -- and converts in registers.  The carried state stays rotated cf32: cf32, sc16, sc8 and cu8 calls may alternate on one handle and
+ * give the result of the concatenated stream; options, per-stream carrier offsets, profiling (the same kernel names) and the scope tap work as
+ * with cf32.  The setters refuse a zero or non-finite scale and a non-finite bias with QRL_ERR_ARG and take effect from the next call.
+ * iq must be 16-byte aligned and stride a multiple of 8 samples, else QRL_ERR_ARG before anything is launched (qrl_last_error names the rule);
+ * any n <= max_chunk (the LDS-DMA kernel streams calls with n % 8 == 0, other n take the per-output kernels).
+ * Handles with device_samp_rate >= 2000000 take 8-bit calls as they are, every modem type and every rate qrl_demod_create accepts.  A 1 Msps
+ * handle has no front end and returns QRL_ERR_ARG, also under QRL_OPT_SC16_BASEBAND (which widened the modes' first stages for int16 only);
+ * it changes nothing and stays usable. */
+int qrl_demod_process_sc8(qrl_demod* d, const int8_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
+int qrl_demod_process_cu8(qrl_demod* d, const uint8_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
+int qrl_demod_set_sc8_scale(qrl_demod* d, float scale);
+int qrl_demod_set_cu8_scale(qrl_demod* d, float scale, float bias);
 int qrl_demod_sync(qrl_demod* d);
 void* qrl_demod_stream(qrl_demod* d); /* hipStream_t */
 /* Profiling aid: the HIP streams a call's stages are launched on -- out[0] the handle's stream (front end), out[1] the stream of the
@@ -232,6 +250,12 @@ int qrl_demod_process_host(qrl_demod* d, const float* iq_host, size_t stride, si
 /* the same for int16 I, Q host samples (iq_host[b*2*stride + 2*i], 4 bytes per sample staged and uploaded): qrl_demod_process_sc16 */
 int qrl_demod_process_sc16_host(qrl_demod* d, const int16_t* iq_host, size_t stride, size_t n,
                                 uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host);
+/* the same for 8-bit I, Q host samples (iq_host[b*2*stride + 2*i], 2 bytes per sample staged and uploaded; the device pitch is rounded up to
+ * 8 samples): qrl_demod_process_sc8 / qrl_demod_process_cu8 */
+int qrl_demod_process_sc8_host(qrl_demod* d, const int8_t* iq_host, size_t stride, size_t n,
+                               uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host);
+int qrl_demod_process_cu8_host(qrl_demod* d, const uint8_t* iq_host, size_t stride, size_t n,
+                               uint8_t* bits_a_host, uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host);
 
 /* ---- TX: the "modulator" top_block (reference src/gr/gr_mod_base.cpp:25) ----------------------------------
  * One handle = make_gr_mod_qpsk(sps, samp_rate, carrier_freq, filter_width) (src/gr/gr_mod_qpsk.cpp:19-30;
@@ -552,6 +576,14 @@ int qrl_fft_process(qrl_fft* f, const float* iq, size_t stride, size_t n);
  * alternate.  iq must be 16-byte aligned and stride a multiple of 4 samples, else QRL_ERR_ARG. */
 int qrl_fft_process_sc16(qrl_fft* f, const int16_t* iq, size_t stride, size_t n);
 int qrl_fft_set_sc16_scale(qrl_fft* f, float scale);
+/* qrl_fft_process on interleaved 8-bit I, Q, stream b at iq + 2*b*stride bytes: sc8 x = (float)v * scale, cu8 x = ((float)u - bias) * scale
+ * (defaults 1.0f / 128 and 127.5f; the setters refuse a zero or non-finite scale and a non-finite bias with QRL_ERR_ARG), in front of the window
+ * multiply -- bit for bit qrl_fft_process fed those floats; the formats may alternate.  iq must be 16-byte aligned and stride a multiple of
+ * 8 samples, else QRL_ERR_ARG. */
+int qrl_fft_process_sc8(qrl_fft* f, const int8_t* iq, size_t stride, size_t n);
+int qrl_fft_process_cu8(qrl_fft* f, const uint8_t* iq, size_t stride, size_t n);
+int qrl_fft_set_sc8_scale(qrl_fft* f, float scale);
+int qrl_fft_set_cu8_scale(qrl_fft* f, float scale, float bias);
 int qrl_fft_get_fft_data(qrl_fft* f, float* fft_points, size_t out_stride, unsigned* fft_size);
 int qrl_fft_sync(qrl_fft* f);
 void* qrl_fft_stream(qrl_fft* f);

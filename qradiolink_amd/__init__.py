@@ -168,6 +168,10 @@ def load_library():
     lib.qrl_demod_process.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
     lib.qrl_demod_process_sc16.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
     lib.qrl_demod_set_sc16_scale.argtypes = [vp, C.c_float]
+    lib.qrl_demod_process_sc8.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
+    lib.qrl_demod_process_cu8.argtypes = [vp, vp, sz, sz, C.POINTER(_Out)]
+    lib.qrl_demod_set_sc8_scale.argtypes = [vp, C.c_float]
+    lib.qrl_demod_set_cu8_scale.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_demod_sync.argtypes = [vp]
     lib.qrl_rssi_create.argtypes = [vp, C.c_int, C.c_float, vp, C.POINTER(vp)]
     lib.qrl_rssi_destroy.argtypes = [vp]
@@ -186,6 +190,10 @@ def load_library():
     lib.qrl_fft_process.argtypes = [vp, vp, sz, sz]
     lib.qrl_fft_process_sc16.argtypes = [vp, vp, sz, sz]
     lib.qrl_fft_set_sc16_scale.argtypes = [vp, C.c_float]
+    lib.qrl_fft_process_sc8.argtypes = [vp, vp, sz, sz]
+    lib.qrl_fft_process_cu8.argtypes = [vp, vp, sz, sz]
+    lib.qrl_fft_set_sc8_scale.argtypes = [vp, C.c_float]
+    lib.qrl_fft_set_cu8_scale.argtypes = [vp, C.c_float, C.c_float]
     lib.qrl_fft_get_fft_data.argtypes = [vp, vp, sz, C.POINTER(C.c_uint)]
     lib.qrl_fft_sync.argtypes = [vp]
     lib.qrl_demod_stream_wait.argtypes = [vp, vp]
@@ -200,6 +208,8 @@ def load_library():
     lib.qrl_demod_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)]
     lib.qrl_demod_process_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
     lib.qrl_demod_process_sc16_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
+    lib.qrl_demod_process_sc8_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
+    lib.qrl_demod_process_cu8_host.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
     lib.qrl_mod_create.argtypes = [vp, C.POINTER(_ModConfig), C.POINTER(vp)]
     lib.qrl_mod_destroy.argtypes = [vp]
     lib.qrl_mod_reset.argtypes = [vp]
@@ -296,7 +306,8 @@ EXPORTED_SYMBOLS = [
     "qrl_m17_call_start", "qrl_m17_call_encode", "qrl_m17_call_end",
     "qrl_dmr_sink_create", "qrl_dmr_sink_destroy", "qrl_dmr_sink_reset", "qrl_dmr_sink_flush", "qrl_dmr_sink_process", "qrl_dmr_sink_sync",
     "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
-    "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
+    "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host",
+    "qrl_demod_process_sc8", "qrl_demod_process_cu8", "qrl_demod_set_sc8_scale", "qrl_demod_set_cu8_scale", "qrl_demod_process_sc8_host", "qrl_demod_process_cu8_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
     "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_process_sc16", "qrl_mod_set_sc16_scale", "qrl_mod_set_sc16_clip_counts", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
     "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_process_sc16", "qrl_chan_channelize_sc16", "qrl_chan_set_sc16_scale", "qrl_chan_sync",
@@ -304,7 +315,7 @@ EXPORTED_SYMBOLS = [
     "qrl_synth_sync",
     "qrl_rssi_create", "qrl_rssi_destroy", "qrl_rssi_reset", "qrl_rssi_set_level", "qrl_rssi_process", "qrl_rssi_sync", "qrl_rssi_stream",
     "qrl_fft_create", "qrl_fft_destroy", "qrl_fft_set_enabled", "qrl_fft_set_fft_size", "qrl_fft_get_fft_size", "qrl_fft_set_window_type",
-    "qrl_fft_get_window_type", "qrl_fft_process", "qrl_fft_process_sc16", "qrl_fft_set_sc16_scale", "qrl_fft_get_fft_data", "qrl_fft_sync", "qrl_fft_stream",
+    "qrl_fft_get_window_type", "qrl_fft_process", "qrl_fft_process_sc16", "qrl_fft_set_sc16_scale", "qrl_fft_process_sc8", "qrl_fft_process_cu8", "qrl_fft_set_sc8_scale", "qrl_fft_set_cu8_scale", "qrl_fft_get_fft_data", "qrl_fft_sync", "qrl_fft_stream",
     "qrl_deframer_create", "qrl_deframer_destroy", "qrl_deframer_reset", "qrl_deframer_process", "qrl_deframer_sync",
     "qrl_framesync_create", "qrl_framesync_destroy", "qrl_framesync_reset", "qrl_framesync_frame_bytes", "qrl_framesync_process",
     "qrl_framesync_sync", "qrl_framesync_set_activity_output", "qrl_framesync_stream",
@@ -489,6 +500,42 @@ class Demod:
     def set_sc16_scale(self, scale):
         """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_demod_set_sc16_scale)"""
         _check(self.lib.qrl_demod_set_sc16_scale(self.h, C.c_float(scale)), "qrl_demod_set_sc16_scale")
+
+    def _process_iq8_async(self, iq, dtype, name):
+        assert iq.is_cuda and iq.dtype == dtype and iq.dim() == 2 and iq.shape[0] == self.batch
+        assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
+        self.torch.cuda.current_stream().synchronize()
+        _check(getattr(self.lib, name)(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2, C.byref(self._out)), name)
+        self._dmo_l2_async()
+        self._dmr_sink_async()
+
+    def process_sc8_async(self, iq):
+        """Queue one pass over signed 8-bit IQ: iq is an int8 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_sc8; what a HackRF
+        delivers).  Handles with device_samp_rate >= 2 Msps only; the row pitch must be a multiple of 8 samples and the base 16-byte aligned."""
+        self._process_iq8_async(iq, self.torch.int8, "qrl_demod_process_sc8")
+
+    def process_sc8(self, iq):
+        self.process_sc8_async(iq)
+        self.sync()
+        return self._ports()
+
+    def process_cu8_async(self, iq):
+        """Queue one pass over unsigned 8-bit IQ: iq is a uint8 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_cu8; what an
+        RTL-SDR dongle delivers).  The same rules as process_sc8_async."""
+        self._process_iq8_async(iq, self.torch.uint8, "qrl_demod_process_cu8")
+
+    def process_cu8(self, iq):
+        self.process_cu8_async(iq)
+        self.sync()
+        return self._ports()
+
+    def set_sc8_scale(self, scale):
+        """x = float(v) * scale for the sc8 calls from the next one on (default 1 / 128; qrl_demod_set_sc8_scale)"""
+        _check(self.lib.qrl_demod_set_sc8_scale(self.h, C.c_float(scale)), "qrl_demod_set_sc8_scale")
+
+    def set_cu8_scale(self, scale, bias=127.5):
+        """x = (float(u) - bias) * scale for the cu8 calls from the next one on (defaults 1 / 128, 127.5; qrl_demod_set_cu8_scale)"""
+        _check(self.lib.qrl_demod_set_cu8_scale(self.h, C.c_float(scale), C.c_float(bias)), "qrl_demod_set_cu8_scale")
 
     def enable_sc16_baseband(self, on=True):
         """A handle without a device-rate front end (1 Msps) takes int16 IQ from the next call on (QRL_OPT_SC16_BASEBAND); off again: such
@@ -946,6 +993,45 @@ class Fft:
     def set_sc16_scale(self, scale):
         """x = float(v) * scale for the int16 calls from the next one on (default 1 / 32768; qrl_fft_set_sc16_scale)"""
         _check(self.lib.qrl_fft_set_sc16_scale(self.h, C.c_float(scale)), "qrl_fft_set_sc16_scale")
+
+    def _process_iq8(self, iq, dtype, name):
+        t = self.torch
+        assert iq.is_cuda and iq.dtype == dtype and iq.dim() == 2 and iq.shape[0] == self.batch
+        assert iq.stride(1) == 1 and iq.shape[1] % 2 == 0 and iq.stride(0) % 2 == 0
+        t.cuda.current_stream().synchronize()
+        _check(getattr(self.lib, name)(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2), name)
+        _check(self.lib.qrl_fft_sync(self.h), "qrl_fft_sync")
+
+    def process_sc8(self, iq):
+        """work() over signed 8-bit IQ: iq is an int8 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_fft_process_sc8); row pitch a multiple of
+        8 samples, base 16-byte aligned"""
+        self._process_iq8(iq, self.torch.int8, "qrl_fft_process_sc8")
+
+    def process_cu8(self, iq):
+        """work() over unsigned 8-bit IQ: a uint8 cuda tensor [batch, 2 * n] (qrl_fft_process_cu8); the same rules"""
+        self._process_iq8(iq, self.torch.uint8, "qrl_fft_process_cu8")
+
+    def process_sc8_async(self, iq):
+        """process_sc8 without the wait for the handle's stream: the caller keeps iq alive until sync()"""
+        t = self.torch
+        assert iq.is_cuda and iq.dtype == t.int8 and iq.dim() == 2 and iq.shape[0] == self.batch and iq.stride(1) == 1 and iq.stride(0) % 2 == 0
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_fft_process_sc8(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2), "qrl_fft_process_sc8")
+
+    def process_cu8_async(self, iq):
+        """process_cu8 without the wait for the handle's stream: the caller keeps iq alive until sync()"""
+        t = self.torch
+        assert iq.is_cuda and iq.dtype == t.uint8 and iq.dim() == 2 and iq.shape[0] == self.batch and iq.stride(1) == 1 and iq.stride(0) % 2 == 0
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_fft_process_cu8(self.h, iq.data_ptr(), iq.stride(0) // 2, iq.shape[1] // 2), "qrl_fft_process_cu8")
+
+    def set_sc8_scale(self, scale):
+        """x = float(v) * scale for the sc8 calls from the next one on (default 1 / 128; qrl_fft_set_sc8_scale)"""
+        _check(self.lib.qrl_fft_set_sc8_scale(self.h, C.c_float(scale)), "qrl_fft_set_sc8_scale")
+
+    def set_cu8_scale(self, scale, bias=127.5):
+        """x = (float(u) - bias) * scale for the cu8 calls from the next one on (defaults 1 / 128, 127.5; qrl_fft_set_cu8_scale)"""
+        _check(self.lib.qrl_fft_set_cu8_scale(self.h, C.c_float(scale), C.c_float(bias)), "qrl_fft_set_cu8_scale")
 
     def get_fft_data(self):
         t = self.torch

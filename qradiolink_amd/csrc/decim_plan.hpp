@@ -178,15 +178,19 @@ inline uint32_t decim_lookback(const DecimChoice& c, int nt, int D)
 // ---- can the streaming kernel read this call's buffer? (the `stream_ok` of decim_split) ----
 // What a launcher knows about the call's input: the caller's buffer (in_base = 0: the stage reads an engine ring), whether the rotator runs
 // in this stage, the row pitch and the call's length in samples, the sample format, and the stage's edge scratch (cf32 whatever the format).
-struct CallInput { uint64_t in_base; uint64_t in_stride; uint32_t n; bool sc16; bool rot; uint64_t edge_base; uint32_t edge_stride; };
-// samples per 16-byte piece, minus one: cf32 rows are whole pieces at even sample counts, int16 rows at multiples of FOUR samples
-inline uint32_t pm_piece_mask(bool sc16) { return sc16 ? 3u : 1u; }
+// iq8 (appended, so that the seven-field initialisers of older callers stay valid): the buffer holds 8-bit pairs, 2 bytes per sample (sc8 / cu8).
+struct CallInput { uint64_t in_base; uint64_t in_stride; uint32_t n; bool sc16; bool rot; uint64_t edge_base; uint32_t edge_stride; bool iq8 = false; };
+// log2 of the bytes per sample of the caller's buffer: cf32 3, int16 pairs 2, 8-bit pairs 1
+inline uint32_t in_sample_shift(bool sc16, bool iq8 = false) { return iq8 ? 1u : sc16 ? 2u : 3u; }
+// samples per 16-byte piece, minus one: cf32 rows are whole pieces at even sample counts, int16 rows at multiples of FOUR samples, 8-bit rows at
+// multiples of EIGHT
+inline uint32_t pm_piece_mask(bool sc16, bool iq8 = false) { return (16u >> in_sample_shift(sc16, iq8)) - 1u; }
 // pm: the matrix kernel streams the rows of the buffer as 16-byte LDS-DMA pieces, so the base, the row pitch and the row length are whole
-// pieces, in EITHER format and at every lag-tile count (one tile: the 1:50 first stages; three: the device-rate front ends); the edge unit of
+// pieces, in EVERY format and at every lag-tile count (one tile: the 1:50 first stages; three: the device-rate front ends); the edge unit of
 // the same launch reads the scratch the same way.  Anything else: one thread per output (k_decim_pm_gen).
 inline bool decim_pm_streamable(const CallInput& c)
 {
-    const uint32_t amask = pm_piece_mask(c.sc16);
+    const uint32_t amask = pm_piece_mask(c.sc16, c.iq8);
     return c.in_base && c.rot && (c.in_base & 15u) == 0 && (c.in_stride & amask) == 0 && (c.n & amask) == 0 &&
            c.edge_base && (c.edge_base & 15u) == 0 && (c.edge_stride & 1u) == 0;
 }

@@ -15,6 +15,9 @@
 #define QRL_DEV_SKIP 0   // developer builds only (tools/engine_variants.sh): bit 0 no FLL, 1 no fused 2FSK feed-forward kernel, 2 no symbol sync, 3 no decoder launch -- WRONG results, timing experiments on who stretches the front end
 #endif
 
+// the entry point an 8-bit call came through, for the error text
+static const char* in_fmt_entry(int fmt) { return fmt == IN_SC8 ? "qrl_demod_process_sc8" : "qrl_demod_process_cu8"; }
+
 int qrl_demod::flush_fec(bool behind_front_end)
 {
     if (!fec_deferred) return QRL_OK;
@@ -325,10 +328,14 @@ int qrl_demod::build()
 
 int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt)
 {
+    if (fmt >= IN_SC8 && !fe.used)   // (QRL_OPT_SC16_BASEBAND widened the modes' first stages for int16 only)
+        return qrl_set_error(QRL_ERR_ARG, std::string(in_fmt_entry(fmt)) + ": 8-bit input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps and its missing front end is what converts");
     if (fmt == IN_SC16 && !fe.used && !sc16_baseband)
         return qrl_set_error(QRL_ERR_ARG, "qrl_demod_process_sc16: int16 input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps");
     if (n > cfg.max_chunk) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_chunk");
-    if (fmt == IN_SC16) {
+    if (fmt >= IN_SC8) {
+        if (!iq8_rows_ok(in_fmt_entry(fmt), iq, stride)) return QRL_ERR_ARG;
+    } else if (fmt == IN_SC16) {
         if (!sc16_rows_ok("qrl_demod_process_sc16", iq, stride)) return QRL_ERR_ARG;
     } else if ((reinterpret_cast<uintptr_t>(iq) & 15u) || (stride & 1u)) return qrl_set_error(QRL_ERR_ARG, "iq must be 16-byte aligned, stride even");
     const int B = cfg.batch;
@@ -371,7 +378,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         p.out = RingC{s1.p, s1_mask}; p.m0 = n1_0; p.m_count = (uint32_t)(n1_1 - n1_0);
         p.taps = fe.taps.p; p.D = fe.D; p.Jpad = fe.c.Jpad;
         p.rot_enable = 1; rot.fill(p);
-        p.in_fmt = fmt; p.in_scale = sc16_scale;
+        in_format_fill(p, in_format(fmt));
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
         if (fe.launch(p, B, stream, use_pre ? slot : 0)) return qrl_set_error(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
     }
@@ -421,7 +428,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         h.in = in; h.in_stride = stride; h.n0 = n_in0; h.n = (uint32_t)n;
         h.hist_old = hist_old; h.hist_new = hist_new; h.hist_len = hist_len;
         h.rot_enable = 1; rot.fill(h);
-        h.in_fmt = fmt; h.in_scale = sc16_scale;
+        in_format_fill(h, in_format(fmt));
         if (pre) { HIPCHK(hipEventRecord(ev_fe[slot], stream)); fe_valid[slot] = true; }   // everything of this call that reads the history on the handle's stream has been launched
         if (use_pre) {
             if (fe_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(pre, ev_fe[slot ^ 1], 0));   // hist_new was the history of the call before
@@ -854,6 +861,34 @@ int qrl_demod_set_sc16_scale(qrl_demod* d, float scale)
     d->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
     return QRL_OK;
 }
+int qrl_demod_process_sc8(qrl_demod* d, const int8_t* iq, size_t stride, size_t n, const qrl_demod_out* out)
+{
+    if (!d || (!iq && n)) return QRL_ERR_ARG;
+    HIPCHK(hipSetDevice(d->ctx->device));
+    (void)take_launch_error();
+    return d->process(iq, stride, n, out, IN_SC8);
+}
+int qrl_demod_process_cu8(qrl_demod* d, const uint8_t* iq, size_t stride, size_t n, const qrl_demod_out* out)
+{
+    if (!d || (!iq && n)) return QRL_ERR_ARG;
+    HIPCHK(hipSetDevice(d->ctx->device));
+    (void)take_launch_error();
+    return d->process(iq, stride, n, out, IN_CU8);
+}
+int qrl_demod_set_sc8_scale(qrl_demod* d, float scale)
+{
+    if (!d) return QRL_ERR_ARG;
+    if (!sc16_scale_ok("qrl_demod_set_sc8_scale", scale)) return QRL_ERR_ARG;
+    d->sc8_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
+    return QRL_OK;
+}
+int qrl_demod_set_cu8_scale(qrl_demod* d, float scale, float bias)
+{
+    if (!d) return QRL_ERR_ARG;
+    if (!sc16_scale_ok("qrl_demod_set_cu8_scale", scale) || !iq8_bias_ok("qrl_demod_set_cu8_scale", bias)) return QRL_ERR_ARG;
+    d->cu8_scale = scale; d->cu8_bias = bias;
+    return QRL_OK;
+}
 int qrl_demod_sync(qrl_demod* d)
 {
     if (!d) return QRL_ERR_ARG;
@@ -908,6 +943,7 @@ static int process_host(qrl_demod* d, const void* iq_host, size_t stride, size_t
     HIPCHK(hipSetDevice(d->ctx->device));
     (void)take_launch_error();
     if (fmt == IN_SC16 && !d->fe.used && !d->sc16_baseband) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
+    if (fmt >= IN_SC8 && !d->fe.used) return d->process(nullptr, 0, 0, nullptr, fmt);
     const size_t B = (size_t)d->cfg.batch;
     const size_t st = (n + round - 1) / round * round;
     DevBuf<unsigned char> iq; DevBuf<uint8_t> ba, bb; DevBuf<uint32_t> cnt;
@@ -932,6 +968,17 @@ int qrl_demod_process_sc16_host(qrl_demod* d, const int16_t* iq_host, size_t str
                                 uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
 {
     return process_host(d, iq_host, stride, n, bits_a_host, bits_b_host, bits_cap, counts_host, 4, 4, IN_SC16);
+}
+// 2 bytes per sample staged and uploaded; the device pitch is rounded up to 8 samples (whole 16-byte pieces)
+int qrl_demod_process_sc8_host(qrl_demod* d, const int8_t* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
+                               uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
+{
+    return process_host(d, iq_host, stride, n, bits_a_host, bits_b_host, bits_cap, counts_host, 2, 8, IN_SC8);
+}
+int qrl_demod_process_cu8_host(qrl_demod* d, const uint8_t* iq_host, size_t stride, size_t n, uint8_t* bits_a_host,
+                               uint8_t* bits_b_host, size_t bits_cap, uint32_t* counts_host)
+{
+    return process_host(d, iq_host, stride, n, bits_a_host, bits_b_host, bits_cap, counts_host, 2, 8, IN_CU8);
 }
 
 // ---- host-only design helpers

@@ -62,24 +62,40 @@ void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set
 // x = (float)v * in_scale per component: one exact int -> float conversion, one rounded multiply, in front of the rotator.  Only the kernels
 // that read the caller's buffer know the format (the front-end stage -- without a front end, under QRL_OPT_SC16_BASEBAND, the mode's first stage and the
 // scope tap -- and k_hist); history, edge scratch and rings stay rotated cf32.
-enum { IN_CF32 = 0, IN_SC16 = 1 };
+// IN_SC8 / IN_CU8 (qrl_demod_process_sc8 / _cu8; handles with a front end): `in` points at interleaved 8-bit I, Q pairs, 2 bytes per sample.
+// ONE device path serves both: u = byte ^ mask (0x80 for sc8, 0 for cu8), x = ((float)u - in_bias) * in_scale -- one exact conversion, one f32
+// subtract, one rounded f32 multiply.  (float)(uint8_t)(v ^ 0x80) - 128.0f == (float)v exactly for every int8 v, so the host hands sc8 the bias 128
+// and the result is (float)v * scale; for cu8 the bias is the caller's (default 127.5).
+enum { IN_CF32 = 0, IN_SC16 = 1, IN_SC8 = 2, IN_CU8 = 3 };
+enum { IN_W_CF32 = 0, IN_W_SC16 = 1, IN_W_IQ8 = 2 };   // sample width class: what the kernels with an instantiation per format are instantiated on
 __device__ __forceinline__ float2 sc16_to_f2(uint32_t w, float scale)
 {
     return make_float2((float)(int16_t)(w & 0xffffu) * scale, (float)((int32_t)w >> 16) * scale);
 }
+__device__ __forceinline__ uint32_t iq8_mask(int fmt) { return fmt == IN_SC8 ? 0x8080u : 0u; }   // wave uniform
+// the 16-bit word of one 8-bit sample (I in the low byte), any upper bits ignored
+__device__ __forceinline__ float2 iq8_to_f2(uint32_t w, uint32_t mask, float bias, float scale)
+{
+    const uint32_t u = w ^ mask;
+    return make_float2(((float)(u & 0xffu) - bias) * scale, ((float)((u >> 8) & 0xffu) - bias) * scale);
+}
 // sample r of stream b of the caller's buffer of a parameter block (DecimParams, HistParams), converted.  in_load: the format read from
-// the block (the checked per-sample paths); in_load_as<SC>: the format a compile-time flag (kernels that have an instantiation per format,
-// so that their cf32 code stays what it was)
+// the block (the checked per-sample paths); in_load_as<W>: the width class a compile-time value (kernels that have an instantiation per format,
+// so that their cf32 code stays what it was); a block without in_bias (ResampParams) is never instantiated with IN_W_IQ8
+template <class Pp, class = void> struct in_has_iq8 { static constexpr bool value = false; };   // blocks with an in_bias take 8-bit pairs (ChanParams: cf32 and int16 only)
+template <class Pp> struct in_has_iq8<Pp, decltype((void)Pp::in_bias)> { static constexpr bool value = true; };
 template <class Pp>
 __device__ __forceinline__ float2 in_load(const Pp& P, size_t b, size_t r)
 {
     if (P.in_fmt == IN_SC16) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[b * P.in_stride + r], P.in_scale);
+    if constexpr (in_has_iq8<Pp>::value) if (P.in_fmt >= IN_SC8) return iq8_to_f2(reinterpret_cast<const uint16_t*>(P.in)[b * P.in_stride + r], iq8_mask(P.in_fmt), P.in_bias, P.in_scale);
     return P.in[b * P.in_stride + r];
 }
-template <bool SC, class Pp>
+template <int W, class Pp>
 __device__ __forceinline__ float2 in_load_as(const Pp& P, size_t b, size_t r)
 {
-    if constexpr (SC) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[b * P.in_stride + r], P.in_scale);
+    if constexpr (W == IN_W_IQ8) return iq8_to_f2(reinterpret_cast<const uint16_t*>(P.in)[b * P.in_stride + r], iq8_mask(P.in_fmt), P.in_bias, P.in_scale);
+    else if constexpr (W == IN_W_SC16) return sc16_to_f2(reinterpret_cast<const uint32_t*>(P.in)[b * P.in_stride + r], P.in_scale);
     else return P.in[b * P.in_stride + r];
 }
 
@@ -94,6 +110,7 @@ struct DecimParams {
     const float2* in; size_t in_stride;  // caller IQ (or nullptr when in_ring is used); in_fmt below says what it points at
     RingC in_ring;                       // alternative input: an engine ring (second-stage decimators)
     uint64_t n0; uint32_t n;             // absolute index of in[0], samples in this call
+    float in_bias;                       // IN_SC8 / IN_CU8: x = ((float)u - in_bias) * in_scale (in what was padding: no other field moves)
     const float2* hist; uint32_t hist_len;  // last hist_len (rotated) samples before n0, per stream
     RingC out;
     uint64_t m0; uint32_t m_count;       // absolute first output, number of outputs
@@ -117,10 +134,14 @@ struct DecimParams {
     // nothing the call before produces on the launch stream), `pre_event` is recorded behind it and the launch stream waits for that
     hipStream_t pre_stream; hipEvent_t pre_event;
     const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;   // per-stream rotator (see rot_select below), or nullptr: the shared one above
-    int in_fmt; float in_scale;                             // IN_CF32 (0, what a zeroed block means) | IN_SC16 and its scale
+    int in_fmt; float in_scale;                             // IN_CF32 (0, what a zeroed block means) | IN_SC16 | IN_SC8 | IN_CU8 and its scale
 };
+// the format of one call as the host hands it to a parameter block (DecimParams, HistParams)
+struct InFormat { int fmt; float scale, bias; };
+template <class Pp> inline void in_format_fill(Pp& p, const InFormat& f) { p.in_fmt = f.fmt; p.in_scale = f.scale; p.in_bias = f.bias; }
 struct HistParams {
     const float2* in; size_t in_stride; uint64_t n0; uint32_t n;
+    float in_bias;                       // as in DecimParams, in what was padding
     const float2* hist_old; float2* hist_new; uint32_t hist_len;
     int rot_enable; uint64_t rot_acc; uint64_t rot_inc; uint64_t rot_nbase; const float2* rot_lo;
     const uint64_t* rot_acc_s; const uint64_t* rot_inc_s;
@@ -494,9 +515,10 @@ struct RssiBlockParams {
     float* out; size_t out_cap; float* last; uint32_t* out_counts;
 };
 void launch_rssi(const RssiBlockParams& p, hipStream_t s);
-// in_fmt IN_SC16: `in` points at int16 I, Q pairs and a sample is converted ((float)v * in_scale) in front of the window multiply
+// in_fmt IN_SC16: `in` points at int16 I, Q pairs and a sample is converted ((float)v * in_scale) in front of the window multiply;
+// IN_SC8 / IN_CU8: 8-bit pairs, ((float)u - in_bias) * in_scale (iq8_to_f2)
 void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s,
-                     int in_fmt = IN_CF32, float in_scale = 0.0f);
+                     int in_fmt = IN_CF32, float in_scale = 0.0f, float in_bias = 0.0f);
 void launch_fft_power(const float2* X, float* out, uint32_t N, int batch, hipStream_t s);
 void launch_fft_shift(const float* pts, float* out, size_t out_stride, uint32_t N, int batch, hipStream_t s);
 

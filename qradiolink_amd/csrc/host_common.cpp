@@ -65,6 +65,18 @@ bool sc16_rows_ok(const char* who, const void* iq, size_t stride)
     qrl_set_error(QRL_ERR_ARG, std::string(who) + ": sc16 iq must be 16-byte aligned, stride a multiple of 4 samples");
     return false;
 }
+bool iq8_bias_ok(const char* who, float bias)
+{
+    if (std::isfinite(bias)) return true;
+    qrl_set_error(QRL_ERR_ARG, std::string(who) + ": bias must be finite");
+    return false;
+}
+bool iq8_rows_ok(const char* who, const void* iq, size_t stride)
+{
+    if (reinterpret_cast<uintptr_t>(iq) & 15u) { qrl_set_error(QRL_ERR_ARG, std::string(who) + ": 8-bit iq must be 16-byte aligned"); return false; }
+    if (stride & 7u) { qrl_set_error(QRL_ERR_ARG, std::string(who) + ": the stride of 8-bit iq must be a multiple of 8 samples (16 bytes)"); return false; }
+    return true;
+}
 
 std::vector<float2> rot_fine_table(uint64_t inc)
 {

@@ -73,6 +73,9 @@ private:
 // ---- sc16 input (qrl_*_process_sc16 of the receivers and the spectrum tap): false = refused, with the error text set ----
 bool sc16_scale_ok(const char* who, float scale);                       // finite and non-zero
 bool sc16_rows_ok(const char* who, const void* iq, size_t stride);     // 16-byte aligned base, stride a multiple of 4 samples
+// ---- 8-bit input (qrl_*_process_sc8 / _cu8): the scale by sc16_scale_ok; each broken rule has its own text ----
+bool iq8_bias_ok(const char* who, float bias);                         // finite
+bool iq8_rows_ok(const char* who, const void* iq, size_t stride);      // 16-byte aligned base, stride a multiple of 8 samples
 
 // ---- the carrier NCO of a handle (qrl_demod, qrl_mod, qrl_amod): exact 2^-64-turn accumulator, phase continuous across retunes ----
 // Shared form: one (acc, inc) for every stream, phase of sample n = acc + (n - nbase) inc, and the 512-entry fine table of inc.

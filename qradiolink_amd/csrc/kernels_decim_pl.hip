@@ -184,6 +184,10 @@ __device__ __forceinline__ uint32_t pm_lds32(uint32_t addr)   // ds_read_b32 fro
 {
     return *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)addr;
 }
+__device__ __forceinline__ uint32_t pm_lds16(uint32_t addr)   // ds_read_u16 from a raw (even) LDS byte address
+{
+    return *(const __attribute__((address_space(3))) uint16_t*)(uintptr_t)addr;
+}
 __device__ __forceinline__ uint32_t pm_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
 template <int N> __device__ __forceinline__ void pm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ void pm_wait_vm_dyn(uint32_t allowed)   // wave uniform; at most `allowed` DMA pieces may still be in flight
@@ -226,7 +230,10 @@ constexpr int PM_NHI = 64;   // coarse rotator entries per wave (64 x 512 sample
 // rotator.  The edge units of the same launch still read the rotated cf32 scratch, so the sample size is a per-wave (wave-uniform) shift
 // `ssh`; with SC = false it is the constant 3 and the code is what it was.  NCO indices count SAMPLES whatever the format: kb8 / kg8 are
 // 8 x index (byte offsets into the float2 tables), the data offsets (gbytes, lane_byte, GB) are bytes of the wave's stream.
-template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false, bool SC = false>
+// SC = IN_W_IQ8 (in_fmt IN_SC8 / IN_CU8; three lag tiles only): 2-byte samples -- ssh = 1 for the regular units, a group is 16 D 2 bytes, the lane
+// reads its sample's 16-bit word (ds_read_u16 at lane_byte + 8 s) and converts in registers (iq8_to_f2: xor, two byte conversions, subtract,
+// multiply); the xor mask and the bias are wave uniform.  SC is an int so that the three widths are one parameter; 0 and 1 are the code they were.
+template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false, int SC = IN_W_CF32>
 __global__ __launch_bounds__(NW * 64)
 void k_decim_pm(const DecimParams P_)
 {
@@ -291,12 +298,13 @@ void k_decim_pm(const DecimParams P_)
 #pragma unroll
     for (int t = 0; t < NT; ++t) a1[t] = K1 ? __shfl(a[t][NS - 1], 4 * q + (nn & 3), 64) : 0.f;   // held by lane (row 0, column 4 q + (n & 3)) of the K = 4 layout
     // the wave's byte stream: row = the stream's buffer (or its edge scratch), first byte of block 16 G0 at row + off0
-    const uint32_t ssh = (SC && !edge) ? 2u : 3u;                    // log2 of the sample size of this wave's stream
-    const bool raw16 = SC && !edge;
+    const uint32_t ssh = (SC && !edge) ? (SC == IN_W_IQ8 ? 1u : 2u) : 3u;   // log2 of the sample size of this wave's stream
+    const bool raw16 = SC && !edge;                                  // raw words in the ring (4-byte or 2-byte samples)
+    const uint32_t m8 = SC == IN_W_IQ8 ? iq8_mask(P.in_fmt) : 0u;
     const unsigned char* rowp = edge ? reinterpret_cast<const unsigned char*>(P.pl_edge + (size_t)b * P.pl_edge_stride)
                                      : reinterpret_cast<const unsigned char*>(P.in) + (((size_t)b * P.in_stride) << ssh);   // (in_stride counts samples)
     const uint64_t off0 = edge ? 0ull : (uint64_t)(i_first - P.n0) << ssh;
-    const uint64_t row_bytes = edge ? (uint64_t)P.pl_edge_stride * 8ull : (uint64_t)P.n << ssh;   // multiples of 16 (cf32: even sample counts, sc16: multiples of 4)
+    const uint64_t row_bytes = edge ? (uint64_t)P.pl_edge_stride * 8ull : (uint64_t)P.n << ssh;   // multiples of 16 (cf32: even sample counts, sc16: multiples of 4, 8-bit: of 8)
     const uint32_t o0 = (uint32_t)(off0 & 127u);                     // offset of the first block inside piece 0
     const uint64_t a_off = off0 - o0;                                // piece 0 starts here (128-byte aligned relative to the row)
     const uint32_t GB = (16u * (uint32_t)D) << ssh;                  // bytes per group
@@ -352,10 +360,17 @@ void k_decim_pm(const DecimParams P_)
             const uint32_t xb = gbytes + lane_byte;
             if (raw16) {                                             // (constant false without SC)
                 uint32_t w[NS];
+                if constexpr (SC == IN_W_IQ8) {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) w[s] = pm_lds32(rbase | ((xb + 16u * (uint32_t)s) & (RP * 1024u - 1u)));
+                    for (int s = 0; s < NS; ++s) w[s] = pm_lds16(rbase | ((xb + 8u * (uint32_t)s) & (RP * 1024u - 1u)));
 #pragma unroll
-                for (int s = 0; s < NS; ++s) x[s] = sc16_to_f2(w[s], P.in_scale);
+                    for (int s = 0; s < NS; ++s) x[s] = iq8_to_f2(w[s], m8, P.in_bias, P.in_scale);
+                } else {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) w[s] = pm_lds32(rbase | ((xb + 16u * (uint32_t)s) & (RP * 1024u - 1u)));
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) x[s] = sc16_to_f2(w[s], P.in_scale);
+                }
             } else {
 #pragma unroll
                 for (int s = 0; s < NS; ++s) x[s] = pm_lds(rbase | ((xb + 32u * (uint32_t)s) & (RP * 1024u - 1u)));
@@ -582,8 +597,9 @@ __device__ __forceinline__ v2f plx_mul(v2f hpair, v2f x)
 }
 
 // SC: int16 input -- the regular units load the raw 4-byte pairs (the prefetch registers hold the words) and convert when a block is
-// taken out of the prefetch ring; edge units read the rotated cf32 scratch as before (wave-uniform choice).
-template <int E, int R, int U, bool PS = false, bool SC = false>
+// taken out of the prefetch ring; edge units read the rotated cf32 scratch as before (wave-uniform choice).  SC = IN_W_IQ8: the same with the
+// 16-bit words of 8-bit pairs (exact, not tuned: two 2-byte loads per lane and block).
+template <int E, int R, int U, bool PS = false, int SC = IN_W_CF32>
 __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 {
     constexpr int G = 16 / R;              // blocks per group of 16 outputs
@@ -651,9 +667,12 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
     // waves keep their raw words in the same registers (.x, moves only) rather than in a second array
     const bool raw16 = SC && !edge;
     const float2* ub = (edge ? P.pl_edge + (size_t)b * P.pl_edge_stride : raw16 ? P.pl_edge : P.in + (size_t)b * P.in_stride + (size_t)(i_first - P.n0)) + (size_t)(E * lo);   // lane's first sample of block 0
-    const uint32_t* ub16 = reinterpret_cast<const uint32_t*>(P.in) + (raw16 ? (size_t)b * P.in_stride + (size_t)(i_first - P.n0) + (size_t)(E * lo) : (size_t)0);   // (raw16 only)
+    const uint32_t* ub16 = reinterpret_cast<const uint32_t*>(P.in) + (raw16 && SC != IN_W_IQ8 ? (size_t)b * P.in_stride + (size_t)(i_first - P.n0) + (size_t)(E * lo) : (size_t)0);   // (raw16 only)
+    const uint16_t* ub8 = reinterpret_cast<const uint16_t*>(P.in) + (raw16 && SC == IN_W_IQ8 ? (size_t)b * P.in_stride + (size_t)(i_first - P.n0) + (size_t)(E * lo) : (size_t)0);   // (8-bit pairs only)
+    const uint32_t m8 = SC == IN_W_IQ8 ? iq8_mask(P.in_fmt) : 0u;
     auto fetch = [&](size_t idx) -> v2f {                              // what the prefetch ring holds: the sample, or the raw word in .x
-        if (raw16) return v2f{__uint_as_float(ub16[idx]), 0.f};
+        if constexpr (SC == IN_W_IQ8) { if (raw16) return v2f{__uint_as_float((uint32_t)ub8[idx]), 0.f}; }
+        else if (raw16) return v2f{__uint_as_float(ub16[idx]), 0.f};
         const float2 v = ub[idx];
         return v2f{v.x, v.y};
     };
@@ -684,7 +703,8 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 x[e] = pf[i % PLX_PF][e];
-                if (raw16) { const float2 c = sc16_to_f2(__float_as_uint(x[e].x), P.in_scale); x[e] = v2f{c.x, c.y}; }
+                if constexpr (SC == IN_W_IQ8) { if (raw16) { const float2 c = iq8_to_f2(__float_as_uint(x[e].x), m8, P.in_bias, P.in_scale); x[e] = v2f{c.x, c.y}; } }
+                else if (raw16) { const float2 c = sc16_to_f2(__float_as_uint(x[e].x), P.in_scale); x[e] = v2f{c.x, c.y}; }
             }
             {   // keep PLX_PF blocks in flight (past the end of the segment: harmless re-read of its last block)
                 const int tn = t + PLX_PF < nblk ? t + PLX_PF : nblk - 1;
@@ -730,7 +750,7 @@ __global__ __launch_bounds__(256, 2) void k_decim_plx(const DecimParams P_)
 
 // Edge scratch of one call: for every stream the ROTATED samples i0 .. i0 + len - 1 (absolute indices, i0 may be negative): zeros in
 // front of the stream, the carried (already rotated) history in front of this call's buffer, the buffer's head through the exact NCO
-template <bool PS, bool SC>
+template <bool PS, int SC>
 __device__ __forceinline__ void pl_edge_stage_body(const DecimParams& P_, int64_t i0, uint32_t len)
 {
     ROT_VIEW(DecimParams, PS, P, P_, blockIdx.y);
@@ -757,9 +777,11 @@ __device__ __forceinline__ void pl_edge_stage_body(const DecimParams& P_, int64_
 }
 
 template <bool PS = false>
-__global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, false>(P_, i0, len); }
+__global__ __launch_bounds__(256) void k_pl_edge_stage(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, IN_W_CF32>(P_, i0, len); }
 template <bool PS = false>
-__global__ __launch_bounds__(256) void k_pl_edge_stage_sc16(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, true>(P_, i0, len); }   // int16 input
+__global__ __launch_bounds__(256) void k_pl_edge_stage_sc16(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, IN_W_SC16>(P_, i0, len); }   // int16 input
+template <bool PS = false>
+__global__ __launch_bounds__(256) void k_pl_edge_stage_iq8(const DecimParams P_, int64_t i0, uint32_t len) { pl_edge_stage_body<PS, IN_W_IQ8>(P_, i0, len); }   // sc8 / cu8 input
 // Everything of a call but the streaming kernel's launch.  Names the main and the edge range in the parameter block, stages the edge scratch
 // (on the handle's pre-stream when it has one: the kernel reads the caller's buffer and the carried history, nothing the call before
 // produces on the launch stream) and runs the per-output kernel `gen`, `per_wg` outputs per workgroup, on the two ranges left to it.
@@ -769,7 +791,7 @@ typedef void (*DecimGenKernel)(const DecimParams, uint64_t, uint32_t);
 static CallInput call_input(const DecimParams& p)
 {
     return CallInput{(uint64_t)reinterpret_cast<uintptr_t>(p.in), (uint64_t)p.in_stride, p.n, p.in_fmt == IN_SC16, p.rot_enable != 0,
-                     (uint64_t)reinterpret_cast<uintptr_t>(p.pl_edge), p.pl_edge_stride};
+                     (uint64_t)reinterpret_cast<uintptr_t>(p.pl_edge), p.pl_edge_stride, p.in_fmt >= IN_SC8};
 }
 static bool launch_split(DecimParams& q, const DecimSplit& sp, DecimGenKernel gen, uint32_t per_wg, int batch, hipStream_t s)
 {
@@ -778,7 +800,8 @@ static bool launch_split(DecimParams& q, const DecimSplit& sp, DecimGenKernel ge
     if (!sp.edge.empty()) {
         const hipStream_t st = q.pre_stream ? q.pre_stream : s;
         const dim3 grid((sp.edge_len + 255) / 256, batch);
-        if (q.in_fmt == IN_SC16) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_sc16<true> : k_pl_edge_stage_sc16<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
+        if (q.in_fmt >= IN_SC8) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_iq8<true> : k_pl_edge_stage_iq8<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
+        else if (q.in_fmt == IN_SC16) hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage_sc16<true> : k_pl_edge_stage_sc16<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
         else hipLaunchKernelGGL(q.rot_acc_s ? k_pl_edge_stage<true> : k_pl_edge_stage<false>, grid, dim3(256), 0, st, q, sp.edge_i0, sp.edge_len);
         if (q.pre_stream) { (void)hipEventRecord(q.pre_event, q.pre_stream); (void)hipStreamWaitEvent(s, q.pre_event, 0); }
         q.pl_edge_ms = sp.edge.lo; q.pl_edge_me = sp.edge.hi;
@@ -884,9 +907,12 @@ int launch_decim_pl(const DecimParams& p, int batch, hipStream_t s)
     q.pl_S = sg.S; q.pl_nseg = sg.nseg;
     if (!launch_split(q, sp, p.rot_acc_s ? k_decim_pl_gen<true> : k_decim_pl_gen<false>, 4, batch, s)) return 0;
     const dim3 grid((sg.units + 3) / 4);
-    if (p.in_fmt == IN_SC16) {
-        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, true>), grid, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, true>), grid, dim3(256), 0, s, q);
+    if (p.in_fmt >= IN_SC8) {
+        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, IN_W_IQ8>), grid, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, IN_W_IQ8>), grid, dim3(256), 0, s, q);
+    } else if (p.in_fmt == IN_SC16) {
+        if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true, IN_W_SC16>), grid, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((k_decim_plx<2, 1, 42, false, IN_W_SC16>), grid, dim3(256), 0, s, q);
     } else if (p.rot_acc_s) hipLaunchKernelGGL((k_decim_plx<2, 1, 42, true>), grid, dim3(256), 0, s, q);
     else hipLaunchKernelGGL((k_decim_plx<2, 1, 42>), grid, dim3(256), 0, s, q);
     return 0;
@@ -926,7 +952,7 @@ std::vector<float> decim_pm_layout(const std::vector<float>& h, int D)
 #ifndef QRL_PM_RP_SMALL
 #define QRL_PM_RP_SMALL 8   // ring pieces per wave for D <= 28 (a group is <= 3.5 KiB there)
 #endif
-template <int J, int NS, int RP, bool K1, bool PS, bool SC = false>
+template <int J, int NS, int RP, bool K1, bool PS, int SC = IN_W_CF32>
 static int pm_launch_main_k(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
     // RP = ring pieces per wave (a power of two: one 16-block group -- 128 D bytes -- + what is in flight).
@@ -962,8 +988,14 @@ template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
 static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
     // int16 input: the SC instantiation of the same geometry (front ends: three lag tiles; the first stages of a 1 Msps handle: one)
+    // 8-bit pairs: the 2-byte instantiation, which exists for the three-tile front-end geometries only (a 1 Msps handle refuses the format)
+    if (q.in_fmt >= IN_SC8) {
+        if constexpr (J > 16)
+            return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, IN_W_IQ8>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, IN_W_IQ8>(q, M, batch, edge_unit, s);
+        else return -1;
+    }
     if (q.in_fmt == IN_SC16)
-        return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, true>(q, M, batch, edge_unit, s);
+        return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, IN_W_SC16>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, IN_W_SC16>(q, M, batch, edge_unit, s);
     return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false>(q, M, batch, edge_unit, s);
 }
 int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
@@ -975,7 +1007,7 @@ int launch_decim_pm(const DecimParams& p, int batch, hipStream_t s)
     q.pl_J = J; q.pl_E = 1; q.pl_R = 1;
     q.pl_hraw = p.pl_taps + (size_t)pm_tiles(J) * NS * 64;
     // the matrix kernel streams rows of the caller's buffer as 16-byte LDS-DMA pieces (decim_pm_streamable: what qrl_demod_process and
-    // qrl_demod_process_sc16 demand, the latter with n % 4 == 0; the edge scratch is built that way).  Anything else: one thread per output.
+    // qrl_demod_process_sc16 demand, the latter with n % 4 == 0, the 8-bit calls with n % 8 == 0; the edge scratch is built that way).  Anything else: one thread per output.
     const DecimSplit sp = decim_pm_plan_call(p.n0, p.m0, p.m_count, nt, D, p.pl_edge_cap, call_input(p));
     if (!launch_split(q, sp, p.rot_acc_s ? k_decim_pm_gen<true> : k_decim_pm_gen<false>, 256, batch, s)) return 0;
     const bool edge_unit = !sp.edge.empty();

@@ -223,7 +223,7 @@ void launch_decim(const DecimParams& p, int batch, int variant, hipStream_t s)
 }
 
 // ---- history keeper: hist_new[k] = rotated sample at absolute index n0 + n - H + k ----
-template <bool PS, bool SC>
+template <bool PS, int SC>
 __device__ __forceinline__ void hist_body(const HistParams& P_)
 {
     ROT_VIEW(HistParams, PS, P, P_, blockIdx.y);
@@ -245,13 +245,17 @@ __device__ __forceinline__ void hist_body(const HistParams& P_)
     }
     P.hist_new[(size_t)b * P.hist_len + k] = x;
 }
-template <bool PS> __global__ __launch_bounds__(256) void k_hist(const HistParams P_) { hist_body<PS, false>(P_); }
-template <bool PS> __global__ __launch_bounds__(256) void k_hist_sc16(const HistParams P_) { hist_body<PS, true>(P_); }   // int16 input
+template <bool PS> __global__ __launch_bounds__(256) void k_hist(const HistParams P_) { hist_body<PS, IN_W_CF32>(P_); }
+template <bool PS> __global__ __launch_bounds__(256) void k_hist_sc16(const HistParams P_) { hist_body<PS, IN_W_SC16>(P_); }   // int16 input
+template <bool PS> __global__ __launch_bounds__(256) void k_hist_iq8(const HistParams P_) { hist_body<PS, IN_W_IQ8>(P_); }   // sc8 / cu8 input
 void launch_hist_save(const HistParams& p, int batch, hipStream_t s)
 {
     if (p.hist_len == 0) return;
     dim3 grid((p.hist_len + 255) / 256, batch), block(256);
-    if (p.in_fmt == IN_SC16) {
+    if (p.in_fmt >= IN_SC8) {
+        if (p.rot_acc_s) hipLaunchKernelGGL(k_hist_iq8<true>, grid, block, 0, s, p);
+        else hipLaunchKernelGGL(k_hist_iq8<false>, grid, block, 0, s, p);
+    } else if (p.in_fmt == IN_SC16) {
         if (p.rot_acc_s) hipLaunchKernelGGL(k_hist_sc16<true>, grid, block, 0, s, p);
         else hipLaunchKernelGGL(k_hist_sc16<false>, grid, block, 0, s, p);
     } else if (p.rot_acc_s) hipLaunchKernelGGL(k_hist<true>, grid, block, 0, s, p);

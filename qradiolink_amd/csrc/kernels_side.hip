@@ -116,6 +116,18 @@ __global__ __launch_bounds__(256) void k_fft_fill(const float2* __restrict__ in,
     const float w = win[counter + j];
     buf[(size_t)b * N + counter + j] = make_float2(x.x * w, x.y * w);
 }
+// 8-bit pairs (qrl_fft_process_sc8 / _cu8): x = ((float)(byte ^ mask) - in_bias) * in_scale (iq8_to_f2), then window.  A kernel of its own, so
+// that the two above keep their arguments and their code
+__global__ __launch_bounds__(256) void k_fft_fill_iq8(const uint16_t* __restrict__ in, size_t in_stride, uint32_t i0, uint32_t count, const float* __restrict__ win,
+                                                      uint32_t counter, float2* __restrict__ buf, uint32_t N, float in_scale, float in_bias, uint32_t mask)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= count) return;
+    const int b = blockIdx.y;
+    const float2 x = iq8_to_f2(in[(size_t)b * in_stride + i0 + j], mask, in_bias, in_scale);
+    const float w = win[counter + j];
+    buf[(size_t)b * N + counter + j] = make_float2(x.x * w, x.y * w);
+}
 // volk_32fc_s32f_power_spectrum_32f(out, X, N, N): 10 log10(|X / N|^2) as (10 / log2(10)) * log2(re^2 + im^2)
 __global__ __launch_bounds__(256) void k_fft_power(const float2* __restrict__ X, float* __restrict__ out, uint32_t N, float inv_norm)
 {
@@ -137,9 +149,14 @@ __global__ __launch_bounds__(256) void k_fft_shift(const float* __restrict__ pts
     out[(size_t)b * out_stride + j] = pts[(size_t)b * N + (j < h ? j + (N - h) : j - h)];
 }
 void launch_fft_fill(const float2* in, size_t in_stride, uint32_t i0, uint32_t count, const float* win, uint32_t counter, float2* buf, uint32_t N, int batch, hipStream_t s,
-                     int in_fmt, float in_scale)
+                     int in_fmt, float in_scale, float in_bias)
 {
     if (!count) return;
+    if (in_fmt >= IN_SC8) {
+        hipLaunchKernelGGL(k_fft_fill_iq8, dim3((count + 255) / 256, batch), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(in), in_stride, i0, count, win, counter, buf,
+                           N, in_scale, in_bias, in_fmt == IN_SC8 ? 0x8080u : 0u);
+        return;
+    }
     const auto kern = in_fmt == IN_SC16 ? k_fft_fill<true> : k_fft_fill<false>;
     hipLaunchKernelGGL(kern, dim3((count + 255) / 256, batch), dim3(256), 0, s, in, in_stride, i0, count, win, counter, buf, N, in_scale);
 }

@@ -33,6 +33,8 @@ struct qrl_fft {
     DevBuf<float> win, points; DevBuf<float2> buf, spec;
     unsigned counter = 0; int push = 0; bool data_ready = false, enabled = false;
     float sc16_scale = 1.0f / 32768.0f;   // qrl_fft_process_sc16: x = (float)v * sc16_scale
+    float sc8_scale = 1.0f / 128.0f;      // qrl_fft_process_sc8: x = (float)v * sc8_scale
+    float cu8_scale = 1.0f / 128.0f, cu8_bias = 127.5f;   // qrl_fft_process_cu8: x = ((float)u - cu8_bias) * cu8_scale
     void drop_plan() { if (have_plan) { (void)hipfftDestroy(plan); have_plan = false; } }
     ~qrl_fft() { drop_plan(); }
 };
@@ -181,6 +183,9 @@ static int fft_process_impl(qrl_fft* h, const void* iq, size_t stride, size_t n,
     HIPCHK(hipSetDevice(h->ctx->device));
     const float2* in = static_cast<const float2*>(iq);
     const unsigned N = h->fftsize;
+    // (sc8 runs the unsigned path on v ^ 0x80 with the bias 128: (float)v exactly)
+    const float scale = fmt == IN_SC8 ? h->sc8_scale : fmt == IN_CU8 ? h->cu8_scale : h->sc16_scale;
+    const float bias = fmt == IN_SC8 ? 128.0f : fmt == IN_CU8 ? h->cu8_bias : 0.0f;
     size_t i = 0;
     while (i < n) {
         if (h->counter >= N) {
@@ -191,7 +196,7 @@ static int fft_process_impl(qrl_fft* h, const void* iq, size_t stride, size_t n,
             h->push++;
         }
         const size_t chunk = std::min(n - i, (size_t)(N - h->counter));
-        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win.p, h->counter, h->buf.p, N, h->batch, h->stream, fmt, h->sc16_scale);
+        launch_fft_fill(in, stride, (uint32_t)i, (uint32_t)chunk, h->win.p, h->counter, h->buf.p, N, h->batch, h->stream, fmt, scale, bias);
         h->counter += (unsigned)chunk;
         i += chunk;
     }
@@ -214,6 +219,32 @@ int qrl_fft_set_sc16_scale(qrl_fft* h, float scale)
     if (!h) return QRL_ERR_ARG;
     if (!sc16_scale_ok("qrl_fft_set_sc16_scale", scale)) return QRL_ERR_ARG;
     h->sc16_scale = scale;   // a kernel parameter of the calls from now on; calls already queued keep theirs
+    return QRL_OK;
+}
+int qrl_fft_process_sc8(qrl_fft* h, const int8_t* iq, size_t stride, size_t n)
+{
+    if (!h || !iq) return QRL_ERR_ARG;
+    if (!iq8_rows_ok("qrl_fft_process_sc8", iq, stride)) return QRL_ERR_ARG;
+    return fft_process_impl(h, iq, stride, n, IN_SC8);
+}
+int qrl_fft_process_cu8(qrl_fft* h, const uint8_t* iq, size_t stride, size_t n)
+{
+    if (!h || !iq) return QRL_ERR_ARG;
+    if (!iq8_rows_ok("qrl_fft_process_cu8", iq, stride)) return QRL_ERR_ARG;
+    return fft_process_impl(h, iq, stride, n, IN_CU8);
+}
+int qrl_fft_set_sc8_scale(qrl_fft* h, float scale)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (!sc16_scale_ok("qrl_fft_set_sc8_scale", scale)) return QRL_ERR_ARG;
+    h->sc8_scale = scale;
+    return QRL_OK;
+}
+int qrl_fft_set_cu8_scale(qrl_fft* h, float scale, float bias)
+{
+    if (!h) return QRL_ERR_ARG;
+    if (!sc16_scale_ok("qrl_fft_set_cu8_scale", scale) || !iq8_bias_ok("qrl_fft_set_cu8_scale", bias)) return QRL_ERR_ARG;
+    h->cu8_scale = scale; h->cu8_bias = bias;
     return QRL_OK;
 }
 // rx_fft_c::get_fft_data (rx_fft.cpp:113-131): fft_points[b * out_stride + i] (device), *fft_size = 0 when nothing is ready

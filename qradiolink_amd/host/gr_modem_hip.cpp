@@ -115,6 +115,8 @@ try {
     chk(qrl_demod_create(d_rt.ctx(), &c, &h), "qrl_demod_create");
     d_h.reset(h);
     chk(qrl_demod_set_sc16_scale(h, d_sc16_scale), "qrl_demod_set_sc16_scale");
+    chk(qrl_demod_set_sc8_scale(h, d_sc8_scale), "qrl_demod_set_sc8_scale");
+    chk(qrl_demod_set_cu8_scale(h, d_cu8_scale, d_cu8_bias), "qrl_demod_set_cu8_scale");
     chk(qrl_demod_set_option(h, QRL_OPT_SC16_BASEBAND, d_sc16_baseband ? 1 : 0), "qrl_demod_set_option");
     if (d_per_stream) chk(qrl_demod_set_carrier_offsets(h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
     chk(qrl_demod_out_caps(h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
@@ -133,6 +135,8 @@ try {
     d_fft.reset(fft);
     chk(qrl_fft_set_enabled(fft, d_fft_on ? 1 : 0), "qrl_fft_set_enabled");
     chk(qrl_fft_set_sc16_scale(fft, d_sc16_scale), "qrl_fft_set_sc16_scale");
+    chk(qrl_fft_set_sc8_scale(fft, d_sc8_scale), "qrl_fft_set_sc8_scale");
+    chk(qrl_fft_set_cu8_scale(fft, d_cu8_scale, d_cu8_bias), "qrl_fft_set_cu8_scale");
     d_level.assign(N, 0.0f);
     // L1 frame synchronisers on the copy stream, behind the demodulator (digital modes with gr_modem framing: not DMR, not analogue)
     const bool fs_on = d_want_fs && !d_acap && d_mode != QRL_MODEM_DMR;
@@ -297,11 +301,31 @@ void gr_demod_base_hip::set_samp_rate(int device_samp_rate)   // gr_demod_base.c
     d_rate = device_samp_rate;
     if (d_mode >= 0) open();
 }
-void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, false); }
+void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_CF32); }
 // 16-bit integer I/Q as the SDR drivers deliver it (interleaved int16 I, Q): 4 bytes per sample are staged in the pinned buffer and uploaded,
 // and the device-rate front end -- at 1 Msps, under set_sc16_baseband, the mode's first stage -- converts (qrl_demod_process_sc16:
 // x = (float)v * scale).  Replaces the driver's sc16 -> fc32 conversion.
-void gr_demod_base_hip::work(const int16_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, true); }
+void gr_demod_base_hip::work(const int16_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_SC16); }
+// 8-bit I/Q as an RTL-SDR (unsigned) or a HackRF (signed) delivers it: 2 bytes per sample staged and uploaded, the front end converts
+// (qrl_demod_process_sc8 / _cu8).  Device rates with a front end only.
+void gr_demod_base_hip::work(const int8_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_SC8); }
+void gr_demod_base_hip::work(const uint8_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_CU8); }
+void gr_demod_base_hip::set_sc8_scale(float scale)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_demod_base_hip::set_sc8_scale: finite, non-zero");
+    d_sc8_scale = scale;
+    if (d_h.get()) chk(qrl_demod_set_sc8_scale(d_h.get(), scale), "qrl_demod_set_sc8_scale");
+    if (d_fft.get()) chk(qrl_fft_set_sc8_scale(d_fft.get(), scale), "qrl_fft_set_sc8_scale");   // the spectrum tap reads the same 8-bit slot
+}
+void gr_demod_base_hip::set_cu8_scale(float scale, float bias)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (!std::isfinite(scale) || scale == 0.0f || !std::isfinite(bias)) throw std::invalid_argument("gr_demod_base_hip::set_cu8_scale: scale finite and non-zero, bias finite");
+    d_cu8_scale = scale; d_cu8_bias = bias;
+    if (d_h.get()) chk(qrl_demod_set_cu8_scale(d_h.get(), scale, bias), "qrl_demod_set_cu8_scale");
+    if (d_fft.get()) chk(qrl_fft_set_cu8_scale(d_fft.get(), scale, bias), "qrl_fft_set_cu8_scale");
+}
 void gr_demod_base_hip::set_sc16_scale(float scale)
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
@@ -316,8 +340,9 @@ void gr_demod_base_hip::set_sc16_baseband(bool on)
     d_sc16_baseband = on;
     if (d_h.get()) chk(qrl_demod_set_option(d_h.get(), QRL_OPT_SC16_BASEBAND, on ? 1 : 0), "qrl_demod_set_option");
 }
-void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
+void gr_demod_base_hip::work_any(const void* const* iq, size_t n, int fmt)
 {
+    const bool sc16 = fmt == FMT_SC16, iq8 = fmt == FMT_SC8 || fmt == FMT_CU8;
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);
     if (!d_h) throw std::runtime_error("gr_demod_base_hip::work before set_mode");
     if (n == 0) return;
@@ -327,10 +352,21 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         if (d_rate < 2000000 && !d_sc16_baseband) throw std::invalid_argument("gr_demod_base_hip::work(int16): needs the device-rate front end (device_samp_rate >= 2000000)");
         if (d_chunk & 3) throw std::invalid_argument("gr_demod_base_hip::work(int16): max_chunk (the row pitch) must be a multiple of 4 samples");
     }
+    if (iq8) {   // as for int16: what the C ABI would refuse, before anything is staged or queued
+        if (d_rate < 2000000) throw std::invalid_argument("gr_demod_base_hip::work(8-bit): needs the device-rate front end (device_samp_rate >= 2000000)");
+        if (d_chunk & 7) throw std::invalid_argument("gr_demod_base_hip::work(8-bit): max_chunk (the row pitch) must be a multiple of 8 samples");
+    }
     if (!d_demod_on && !d_fft_on) return;                        // _demod_valve closed and nobody else listens: the samples are dropped
     const int cur = (int)(d_calls & 1);
     slot& sl = *d_slot[cur];
-    const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the pitch stays d_chunk samples
+    const size_t sb = iq8 ? 2 : sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the pitch stays d_chunk samples
+    // the spectrum tap on the uploaded slot, in the slot's format
+    auto fft_tap = [&]() {
+        if (fmt == FMT_SC8) chk(qrl_fft_process_sc8(d_fft.get(), reinterpret_cast<const int8_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc8");
+        else if (fmt == FMT_CU8) chk(qrl_fft_process_cu8(d_fft.get(), reinterpret_cast<const uint8_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_cu8");
+        else if (sc16) chk(qrl_fft_process_sc16(d_fft.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc16");
+        else chk(qrl_fft_process(d_fft.get(), sl.d_iq.get(), d_chunk, n), "qrl_fft_process");
+    };
     // slot `cur` was last used by call k - 2, which work(k - 1) has harvested: its buffers are free
     for (int s = 0; s < d_n; ++s) std::memcpy(reinterpret_cast<char*>(sl.h_iq.get()) + (size_t)s * d_chunk * sb, iq[s], n * sb);
     hipStream_t hs = static_cast<hipStream_t>(qrl_demod_stream(d_h.get())), cs = d_copy.get();
@@ -338,8 +374,7 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         // everything of this call on the spectrum block's own stream (d_copy): the upload, the FFT fill behind it, and the host waits for THAT
         // stream before the slot is reused (the upload used to go on the demodulator's stream, which nothing ordered the FFT behind)
         hchk(hipMemcpyAsync(sl.d_iq.get(), sl.h_iq.get(), (size_t)d_n * d_chunk * sb, hipMemcpyHostToDevice, cs), "H2D");
-        if (sc16) chk(qrl_fft_process_sc16(d_fft.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc16");
-        else chk(qrl_fft_process(d_fft.get(), sl.d_iq.get(), d_chunk, n), "qrl_fft_process");
+        fft_tap();
         hchk(hipStreamSynchronize(cs), "hipStreamSynchronize");  // (d_calls does not advance: the next call takes the same slot; no harvest belongs to this call)
         return;
     }
@@ -351,7 +386,9 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
     o.filtered = sl.d_filt.get(); o.filtered_cap = d_fcap; o.constellation = reinterpret_cast<float*>(sl.konst.dev()); o.constellation_cap = d_ccap;
     o.bits_a = sl.a.dev(); o.bits_b = sl.b.dev(); o.bits_cap = d_bcap; o.counts = sl.cnt.dev();
     o.audio = sl.audio.dev(); o.audio_cap = d_acap;
-    if (sc16) chk(qrl_demod_process_sc16(d_h.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n, &o), "qrl_demod_process_sc16");
+    if (fmt == FMT_SC8) chk(qrl_demod_process_sc8(d_h.get(), reinterpret_cast<const int8_t*>(sl.d_iq.get()), d_chunk, n, &o), "qrl_demod_process_sc8");
+    else if (fmt == FMT_CU8) chk(qrl_demod_process_cu8(d_h.get(), reinterpret_cast<const uint8_t*>(sl.d_iq.get()), d_chunk, n, &o), "qrl_demod_process_cu8");
+    else if (sc16) chk(qrl_demod_process_sc16(d_h.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n, &o), "qrl_demod_process_sc16");
     else chk(qrl_demod_process(d_h.get(), sl.d_iq.get(), d_chunk, n, &o), "qrl_demod_process");
     chk(qrl_demod_stream_wait(d_h.get(), cs), "qrl_demod_stream_wait");
     const size_t N = (size_t)d_n;
@@ -416,10 +453,7 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, bool sc16)
         chk(qrl_rssi_process(d_rssi.get(), sl.d_filt.get(), d_fcap, d_fcap, sl.cnt.dev(), 4, nullptr, 0, sl.rssi.dev(), nullptr), "qrl_rssi_process");
         sl.rssi.download(cs);
     }
-    if (d_fft_on) {
-        if (sc16) chk(qrl_fft_process_sc16(d_fft.get(), reinterpret_cast<const int16_t*>(sl.d_iq.get()), d_chunk, n), "qrl_fft_process_sc16");
-        else chk(qrl_fft_process(d_fft.get(), sl.d_iq.get(), d_chunk, n), "qrl_fft_process");
-    }
+    if (d_fft_on) fft_tap();
     hchk(hipEventRecord(sl.done.get(), cs), "hipEventRecord");
     const int prev = d_inflight;
     d_inflight = cur;

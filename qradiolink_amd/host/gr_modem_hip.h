@@ -59,6 +59,14 @@ public:
     // demodulator valve open or closed
     void work(const int16_t* const* iq, size_t n);
     void set_sc16_scale(float scale);
+    // the same for 8-bit I/Q, 2 bytes per sample staged and uploaded: signed (HackRF: x = (float)v * scale, scale 1 / 128 unless set_sc8_scale) and
+    // unsigned (RTL-SDR: x = ((float)u - bias) * scale, 1 / 128 and 127.5 unless set_cu8_scale).  Handles at device_samp_rate >= 2 Msps only
+    // (std::invalid_argument at 1 Msps, also under set_sc16_baseband); max_chunk a multiple of 8.  The spectrum tap reads the same uploaded
+    // 8-bit slot (qrl_fft_process_sc8 / _cu8).  The setters are kept across set_mode / set_samp_rate
+    void work(const int8_t* const* iq, size_t n);
+    void work(const uint8_t* const* iq, size_t n);
+    void set_sc8_scale(float scale);
+    void set_cu8_scale(float scale, float bias = 127.5f);
     // a 1 Msps receiver takes work(int16) too: the per-mode first stage reads the raw pairs (QRL_OPT_SC16_BASEBAND).  Default off: work(int16)
     // at 1 Msps throws std::invalid_argument.  Kept across set_mode / set_samp_rate; no effect at device rates with a front end
     void set_sc16_baseband(bool on);
@@ -167,8 +175,10 @@ private:
     std::vector<size_t> d_fbits[2], d_fact[2];   // per branch and stream: bits consumed / bits collected under a sync since the last takeFrames
     dev_buf<float> d_fftout; std::vector<float> d_level, d_fftlast;
     std::unique_ptr<slot> d_slot[2];
-    void work_any(const void* const* iq, size_t n, bool sc16);   // both work() overloads
+    enum { FMT_CF32 = 0, FMT_SC16 = 1, FMT_SC8 = 2, FMT_CU8 = 3 };
+    void work_any(const void* const* iq, size_t n, int fmt);     // every work() overload
     float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
+    float d_sc8_scale = 1.0f / 128.0f, d_cu8_scale = 1.0f / 128.0f, d_cu8_bias = 127.5f;   // re-applied by open()
     bool d_sc16_baseband = false;                                // set_sc16_baseband; re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0, d_acap = 0;
@@ -334,6 +344,9 @@ public:
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
     // the receiver at 1 Msps takes work(int16) (gr_demod_base_hip::set_sc16_baseband; default off)
     void set_sc16_baseband(bool on) { if (_gr_demod_base) _gr_demod_base->set_sc16_baseband(on); }
+    // the conversion of the receiver's 8-bit work() overloads (gr_demod_base_hip::set_sc8_scale / set_cu8_scale)
+    void set_sc8_scale(float scale) { if (_gr_demod_base) _gr_demod_base->set_sc8_scale(scale); }
+    void set_cu8_scale(float scale, float bias = 127.5f) { if (_gr_demod_base) _gr_demod_base->set_cu8_scale(scale, bias); }
     // the DMR receive call layer on the device, off by default, behind set_dmr_l2: dmrCallEvents(stream, records128) fires beside dmrFramesDecoded
     void set_dmr_call(bool on, int colour_code = 1, bool promiscuous = false) { if (_gr_demod_base) _gr_demod_base->set_dmr_call(on, colour_code, promiscuous); }
     // the reference's getDMRData(bool dmo) choice: on, dmrFrames / dmrFramesDecoded / dmrCallEvents deliver the bursts of the repeater-mode sink
