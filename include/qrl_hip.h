@@ -138,8 +138,11 @@ int qrl_demod_set_dmo_output(qrl_demod* d, uint8_t* frames, size_t cap_frames, u
  * lets a handle WITHOUT a device-rate front end (device_samp_rate 1000000) take int16 IQ through qrl_demod_process_sc16 /
  * qrl_demod_process_sc16_host; value 0 refuses such calls with QRL_ERR_ARG, as before the option existed.  It allocates nothing and may be
  * set at any stream position (the format belongs to the call, the carried history is rotated cf32); on a handle with a front end it is
- * accepted and does nothing. */
-enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups; for 2FSK-1k / -2k also the FLL and the FIR stages as the two kernels k_fll + k_2fsk_ff instead of k_2fsk_tail (same results) */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5, QRL_OPT_SC16_BASEBAND = 6 };
+ * accepted and does nothing.  QRL_OPT_IQ8_BASEBAND (default 0): the same for 8-bit IQ -- value 1 lets a handle without a device-rate front
+ * end take qrl_demod_process_sc8 / _cu8 and their _host forms (16-byte aligned base, pitch a multiple of 8 samples, as everywhere); value 0
+ * refuses them with QRL_ERR_ARG.  The two options are independent: QRL_OPT_SC16_BASEBAND alone keeps refusing 8-bit input, this one alone
+ * does not admit int16.  Nothing is allocated, any stream position, no effect on a handle with a front end. */
+enum { QRL_OPT_OVERLAP = 1, QRL_OPT_UNFUSED_DEC2 = 2, QRL_OPT_FLL_SLIM = 3 /* tuning: single-wave FLL workgroups; for 2FSK-1k / -2k also the FLL and the FIR stages as the two kernels k_fll + k_2fsk_ff instead of k_2fsk_tail (same results) */, QRL_OPT_GROUPED = 4, QRL_OPT_INPUT_RESIDENT = 5, QRL_OPT_SC16_BASEBAND = 6, QRL_OPT_IQ8_BASEBAND = 7 };
 int qrl_demod_set_option(qrl_demod* d, int option, int value);
 int qrl_demod_out_caps(const qrl_demod* d, size_t n, size_t* filtered_cap, size_t* constellation_cap, size_t* bits_cap);
 /* analogue voice receivers (QRL_MODEM_NBFM2500 / NBFM5000 / AM5000 / WBFM / USB2500 / LSB2500; replace make_gr_demod_nbfm / _am /
@@ -219,8 +222,11 @@ int qrl_demod_set_sc16_scale(qrl_demod* d, float scale);
  * iq must be 16-byte aligned and stride a multiple of 8 samples, else QRL_ERR_ARG before anything is launched (qrl_last_error names the rule);
  * any n <= max_chunk (the LDS-DMA kernel streams calls with n % 8 == 0, other n take the per-output kernels).
  * Handles with device_samp_rate >= 2000000 take 8-bit calls as they are, every modem type and every rate qrl_demod_create accepts.  A 1 Msps
- * handle has no front end and returns QRL_ERR_ARG, also under QRL_OPT_SC16_BASEBAND (which widened the modes' first stages for int16 only);
- * it changes nothing and stays usable. */
+ * handle (an RTL-SDR at the internal rate) takes them once qrl_demod_set_option(d, QRL_OPT_IQ8_BASEBAND, 1) has been called: the per-mode first
+ * stage then reads the raw pairs under the same rule -- the 1:50 matrix-pipe stage streams them with LDS-DMA, 2 bytes per sample (calls with
+ * n % 8 == 0); k_dec2_fir, k_resamp, the other decimators, the analogue and DSSS receivers' first stage and the scope tap convert at the
+ * load, exact but untuned.  Without that option (the default) a 1 Msps handle has nothing that converts and returns QRL_ERR_ARG, also under
+ * QRL_OPT_SC16_BASEBAND (which admits int16 only); it changes nothing and stays usable. */
 int qrl_demod_process_sc8(qrl_demod* d, const int8_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
 int qrl_demod_process_cu8(qrl_demod* d, const uint8_t* iq, size_t stride, size_t n, const qrl_demod_out* out);
 int qrl_demod_set_sc8_scale(qrl_demod* d, float scale);

@@ -25,7 +25,7 @@ MODEM_NBFM2500, MODEM_NBFM5000, MODEM_WBFM, MODEM_AM5000 = 8, 9, 10, 14
 MODEM_USB2500, MODEM_LSB2500, MODEM_CW600USB = 11, 12, 13
 MODEM_M17 = 40
 MODEM_DMR = 41
-OPT_OVERLAP, OPT_UNFUSED_DEC2, OPT_FLL_SLIM, OPT_GROUPED, OPT_INPUT_RESIDENT, OPT_SC16_BASEBAND = 1, 2, 3, 4, 5, 6
+OPT_OVERLAP, OPT_UNFUSED_DEC2, OPT_FLL_SLIM, OPT_GROUPED, OPT_INPUT_RESIDENT, OPT_SC16_BASEBAND, OPT_IQ8_BASEBAND = 1, 2, 3, 4, 5, 6, 7
 CHAN_OPT_LEGACY_PFB, CHAN_OPT_LEGACY_TAIL, CHAN_OPT_SERIAL_TAIL = 1, 2, 3
 WIN_HAMMING, WIN_HANN, WIN_BLACKMAN, WIN_RECTANGULAR, WIN_BLACKMAN_HARRIS = 0, 1, 2, 3, 5
 
@@ -511,20 +511,23 @@ class Demod:
 
     def process_sc8_async(self, iq):
         """Queue one pass over signed 8-bit IQ: iq is an int8 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_sc8; what a HackRF
-        delivers).  Handles with device_samp_rate >= 2 Msps only; the row pitch must be a multiple of 8 samples and the base 16-byte aligned."""
+        delivers).  Handles with device_samp_rate >= 2 Msps take it as they are; a 1 Msps handle takes it after enable_iq8_baseband() (its first
+        stage then reads the raw pairs) and refuses it otherwise.  The row pitch must be a multiple of 8 samples and the base 16-byte aligned."""
         self._process_iq8_async(iq, self.torch.int8, "qrl_demod_process_sc8")
 
     def process_sc8(self, iq):
+        """process_sc8_async, then sync: the ports of this call.  A 1 Msps handle takes it after enable_iq8_baseband()."""
         self.process_sc8_async(iq)
         self.sync()
         return self._ports()
 
     def process_cu8_async(self, iq):
         """Queue one pass over unsigned 8-bit IQ: iq is a uint8 cuda tensor [batch, 2 * n], interleaved I, Q (qrl_demod_process_cu8; what an
-        RTL-SDR dongle delivers).  The same rules as process_sc8_async."""
+        RTL-SDR dongle delivers).  The same rules as process_sc8_async: a 1 Msps handle takes it after enable_iq8_baseband()."""
         self._process_iq8_async(iq, self.torch.uint8, "qrl_demod_process_cu8")
 
     def process_cu8(self, iq):
+        """process_cu8_async, then sync: the ports of this call.  A 1 Msps handle takes it after enable_iq8_baseband()."""
         self.process_cu8_async(iq)
         self.sync()
         return self._ports()
@@ -536,6 +539,12 @@ class Demod:
     def set_cu8_scale(self, scale, bias=127.5):
         """x = (float(u) - bias) * scale for the cu8 calls from the next one on (defaults 1 / 128, 127.5; qrl_demod_set_cu8_scale)"""
         _check(self.lib.qrl_demod_set_cu8_scale(self.h, C.c_float(scale), C.c_float(bias)), "qrl_demod_set_cu8_scale")
+
+    def enable_iq8_baseband(self, on=True):
+        """A handle without a device-rate front end (1 Msps) takes 8-bit IQ (process_sc8 / process_cu8) from the next call on
+        (QRL_OPT_IQ8_BASEBAND); off again: such calls are refused as by default.  Independent of enable_sc16_baseband.  Changes no result,
+        allocates nothing, any stream position; no effect on a handle with a front end."""
+        _check(self.lib.qrl_demod_set_option(self.h, OPT_IQ8_BASEBAND, 1 if on else 0), "qrl_demod_set_option")
 
     def enable_sc16_baseband(self, on=True):
         """A handle without a device-rate front end (1 Msps) takes int16 IQ from the next call on (QRL_OPT_SC16_BASEBAND); off again: such

@@ -223,7 +223,7 @@ struct qrl_demod {
     int init_state();
     int build();
     // fmt: IN_CF32 (iq = interleaved floats) | IN_SC16 (iq = interleaved int16 pairs, stride in samples of 4 bytes; handles with a front end, or sc16_baseband)
-    // | IN_SC8 | IN_CU8 (8-bit pairs, stride in samples of 2 bytes; handles with a front end only).
+    // | IN_SC8 | IN_CU8 (8-bit pairs, stride in samples of 2 bytes; handles with a front end, or iq8_baseband).
     // The format belongs to the CALL: history, edge scratch and rings are rotated cf32 whatever the calls before were fed.
     int process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt = IN_CF32);
     float sc16_scale = 1.0f / 32768.0f;   // qrl_demod_set_sc16_scale
@@ -234,6 +234,7 @@ struct qrl_demod {
         return fmt == IN_SC8 ? InFormat{fmt, sc8_scale, 128.0f} : fmt == IN_CU8 ? InFormat{fmt, cu8_scale, cu8_bias} : InFormat{fmt, sc16_scale, 0.0f};
     }
     bool sc16_baseband = false;           // QRL_OPT_SC16_BASEBAND: a handle without a front end takes int16 IQ (its first stage reads the raw pairs)
+    bool iq8_baseband = false;            // QRL_OPT_IQ8_BASEBAND: the same for sc8 / cu8 (independent of sc16_baseband)
     int init_dmo_state() { DmoState x; std::memset(&x, 0, sizeof x); x.endPtr = 9999; return dmo_st.fill(cfg.batch, x); }
     CallCounts call_counts(size_t n) const {
         const size_t c1 = fe.used ? n / fe_decim + 2 : n, c2 = c1 * interp / decim + 2;
@@ -243,10 +244,10 @@ struct qrl_demod {
     PortC filtered_port(const qrl_demod_out* out) const { return cfg.enable_side_outputs && out ? PortC{reinterpret_cast<float2*>(out->filtered), out->filtered_cap} : PortC{nullptr, 0}; }
     PortC constellation_port(const qrl_demod_out* out) const { return cfg.enable_side_outputs && out ? PortC{reinterpret_cast<float2*>(out->constellation), out->constellation_cap} : PortC{nullptr, 0}; }
     // input of a stage that reads items src0 .. src1 of the 1 Msps signal: ring s1 behind the front end, else the caller's IQ (rotated on the fly; hist_old: the call before)
-    // fmt: what `in` points at (IN_SC16 without a front end: QRL_OPT_SC16_BASEBAND); the ring behind a front end is cf32 whatever the call was fed
+    // fmt: what `in` points at (without a front end IN_SC16: QRL_OPT_SC16_BASEBAND, IN_SC8 / IN_CU8: QRL_OPT_IQ8_BASEBAND); the ring behind a front end is cf32 whatever the call was fed
     template <class P> void input_source(P& p, const float2* in, size_t stride, const float2* hist_old, uint64_t src0, uint64_t src1, int fmt) const {
         if (fe.used) { p.in = nullptr; p.in_ring = RingC{s1.p, s1_mask}; }
-        else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len; p.rot_enable = 1; rot.fill(p); p.in_fmt = fmt; p.in_scale = sc16_scale; }   // (8-bit calls never get here: a handle without a front end refuses them)
+        else { p.in = in; p.in_stride = stride; p.hist = hist_old; p.hist_len = hist_len; p.rot_enable = 1; rot.fill(p); in_format_fill(p, in_format(fmt)); }
         p.n0 = src0; p.n = (uint32_t)(src1 - src0);
     }
 };

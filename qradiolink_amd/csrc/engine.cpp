@@ -328,7 +328,7 @@ int qrl_demod::build()
 
 int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_out* out, int fmt)
 {
-    if (fmt >= IN_SC8 && !fe.used)   // (QRL_OPT_SC16_BASEBAND widened the modes' first stages for int16 only)
+    if (fmt >= IN_SC8 && !fe.used && !iq8_baseband)   // (QRL_OPT_SC16_BASEBAND admits int16 only; 8-bit calls have QRL_OPT_IQ8_BASEBAND)
         return qrl_set_error(QRL_ERR_ARG, std::string(in_fmt_entry(fmt)) + ": 8-bit input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps and its missing front end is what converts");
     if (fmt == IN_SC16 && !fe.used && !sc16_baseband)
         return qrl_set_error(QRL_ERR_ARG, "qrl_demod_process_sc16: int16 input needs the device-rate front end (device_samp_rate >= 2000000); this handle runs at 1 Msps");
@@ -353,7 +353,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     if (grouped && q_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(stream, ev_q[slot ^ 1], 0));   // grouped order: this front end behind the recursion of the call before
     if (pre_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_pre, 0)); pre_pending = false; }   // k_hist of the call before (helper stream)
     const bool use_pre = pre && input_resident;
-    const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16: int16 pairs behind it; only the kernels that read the caller's buffer know: the front end or, without one, what input_source feeds, and k_hist)
+    const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16, IN_SC8, IN_CU8: integer pairs behind it; only the kernels that read the caller's buffer know: the front end or, without one, what input_source feeds, and k_hist)
     const float2* hist_old = hist_flip ? hist_b.p : hist_a.p;
     const PortC fport = filtered_port(out), cport = constellation_port(out);
     float2* hist_new = hist_flip ? hist_a.p : hist_b.p;
@@ -804,6 +804,9 @@ int qrl_demod_set_option(qrl_demod* d, int option, int value)
     case QRL_OPT_SC16_BASEBAND:
         d->sc16_baseband = value != 0;   // read by the calls from now on: no state, nothing to wait for (a handle with a front end takes int16 anyway)
         return QRL_OK;
+    case QRL_OPT_IQ8_BASEBAND:
+        d->iq8_baseband = value != 0;    // the same for sc8 / cu8; the two options are independent
+        return QRL_OK;
     default:
         return qrl_set_error(QRL_ERR_ARG, "unknown option");
     }
@@ -943,7 +946,7 @@ static int process_host(qrl_demod* d, const void* iq_host, size_t stride, size_t
     HIPCHK(hipSetDevice(d->ctx->device));
     (void)take_launch_error();
     if (fmt == IN_SC16 && !d->fe.used && !d->sc16_baseband) return d->process(nullptr, 0, 0, nullptr, IN_SC16);   // the refusal of a 1 Msps handle, before anything is allocated
-    if (fmt >= IN_SC8 && !d->fe.used) return d->process(nullptr, 0, 0, nullptr, fmt);
+    if (fmt >= IN_SC8 && !d->fe.used && !d->iq8_baseband) return d->process(nullptr, 0, 0, nullptr, fmt);
     const size_t B = (size_t)d->cfg.batch;
     const size_t st = (n + round - 1) / round * round;
     DevBuf<unsigned char> iq; DevBuf<uint8_t> ba, bb; DevBuf<uint32_t> cnt;

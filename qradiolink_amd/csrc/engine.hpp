@@ -62,7 +62,7 @@ void launch_rot_ps_fill(uint64_t* acc, uint64_t* inc, float2* lo, int B, int set
 // x = (float)v * in_scale per component: one exact int -> float conversion, one rounded multiply, in front of the rotator.  Only the kernels
 // that read the caller's buffer know the format (the front-end stage -- without a front end, under QRL_OPT_SC16_BASEBAND, the mode's first stage and the
 // scope tap -- and k_hist); history, edge scratch and rings stay rotated cf32.
-// IN_SC8 / IN_CU8 (qrl_demod_process_sc8 / _cu8; handles with a front end): `in` points at interleaved 8-bit I, Q pairs, 2 bytes per sample.
+// IN_SC8 / IN_CU8 (qrl_demod_process_sc8 / _cu8; handles with a front end, or a 1 Msps handle under QRL_OPT_IQ8_BASEBAND): `in` points at interleaved 8-bit I, Q pairs, 2 bytes per sample.
 // ONE device path serves both: u = byte ^ mask (0x80 for sc8, 0 for cu8), x = ((float)u - in_bias) * in_scale -- one exact conversion, one f32
 // subtract, one rounded f32 multiply.  (float)(uint8_t)(v ^ 0x80) - 128.0f == (float)v exactly for every int8 v, so the host hands sc8 the bias 128
 // and the result is (float)v * scale; for cu8 the bias is the caller's (default 127.5).
@@ -81,7 +81,7 @@ __device__ __forceinline__ float2 iq8_to_f2(uint32_t w, uint32_t mask, float bia
 }
 // sample r of stream b of the caller's buffer of a parameter block (DecimParams, HistParams), converted.  in_load: the format read from
 // the block (the checked per-sample paths); in_load_as<W>: the width class a compile-time value (kernels that have an instantiation per format,
-// so that their cf32 code stays what it was); a block without in_bias (ResampParams) is never instantiated with IN_W_IQ8
+// so that their cf32 code stays what it was); a block without in_bias (ChanParams) is never instantiated with IN_W_IQ8
 template <class Pp, class = void> struct in_has_iq8 { static constexpr bool value = false; };   // blocks with an in_bias take 8-bit pairs (ChanParams: cf32 and int16 only)
 template <class Pp> struct in_has_iq8<Pp, decltype((void)Pp::in_bias)> { static constexpr bool value = true; };
 template <class Pp>
@@ -175,6 +175,7 @@ struct ResampParams {
     RingC in_ring;                        // ring path
     RingC out;
     uint64_t q0; uint32_t q_count;        // outputs to produce
+    float in_bias;                        // IN_SC8 / IN_CU8: x = ((float)u - in_bias) * in_scale (in what was padding: no other field moves)
     const float* taps;                    // [I][Jp]: taps[ph*Jp + j] = h[ph + j*I]
     int I, D, Jp;
     int rot_enable; uint64_t rot_acc; uint64_t rot_inc; uint64_t rot_nbase; const float2* rot_lo;

@@ -230,7 +230,8 @@ constexpr int PM_NHI = 64;   // coarse rotator entries per wave (64 x 512 sample
 // rotator.  The edge units of the same launch still read the rotated cf32 scratch, so the sample size is a per-wave (wave-uniform) shift
 // `ssh`; with SC = false it is the constant 3 and the code is what it was.  NCO indices count SAMPLES whatever the format: kb8 / kg8 are
 // 8 x index (byte offsets into the float2 tables), the data offsets (gbytes, lane_byte, GB) are bytes of the wave's stream.
-// SC = IN_W_IQ8 (in_fmt IN_SC8 / IN_CU8; three lag tiles only): 2-byte samples -- ssh = 1 for the regular units, a group is 16 D 2 bytes, the lane
+// SC = IN_W_IQ8 (in_fmt IN_SC8 / IN_CU8; three lag tiles: the front ends, one: the first stages of a 1 Msps handle under QRL_OPT_IQ8_BASEBAND,
+// where a group of 1600 bytes at D = 50 spans at most three of the ring's eight pieces): 2-byte samples -- ssh = 1 for the regular units, a group is 16 D 2 bytes, the lane
 // reads its sample's 16-bit word (ds_read_u16 at lane_byte + 8 s) and converts in registers (iq8_to_f2: xor, two byte conversions, subtract,
 // multiply); the xor mask and the bias are wave uniform.  SC is an int so that the three widths are one parameter; 0 and 1 are the code they were.
 template <int J, int NS, int RP, int NW, bool K1 = false, bool PS = false, int SC = IN_W_CF32>
@@ -988,12 +989,9 @@ template <int J, int NS, int RP = QRL_PM_RP, bool K1 = false>
 static int pm_launch_main(DecimParams& q, uint64_t M, uint32_t batch, bool edge_unit, hipStream_t s)
 {
     // int16 input: the SC instantiation of the same geometry (front ends: three lag tiles; the first stages of a 1 Msps handle: one)
-    // 8-bit pairs: the 2-byte instantiation, which exists for the three-tile front-end geometries only (a 1 Msps handle refuses the format)
-    if (q.in_fmt >= IN_SC8) {
-        if constexpr (J > 16)
-            return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, IN_W_IQ8>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, IN_W_IQ8>(q, M, batch, edge_unit, s);
-        else return -1;
-    }
+    // 8-bit pairs: the 2-byte instantiation of the same geometry (one lag tile: a 1 Msps handle under QRL_OPT_IQ8_BASEBAND)
+    if (q.in_fmt >= IN_SC8)
+        return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, IN_W_IQ8>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, IN_W_IQ8>(q, M, batch, edge_unit, s);
     if (q.in_fmt == IN_SC16)
         return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true, IN_W_SC16>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false, IN_W_SC16>(q, M, batch, edge_unit, s);
     return q.rot_acc_s ? pm_launch_main_k<J, NS, RP, K1, true>(q, M, batch, edge_unit, s) : pm_launch_main_k<J, NS, RP, K1, false>(q, M, batch, edge_unit, s);

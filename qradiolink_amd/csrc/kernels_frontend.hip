@@ -264,8 +264,9 @@ void launch_hist_save(const HistParams& p, int batch, hipStream_t s)
 
 // ---- K2: rational resampler I/D.  One fmaf chain per output, j ascending (oracle orc_resamp_ccf).
 // Tile of 256 outputs; the input span is staged in LDS once (coalesced), taps [I][Jp] in LDS.
-// SC: the caller's buffer holds int16 pairs (qrl_chan_process_sc16 on a single-carrier handle); history and rings are cf32
-template <bool SC>
+// SC, the width class (IN_W_*): the caller's buffer holds int16 pairs (qrl_chan_process_sc16 on a single-carrier handle, a 1 Msps receiver under
+// QRL_OPT_SC16_BASEBAND) or 8-bit pairs (a 1 Msps receiver under QRL_OPT_IQ8_BASEBAND; converted at the load, not tuned); history and rings are cf32
+template <int SC>
 __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int64_t i)
 {
     if (i < 0) return make_float2(0.f, 0.f);
@@ -289,7 +290,7 @@ __device__ __forceinline__ float2 resamp_fetch(const ResampParams& P, int b, int
     return P.in_ring.p[(size_t)b * (P.in_ring.mask + 1u) + ((uint32_t)ui & P.in_ring.mask)];
 }
 
-template <bool PS, bool SC>
+template <bool PS, int SC>
 __global__ __launch_bounds__(256) void k_resamp(const ResampParams P_, int span)
 {
     ROT_VIEW(ResampParams, PS, P, P_, blockIdx.y);
@@ -334,8 +335,9 @@ void launch_resamp(const ResampParams& p, int batch, hipStream_t s)
     int span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2;
     if ((size_t)span * sizeof(float2) > 48 * 1024) { T = 64; span = ((T - 1) * p.D + p.I - 1) / p.I + p.Jp + 2; }
     const size_t lds = (size_t)((p.I * p.Jp + 3) & ~3) * sizeof(float) + (size_t)span * sizeof(float2);
-    const bool sc = p.in && p.in_fmt == IN_SC16;
-    const auto kern = sc ? (p.rot_acc_s ? k_resamp<true, true> : k_resamp<false, true>) : (p.rot_acc_s ? k_resamp<true, false> : k_resamp<false, false>);
+    const bool sc = p.in && p.in_fmt == IN_SC16, iq8 = p.in && p.in_fmt >= IN_SC8;
+    const auto kern = iq8 ? (p.rot_acc_s ? k_resamp<true, IN_W_IQ8> : k_resamp<false, IN_W_IQ8>)
+                    : sc ? (p.rot_acc_s ? k_resamp<true, IN_W_SC16> : k_resamp<false, IN_W_SC16>) : (p.rot_acc_s ? k_resamp<true, IN_W_CF32> : k_resamp<false, IN_W_CF32>);
     if (dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
     dim3 grid((p.q_count + T - 1) / T, batch), block(T);
     hipLaunchKernelGGL(kern, grid, block, lds, s, p, span);
@@ -358,8 +360,9 @@ constexpr int D2_HALO = 24;                      // second-filter taps, padded t
 constexpr int D2_TY = D2_R * D2_NTH - D2_HALO;   // outputs a workgroup delivers
 // SC: the caller's buffer holds int16 pairs (a 1 Msps handle under QRL_OPT_SC16_BASEBAND): a sample is ONE 32-bit word, converted
 // (sc16_to_f2) in front of the rotator in both staging paths; the carried history and the engine rings stay cf32.  The cf32
-// instantiations keep their code.
-template <bool PS, bool SC = false>
+// instantiations keep their code.  SC is the width class (IN_W_*): IN_W_IQ8 (sc8 / cu8 under QRL_OPT_IQ8_BASEBAND) loads the 16-bit word of a
+// sample and converts with iq8_to_f2 in the same two places; exact, not tuned (two 2-byte loads per lane and pair).
+template <bool PS, int SC = IN_W_CF32>
 __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
 {
     const Dec2FirParams& P = P_;
@@ -401,7 +404,23 @@ __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
         } else
 #endif
         if (inb && i_lo >= (int64_t)Q.n0 && i_lo + 2 * 8 * D2_W <= i_end) {   // the whole span lies in the caller's buffer (workgroup uniform)
-            if constexpr (SC) {
+            if constexpr (SC == IN_W_IQ8) {
+                const uint16_t* src = reinterpret_cast<const uint16_t*>(Q.in) + (size_t)b * Q.in_stride + (size_t)(i_lo - (int64_t)Q.n0) + 2 * tid;
+                const uint32_t m8 = iq8_mask(Q.in_fmt);
+                uint32_t w[NK][2];
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const bool ok = tid + D2_NTH * k < 8 * D2_W;
+                    w[k][0] = ok ? (uint32_t)src[2 * D2_NTH * k] : 0u;
+                    w[k][1] = ok ? (uint32_t)src[2 * D2_NTH * k + 1] : 0u;
+                }
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    v[k][0] = iq8_to_f2(w[k][0], m8, Q.in_bias, Q.in_scale);
+                    v[k][1] = iq8_to_f2(w[k][1], m8, Q.in_bias, Q.in_scale);
+                    fresh[k][0] = fresh[k][1] = Q.rot_enable != 0;
+                }
+            } else if constexpr (SC == IN_W_SC16) {
                 const uint32_t* src = reinterpret_cast<const uint32_t*>(Q.in) + (size_t)b * Q.in_stride + (size_t)(i_lo - (int64_t)Q.n0) + 2 * tid;
                 uint32_t w[NK][2];
 #pragma unroll
@@ -439,7 +458,7 @@ __global__ __launch_bounds__(D2_NTH) void k_dec2_fir(const Dec2FirParams P_)
                     if (inb) {
                         if (i >= (int64_t)Q.n0) {
                             fresh[k][e] = Q.rot_enable != 0;
-                            if constexpr (SC) { v[k][e] = in_load_as<true>(Q, (size_t)b, (size_t)(i - (int64_t)Q.n0)); continue; }   // (the raw word, converted)
+                            if constexpr (SC != IN_W_CF32) { v[k][e] = in_load_as<SC>(Q, (size_t)b, (size_t)(i - (int64_t)Q.n0)); continue; }   // (the raw word, converted)
                             else src = inb + (size_t)(i - (int64_t)Q.n0);
                         }
                         else if ((int64_t)Q.n0 - i <= (int64_t)Q.hist_len) src = hb + (Q.hist_len - (uint32_t)((int64_t)Q.n0 - i));
@@ -568,9 +587,12 @@ void launch_dec2_fir(const Dec2FirParams& p, int batch, hipStream_t s)
 {
     if (p.d.m_count == 0) return;
     const dim3 grid((p.d.m_count + D2_TY - 1) / D2_TY, batch);
-    if (p.d.in && p.d.in_fmt == IN_SC16) {
-        if (p.d.rot_acc_s) hipLaunchKernelGGL((k_dec2_fir<true, true>), grid, dim3(D2_NTH), 0, s, p);
-        else hipLaunchKernelGGL((k_dec2_fir<false, true>), grid, dim3(D2_NTH), 0, s, p);
+    if (p.d.in && p.d.in_fmt >= IN_SC8) {
+        if (p.d.rot_acc_s) hipLaunchKernelGGL((k_dec2_fir<true, IN_W_IQ8>), grid, dim3(D2_NTH), 0, s, p);
+        else hipLaunchKernelGGL((k_dec2_fir<false, IN_W_IQ8>), grid, dim3(D2_NTH), 0, s, p);
+    } else if (p.d.in && p.d.in_fmt == IN_SC16) {
+        if (p.d.rot_acc_s) hipLaunchKernelGGL((k_dec2_fir<true, IN_W_SC16>), grid, dim3(D2_NTH), 0, s, p);
+        else hipLaunchKernelGGL((k_dec2_fir<false, IN_W_SC16>), grid, dim3(D2_NTH), 0, s, p);
     } else if (p.d.rot_acc_s) hipLaunchKernelGGL(k_dec2_fir<true>, grid, dim3(D2_NTH), 0, s, p);
     else hipLaunchKernelGGL(k_dec2_fir<false>, grid, dim3(D2_NTH), 0, s, p);
 }

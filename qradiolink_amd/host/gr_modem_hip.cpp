@@ -118,6 +118,7 @@ try {
     chk(qrl_demod_set_sc8_scale(h, d_sc8_scale), "qrl_demod_set_sc8_scale");
     chk(qrl_demod_set_cu8_scale(h, d_cu8_scale, d_cu8_bias), "qrl_demod_set_cu8_scale");
     chk(qrl_demod_set_option(h, QRL_OPT_SC16_BASEBAND, d_sc16_baseband ? 1 : 0), "qrl_demod_set_option");
+    chk(qrl_demod_set_option(h, QRL_OPT_IQ8_BASEBAND, d_iq8_baseband ? 1 : 0), "qrl_demod_set_option");
     if (d_per_stream) chk(qrl_demod_set_carrier_offsets(h, d_offsets.data()), "qrl_demod_set_carrier_offsets");   // the new handle's phases start at 0
     chk(qrl_demod_out_caps(h, d_chunk, &d_fcap, &d_ccap, &d_bcap), "qrl_demod_out_caps");
     chk(qrl_demod_audio_cap(h, d_chunk, &d_acap), "qrl_demod_audio_cap");
@@ -307,7 +308,7 @@ void gr_demod_base_hip::work(const gr_complex* const* iq, size_t n) { work_any(r
 // x = (float)v * scale).  Replaces the driver's sc16 -> fc32 conversion.
 void gr_demod_base_hip::work(const int16_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_SC16); }
 // 8-bit I/Q as an RTL-SDR (unsigned) or a HackRF (signed) delivers it: 2 bytes per sample staged and uploaded, the front end converts
-// (qrl_demod_process_sc8 / _cu8).  Device rates with a front end only.
+// (qrl_demod_process_sc8 / _cu8) -- at 1 Msps, under set_iq8_baseband, the mode's first stage does.
 void gr_demod_base_hip::work(const int8_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_SC8); }
 void gr_demod_base_hip::work(const uint8_t* const* iq, size_t n) { work_any(reinterpret_cast<const void* const*>(iq), n, FMT_CU8); }
 void gr_demod_base_hip::set_sc8_scale(float scale)
@@ -340,6 +341,12 @@ void gr_demod_base_hip::set_sc16_baseband(bool on)
     d_sc16_baseband = on;
     if (d_h.get()) chk(qrl_demod_set_option(d_h.get(), QRL_OPT_SC16_BASEBAND, on ? 1 : 0), "qrl_demod_set_option");
 }
+void gr_demod_base_hip::set_iq8_baseband(bool on)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    d_iq8_baseband = on;
+    if (d_h.get()) chk(qrl_demod_set_option(d_h.get(), QRL_OPT_IQ8_BASEBAND, on ? 1 : 0), "qrl_demod_set_option");
+}
 void gr_demod_base_hip::work_any(const void* const* iq, size_t n, int fmt)
 {
     const bool sc16 = fmt == FMT_SC16, iq8 = fmt == FMT_SC8 || fmt == FMT_CU8;
@@ -353,7 +360,7 @@ void gr_demod_base_hip::work_any(const void* const* iq, size_t n, int fmt)
         if (d_chunk & 3) throw std::invalid_argument("gr_demod_base_hip::work(int16): max_chunk (the row pitch) must be a multiple of 4 samples");
     }
     if (iq8) {   // as for int16: what the C ABI would refuse, before anything is staged or queued
-        if (d_rate < 2000000) throw std::invalid_argument("gr_demod_base_hip::work(8-bit): needs the device-rate front end (device_samp_rate >= 2000000)");
+        if (d_rate < 2000000 && !d_iq8_baseband) throw std::invalid_argument("gr_demod_base_hip::work(8-bit): needs the device-rate front end (device_samp_rate >= 2000000)");
         if (d_chunk & 7) throw std::invalid_argument("gr_demod_base_hip::work(8-bit): max_chunk (the row pitch) must be a multiple of 8 samples");
     }
     if (!d_demod_on && !d_fft_on) return;                        // _demod_valve closed and nobody else listens: the samples are dropped

@@ -60,8 +60,8 @@ public:
     void work(const int16_t* const* iq, size_t n);
     void set_sc16_scale(float scale);
     // the same for 8-bit I/Q, 2 bytes per sample staged and uploaded: signed (HackRF: x = (float)v * scale, scale 1 / 128 unless set_sc8_scale) and
-    // unsigned (RTL-SDR: x = ((float)u - bias) * scale, 1 / 128 and 127.5 unless set_cu8_scale).  Handles at device_samp_rate >= 2 Msps only
-    // (std::invalid_argument at 1 Msps, also under set_sc16_baseband); max_chunk a multiple of 8.  The spectrum tap reads the same uploaded
+    // unsigned (RTL-SDR: x = ((float)u - bias) * scale, 1 / 128 and 127.5 unless set_cu8_scale).  Handles at device_samp_rate >= 2 Msps, or at
+    // 1 Msps after set_iq8_baseband(true) (std::invalid_argument at 1 Msps without it, also under set_sc16_baseband); max_chunk a multiple of 8.  The spectrum tap reads the same uploaded
     // 8-bit slot (qrl_fft_process_sc8 / _cu8).  The setters are kept across set_mode / set_samp_rate
     void work(const int8_t* const* iq, size_t n);
     void work(const uint8_t* const* iq, size_t n);
@@ -70,6 +70,9 @@ public:
     // a 1 Msps receiver takes work(int16) too: the per-mode first stage reads the raw pairs (QRL_OPT_SC16_BASEBAND).  Default off: work(int16)
     // at 1 Msps throws std::invalid_argument.  Kept across set_mode / set_samp_rate; no effect at device rates with a front end
     void set_sc16_baseband(bool on);
+    // the same for work(int8) / work(uint8) (QRL_OPT_IQ8_BASEBAND), independent of set_sc16_baseband.  Default off: the 8-bit overloads throw
+    // std::invalid_argument at 1 Msps.  Kept across set_mode / set_samp_rate; the spectrum tap keeps reading the uploaded 8-bit slot
+    void set_iq8_baseband(bool on);
     void flush();                                              // waits for the call in flight and harvests it
     std::vector<unsigned char>* getData(int stream = 0) { return getData(1, stream); }
     virtual std::vector<unsigned char>* getData(int nr, int stream);   // nr = 1: bits A (port 2), nr = 2: bits B (port 3); nullptr = nothing yet (virtual: tests tap the bits)
@@ -180,6 +183,7 @@ private:
     float d_sc16_scale = 1.0f / 32768.0f;                        // re-applied by open()
     float d_sc8_scale = 1.0f / 128.0f, d_cu8_scale = 1.0f / 128.0f, d_cu8_bias = 127.5f;   // re-applied by open()
     bool d_sc16_baseband = false;                                // set_sc16_baseband; re-applied by open()
+    bool d_iq8_baseband = false;                                 // set_iq8_baseband; re-applied by open()
     int d_inflight = -1; uint64_t d_calls = 0;
     size_t d_fcap = 0, d_ccap = 0, d_bcap = 0, d_acap = 0;
     int d_squelch = -140; float d_agc_attack = 0.1f, d_agc_decay = 0.1f;   // rates, behind the knob mapping (the constructors' 0.1 until a setter is called)
@@ -344,6 +348,8 @@ public:
     void set_dmr_l2(bool on, bool audio_fec = true) { if (_gr_demod_base) _gr_demod_base->set_dmr_l2(on, audio_fec); }
     // the receiver at 1 Msps takes work(int16) (gr_demod_base_hip::set_sc16_baseband; default off)
     void set_sc16_baseband(bool on) { if (_gr_demod_base) _gr_demod_base->set_sc16_baseband(on); }
+    // the receiver at 1 Msps takes work(int8) / work(uint8) (gr_demod_base_hip::set_iq8_baseband; default off)
+    void set_iq8_baseband(bool on) { if (_gr_demod_base) _gr_demod_base->set_iq8_baseband(on); }
     // the conversion of the receiver's 8-bit work() overloads (gr_demod_base_hip::set_sc8_scale / set_cu8_scale)
     void set_sc8_scale(float scale) { if (_gr_demod_base) _gr_demod_base->set_sc8_scale(scale); }
     void set_cu8_scale(float scale, float bias = 127.5f) { if (_gr_demod_base) _gr_demod_base->set_cu8_scale(scale, bias); }
