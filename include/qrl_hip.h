@@ -340,6 +340,23 @@ int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbyt
 int qrl_mod_process_sc16(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int16_t* iq, size_t out_stride);
 int qrl_mod_set_sc16_scale(qrl_mod* m, float scale);
 int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts);
+/* like qrl_mod_process, but iq is interleaved int8 I, Q (sc8, 2 bytes per sample: what a HackRF takes on the wire): sample k of stream b
+ * has I at iq[2*(b*out_stride + k)] and Q one byte behind it.  Per component r = rintf(x * scale) -- one rounded f32 multiply, round to
+ * nearest even -- saturated to [-128, 127]; NaN gives 0; x is exactly the float qrl_mod_process stores.
+ * scale: qrl_mod_set_sc8_scale, default 127.0f (1.0 -> 127); the setter takes effect from the next call and refuses a non-finite or zero
+ * value with QRL_ERR_ARG.  The format belongs to the CALL: cf32, sc16 and sc8 calls may alternate on one handle and give the converted
+ * concatenated stream; counts, M17's multiples of 3 bytes, zero runs, carrier offsets, retune, reset and asynchrony are those of
+ * qrl_mod_process.  Every modem type, with or without the back end, every device rate from 1 to 183 Msps.
+ * iq must be 2-byte aligned, else QRL_ERR_ARG (the handle goes on working); out_stride (samples) may be any value >= the call's sample
+ * count.  A sample is one 2-byte store: nothing outside a row's samples is written, not even the other half of a 4-byte word that a row
+ * shares with its neighbour.
+ * qrl_mod_set_sc8_clip_counts: counts = device pointer to `batch` uint32, or NULL (the default: no counting).  Every following sc8 call
+ * ADDS to counts[b] the components of stream b with r > 127 or r < -128 (I and Q separately; +-inf counts, NaN does not; -128 reached
+ * without saturation is not a clip); the caller zeroes the array; the values are valid once the handle's stream has passed the call.
+ * cf32 and sc16 calls never touch it, and sc8 calls never touch the sc16 counters; the two setters may name the same array. */
+int qrl_mod_process_sc8(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int8_t* iq, size_t out_stride);
+int qrl_mod_set_sc8_scale(qrl_mod* m, float scale);
+int qrl_mod_set_sc8_clip_counts(qrl_mod* m, uint32_t* counts);
 int qrl_mod_sync(qrl_mod* m);
 void* qrl_mod_stream(qrl_mod* m);
 
@@ -496,6 +513,13 @@ int qrl_synth_process(qrl_synth* s, const int16_t* in, size_t stride, size_t n, 
 int qrl_synth_process_sc16(qrl_synth* s, const int16_t* in, size_t stride, size_t n, int16_t* iq, size_t out_stride, size_t* produced);
 int qrl_synth_set_sc16_scale(qrl_synth* s, float scale);
 int qrl_synth_set_sc16_clip_counts(qrl_synth* s, uint32_t* counts);
+/* sc8 output, as qrl_mod_process_sc8: interleaved int8 I, Q, 2 bytes per sample, r = rintf(x * scale) saturated to [-128, 127], NaN -> 0,
+ * default scale 127.0f (a non-finite or zero scale is QRL_ERR_ARG), iq 2-byte aligned else QRL_ERR_ARG, one 2-byte store per sample and
+ * nothing else written, clip counters of its own per stream of the batch (r > 127 or r < -128; the sc16 counters stay untouched).
+ * `produced` and everything else as qrl_synth_process; the kernels that convert are those of qrl_synth_process_sc16. */
+int qrl_synth_process_sc8(qrl_synth* s, const int16_t* in, size_t stride, size_t n, int8_t* iq, size_t out_stride, size_t* produced);
+int qrl_synth_set_sc8_scale(qrl_synth* s, float scale);
+int qrl_synth_set_sc8_clip_counts(qrl_synth* s, uint32_t* counts);
 int qrl_synth_sync(qrl_synth* s);
 
 /* ---- device deframer (reference src/gr/gr_deframer_bb.cpp:24-48,83-185; instances gr_demod_base.cpp:171-178) -----------
@@ -667,6 +691,13 @@ int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, f
 int qrl_amod_process_sc16(qrl_amod* m, const float* audio, size_t stride, size_t n, int16_t* iq, size_t out_stride);
 int qrl_amod_set_sc16_scale(qrl_amod* m, float scale);
 int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts);
+/* sc8 output, as qrl_mod_process_sc8: interleaved int8 I, Q, 2 bytes per sample, r = rintf(x * scale) saturated to [-128, 127], NaN -> 0,
+ * default scale 127.0f (a non-finite or zero scale is QRL_ERR_ARG), iq 2-byte aligned else QRL_ERR_ARG, one 2-byte store per sample and
+ * nothing else written, clip counters of its own (r > 127 or r < -128; the sc16 counters stay untouched).  qrl_amod_last_count, SSB's
+ * whole chunks of 1024 and the out_stride bound (qrl_amod_out_cap) are those of qrl_amod_process. */
+int qrl_amod_process_sc8(qrl_amod* m, const float* audio, size_t stride, size_t n, int8_t* iq, size_t out_stride);
+int qrl_amod_set_sc8_scale(qrl_amod* m, float scale);
+int qrl_amod_set_sc8_clip_counts(qrl_amod* m, uint32_t* counts);
 int qrl_amod_sync(qrl_amod* m);
 void* qrl_amod_stream(qrl_amod* m);
 

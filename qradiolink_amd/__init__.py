@@ -128,6 +128,9 @@ def load_library():
     lib.qrl_amod_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz]
     lib.qrl_amod_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_amod_set_sc16_clip_counts.argtypes = [vp, vp]
+    lib.qrl_amod_process_sc8.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_amod_set_sc8_scale.argtypes = [vp, C.c_float]
+    lib.qrl_amod_set_sc8_clip_counts.argtypes = [vp, vp]
     lib.qrl_amod_sync.argtypes = [vp]
     lib.qrl_amod_stream.argtypes = [vp]
     lib.qrl_amod_stream.restype = vp
@@ -222,6 +225,9 @@ def load_library():
     lib.qrl_mod_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz]
     lib.qrl_mod_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_mod_set_sc16_clip_counts.argtypes = [vp, vp]
+    lib.qrl_mod_process_sc8.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.qrl_mod_set_sc8_scale.argtypes = [vp, C.c_float]
+    lib.qrl_mod_set_sc8_clip_counts.argtypes = [vp, vp]
     lib.qrl_mod_sync.argtypes = [vp]
     lib.qrl_mod_stream.restype = vp
     lib.qrl_mod_stream.argtypes = [vp]
@@ -261,6 +267,9 @@ def load_library():
     lib.qrl_synth_process_sc16.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(sz)]
     lib.qrl_synth_set_sc16_scale.argtypes = [vp, C.c_float]
     lib.qrl_synth_set_sc16_clip_counts.argtypes = [vp, vp]
+    lib.qrl_synth_process_sc8.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(sz)]
+    lib.qrl_synth_set_sc8_scale.argtypes = [vp, C.c_float]
+    lib.qrl_synth_set_sc8_clip_counts.argtypes = [vp, vp]
     lib.qrl_synth_sync.argtypes = [vp]
     lib.qrl_deframer_create.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     lib.qrl_deframer_destroy.argtypes = [vp]
@@ -305,13 +314,13 @@ EXPORTED_SYMBOLS = [
     "qrl_m17_rx_create", "qrl_m17_rx_destroy", "qrl_m17_rx_reset", "qrl_m17_rx_set_config", "qrl_m17_rx_process", "qrl_m17_rx_get_state",
     "qrl_m17_call_start", "qrl_m17_call_encode", "qrl_m17_call_end",
     "qrl_dmr_sink_create", "qrl_dmr_sink_destroy", "qrl_dmr_sink_reset", "qrl_dmr_sink_flush", "qrl_dmr_sink_process", "qrl_dmr_sink_sync",
-    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
+    "qrl_amod_create", "qrl_amod_destroy", "qrl_amod_reset", "qrl_amod_set_bb_gain", "qrl_amod_set_ctcss", "qrl_amod_set_filter_width", "qrl_amod_set_carrier_offset", "qrl_amod_set_carrier_offsets", "qrl_amod_set_cw_k", "qrl_amod_samples_per_sample", "qrl_amod_last_count", "qrl_amod_out_cap", "qrl_amod_process", "qrl_amod_process_sc16", "qrl_amod_set_sc16_scale", "qrl_amod_set_sc16_clip_counts", "qrl_amod_process_sc8", "qrl_amod_set_sc8_scale", "qrl_amod_set_sc8_clip_counts", "qrl_amod_sync", "qrl_amod_stream",
     "qrl_demod_process", "qrl_demod_process_sc16", "qrl_demod_set_sc16_scale", "qrl_demod_process_sc16_host",
     "qrl_demod_process_sc8", "qrl_demod_process_cu8", "qrl_demod_set_sc8_scale", "qrl_demod_set_cu8_scale", "qrl_demod_process_sc8_host", "qrl_demod_process_cu8_host", "qrl_demod_sync", "qrl_demod_stream", "qrl_demod_internal_streams", "qrl_chan_internal_streams", "qrl_demod_process_host", "qrl_demod_profile",
     "qrl_demod_profile_read", "qrl_mod_create", "qrl_mod_destroy", "qrl_mod_reset", "qrl_mod_set_bb_gain", "qrl_mod_set_carrier_offset", "qrl_mod_set_carrier_offsets",
-    "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_process_sc16", "qrl_mod_set_sc16_scale", "qrl_mod_set_sc16_clip_counts", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
+    "qrl_mod_samples_per_byte", "qrl_mod_samples_per_block", "qrl_mod_add_zero_runs", "qrl_mod_process", "qrl_mod_process_sc16", "qrl_mod_set_sc16_scale", "qrl_mod_set_sc16_clip_counts", "qrl_mod_process_sc8", "qrl_mod_set_sc8_scale", "qrl_mod_set_sc8_clip_counts", "qrl_mod_sync", "qrl_mod_stream", "qrl_chan_set_option", "qrl_chan_channelize", "qrl_chan_process_channels", "qrl_chan_wait_for", "qrl_chan_stream_wait", "qrl_chan_stream", "qrl_chan_profile", "qrl_chan_profile_read", "qrl_chan_profile_read_kernels", "qrl_debug_decim_prof", "qrl_debug_decim_prof_enable", "qrl_chan_create",
     "qrl_chan_destroy", "qrl_chan_reset", "qrl_chan_set_level", "qrl_chan_calibrate_rssi", "qrl_chan_set_rssi_output", "qrl_chan_set_4fsk_output", "qrl_chan_out_cap", "qrl_chan_process", "qrl_chan_process_sc16", "qrl_chan_channelize_sc16", "qrl_chan_set_sc16_scale", "qrl_chan_sync",
-    "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process", "qrl_synth_process_sc16", "qrl_synth_set_sc16_scale", "qrl_synth_set_sc16_clip_counts",
+    "qrl_synth_create", "qrl_synth_destroy", "qrl_synth_reset", "qrl_synth_set_bb_gain", "qrl_synth_add_zero_runs", "qrl_synth_out_cap", "qrl_synth_process", "qrl_synth_process_sc16", "qrl_synth_set_sc16_scale", "qrl_synth_set_sc16_clip_counts", "qrl_synth_process_sc8", "qrl_synth_set_sc8_scale", "qrl_synth_set_sc8_clip_counts",
     "qrl_synth_sync",
     "qrl_rssi_create", "qrl_rssi_destroy", "qrl_rssi_reset", "qrl_rssi_set_level", "qrl_rssi_process", "qrl_rssi_sync", "qrl_rssi_stream",
     "qrl_fft_create", "qrl_fft_destroy", "qrl_fft_set_enabled", "qrl_fft_set_fft_size", "qrl_fft_get_fft_size", "qrl_fft_set_window_type",
@@ -1057,9 +1066,11 @@ class Fft:
             self.h = C.c_void_p()
 
 
-class _Sc16Tx:
-    """int16 IQ (sc16) output of the transmitters: the setters of qrl_{mod,amod,synth}_set_sc16_*; `_sc16_abi` names the family."""
+class _IntIqTx:
+    """integer IQ output of the transmitters, int16 (sc16) and int8 (sc8): the setters of qrl_{mod,amod,synth}_set_{sc16,sc8}_*; `_sc16_abi`
+    names the family."""
     _sc16_clip = None
+    _sc8_clip = None
 
     def set_sc16_scale(self, scale):
         """r = rint(x * scale) per component for the int16 calls from the next one on (default 32767: 1.0 -> 32767)"""
@@ -1075,19 +1086,33 @@ class _Sc16Tx:
         _check(getattr(self.lib, name)(self.h, None if counts is None else counts.data_ptr()), name)
         self._sc16_clip = counts
 
-    def _sc16_out(self, out, count, device, bound=True):
-        """the [batch, stride, 2] int16 buffer of a call of `count` samples per stream: the caller's (its pitch is out_stride), or a fresh one.
-        bound=False: `count` is an upper bound only and the library checks out_stride against the call's own count"""
+    def set_sc8_scale(self, scale):
+        """r = rint(x * scale) per component for the int8 calls from the next one on (default 127: 1.0 -> 127)"""
+        name = "qrl_%s_set_sc8_scale" % self._sc16_abi
+        _check(getattr(self.lib, name)(self.h, C.c_float(scale)), name)
+
+    def set_sc8_clip_counts(self, counts):
+        """set_sc16_clip_counts for the process_sc8 calls: counters of their own (the same tensor may serve both)"""
+        name = "qrl_%s_set_sc8_clip_counts" % self._sc16_abi
+        if counts is not None:
+            assert counts.is_cuda and counts.element_size() == 4 and counts.dim() == 1 and counts.shape[0] == self.batch and counts.is_contiguous()
+        _check(getattr(self.lib, name)(self.h, None if counts is None else counts.data_ptr()), name)
+        self._sc8_clip = counts
+
+    def _sc16_out(self, out, count, device, bound=True, dtype=None):
+        """the [batch, stride, 2] int16 (dtype: int8 for sc8) buffer of a call of `count` samples per stream: the caller's (its pitch is out_stride),
+        or a fresh one.  bound=False: `count` is an upper bound only and the library checks out_stride against the call's own count"""
         t = self.torch
+        dtype = dtype or t.int16
         if out is None:
-            return t.empty((self.batch, max(count, 1), 2), dtype=t.int16, device=device)
-        assert out.is_cuda and out.dtype == t.int16 and out.dim() == 3 and out.shape[0] == self.batch and out.shape[2] == 2
+            return t.empty((self.batch, max(count, 1), 2), dtype=dtype, device=device)
+        assert out.is_cuda and out.dtype == dtype and out.dim() == 3 and out.shape[0] == self.batch and out.shape[2] == 2
         assert out.stride(2) == 1 and out.stride(1) == 2 and out.stride(0) % 2 == 0
         assert not bound or out.shape[1] >= count
         return out
 
 
-class Synth(_Sc16Tx):
+class Synth(_IntIqTx):
     """Multi-carrier MMDVM transmitter: mirrors make_gr_mod_mmdvm_multi2 (reference src/gr/gr_mod_mmdvm_multi2.cpp).
     process(x) takes int16 cuda [batch, num_channels, n] (24 ksps FM baseband per channel) and returns complex64 cuda
     [batch, produced] at 250 ksps."""
@@ -1128,6 +1153,19 @@ class Synth(_Sc16Tx):
         produced = C.c_size_t(0)
         t.cuda.current_stream().synchronize()
         _check(self.lib.qrl_synth_process_sc16(self.h, x.data_ptr(), n, n, out.data_ptr(), out.stride(0) // 2, C.byref(produced)), "qrl_synth_process_sc16")
+        _check(self.lib.qrl_synth_sync(self.h), "qrl_synth_sync")
+        return out[:, :produced.value]
+
+    def process_sc8(self, x, out=None):
+        """process() with int8 IQ out: [batch, produced, 2] (qrl_synth_process_sc8); out: a preallocated [batch, stride, 2] int8 cuda tensor"""
+        t = self.torch
+        assert x.is_cuda and x.dtype == t.int16 and x.dim() == 3 and x.shape[0] == self.batch and x.shape[1] == self.nch
+        x = x.contiguous()
+        n = x.shape[2]
+        out = self._sc16_out(out, self.lib.qrl_synth_out_cap(self.h, n), x.device, bound=False, dtype=t.int8)
+        produced = C.c_size_t(0)
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_synth_process_sc8(self.h, x.data_ptr(), n, n, out.data_ptr(), out.stride(0) // 2, C.byref(produced)), "qrl_synth_process_sc8")
         _check(self.lib.qrl_synth_sync(self.h), "qrl_synth_sync")
         return out[:, :produced.value]
 
@@ -1209,7 +1247,7 @@ class FrameSync:
             self.h = C.c_void_p()
 
 
-class Mod(_Sc16Tx):
+class Mod(_IntIqTx):
     """Batch TX modulator: mirrors make_gr_mod_qpsk (reference src/gr/gr_mod_qpsk.cpp:19-30).
     process(bytes) takes a torch cuda uint8 tensor [batch, nbytes] (packed bytes, as gr_byte_source hands them
     out) and returns a complex64 cuda tensor [batch, nbytes * 8 * sps]."""
@@ -1275,6 +1313,24 @@ class Mod(_Sc16Tx):
         self.sync()
         return out
 
+    def process_sc8_async(self, data, out=None):
+        """Queue one call with int8 IQ out (qrl_mod_process_sc8): returns the int8 cuda tensor [batch, count, 2], a view of `out` when a
+        preallocated [batch, stride, 2] buffer is given (its pitch is out_stride).  Valid after sync()."""
+        assert data.is_cuda and data.dtype == self.torch.uint8 and data.dim() == 2 and data.shape[0] == self.batch
+        assert data.stride(1) == 1
+        n = data.shape[1]
+        count = n // self.bytes_per_block * self.spblock
+        out = self._sc16_out(out, count, data.device, dtype=self.torch.int8)
+        self.torch.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_mod_process_sc8(self.h, data.data_ptr(), data.stride(0), n, out.data_ptr(), out.stride(0) // 2),
+               "qrl_mod_process_sc8")
+        return out[:, :count]
+
+    def process_sc8(self, data, out=None):
+        out = self.process_sc8_async(data, out)
+        self.sync()
+        return out
+
     def reset(self):
         _check(self.lib.qrl_mod_reset(self.h), "qrl_mod_reset")
 
@@ -1301,7 +1357,7 @@ class Mod(_Sc16Tx):
             self.h = C.c_void_p()
 
 
-class AMod(_Sc16Tx):
+class AMod(_IntIqTx):
     """Batch analogue voice modulator: mirrors make_gr_mod_nbfm (src/gr/gr_mod_nbfm.cpp:19-77) and make_gr_mod_ssb (gr_mod_ssb.cpp:19-82).
     process(audio) takes a float32 cuda tensor [batch, n] at 8 ksps (NBFM: n a multiple of 4) and returns complex64 at 1 Msps:
     [batch, 125 n] for NBFM, 125 x the audio items of the 1024-chunks the call completed for SSB."""
@@ -1334,6 +1390,17 @@ class AMod(_Sc16Tx):
         out = self._sc16_out(out, self.lib.qrl_amod_out_cap(self.h, n), audio.device, bound=False)
         t.cuda.current_stream().synchronize()
         _check(self.lib.qrl_amod_process_sc16(self.h, audio.data_ptr(), audio.stride(0), n, out.data_ptr(), out.stride(0) // 2), "qrl_amod_process_sc16")
+        _check(self.lib.qrl_amod_sync(self.h), "qrl_amod_sync")
+        return out[:, :self.lib.qrl_amod_last_count(self.h)]
+
+    def process_sc8(self, audio, out=None):
+        """process() with int8 IQ out: [batch, count, 2] (qrl_amod_process_sc8); out: a preallocated [batch, stride, 2] int8 cuda tensor"""
+        t = self.torch
+        assert audio.is_cuda and audio.dtype == t.float32 and audio.dim() == 2 and audio.shape[0] == self.batch and audio.stride(1) == 1
+        n = audio.shape[1]
+        out = self._sc16_out(out, self.lib.qrl_amod_out_cap(self.h, n), audio.device, bound=False, dtype=t.int8)
+        t.cuda.current_stream().synchronize()
+        _check(self.lib.qrl_amod_process_sc8(self.h, audio.data_ptr(), audio.stride(0), n, out.data_ptr(), out.stride(0) // 2), "qrl_amod_process_sc8")
         _check(self.lib.qrl_amod_sync(self.h), "qrl_amod_sync")
         return out[:, :self.lib.qrl_amod_last_count(self.h)]
 

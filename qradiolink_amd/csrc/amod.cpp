@@ -58,6 +58,7 @@ struct qrl_amod {
     uint64_t n8 = 0, n50 = 0;
     TxBackEnd be;   // gr_mod_base back end (src/gr/gr_mod_base.cpp:38,215-258), as behind the digital modulators (tx.cpp)
     Sc16Sink sc;    // qrl_amod_process_sc16
+    Sc8Sink sc8;    // qrl_amod_process_sc8
     size_t cap_1msps(size_t n) const { return am ? n * (size_t)sps : ssb ? (n + 1024) * (size_t)sps : n * 25 / 4 * (size_t)sps; }
     int init_back_end() { return be.init("amod", "analogue modulator", cfg.device_samp_rate, cfg.carrier_offset_hz, cfg.batch, cap_1msps(cfg.max_samples)); }
     int init_state(bool keep_tone_phase = false)
@@ -238,8 +239,8 @@ int qrl_amod_sync(qrl_amod* m) { if (!m) return QRL_ERR_ARG; HIPCHK(hipStreamSyn
 
 }  // extern "C"
 
-// qrl_amod_process / qrl_amod_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out), seen only by the kernel that stores to it
-static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, void* iq, size_t out_stride, const Sc16Out sc)
+// qrl_amod_process / qrl_amod_process_sc16 / qrl_amod_process_sc8: `sc` is the format of `iq` (cf32: a zeroed TxOut), seen only by the kernel that stores to it
+static int amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, void* iq, size_t out_stride, const TxOut sc)
 {
     if (!m || (!audio && n && !m->cw) || (!iq && n)) return QRL_ERR_ARG;
     if (n > m->cfg.max_samples) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_samples");
@@ -351,15 +352,23 @@ extern "C" {
 
 int qrl_amod_process(qrl_amod* m, const float* audio, size_t stride, size_t n, float* iq, size_t out_stride)
 {
-    return amod_process(m, audio, stride, n, iq, out_stride, Sc16Out{});
+    return amod_process(m, audio, stride, n, iq, out_stride, TxOut{});
 }
 int qrl_amod_process_sc16(qrl_amod* m, const float* audio, size_t stride, size_t n, int16_t* iq, size_t out_stride)
 {
-    Sc16Out sc;
+    TxOut sc;
     if (int r = m ? m->sc.for_call("qrl_amod_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
     return amod_process(m, audio, stride, n, iq, out_stride, sc);
 }
 int qrl_amod_set_sc16_scale(qrl_amod* m, float scale) { return m ? m->sc.set_scale("qrl_amod_set_sc16_scale", scale) : QRL_ERR_ARG; }
 int qrl_amod_set_sc16_clip_counts(qrl_amod* m, uint32_t* counts) { return m ? m->sc.set_clip(counts) : QRL_ERR_ARG; }
+int qrl_amod_process_sc8(qrl_amod* m, const float* audio, size_t stride, size_t n, int8_t* iq, size_t out_stride)
+{
+    TxOut sc;
+    if (int r = m ? m->sc8.for_call("qrl_amod_process_sc8", iq, sc) : QRL_ERR_ARG) return r;
+    return amod_process(m, audio, stride, n, iq, out_stride, sc);
+}
+int qrl_amod_set_sc8_scale(qrl_amod* m, float scale) { return m ? m->sc8.set_scale("qrl_amod_set_sc8_scale", scale) : QRL_ERR_ARG; }
+int qrl_amod_set_sc8_clip_counts(qrl_amod* m, uint32_t* counts) { return m ? m->sc8.set_clip(counts) : QRL_ERR_ARG; }
 
 }

@@ -138,6 +138,31 @@ __device__ __forceinline__ void sc16_store(uint32_t* row, size_t idx, float2 v, 
     }
 }
 
+// ---- float -> int8 in front of the transmitters' sc8 stores (qrl_*_process_sc8): the same rule one format narrower ----
+// per component r = rintf(x * scale), saturated to [-128, 127]; NaN gives 0.  nclip = components with r > 127 or r < -128 (+-inf included,
+// NaN not; -128 reached by rounding, as from -128.5, is in range).  The pair is packed I low byte, Q high byte: one 2-byte store.
+__device__ __forceinline__ int sc8_sat(float r) { return r != r ? 0 : (int)fminf(fmaxf(r, -128.0f), 127.0f); }
+__device__ __forceinline__ uint16_t f2_to_sc8(float2 v, float scale, uint32_t& nclip)
+{
+    const float ri = rintf(v.x * scale), rq = rintf(v.y * scale);
+    nclip = (uint32_t)(ri > 127.0f || ri < -128.0f) + (uint32_t)(rq > 127.0f || rq < -128.0f);
+    return (uint16_t)(((uint32_t)sc8_sat(ri) & 0xffu) | (((uint32_t)sc8_sat(rq) & 0xffu) << 8));
+}
+// The sc8 store of every terminal TX kernel, under sc16_store's divergence rule.  A sample is ONE 2-byte store: the other half of the 32-bit word
+// belongs to the neighbouring sample, which another lane, wave or workgroup (or, behind a row's end, the caller) owns, and is never written here.
+__device__ __forceinline__ void sc8_store(uint16_t* row, size_t idx, float2 v, bool valid, float scale, uint32_t* clip)
+{
+    uint32_t nclip;
+    const uint16_t w = f2_to_sc8(v, scale, nclip);
+    if (valid) row[idx] = w;
+    if (clip) {
+        if (!valid) nclip = 0;
+        const uint32_t n = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(nclip >= 1u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(nclip == 2u));
+        const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+        if (n && (int)__lane_id() == __ffsll((unsigned long long)act) - 1) atomicAdd(clip, n);
+    }
+}
+
 __device__ __forceinline__ float phase_wrap(float phase)
 {
     const double TWO_PI = 6.283185307179586476925286766559;

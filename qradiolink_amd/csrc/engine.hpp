@@ -99,11 +99,13 @@ __device__ __forceinline__ float2 in_load_as(const Pp& P, size_t b, size_t r)
     else return P.in[b * P.in_stride + r];
 }
 
-// ---- format of the caller's TX buffer (qrl_*_process / qrl_*_process_sc16) ----
-// on = 0 (what a zeroed block means): `out` is float2.  on = 1: `out` points at packed int16 I, Q pairs (4 bytes per sample, out_stride still in
-// samples) and the terminal kernel stores through sc16_store (devmath.hpp); clip = nullptr or the caller's [batch] counters of clipped components.
-// Kernels take the format as a template flag and launchers pick it from `on`, so the cf32 instantiations keep their code.
-struct Sc16Out { int on; float scale; uint32_t* clip; };
+// ---- format of the caller's TX buffer (qrl_*_process / qrl_*_process_sc16 / qrl_*_process_sc8) ----
+// fmt = OUT_CF32 (0, what a zeroed block means): `out` is float2.  OUT_SC16: `out` points at packed int16 I, Q pairs (4 bytes per sample, out_stride
+// still in samples) and the terminal kernel stores through sc16_store (devmath.hpp).  OUT_SC8: int8 I, Q pairs (2 bytes per sample, rows 2-byte aligned
+// only) through sc8_store, one 2-byte store per sample.  clip = nullptr or the caller's [batch] counters of clipped components of that format.
+// Kernels take the format as a template parameter and launchers pick it from `fmt`, so the cf32 and sc16 instantiations keep their code.
+enum { OUT_CF32 = 0, OUT_SC16 = 1, OUT_SC8 = 2 };
+struct TxOut { int fmt; float scale; uint32_t* clip; };
 
 // ---- K1: rotator + decimating FIR (rotator_cc + rational_resampler_ccf(1,D)) ----
 struct DecimParams {
@@ -354,14 +356,14 @@ struct SynthParams {
     const float* taps; const float2* twiddle; int M, J;  // taps[i + M j] zero padded to J*M; W[q] = e^{+j 2 pi q / M}
     float level, bb_gain;
     float2* out; size_t out_stride, out_cap;
-    Sc16Out sc;
+    TxOut sc;
 };
 void launch_s2f_in(const S2fInParams& p, int streams, hipStream_t s);
 void launch_scale_c(RingC r, uint64_t q0, uint32_t count, float k, int streams, hipStream_t s);
 void launch_zero_runs(RingC r, const ZeroRun* runs, uint32_t nruns, uint64_t lo, uint64_t hi, hipStream_t s);   // gr_zero_idle_bursts
 void launch_pfb_synth(const SynthParams& p, int batch, hipStream_t s);
-// items [q0, q0 + count) of every ring row, converted, to out[row * out_stride + t] (qrl_synth single carrier: the resampler's ring -> the caller's sc16 buffer)
-void launch_ring_store_sc16(RingC in, uint64_t q0, uint32_t count, uint32_t* out, size_t out_stride, Sc16Out sc, int rows, hipStream_t s);
+// items [q0, q0 + count) of every ring row, converted, to out[row * out_stride + t] (qrl_synth single carrier: the resampler's ring -> the caller's sc16 or sc8 buffer)
+void launch_ring_store_fmt(RingC in, uint64_t q0, uint32_t count, void* out, size_t out_stride, TxOut sc, int rows, hipStream_t s);
 size_t synth_lds_bytes(int M, int J);
 
 // ---- TX: gr_mod_qpsk (kernels_tx.hip) ----
@@ -376,25 +378,25 @@ struct TxInterpParams {
     RingB sym; uint64_t n0; uint32_t count;      // absolute first output sample, outputs of this call
     const float* taps; int nt; int interp; float2 table[4]; float amp, bb_gain;
     float2* out; size_t out_stride;
-    Sc16Out sc;
+    TxOut sc;
 };
 struct TxShapeParams { RingB sym; RingF out; uint64_t n0; uint32_t count; int sps; const float* taps; int nt;   // nt = 0: repeat
                        int levels; float scale; };   // levels 2 | 4; scale 0 = none
 struct TxFmParams { RingF in; RingC out; uint64_t n0; uint32_t count; float k, amp; float* phase; };
 struct TxInterpCParams { RingC in; uint64_t n0; uint32_t count; const float* taps; int nt; int interp; float2* out; size_t out_stride;
-                         int decim; RingC out_ring; Sc16Out sc; };   // out_ring.p != nullptr: the samples go to ring item n0 + t instead of out (gr_mod_am: a filter follows)   // decim > 1: rational_resampler_ccf(interp, decim) (gr_mod_m17: 125 / 3)
+                         int decim; RingC out_ring; TxOut sc; };   // out_ring.p != nullptr: the samples go to ring item n0 + t instead of out (gr_mod_am: a filter follows)   // decim > 1: rational_resampler_ccf(interp, decim) (gr_mod_m17: 125 / 3)
 // k_tx_interp_mfma (kernels_tx_mfma.hip): the back-end interpolator on the f32 matrix pipe.  taps: the layout of tx_mfma_taps (tx_common.cpp),
 // [phase tile][lag][phase in tile], kTxMfmaLags x kTxMfmaPhases floats per tile, zero where ph + lag I >= nt and for phases >= I.
-// in: the rotated 1 Msps ring; sample n0 + c of it, c < n1, gives outputs c I .. c I + I - 1 of this call in out (cf32, or sc16 when sc.on).
+// in: the rotated 1 Msps ring; sample n0 + c of it, c < n1, gives outputs c I .. c I + I - 1 of this call in out (cf32, sc16 or sc8 by sc.fmt).
 constexpr int kTxMfmaPhases = 32, kTxMfmaLags = 210;   // an MFMA tile's rows; lags per phase of low_pass(I, I * 1e6, 480k, 20k, BH) (209 or 210), even
 struct TxInterpMfmaParams { RingC in; uint64_t n0; uint32_t n1; const float* taps; int interp; uint32_t cpw;   // cpw: blocks per workgroup (launcher)
-                            float2* out; size_t out_stride; Sc16Out sc; };
+                            float2* out; size_t out_stride; TxOut sc; };
 void launch_tx_interp_mfma(const TxInterpMfmaParams& p, int batch, hipStream_t s);
 void launch_tx_spread(RingB coded, RingB chips, uint64_t c0, uint32_t ncoded, int batch, hipStream_t s);   // gr_mod_dsss: Barker-13 spreading
 void launch_tx_f2c(RingF in, RingC out, uint64_t n0, uint32_t count, float g, int batch, hipStream_t s);
 void launch_tx_raw_dibits(const uint8_t* bytes, size_t stride, uint32_t nbytes, RingB sym, uint64_t s0, int batch, hipStream_t s);
 struct TxRotParams { const float2* in; size_t in_stride; uint64_t n0; uint32_t count; uint64_t rot_acc, rot_inc, rot_nbase; const float2* rot_lo;
-                     RingC out_ring; float2* out; size_t out_stride; const uint64_t* rot_acc_s; const uint64_t* rot_inc_s; Sc16Out sc; };
+                     RingC out_ring; float2* out; size_t out_stride; const uint64_t* rot_acc_s; const uint64_t* rot_inc_s; TxOut sc; };
 void launch_tx_rot(const TxRotParams& p, int batch, hipStream_t s);
 void launch_tx_shape(const TxShapeParams& p, int batch, hipStream_t s);
 void launch_tx_fm(const TxFmParams& p, int batch, hipStream_t s);
@@ -417,7 +419,7 @@ void launch_dsss_tail(const DsssTailParams& p, int batch, hipStream_t s);
 // ---- analogue voice receivers (kernels_analog.hip) ----
 constexpr int AN_MAX_RAMP = 1024;
 struct FirCccParams { RingC in, out; uint64_t q0; uint32_t count; const float2* taps; int nt; float2* port; size_t port_cap; uint32_t* counts;
-                      Sc16Out sc; };   // sc.on: `port` is the caller's sc16 buffer (gr_mod_am's channel filter as the terminal kernel)
+                      TxOut sc; };   // sc.fmt != OUT_CF32: `port` is the caller's sc16 / sc8 buffer (gr_mod_am's channel filter as the terminal kernel)
 void launch_an_fir_ccc(const FirCccParams& p, int batch, hipStream_t s);
 // g / g_prev: items that passed the gating squelch up to the end of this / the previous call
 struct AnState { double pwr, iir_y, de_y; uint64_t g, g_prev; float2 prev; float iir_x, de_x, gain, env; int state, ramped; };

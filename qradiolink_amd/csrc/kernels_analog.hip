@@ -23,7 +23,7 @@ __device__ __forceinline__ uint64_t an_decim_count(uint64_t n, int I, int D)
 
 // fft_filter_ccc as the direct FIR it implements (AM channel filter, 571 complex taps at 20 ksps): one fmaf chain per component,
 // k ascending, re += hr xr; re += (-hi) xi; im += hr xi; im += hi xr
-template <bool SC>
+template <int FMT>
 __global__ __launch_bounds__(256) void k_an_fir_ccc(const FirCccParams P)
 {
     extern __shared__ float2 an_taps[];
@@ -46,14 +46,16 @@ __global__ __launch_bounds__(256) void k_an_fir_ccc(const FirCccParams P)
     }
     const float2 y = make_float2(ar, ai);
     P.out.p[(size_t)b * (P.out.mask + 1u) + ((uint32_t)n & P.out.mask)] = y;
-    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.port) + (size_t)b * P.port_cap, t, y, t < P.port_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(P.port) + (size_t)b * P.port_cap, t, y, t < P.port_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if constexpr (FMT == OUT_SC8) sc8_store(reinterpret_cast<uint16_t*>(P.port) + (size_t)b * P.port_cap, t, y, t < P.port_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
     else if (P.port && t < P.port_cap) P.port[(size_t)b * P.port_cap + t] = y;
 }
 void launch_an_fir_ccc(const FirCccParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    if (p.sc.on && p.port) hipLaunchKernelGGL(k_an_fir_ccc<true>, dim3((p.count + 255) / 256, batch), dim3(256), (size_t)p.nt * sizeof(float2), s, p);
-    else hipLaunchKernelGGL(k_an_fir_ccc<false>, dim3((p.count + 255) / 256, batch), dim3(256), (size_t)p.nt * sizeof(float2), s, p);
+    const int fmt = p.port ? p.sc.fmt : OUT_CF32;
+    const auto kern = fmt == OUT_SC8 ? k_an_fir_ccc<OUT_SC8> : fmt == OUT_SC16 ? k_an_fir_ccc<OUT_SC16> : k_an_fir_ccc<OUT_CF32>;
+    hipLaunchKernelGGL(kern, dim3((p.count + 255) / 256, batch), dim3(256), (size_t)p.nt * sizeof(float2), s, p);
 }
 
 // KIND 0 NBFM, 1 AM, 2 WBFM, 3 SSB (gr_demod_ssb.cpp:28-81: squelch -> agc2_cc -> cessb clipper, complex items out)

@@ -649,7 +649,7 @@ void launch_zero_runs(RingC r, const ZeroRun* runs, uint32_t nruns, uint64_t lo,
 }
 
 constexpr int SY_TB = 96;   // output blocks per workgroup
-template <bool SC>
+template <int FMT>
 __global__ __launch_bounds__(256) void k_pfb_synth(const SynthParams P)
 {
     extern __shared__ __align__(16) unsigned char sy_smem[];
@@ -684,9 +684,9 @@ __global__ __launch_bounds__(256) void k_pfb_synth(const SynthParams P)
     }
     __syncthreads();
     // branch filters: out[(blk - P.blk0) M + i] = lvl * sum_j h[i + M j] V_i[blk - j]
-    // (SC: every lane runs the same number of trips, so that a wave reaches sc16_store converged and adds its clip count with one atomic; the lanes behind the end
+    // (sc16 / sc8: every lane runs the same number of trips, so that a wave reaches sc16_store / sc8_store converged and adds its clip count with one atomic; the lanes behind the end
     //  compute block 0 again and drop it)
-    for (int w = tid; (SC ? w - tid : w) < nb * M; w += 256) {
+    for (int w = tid; (FMT != OUT_CF32 ? w - tid : w) < nb * M; w += 256) {
         const bool live = w < nb * M;
         const int r = live ? w / M : 0, i = live ? w - r * M : 0;
         const float2* vp = V + (r + J - 1) * (M + 1) + i;
@@ -699,29 +699,33 @@ __global__ __launch_bounds__(256) void k_pfb_synth(const SynthParams P)
         ar *= P.level; ai *= P.level;
         ar *= P.bb_gain; ai *= P.bb_gain;
         const size_t o = (size_t)(blk0 - P.blk0 + r) * M + i;
-        if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, o, make_float2(ar, ai), live && o < P.out_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+        if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, o, make_float2(ar, ai), live && o < P.out_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+        else if constexpr (FMT == OUT_SC8) sc8_store(reinterpret_cast<uint16_t*>(P.out) + (size_t)b * P.out_stride, o, make_float2(ar, ai), live && o < P.out_cap, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
         else if (o < P.out_cap) P.out[(size_t)b * P.out_stride + o] = make_float2(ar, ai);
     }
 }
 // single-carrier qrl_synth: the 250 ksps signal is the resampler's ring (k_resamp is shared with the receivers and stays as it is)
-__global__ __launch_bounds__(256) void k_ring_store_sc16(RingC in, uint64_t q0, uint32_t count, uint32_t* out, size_t out_stride, Sc16Out sc)
+template <int FMT>
+__global__ __launch_bounds__(256) void k_ring_store_fmt(RingC in, uint64_t q0, uint32_t count, void* out, size_t out_stride, TxOut sc)
 {
+    static_assert(FMT == OUT_SC16 || FMT == OUT_SC8, "cf32 leaves through k_resamp's port");
     const int b = blockIdx.y;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= count) return;
     const float2 v = in.p[(size_t)b * (in.mask + 1u) + ((uint32_t)(q0 + t) & in.mask)];
-    sc16_store(out + (size_t)b * out_stride, t, v, true, sc.scale, sc.clip ? sc.clip + b : nullptr);
+    if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(out) + (size_t)b * out_stride, t, v, true, sc.scale, sc.clip ? sc.clip + b : nullptr);
+    else sc8_store(reinterpret_cast<uint16_t*>(out) + (size_t)b * out_stride, t, v, true, sc.scale, sc.clip ? sc.clip + b : nullptr);
 }
-void launch_ring_store_sc16(RingC in, uint64_t q0, uint32_t count, uint32_t* out, size_t out_stride, Sc16Out sc, int rows, hipStream_t s)
+void launch_ring_store_fmt(RingC in, uint64_t q0, uint32_t count, void* out, size_t out_stride, TxOut sc, int rows, hipStream_t s)
 {
     if (!count) return;
-    hipLaunchKernelGGL(k_ring_store_sc16, dim3((count + 255) / 256, rows), dim3(256), 0, s, in, q0, count, out, out_stride, sc);
+    hipLaunchKernelGGL(sc.fmt == OUT_SC8 ? k_ring_store_fmt<OUT_SC8> : k_ring_store_fmt<OUT_SC16>, dim3((count + 255) / 256, rows), dim3(256), 0, s, in, q0, count, out, out_stride, sc);
 }
 size_t synth_lds_bytes(int M, int J) { return (size_t)((SY_TB + J - 1) * (M + 1) + M) * sizeof(float2) + (size_t)J * M * sizeof(float); }
 void launch_pfb_synth(const SynthParams& p, int batch, hipStream_t s)
 {
     if (!p.nblk) return;
-    const auto kern = p.sc.on ? k_pfb_synth<true> : k_pfb_synth<false>;
+    const auto kern = p.sc.fmt == OUT_SC8 ? k_pfb_synth<OUT_SC8> : p.sc.fmt == OUT_SC16 ? k_pfb_synth<OUT_SC16> : k_pfb_synth<OUT_CF32>;
     if (dyn_lds_limit(reinterpret_cast<const void*>(kern), 160 * 1024) != hipSuccess) return;
     hipLaunchKernelGGL(kern, dim3((p.nblk + SY_TB - 1) / SY_TB, batch), dim3(256), synth_lds_bytes(p.M, p.J), s, p);
 }

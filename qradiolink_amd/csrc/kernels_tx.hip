@@ -184,7 +184,7 @@ void launch_tx_qpsk_bits(const TxBitsParams& p, int batch, hipStream_t s)
     hipLaunchKernelGGL(k_tx_qpsk_bits, dim3(batch), dim3(64), lds, s, p);
 }
 
-template <bool SC>
+template <int FMT>
 __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
 {
     __shared__ float taps_s[256];
@@ -209,7 +209,8 @@ __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
     }
     ar *= P.amp; ai *= P.amp;                          // multiply_const_cc(0.6)
     ar *= P.bb_gain; ai *= P.bb_gain;                  // multiply_const_cc(bb_gain)
-    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if constexpr (FMT == OUT_SC8) sc8_store(reinterpret_cast<uint16_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
     else P.out[(size_t)b * P.out_stride + t] = make_float2(ar, ai);
 }
 
@@ -218,8 +219,8 @@ __global__ __launch_bounds__(256) void k_tx_interp(const TxInterpParams P)
 // ~16 byte loads and ~16 table loads per output sample (C5: 4.7 ms for 268 M samples, 0.45 TB/s of stores); the taps are scalar
 // operands (round 4: they were LDS broadcasts, 64 ds_reads per thread beside 64 packed fmas).
 // Same fmaf chain per output (j ascending); the zero-padded taps / the zero symbols in front of the stream add +0.
-// SC: the packed int16 pair is made where the ordered store reads ys[][] (256 contiguous bytes per wave and store instruction).
-template <int I, int J, bool SC>
+// OUT_SC16 / OUT_SC8: the packed pair is made where the ordered store reads ys[][] (256 / 128 contiguous bytes per wave and store instruction).
+template <int I, int J, int FMT>
 __global__ __launch_bounds__(256) void k_tx_interp_sym(const TxInterpParams P)
 {
     __shared__ float2 xs[256 + J];
@@ -258,7 +259,7 @@ __global__ __launch_bounds__(256) void k_tx_interp_sym(const TxInterpParams P)
     // 32-byte stride.  Through the LDS they leave in order, 512 contiguous bytes per store instruction (k_dec2_fir: same finding).
     float2* o = P.out + (size_t)b * P.out_stride + (size_t)s0 * I;
     const uint32_t nout = (nsym > s0 ? (nsym - s0 < 256u ? nsym - s0 : 256u) : 0u) * (uint32_t)I;
-    if constexpr (SC) {
+    if constexpr (FMT == OUT_SC16) {
         uint32_t* o16 = reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride + (size_t)s0 * I;
         uint32_t* clip = P.sc.clip ? P.sc.clip + b : nullptr;
 #pragma unroll
@@ -266,6 +267,15 @@ __global__ __launch_bounds__(256) void k_tx_interp_sym(const TxInterpParams P)
             const uint32_t idx = (uint32_t)tid + 256u * k;
             const bool ok = idx < nout;                           // (ys[] behind nout was never written: read column 0 there, the value is dropped)
             sc16_store(o16, idx, ys[idx % I][ok ? idx / I : 0u], ok, P.sc.scale, clip);
+        }
+    } else if constexpr (FMT == OUT_SC8) {
+        uint16_t* o8 = reinterpret_cast<uint16_t*>(P.out) + (size_t)b * P.out_stride + (size_t)s0 * I;
+        uint32_t* clip = P.sc.clip ? P.sc.clip + b : nullptr;
+#pragma unroll
+        for (int k = 0; k < I; ++k) {
+            const uint32_t idx = (uint32_t)tid + 256u * k;
+            const bool ok = idx < nout;
+            sc8_store(o8, idx, ys[idx % I][ok ? idx / I : 0u], ok, P.sc.scale, clip);
         }
     } else {
 #pragma unroll
@@ -281,12 +291,12 @@ void launch_tx_interp(const TxInterpParams& p, int batch, hipStream_t s)
     if (!p.count) return;
     if (p.interp == 4 && p.nt <= 64 && p.n0 % 4 == 0 && p.count % 4 == 0) {
         const dim3 grid((p.count / 4 + 255) / 256, batch);
-        if (p.sc.on) hipLaunchKernelGGL((k_tx_interp_sym<4, 16, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_tx_interp_sym<4, 16, false>), grid, dim3(256), 0, s, p);
+        const auto kern = p.sc.fmt == OUT_SC8 ? k_tx_interp_sym<4, 16, OUT_SC8> : p.sc.fmt == OUT_SC16 ? k_tx_interp_sym<4, 16, OUT_SC16> : k_tx_interp_sym<4, 16, OUT_CF32>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, p);
         return;
     }
-    if (p.sc.on) hipLaunchKernelGGL(k_tx_interp<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(k_tx_interp<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    const auto kern = p.sc.fmt == OUT_SC8 ? k_tx_interp<OUT_SC8> : p.sc.fmt == OUT_SC16 ? k_tx_interp<OUT_SC16> : k_tx_interp<OUT_CF32>;
+    hipLaunchKernelGGL(kern, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 // ---- FSK family (gr_mod_2fsk.cpp:63-99, gr_mod_gmsk.cpp:68-95):
@@ -370,7 +380,7 @@ void launch_tx_fm(const TxFmParams& p, int batch, hipStream_t s)
     hipLaunchKernelGGL(k_tx_fm, dim3((batch + 63) / 64), dim3(64), 0, s, p, batch);
 }
 
-template <bool SC>
+template <int FMT>
 __global__ __launch_bounds__(256) void k_tx_interp_c(const TxInterpCParams P)
 {
     __shared__ float taps_s[2048];
@@ -394,7 +404,8 @@ __global__ __launch_bounds__(256) void k_tx_interp_c(const TxInterpCParams P)
         ar = fmaf(h, x.x, ar);
         ai = fmaf(h, x.y, ai);
     }
-    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if constexpr (FMT == OUT_SC8) sc8_store(reinterpret_cast<uint16_t*>(P.out) + (size_t)b * P.out_stride, t, make_float2(ar, ai), true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
     else if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = make_float2(ar, ai);
     else P.out[(size_t)b * P.out_stride + t] = make_float2(ar, ai);
 }
@@ -448,13 +459,14 @@ void launch_tx_f2c(RingF in, RingC out, uint64_t n0, uint32_t count, float g, in
 void launch_tx_interp_c(const TxInterpCParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    if (p.sc.on && !p.out_ring.p) hipLaunchKernelGGL(k_tx_interp_c<true>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(k_tx_interp_c<false>, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
+    const int fmt = p.out_ring.p ? OUT_CF32 : p.sc.fmt;   // a ring is never the caller's buffer
+    const auto kern = fmt == OUT_SC8 ? k_tx_interp_c<OUT_SC8> : fmt == OUT_SC16 ? k_tx_interp_c<OUT_SC16> : k_tx_interp_c<OUT_CF32>;
+    hipLaunchKernelGGL(kern, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 
 // ---- gr_mod_base back end (reference src/gr/gr_mod_base.cpp:38,249-258): rotator_cc(2 pi offset / 1e6) at 1 Msps, then
 // rational_resampler_ccf(fs/1e6, 1, low_pass(I, fs, 480k, 20k, BH)) (k_tx_interp_c).  Exact 2^-64-turn NCO as on RX.
-template <bool PS, bool SC>
+template <bool PS, int FMT>
 __global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P_)
 {
     ROT_VIEW(TxRotParams, PS, P, P_, blockIdx.y);
@@ -466,15 +478,17 @@ __global__ __launch_bounds__(256) void k_tx_rot(const TxRotParams P_)
     const uint64_t kk = n - P.rot_nbase;
     const float2 hi = sincos_turn(P.rot_acc + ((kk >> 9) << 9) * P.rot_inc);
     const float2 y = cmul_fma(x, cmul_fma(hi, P.rot_lo[(uint32_t)kk & 511u]));
-    if constexpr (SC) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, y, true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    if constexpr (FMT == OUT_SC16) sc16_store(reinterpret_cast<uint32_t*>(P.out) + (size_t)b * P.out_stride, t, y, true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
+    else if constexpr (FMT == OUT_SC8) sc8_store(reinterpret_cast<uint16_t*>(P.out) + (size_t)b * P.out_stride, t, y, true, P.sc.scale, P.sc.clip ? P.sc.clip + b : nullptr);
     else if (P.out_ring.p) P.out_ring.p[(size_t)b * (P.out_ring.mask + 1u) + ((uint32_t)n & P.out_ring.mask)] = y;
     else P.out[(size_t)b * P.out_stride + t] = y;
 }
 void launch_tx_rot(const TxRotParams& p, int batch, hipStream_t s)
 {
     if (!p.count) return;
-    const bool sc = p.sc.on && !p.out_ring.p;   // the offset-only back end: the rotator is the terminal kernel
-    const auto kern = p.rot_acc_s ? (sc ? k_tx_rot<true, true> : k_tx_rot<true, false>) : (sc ? k_tx_rot<false, true> : k_tx_rot<false, false>);
+    const int fmt = p.out_ring.p ? OUT_CF32 : p.sc.fmt;   // the offset-only back end: the rotator is the terminal kernel
+    const auto kern = p.rot_acc_s ? (fmt == OUT_SC8 ? k_tx_rot<true, OUT_SC8> : fmt == OUT_SC16 ? k_tx_rot<true, OUT_SC16> : k_tx_rot<true, OUT_CF32>)
+                                  : (fmt == OUT_SC8 ? k_tx_rot<false, OUT_SC8> : fmt == OUT_SC16 ? k_tx_rot<false, OUT_SC16> : k_tx_rot<false, OUT_CF32>);
     hipLaunchKernelGGL(kern, dim3((p.count + 255) / 256, batch), dim3(256), 0, s, p);
 }
 

@@ -19,7 +19,7 @@
 // once and walks `cpw` blocks of 128 ring samples; per block the window c0 - 210 .. c0 + 127 of the ring goes to LDS once (re plane, im
 // plane) and each of the 4 waves computes one 32 phases x 32 samples tile: 2 x 105 MFMAs, 3 ds_read_b32 per MFMA pair.
 // Store: direct from the accumulators.  A lane holds, for one c, four groups of four consecutive phases = four runs of 32 contiguous
-// bytes (cf32) or 16 (sc16); the two lane halves hold the two halves of a 64-byte run, and a wave's stores of one tile fill 32 runs of
+// bytes (cf32), 16 (sc16) or 8 (sc8, as four 2-byte stores); the two lane halves hold the two halves of a 64-byte run, and a wave's stores of one tile fill 32 runs of
 // 256 contiguous bytes (32 phases of one c), which the L2 merges before they leave for HBM.  Partial c-tiles and phase tiles are computed
 // padded and their stores predicated per element.
 #include <algorithm>
@@ -33,7 +33,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int TXM_CB = 128;                          // ring samples per block: 4 waves x 32 columns
 constexpr int TXM_WIN = TXM_CB + kTxMfmaLags;        // the block's window of the ring
 
-template <bool SC>
+template <int FMT>
 __global__ __launch_bounds__(256) void k_tx_interp_mfma(const TxInterpMfmaParams P)
 {
     __shared__ __align__(16) float taps_s[kTxMfmaLags * kTxMfmaPhases];
@@ -83,9 +83,13 @@ __global__ __launch_bounds__(256) void k_tx_interp_mfma(const TxInterpMfmaParams
                 for (int r = 0; r < 4; ++r) {
                     if (ph0 + r < I) {
                         const float2 y = make_float2(ar[4 * g + r], ai[4 * g + r]);
-                        if constexpr (SC) {
+                        if constexpr (FMT == OUT_SC16) {
                             uint32_t nc;
                             reinterpret_cast<uint32_t*>(P.out)[(size_t)b * P.out_stride + t0 + (size_t)(ph0 + r)] = f2_to_sc16(y, P.sc.scale, nc);
+                            nclip += nc;
+                        } else if constexpr (FMT == OUT_SC8) {
+                            uint32_t nc;
+                            reinterpret_cast<uint16_t*>(P.out)[(size_t)b * P.out_stride + t0 + (size_t)(ph0 + r)] = f2_to_sc8(y, P.sc.scale, nc);
                             nclip += nc;
                         } else {
                             P.out[(size_t)b * P.out_stride + t0 + (size_t)(ph0 + r)] = y;
@@ -95,7 +99,7 @@ __global__ __launch_bounds__(256) void k_tx_interp_mfma(const TxInterpMfmaParams
             }
         }
     }
-    if constexpr (SC) {
+    if constexpr (FMT != OUT_CF32) {
         // clipped components of everything this wave stored: one atomic per wave, none when nothing clipped
         if (P.sc.clip) {
 #pragma unroll
@@ -114,8 +118,8 @@ void launch_tx_interp_mfma(const TxInterpMfmaParams& p, int batch, hipStream_t s
     const uint64_t total = (uint64_t)nblk * (uint64_t)batch * ptiles;
     q.cpw = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, total / 4096));
     const dim3 grid((nblk + q.cpw - 1) / q.cpw, batch, ptiles);
-    if (p.sc.on) hipLaunchKernelGGL(k_tx_interp_mfma<true>, grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL(k_tx_interp_mfma<false>, grid, dim3(256), 0, s, q);
+    const auto kern = p.sc.fmt == OUT_SC8 ? k_tx_interp_mfma<OUT_SC8> : p.sc.fmt == OUT_SC16 ? k_tx_interp_mfma<OUT_SC16> : k_tx_interp_mfma<OUT_CF32>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q);
 }
 
 }  // namespace qrl

@@ -16,6 +16,7 @@ struct qrl_synth {
     uint32_t m1 = 0, m25 = 0; uint64_t n1 = 0, n25 = 0;
     int port_chan[16];
     Sc16Sink sc;     // qrl_synth_process_sc16
+    Sc8Sink sc8;    // qrl_synth_process_sc8
     ZeroRuns zero;   // gr_zero_idle_bursts (qrl_synth_add_zero_runs)
     int reset_state() {
         if (rA.zero() || rB.zero() || rC.zero() || rD.zero() || phase.zero()) return QRL_ERR_HIP;
@@ -94,8 +95,8 @@ size_t qrl_synth_out_cap(const qrl_synth* h, size_t n) { return h ? (n * h->rs_I
 
 }  // extern "C"
 
-// qrl_synth_process / qrl_synth_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out)
-static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, void* iq, size_t out_stride, size_t* produced, const Sc16Out sc)
+// qrl_synth_process / qrl_synth_process_sc16 / qrl_synth_process_sc8: `sc` is the format of `iq` (cf32: a zeroed TxOut)
+static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, void* iq, size_t out_stride, size_t* produced, const TxOut sc)
 {
     if (!h || (!in && n) || (!iq && n)) return QRL_ERR_ARG;
     if (n > h->cfg.max_samples) return qrl_set_error(QRL_ERR_TOO_BIG, "n exceeds max_samples");
@@ -119,11 +120,11 @@ static int synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t 
     if (h->single) launch_scale_c(ff.out, h->n1, c1, h->bb_gain, S, h->stream);                      // gr_mod_mmdvm.cpp:59-61: bb gain BEFORE the resampler
     ResampParams rp{}; rp.in = nullptr; rp.in_ring = ff.out; rp.n0 = h->n1; rp.n = c1;
     rp.out = RingC{h->rD.p, h->m25}; rp.q0 = h->n25; rp.q_count = c25; rp.taps = h->rs_taps.p; rp.I = h->rs_I; rp.D = h->rs_D; rp.Jp = h->rs_Jp;
-    if (h->single && !sc.on) { rp.port = reinterpret_cast<float2*>(iq); rp.port_cap = out_stride; }   // the resampler output IS the 250 ksps signal
+    if (h->single && !sc.fmt) { rp.port = reinterpret_cast<float2*>(iq); rp.port_cap = out_stride; }   // the resampler output IS the 250 ksps signal
     launch_resamp(rp, S, h->stream);
     if (h->single) {
-        // sc16: k_resamp is shared with the receivers and keeps its code; its ring row of this call is converted by a kernel of its own
-        if (sc.on) launch_ring_store_sc16(rp.out, h->n25, (uint32_t)std::min<size_t>(c25, out_stride), reinterpret_cast<uint32_t*>(iq), out_stride, sc, S, h->stream);
+        // sc16 / sc8: k_resamp is shared with the receivers and keeps its code; its ring row of this call is converted by a kernel of its own
+        if (sc.fmt) launch_ring_store_fmt(rp.out, h->n25, (uint32_t)std::min<size_t>(c25, out_stride), iq, out_stride, sc, S, h->stream);
         HIPCHK(hipGetLastError());
         if (qrl::take_launch_error()) return QRL_ERR_HIP;
         h->n1 = n1_1; h->n25 = n25_1;
@@ -147,16 +148,24 @@ extern "C" {
 
 int qrl_synth_process(qrl_synth* h, const int16_t* in, size_t stride, size_t n, float* iq, size_t out_stride, size_t* produced)
 {
-    return synth_process(h, in, stride, n, iq, out_stride, produced, Sc16Out{});
+    return synth_process(h, in, stride, n, iq, out_stride, produced, TxOut{});
 }
 int qrl_synth_process_sc16(qrl_synth* h, const int16_t* in, size_t stride, size_t n, int16_t* iq, size_t out_stride, size_t* produced)
 {
-    Sc16Out sc;
+    TxOut sc;
     if (int r = h ? h->sc.for_call("qrl_synth_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
     return synth_process(h, in, stride, n, iq, out_stride, produced, sc);
 }
 int qrl_synth_set_sc16_scale(qrl_synth* h, float scale) { return h ? h->sc.set_scale("qrl_synth_set_sc16_scale", scale) : QRL_ERR_ARG; }
 int qrl_synth_set_sc16_clip_counts(qrl_synth* h, uint32_t* counts) { return h ? h->sc.set_clip(counts) : QRL_ERR_ARG; }
+int qrl_synth_process_sc8(qrl_synth* h, const int16_t* in, size_t stride, size_t n, int8_t* iq, size_t out_stride, size_t* produced)
+{
+    TxOut sc;
+    if (int r = h ? h->sc8.for_call("qrl_synth_process_sc8", iq, sc) : QRL_ERR_ARG) return r;
+    return synth_process(h, in, stride, n, iq, out_stride, produced, sc);
+}
+int qrl_synth_set_sc8_scale(qrl_synth* h, float scale) { return h ? h->sc8.set_scale("qrl_synth_set_sc8_scale", scale) : QRL_ERR_ARG; }
+int qrl_synth_set_sc8_clip_counts(qrl_synth* h, uint32_t* counts) { return h ? h->sc8.set_clip(counts) : QRL_ERR_ARG; }
 int qrl_synth_sync(qrl_synth* h)
 {
     if (!h) return QRL_ERR_ARG;

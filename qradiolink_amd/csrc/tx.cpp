@@ -34,6 +34,7 @@ struct qrl_mod {
     uint64_t nsym = 0;   // symbols (= input bits) so far
     TxBackEnd be;   // gr_mod_base back end (gr_mod_base.cpp:38,215-258): rotator at 1 Msps, then interpolation to the device rate
     Sc16Sink sc;    // qrl_mod_process_sc16
+    Sc8Sink sc8;    // qrl_mod_process_sc8
     size_t spb_1msps() const   // 1 Msps samples per byte of the chains that may have a back end; 0 for m17 / dmr / dsss, which have none
     { return m17 || dsss ? 0 : fsk4 ? (size_t)8 * sps * interp2 : fam == F_FSK ? (size_t)16 * sps * interp2 : (size_t)(bpsk ? 16 : 8) * sps; }
     int init_state() {
@@ -264,8 +265,8 @@ size_t qrl_mod_samples_per_byte(const qrl_mod* m)
 
 }  // extern "C"
 
-// qrl_mod_process / qrl_mod_process_sc16: `sc` is the format of `iq` (cf32: a zeroed Sc16Out).  Only the kernel that stores to `iq` sees it.
-static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, void* iq, size_t out_stride, const Sc16Out sc)
+// qrl_mod_process / qrl_mod_process_sc16 / qrl_mod_process_sc8: `sc` is the format of `iq` (cf32: a zeroed TxOut).  Only the kernel that stores to `iq` sees it.
+static int mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, void* iq, size_t out_stride, const TxOut sc)
 {
     if (!m || (!bytes && nbytes) || (!iq && nbytes)) return QRL_ERR_ARG;
     if (nbytes > m->cfg.max_bytes) return qrl_set_error(QRL_ERR_TOO_BIG, "nbytes exceeds max_bytes");
@@ -370,16 +371,24 @@ extern "C" {
 
 int qrl_mod_process(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, float* iq, size_t out_stride)
 {
-    return mod_process(m, bytes, stride, nbytes, iq, out_stride, Sc16Out{});
+    return mod_process(m, bytes, stride, nbytes, iq, out_stride, TxOut{});
 }
 int qrl_mod_process_sc16(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int16_t* iq, size_t out_stride)
 {
-    Sc16Out sc;
+    TxOut sc;
     if (int r = m ? m->sc.for_call("qrl_mod_process_sc16", iq, sc) : QRL_ERR_ARG) return r;
     return mod_process(m, bytes, stride, nbytes, iq, out_stride, sc);
 }
 int qrl_mod_set_sc16_scale(qrl_mod* m, float scale) { return m ? m->sc.set_scale("qrl_mod_set_sc16_scale", scale) : QRL_ERR_ARG; }
 int qrl_mod_set_sc16_clip_counts(qrl_mod* m, uint32_t* counts) { return m ? m->sc.set_clip(counts) : QRL_ERR_ARG; }
+int qrl_mod_process_sc8(qrl_mod* m, const uint8_t* bytes, size_t stride, size_t nbytes, int8_t* iq, size_t out_stride)
+{
+    TxOut sc;
+    if (int r = m ? m->sc8.for_call("qrl_mod_process_sc8", iq, sc) : QRL_ERR_ARG) return r;
+    return mod_process(m, bytes, stride, nbytes, iq, out_stride, sc);
+}
+int qrl_mod_set_sc8_scale(qrl_mod* m, float scale) { return m ? m->sc8.set_scale("qrl_mod_set_sc8_scale", scale) : QRL_ERR_ARG; }
+int qrl_mod_set_sc8_clip_counts(qrl_mod* m, uint32_t* counts) { return m ? m->sc8.set_clip(counts) : QRL_ERR_ARG; }
 int qrl_mod_sync(qrl_mod* m)
 {
     if (!m) return QRL_ERR_ARG;

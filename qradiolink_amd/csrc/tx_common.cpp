@@ -63,7 +63,7 @@ int TxBackEnd::retune_streams(const double* hz, int batch, hipStream_t s)
     HIPCHK(hipStreamSynchronize(s));
     return rot.retune_streams(n_bb, ni, s);
 }
-void TxBackEnd::run(uint32_t n1, void* iq, size_t out_stride, Sc16Out sc, int batch, hipStream_t s)
+void TxBackEnd::run(uint32_t n1, void* iq, size_t out_stride, TxOut sc, int batch, hipStream_t s)
 {
     if (!on_ || !n1) return;
     TxRotParams rp{}; rp.in = bb.p; rp.in_stride = bb_stride; rp.n0 = n_bb; rp.count = n1;

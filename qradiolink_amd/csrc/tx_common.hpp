@@ -1,5 +1,5 @@
-// tx_common.hpp — what the transmitters (tx.cpp, amod.cpp, synth.cpp) share on the host side: the gr_mod_base back end, the sc16 output
-// sink and the device step of the gr_zero_idle_bursts run list.  Host only, like host_common.hpp.
+// tx_common.hpp — what the transmitters (tx.cpp, amod.cpp, synth.cpp) share on the host side: the gr_mod_base back end, the sc16 and sc8
+// output sinks and the device step of the gr_zero_idle_bursts run list.  Host only, like host_common.hpp.
 #pragma once
 #include "host_common.hpp"
 
@@ -26,13 +26,13 @@ struct TxBackEnd {
     int retune(double hz, hipStream_t s);
     int retune_streams(const double* hz, int batch, hipStream_t s);
     // where the chain's last kernel stores and in which format: the caller's buffer, or bb (cf32) when the back end is on
-    struct Target { float2* out; size_t stride; Sc16Out sc; };
-    Target target(void* iq, size_t out_stride, Sc16Out sc) const
+    struct Target { float2* out; size_t stride; TxOut sc; };
+    Target target(void* iq, size_t out_stride, TxOut sc) const
     {
-        return on_ ? Target{bb.p, bb_stride, Sc16Out{}} : Target{reinterpret_cast<float2*>(iq), out_stride, sc};
+        return on_ ? Target{bb.p, bb_stride, TxOut{}} : Target{reinterpret_cast<float2*>(iq), out_stride, sc};
     }
     // n1 samples per stream at 1 Msps are in bb: rotator (+ interpolator) to iq.  Nothing when the back end is off or n1 = 0.
-    void run(uint32_t n1, void* iq, size_t out_stride, Sc16Out sc, int batch, hipStream_t s);
+    void run(uint32_t n1, void* iq, size_t out_stride, TxOut sc, int batch, hipStream_t s);
     int interp() const { return interp_; }   // device samples per 1 Msps sample
 private:
     const char* noun_ = "";
@@ -48,10 +48,23 @@ struct Sc16Sink {
     float scale = 32767.0f; uint32_t* clip = nullptr;
     int set_scale(const char* who, float v) { if (!sc16_scale_ok(who, v)) return QRL_ERR_ARG; scale = v; return QRL_OK; }
     int set_clip(uint32_t* counts) { clip = counts; return QRL_OK; }
-    int for_call(const char* who, const void* iq, Sc16Out& out) const
+    int for_call(const char* who, const void* iq, TxOut& out) const
     {
         if (reinterpret_cast<uintptr_t>(iq) & 3u) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": iq must be 4-byte aligned (one packed store per sample)");
-        out = Sc16Out{1, scale, clip};
+        out = TxOut{OUT_SC16, scale, clip};
+        return QRL_OK;
+    }
+};
+
+// qrl_*_process_sc8 of a transmitter: a scale and clip counters of its own beside the sc16 ones; a sample is one 2-byte store
+struct Sc8Sink {
+    float scale = 127.0f; uint32_t* clip = nullptr;
+    int set_scale(const char* who, float v) { if (!sc16_scale_ok(who, v)) return QRL_ERR_ARG; scale = v; return QRL_OK; }
+    int set_clip(uint32_t* counts) { clip = counts; return QRL_OK; }
+    int for_call(const char* who, const void* iq, TxOut& out) const
+    {
+        if (reinterpret_cast<uintptr_t>(iq) & 1u) return qrl_set_error(QRL_ERR_ARG, std::string(who) + ": iq must be 2-byte aligned (one 2-byte store per sample)");
+        out = TxOut{OUT_SC8, scale, clip};
         return QRL_OK;
     }
 };

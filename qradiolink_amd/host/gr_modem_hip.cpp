@@ -755,6 +755,8 @@ void gr_mod_base_hip::open()
         if (d_mode == QRL_MODEM_CW600USB && d_cw_key) chk(qrl_amod_set_cw_k(h, 1), "qrl_amod_set_cw_k");
         chk(qrl_amod_set_sc16_scale(h, d_sc16_scale), "qrl_amod_set_sc16_scale");
         chk(qrl_amod_set_sc16_clip_counts(h, d_clip.get()), "qrl_amod_set_sc16_clip_counts");
+        chk(qrl_amod_set_sc8_scale(h, d_sc8_scale), "qrl_amod_set_sc8_scale");
+        chk(qrl_amod_set_sc8_clip_counts(h, d_clip.get()), "qrl_amod_set_sc8_clip_counts");   // a pass has one format: the counters are shared
         naudio.alloc((size_t)d_n * d_max);
         niq.alloc(2 * (size_t)d_n * qrl_amod_out_cap(h, d_max));   // interleaved cf32
     } else {
@@ -766,6 +768,8 @@ void gr_mod_base_hip::open()
         nh.reset(h);
         chk(qrl_mod_set_sc16_scale(h, d_sc16_scale), "qrl_mod_set_sc16_scale");
         chk(qrl_mod_set_sc16_clip_counts(h, d_clip.get()), "qrl_mod_set_sc16_clip_counts");
+        chk(qrl_mod_set_sc8_scale(h, d_sc8_scale), "qrl_mod_set_sc8_scale");
+        chk(qrl_mod_set_sc8_clip_counts(h, d_clip.get()), "qrl_mod_set_sc8_clip_counts");   // a pass has one format: the counters are shared
         if (d_per_stream && backend && tx_mode_has_back_end(d_mode)) chk(qrl_mod_set_carrier_offsets(h, d_offsets.data()), "qrl_mod_set_carrier_offsets");
         nbytes.alloc((size_t)d_n * d_max);
         spblock = qrl_mod_samples_per_block(h, &bpb);     // M17: 2500 samples per 3 bytes; every other mode: samples per byte, 1
@@ -1078,31 +1082,43 @@ void gr_mod_base_hip::set_sc16_scale(float scale)
     if (d_h.get()) chk(qrl_mod_set_sc16_scale(d_h.get(), scale), "qrl_mod_set_sc16_scale");
     if (d_ah.get()) chk(qrl_amod_set_sc16_scale(d_ah.get(), scale), "qrl_amod_set_sc16_scale");
 }
+// int8 I/Q out (out[s] = interleaved int8 I, Q pairs, what a HackRF takes): qrl_mod_process_sc8 / qrl_amod_process_sc8, 2 bytes per sample downloaded
+void gr_mod_base_hip::set_sc8_scale(float scale)
+{
+    std::lock_guard<std::recursive_mutex> hg(d_hmutex);
+    if (!std::isfinite(scale) || scale == 0.0f) throw std::invalid_argument("gr_mod_base_hip::set_sc8_scale: finite, non-zero");
+    d_sc8_scale = scale;
+    if (d_h.get()) chk(qrl_mod_set_sc8_scale(d_h.get(), scale), "qrl_mod_set_sc8_scale");
+    if (d_ah.get()) chk(qrl_amod_set_sc8_scale(d_ah.get(), scale), "qrl_amod_set_sc8_scale");
+}
 uint64_t gr_mod_base_hip::clipped(int stream) const
 {
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // work() adds to the totals under this lock: another thread may poll
     return d_clipped.at((size_t)stream);
 }
-size_t gr_mod_base_hip::work(gr_complex* const* out) { return work_any(reinterpret_cast<void* const*>(out), false); }
-size_t gr_mod_base_hip::work(int16_t* const* out) { return work_any(reinterpret_cast<void* const*>(out), true); }
-size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
+size_t gr_mod_base_hip::work(gr_complex* const* out) { return work_any(reinterpret_cast<void* const*>(out), FMT_CF32); }
+size_t gr_mod_base_hip::work(int16_t* const* out) { return work_any(reinterpret_cast<void* const*>(out), FMT_SC16); }
+size_t gr_mod_base_hip::work(int8_t* const* out) { return work_any(reinterpret_cast<void* const*>(out), FMT_SC8); }
+size_t gr_mod_base_hip::work_any(void* const* out, int fmt)
 {
-    const size_t sb = sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the row pitch stays `stride` samples
+    const bool sc16 = fmt == FMT_SC16, sc8 = fmt == FMT_SC8;
+    const size_t sb = sc8 ? 2 * sizeof(int8_t) : sc16 ? 2 * sizeof(int16_t) : sizeof(gr_complex);   // bytes per sample; the row pitch stays `stride` samples
     // one call of the open analogue handle into d_iq, in the format asked for
     auto amod = [&](const float* audio, size_t astride, size_t n, size_t stride) {
         if (sc16) chk(qrl_amod_process_sc16(d_ah.get(), audio, astride, n, reinterpret_cast<int16_t*>(d_iq.get()), stride), "qrl_amod_process_sc16");
+        else if (sc8) chk(qrl_amod_process_sc8(d_ah.get(), audio, astride, n, reinterpret_cast<int8_t*>(d_iq.get()), stride), "qrl_amod_process_sc8");
         else chk(qrl_amod_process(d_ah.get(), audio, astride, n, d_iq.get(), stride), "qrl_amod_process");
     };
-    // the samples of every stream, and for int16 the clip counters of this pass
+    // the samples of every stream, and for int16 / int8 the clip counters of this pass
     auto download = [&](size_t ns, size_t stride) {
         for (int s = 0; s < d_n && ns; ++s)
             hchk(hipMemcpy(out[s], reinterpret_cast<const char*>(d_iq.get()) + (size_t)s * stride * sb, ns * sb, hipMemcpyDeviceToHost), "D2H");
-        if (!sc16) return;
+        if (!sc16 && !sc8) return;
         std::vector<uint32_t> c((size_t)d_n);
         hchk(hipMemcpy(c.data(), d_clip.get(), c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H");
         for (int s = 0; s < d_n; ++s) d_clipped[(size_t)s] += c[(size_t)s];
     };
-    auto zero_clip = [&](hipStream_t ms) { if (sc16) hchk(hipMemsetAsync(d_clip.get(), 0, (size_t)d_n * sizeof(uint32_t), ms), "hipMemsetAsync"); };
+    auto zero_clip = [&](hipStream_t ms) { if (sc16 || sc8) hchk(hipMemsetAsync(d_clip.get(), 0, (size_t)d_n * sizeof(uint32_t), ms), "hipMemsetAsync"); };
 
     std::lock_guard<std::recursive_mutex> hg(d_hmutex);   // the handle and its zero-run list for the whole pass; the byte / audio queues stay under d_mutex
     if (d_ah && d_mode == QRL_MODEM_CW600USB) {   // the tone source lives on the device: nothing to upload
@@ -1160,6 +1176,7 @@ size_t gr_mod_base_hip::work_any(void* const* out, bool sc16)
     const size_t ns = nb / d_bpb * d_spblock, stride = (d_max / d_bpb + 1) * d_spblock;
     zero_clip(ms);
     if (sc16) chk(qrl_mod_process_sc16(d_h.get(), d_bytes.get(), d_max, nb, reinterpret_cast<int16_t*>(d_iq.get()), stride), "qrl_mod_process_sc16");
+    else if (sc8) chk(qrl_mod_process_sc8(d_h.get(), d_bytes.get(), d_max, nb, reinterpret_cast<int8_t*>(d_iq.get()), stride), "qrl_mod_process_sc8");
     else chk(qrl_mod_process(d_h.get(), d_bytes.get(), d_max, nb, d_iq.get(), stride), "qrl_mod_process");
     chk(qrl_mod_sync(d_h.get()), "qrl_mod_sync");
     download(ns, stride);

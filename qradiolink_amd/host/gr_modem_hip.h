@@ -253,6 +253,10 @@ public:
     // clipped(s): components of stream s that saturated in the int16 passes since construction (I and Q counted separately), read back with the samples.
     size_t work(int16_t* const* out);
     void set_sc16_scale(float scale);
+    // the same with 8-bit integer I/Q out (out[s] = interleaved int8 I, Q pairs, 2 bytes per sample downloaded: the HackRF's wire format).  r = rintf(x * scale)
+    // saturated to [-128, 127], scale 127 unless set_sc8_scale (kept across set_mode); clipped(s) counts the saturated components of these passes too.
+    size_t work(int8_t* const* out);
+    void set_sc8_scale(float scale);
     uint64_t clipped(int stream) const;
     size_t samples_per_byte() const;
     int streams() const { return d_n; }
@@ -275,15 +279,16 @@ public:
 
 private:
     void open();
-    size_t work_any(void* const* out, bool sc16);               // both work() overloads
-    float d_sc16_scale = 32767.0f;                              // re-applied by open()
+    enum { FMT_CF32 = 0, FMT_SC16 = 1, FMT_SC8 = 2 };
+    size_t work_any(void* const* out, int fmt);                 // every work() overload
+    float d_sc16_scale = 32767.0f, d_sc8_scale = 127.0f;        // re-applied by open()
     qrl_runtime& d_rt;
     int d_n, d_rate, d_mode = -1; double d_offset; size_t d_max; float d_gain = 1.0f;
     std::vector<double> d_offsets; bool d_per_stream = false;   // per-stream offsets (re-applied by open() once one was set)
     bool any_offset() const;
     // the device buffers are declared before the handles that work on them: released after them, as the destructor always did
     dev_buf<uint8_t> d_bytes; dev_buf<float> d_iq, d_audio;
-    dev_buf<uint32_t> d_clip;      // device counters of one int16 pass (zeroed in front of it), one per stream
+    dev_buf<uint32_t> d_clip;      // device counters of one int16 or int8 pass (zeroed in front of it), one per stream
     dev_buf<uint8_t> d_dmr_dev;    // device staging of a pass: descriptors, first indices, codec bytes, straddling slots
     mod_handle d_h; amod_handle d_ah; float d_ctcss = 0.0f; bool d_ctcss_touched = false; std::map<int, int> d_width;
     bool d_cw_key = false; size_t d_cw_n = 1024;   // clamped to max_bytes by the constructor and by open()
