@@ -17,7 +17,7 @@ using namespace qrl;
 struct qrl_chan {
     qrl_ctx* ctx = nullptr;
     qrl_chan_config cfg{};
-    hipStream_t stream = nullptr; bool own_stream = false;
+    HandleStream stream, tail, mid;   // the caller's or the handle's own; the symbol-sync stream and the per-channel stream (below).  In front of the events: those are destroyed first
     int M = 10, J = 0, nt = 0, rs_Jp = 0, filt_nt = 0;
     DevBuf<float> taps, rs_taps, filt_taps, atan_tab; DevBuf<float2> twiddle;
     DevBuf<float> ct_a, ct_b, ct_e;   // step-major tap tables of the fused per-channel kernel
@@ -28,23 +28,23 @@ struct qrl_chan {
     float sc16_scale = 1.0f / 32768.0f;   // qrl_chan_process_sc16 / qrl_chan_channelize_sc16: x = (float)v * sc16_scale
     bool tail_only = false;   // form 3: only the per-channel chain; its input = 25 ksps channel streams (qrl_chan_process_channels)
     bool xlat2 = false;   // form 2: N freq-xlating FIR decimators 1:N with the PFB prototype in front of the multi2 per-channel chain (BASELINE configs[3])
-    hipEvent_t ev_user = nullptr, ev_user2 = nullptr, ev_ext = nullptr;
+    Event ev_user, ev_user2, ev_user3, ev_ext;   // qrl_chan_stream_wait (one per stream), qrl_chan_wait_for
     // the serial symbol-sync tail (64 waves for 4096 channel streams: latency bound) runs on its own stream so that it overlaps the
     // channelizer and the fused per-channel kernel of the NEXT call; ring r6 holds two calls, ev_tail[slot] guards its reuse
-    hipStream_t tail = nullptr; hipEvent_t ev_ff = nullptr, ev_tail[2] = {nullptr, nullptr}; bool tail_valid[2] = {false, false}; uint64_t call_no = 0;
+    Event ev_ff; Fence ev_tail[2]; uint64_t call_no = 0;   // (sticky fences, host_common.hpp, here and below)
     uint32_t m6 = 0;
     // round 5: the fused per-channel kernel of call k runs on its own stream (`mid`) BESIDE the channelizers of the calls after it (the PFB form on a
     // handle-owned stream only: with a caller's stream the int16 / RSSI outputs stay ordered on that stream).  The channel ring r1 holds ring_calls = 3
     // calls + the tail's look-back: ev_pfb orders the per-channel kernel behind its channelizer, ev_mid[slot] the channelizer of call k + 3 behind the
     // per-channel kernel of call k (the last reader of the ring items it overwrites).  With TWO calls the channelizer of call k + 2 and the per-channel
     // kernel of call k + 1 became ready at the same instant and the step was bimodal (docs/KERNELS.md 10).
-    hipStream_t mid = nullptr; hipEvent_t ev_pfb = nullptr, ev_mid[3] = {nullptr, nullptr, nullptr}, ev_user3 = nullptr; bool mid_valid[3] = {false, false, false};
+    Event ev_pfb; Fence ev_mid[3];
     int ring_calls = 3;   // calls the channel ring holds: the channelizer may run this many calls minus one ahead of the per-channel kernel
     bool opt_serial_tail = false;
     bool mid_used = false, tail_used = false;   // anything ever enqueued there: qrl_chan_stream_wait leaves idle internal streams alone (a marker on an idle low-priority queue held the waiter back ~0.5 ms)
     int opt_legacy_pfb = 0, opt_legacy_tail = 0;   // qrl_chan_set_option
-    bool profiling = false; std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;   // qrl_chan_profile: the HBM-facing kernel(s) of each call
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_tail, prof_ss;                      // ... the fused per-channel kernel and the symbol synchroniser (qrl_chan_profile_read_kernels)
+    bool profiling = false; ProfSpans prof;   // qrl_chan_profile: the HBM-facing kernel(s) of each call
+    ProfSpans prof_tail, prof_ss;             // ... the fused per-channel kernel and the symbol synchroniser (qrl_chan_profile_read_kernels)
     bool xlat = false; int xl_D = 10, xl_nt = 0, xl_S = 0; DevBuf<float> xl_taps; DevBuf<float2> xl_rot_lo; std::vector<uint64_t> xl_inc;   // form 1
     bool single = false; int rs_I = 24, rs_D = 25;   // single: gr_demod_mmdvm (one carrier at 250 ksps, 12/125 resampler, no channelizer)
     float* rssi_out = nullptr; size_t rssi_cap = 0; uint32_t* rssi_counts = nullptr;
@@ -56,25 +56,20 @@ struct qrl_chan {
         return ss.fill((size_t)cfg.batch * cfg.channel_count, x);
     }
     size_t zeroed = 0;
-    ~qrl_chan() { for (auto* v : {&prof_events, &prof_tail, &prof_ss}) for (auto& e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-                  if (ev_user2) (void)hipEventDestroy(ev_user2);
-                  if (ev_ext) (void)hipEventDestroy(ev_ext);
-                  if (ev_ff) (void)hipEventDestroy(ev_ff);
-                  for (auto e : ev_tail) if (e) (void)hipEventDestroy(e);
-                  for (auto e : ev_mid) if (e) (void)hipEventDestroy(e);
-                  if (ev_pfb) (void)hipEventDestroy(ev_pfb);
-                  if (ev_user3) (void)hipEventDestroy(ev_user3);
-                  if (mid) (void)hipStreamDestroy(mid);
-                  if (tail) (void)hipStreamDestroy(tail);
-                  if (ev_user) (void)hipEventDestroy(ev_user); if (own_stream && stream) (void)hipStreamDestroy(stream); }
+    int sync_all() {
+        HIPCHK(hipStreamSynchronize(stream));
+        if (mid) HIPCHK(hipStreamSynchronize(mid));
+        if (tail) HIPCHK(hipStreamSynchronize(tail));
+        return QRL_OK;
+    }
     int reset_state() {
         if (hist_a.zero() || hist_b.zero() || r1.zero() || r2.zero() || r3.zero() || r4.zero()) return QRL_ERR_HIP;
         n_in = n1 = n2 = 0; flip = false;
-        mid_valid[0] = mid_valid[1] = mid_valid[2] = false;
+        for (Fence& f : ev_mid) f.disarm();
         if (!ss.p) call_no = 0;
         if (ss.p) {
             if (r5.zero() || r6.zero()) return QRL_ERR_HIP;
-            tail_valid[0] = tail_valid[1] = false; call_no = 0;
+            ev_tail[0].disarm(); ev_tail[1].disarm(); call_no = 0;
             return init_ss();
         }
         return QRL_OK;
@@ -103,13 +98,7 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
         return qrl_set_error(QRL_ERR_ARG, "bad batch / max_chunk");
     const int M = h->M = (h->xlat || h->xlat2) ? 1 : c.num_channels;   // M = samples consumed per channel-rate instant of the PFB form
     HIPCHK(hipSetDevice(ctx->device));
-    if (c.hip_stream) h->stream = static_cast<hipStream_t>(c.hip_stream);
-    else {
-        int r0;
-        if (std::getenv("QRL_CU_CHAN_MAIN")) { if ((r0 = qrl::create_role_stream(&h->stream, 0, "CHAN_MAIN"))) return r0; }
-        else HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
+    QRLCHK(h->stream.open(c.hip_stream, "CHAN_MAIN"));
     int r;
     // prototype: low_pass_2(1, fs, 5000, 2000, 60, BH), fs = 25 kHz * M (gr_demod_mmdvm_multi2.cpp:58-60; 250 ksps for M = 10)
     // _filter_width of the reference factories (gr_demod_mmdvm_multi2.cpp:47,58-63; gr_demod_mmdvm.cpp:40-52); 0 = their default call site value
@@ -205,7 +194,7 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
     const size_t max1 = c.max_chunk / (h->xlat2 ? h->xl_D : M) + 2, max2 = max1 * h->rs_I / h->rs_D + 2;
     // (the fused per-channel kernel recomputes the halo of its first tile from the channel ring: chan_tail_lookback() items in front of a call)
     // (PFB form on a handle-owned stream: TWO calls, the channelizer of call k + 1 writes while the per-channel kernel of call k still reads)
-    const bool can_overlap = h->own_stream && !h->single && !h->xlat && !h->xlat2 && !h->tail_only && ct_ok;
+    const bool can_overlap = h->stream.owned() && !h->single && !h->xlat && !h->xlat2 && !h->tail_only && ct_ok;
     if (const char* e = std::getenv("QRL_CHAN_RING_CALLS")) { const int v = std::atoi(e); if (v == 2 || v == 3) h->ring_calls = v; }
     h->m1 = (h->single || h->xlat) ? 63 : pow2_at_least((can_overlap ? h->ring_calls : 1) * max1 + h->rs_Jp + 64 + chan_tail_lookback(), 64) - 1;   // the single-carrier chain reads the caller's IQ directly
     h->m2 = pow2_at_least(max2 + h->filt_nt + 64 + 300, 64) - 1;   // + one rssi_tag_block window
@@ -216,23 +205,19 @@ int qrl_chan_create(qrl_ctx* ctx, const qrl_chan_config* cfg, qrl_chan** outp)
     if (can_overlap) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        { int r0; if ((r0 = qrl::create_role_stream(&h->mid, lo, "CHAN_MID"))) return r0; }   // a priority of its own (never the hardware queue of the main or the symbol-sync stream), and BELOW the channelizer's:
-                                                                                  // the persistent channelizer workgroups of call k + 1 are placed as the tail of call k drains
-        HIPCHK(hipEventCreateWithFlags(&h->ev_pfb, hipEventDisableTiming));
-        for (auto& e : h->ev_mid) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        QRLCHK(h->mid.open_internal(lo, "CHAN_MID"));   // a priority of its own (never the hardware queue of the main or the symbol-sync stream), and BELOW the channelizer's:
+                                                        // the persistent channelizer workgroups of call k + 1 are placed as the tail of call k drains
         const char* env = std::getenv("QRL_CHAN_SERIAL_TAIL");
         h->opt_serial_tail = env && env[0] == '1';
     }
     *outp = h.release();
     return QRL_OK;
 }
-void qrl_chan_destroy(qrl_chan* h) { if (h) { (void)hipStreamSynchronize(h->stream); if (h->mid) (void)hipStreamSynchronize(h->mid); if (h->tail) (void)hipStreamSynchronize(h->tail); delete h; } }
+void qrl_chan_destroy(qrl_chan* h) { if (h) { (void)h->sync_all(); delete h; } }
 int qrl_chan_reset(qrl_chan* h)
 {
     if (!h) return QRL_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->mid) HIPCHK(hipStreamSynchronize(h->mid));
-    if (h->tail) HIPCHK(hipStreamSynchronize(h->tail));
+    QRLCHK(h->sync_all());
     return h->reset_state();
 }
 int qrl_chan_set_option(qrl_chan* h, int option, int value)
@@ -246,10 +231,8 @@ int qrl_chan_set_option(qrl_chan* h, int option, int value)
     }
     else if (option == QRL_CHAN_OPT_SERIAL_TAIL) {
         // every stream drained: the switch needs no ordering between the two forms
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->mid) HIPCHK(hipStreamSynchronize(h->mid));
-        if (h->tail) HIPCHK(hipStreamSynchronize(h->tail));
-        h->mid_valid[0] = h->mid_valid[1] = h->mid_valid[2] = false;
+        QRLCHK(h->sync_all());
+        for (Fence& f : h->ev_mid) f.disarm();
         h->opt_serial_tail = value != 0;
     }
     else return qrl_set_error(QRL_ERR_ARG, "unknown channelizer option");
@@ -282,14 +265,10 @@ int qrl_chan_set_4fsk_output(qrl_chan* h, uint8_t* bits, size_t bits_cap, float*
         if (!h->tail) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            { int r0; if ((r0 = qrl::create_role_stream(&h->tail, hi, "CHAN_TAIL"))) return r0; }   // a priority of its own: never the hardware queue of the main stream (engine.cpp, stream creation)
-            HIPCHK(hipEventCreateWithFlags(&h->ev_ff, hipEventDisableTiming));
-            for (auto& e : h->ev_tail) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            QRLCHK(h->tail.open_internal(hi, "CHAN_TAIL"));   // a priority of its own: never the hardware queue of the main stream (engine.cpp, stream creation)
         }
         clock_loop_gains((float)(2 * M_PI / 100.0f), 1.0f, 0.2869f, h->ss_alpha, h->ss_beta);  // :70-71
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->mid) HIPCHK(hipStreamSynchronize(h->mid));
-        HIPCHK(hipStreamSynchronize(h->tail));
+        QRLCHK(h->sync_all());
         if ((r = h->init_ss())) return r;
     }
     h->fsk_bits = bits; h->fsk_bits_cap = bits_cap; h->fsk_const = constellation; h->fsk_const_cap = constellation_cap; h->fsk_counts = counts;
@@ -374,12 +353,12 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
     if (h->tail_only && !fused) launch_ring_load(in, stride, RingC{h->r1.p, h->m1}, h->n1, (uint32_t)n, S, h->stream);
     const int slot2 = (int)(h->call_no & 1), slotr = (int)(h->call_no % (uint64_t)h->ring_calls);
     if (use_mid) h->mid_used = true;
-    if (use_mid && h->mid_valid[slotr]) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_mid[slotr], 0));   // per-channel kernel of call k - ring_calls done: the ring items this call's channelizer overwrites are free
+    if (use_mid) QRLCHK(h->ev_mid[slotr].wait(h->stream));   // per-channel kernel of call k - ring_calls done: the ring items this call's channelizer overwrites are free
     // rssi counts: the fused kernel writes every row's count itself; a fill kernel in front of it sat on the critical path of every step
     // (0.5 ms in the one-rank cluster order: it is dispatched behind the persistent channelizer workgroups of the next call)
     const bool tail_runs = fused && !chan_out && n1_1 > 0 && ((n1_1 - 1) * (uint64_t)h->rs_I + ((uint64_t)h->rs_I - 1)) / (uint64_t)h->rs_D + 1 > h->n2;   // the fused kernel has outputs to produce
     if (h->rssi_out && h->rssi_counts && !tail_runs) HIPCHK(hipMemsetAsync(h->rssi_counts, 0, (size_t)S * sizeof(uint32_t), ts));
-    if (h->tail && h->tail_valid[slot2]) HIPCHK(hipStreamWaitEvent(ts, h->ev_tail[slot2], 0));   // symbol sync of call k - 2 done: its half of ring r6 is free
+    QRLCHK(h->ev_tail[slot2].wait(ts));   // symbol sync of call k - 2 done: its half of ring r6 is free
     ChanParams p{};
     p.in = in; p.in_stride = stride; p.n0 = h->n_in; p.n = (uint32_t)n; p.hist = hist_old; p.hist_len = h->hist_len;
     p.in_fmt = in_fmt; p.in_scale = in_scale;
@@ -387,14 +366,14 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
     p.taps = h->taps.p; p.twiddle = h->twiddle.p; p.M = M; p.J = h->J; p.c_first = h->cfg.channel_first; p.c_count = CC;
     p.legacy = h->opt_legacy_pfb;
     // the HBM-facing kernel(s) = whatever reads the caller's wideband IQ: the PFB, or the per-channel decimators of forms 1 / 2
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (h->profiling && !h->single && !h->tail_only) { HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1)); HIPCHK(hipEventRecord(ev0, h->stream)); }
+    const bool timed = h->profiling && !h->single && !h->tail_only;
+    if (timed) QRLCHK(h->prof.begin(h->stream));
     if (chan_out) {   // qrl_chan_channelize: linear rows of chan_pitch items, grouped by destination rank
         p.out = RingC{reinterpret_cast<float2*>(chan_out), 0}; p.out_pitch = chan_pitch; p.row_cpd = (uint32_t)(CC / chan_groups);
     }
     if (!h->single && !h->xlat && !h->xlat2 && !h->tail_only) {
         launch_pfb_chan(p, B, h->stream);
-        if (ev1) { HIPCHK(hipEventRecord(ev1, h->stream)); h->prof_events.emplace_back(ev0, ev1); }
+        if (timed) QRLCHK(h->prof.end(h->stream));
     }
     HistParams hp{};
     hp.in = in; hp.in_stride = stride; hp.n0 = h->n_in; hp.n = (uint32_t)n;
@@ -423,9 +402,9 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
             dp.in_fmt = in_fmt; dp.in_scale = in_scale;
             if (launch_decim_mfma(dp, B, h->stream)) return qrl_set_error(QRL_ERR_HIP, "freq-xlating front end: hipFuncSetAttribute failed");
         }
-        if (ev1) { HIPCHK(hipEventRecord(ev1, h->stream)); h->prof_events.emplace_back(ev0, ev1); }
+        if (timed) QRLCHK(h->prof.end(h->stream));
     }
-    if (use_mid) { HIPCHK(hipEventRecord(h->ev_pfb, h->stream)); HIPCHK(hipStreamWaitEvent(ts, h->ev_pfb, 0)); }
+    if (use_mid) QRLCHK(h->ev_pfb.relay(h->stream, ts));
     ResampParams rp{};
     if (h->xlat) {
     } else if (h->single) { rp.in = in; rp.in_stride = stride; rp.hist = hist_old; rp.hist_len = h->hist_len; rp.n0 = h->n_in; rp.n = (uint32_t)n;
@@ -450,11 +429,10 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
         if (h->fsk_bits) tp.out_sym = RingF{h->r6.p, h->m6};
         if (h->rssi_out) { tp.rssi = h->rssi_out; tp.rssi_cap = h->rssi_cap; tp.rssi_counts = h->rssi_counts; tp.rssi_cal = h->rssi_cal;
                            tp.tag0 = h->n2 / 300; tp.ntags = (uint32_t)(n2_1 / 300 - h->n2 / 300); }
-        hipEvent_t et0 = nullptr, et1 = nullptr;
-        if (h->profiling) { HIPCHK(hipEventCreate(&et0)); HIPCHK(hipEventCreate(&et1)); HIPCHK(hipEventRecord(et0, ts)); }
+        if (h->profiling) QRLCHK(h->prof_tail.begin(ts));
         launch_chan_tail(tp, S, ts);
-        if (et1) { HIPCHK(hipEventRecord(et1, ts)); h->prof_tail.emplace_back(et0, et1); }
-        if (use_mid) { HIPCHK(hipEventRecord(h->ev_mid[slotr], ts)); h->mid_valid[slotr] = true; }
+        if (h->profiling) QRLCHK(h->prof_tail.end(ts));
+        if (use_mid) QRLCHK(h->ev_mid[slotr].record(ts));
         if (h->tail_only) {   // the last hist_len channel samples of every row for the next call (k_hist, as for the wideband input of the other forms).
                               // BEHIND the per-channel kernel: the cluster records "this buffer has been read" behind it, so the channelizer that waits for that
                               // record cannot grab the chip between two per-channel kernels (in front of the kernel, this small launch and the persistent
@@ -488,8 +466,7 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
         if (h->fsk_bits) {   // gr_demod_dmr.cpp:70-105: symbol_sync_ff -> level -> phase modulator -> slicer -> dibits, on the RRC output ring
             // on the tail stream, behind this call's feed-forward kernels; the ring slot it reads is rewritten two calls later
             h->tail_used = true;
-            HIPCHK(hipEventRecord(h->ev_ff, ts));
-            HIPCHK(hipStreamWaitEvent(h->tail, h->ev_ff, 0));
+            QRLCHK(h->ev_ff.relay(ts, h->tail));
             // (counts[s*4 + 1] and [s*4 + 2] are written for every stream by the kernel; [0] and [3] are not touched: no fill kernel per call)
             SymSyncParams s{};
             s.in = RingF{h->r6.p, h->m6}; s.avail = n2_1; s.soft = RingB{h->soft_dummy.p, 63}; s.st = h->ss.p; s.mmse = h->mmse.p;
@@ -497,13 +474,10 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
             s.ted = 0; s.soft_mul = 128.0f; s.soft_add = 128.0f; s.slicer = 1; s.tail = 1; s.tail_scale = 0.9f; s.slim = 2;   // gr_demod_dmr.cpp:73 _level_control (tail_scale); slim = 16-sample windows, 96-thread workgroups (k_symsync_ff<16, 96>)
             s.bits = h->fsk_bits; s.bits_cap = h->fsk_bits_cap;
             s.port = reinterpret_cast<float2*>(h->fsk_const); s.port_cap = h->fsk_const ? h->fsk_const_cap : 0; s.counts = h->fsk_counts;
-            hipEvent_t es0 = nullptr, es1 = nullptr;
-            if (h->profiling) { HIPCHK(hipEventCreate(&es0)); HIPCHK(hipEventCreate(&es1)); HIPCHK(hipEventRecord(es0, h->tail)); }
+            if (h->profiling) QRLCHK(h->prof_ss.begin(h->tail));
             launch_symsync_ff(s, S, h->tail);
-            if (es1) { HIPCHK(hipEventRecord(es1, h->tail)); h->prof_ss.emplace_back(es0, es1); }
-            const int slot = (int)(h->call_no & 1);
-            HIPCHK(hipEventRecord(h->ev_tail[slot], h->tail));
-            h->tail_valid[slot] = true;
+            if (h->profiling) QRLCHK(h->prof_ss.end(h->tail));
+            QRLCHK(h->ev_tail[slot2].record(h->tail));
         }
     }
     ++h->call_no;
@@ -515,28 +489,17 @@ static int chan_process_impl(qrl_chan* h, const void* iq, size_t stride, size_t 
 int qrl_chan_stream_wait(qrl_chan* h, void* hip_stream)
 {
     if (!h) return QRL_ERR_ARG;
-    if (!h->ev_user) HIPCHK(hipEventCreateWithFlags(&h->ev_user, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(h->ev_user, h->stream));
-    HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_user, 0));
-    if (h->tail && h->tail_used) {
-        if (!h->ev_user2) HIPCHK(hipEventCreateWithFlags(&h->ev_user2, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(h->ev_user2, h->tail));
-        HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_user2, 0));
-    }
-    if (h->mid && h->mid_used) {
-        if (!h->ev_user3) HIPCHK(hipEventCreateWithFlags(&h->ev_user3, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(h->ev_user3, h->mid));
-        HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_user3, 0));
-    }
+    const hipStream_t user = static_cast<hipStream_t>(hip_stream);
+    QRLCHK(h->ev_user.relay(h->stream, user));
+    if (h->tail && h->tail_used) QRLCHK(h->ev_user2.relay(h->tail, user));
+    if (h->mid && h->mid_used) QRLCHK(h->ev_user3.relay(h->mid, user));
     return QRL_OK;
 }
 int qrl_chan_wait_for(qrl_chan* h, void* hip_stream)
 {
     if (!h) return QRL_ERR_ARG;
-    if (!h->ev_ext) HIPCHK(hipEventCreateWithFlags(&h->ev_ext, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(h->ev_ext, static_cast<hipStream_t>(hip_stream)));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ext, 0));
-    if (h->mid && h->mid_used) HIPCHK(hipStreamWaitEvent(h->mid, h->ev_ext, 0));   // (the int16 / RSSI outputs are written on this stream)
+    QRLCHK(h->ev_ext.relay(static_cast<hipStream_t>(hip_stream), h->stream));
+    if (h->mid && h->mid_used) QRLCHK(h->ev_ext.wait(h->mid));   // (the int16 / RSSI outputs are written on this stream)
     return QRL_OK;
 }
 void* qrl_chan_stream(qrl_chan* h) { return h ? h->stream : nullptr; }
@@ -551,47 +514,27 @@ int qrl_chan_profile_read(qrl_chan* h, double* kernel_ms, uint64_t* launches, co
 {
     if (!h) return QRL_ERR_ARG;
     HIPCHK(hipStreamSynchronize(h->stream));
-    double total = 0;
-    for (auto& e : h->prof_events) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-        total += ms;
-        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
-    }
+    double total = 0; uint64_t count = 0;
+    const int r = h->prof.read(total, count);
+    h->prof_tail.clear(); h->prof_ss.clear();   // (not waited for, not read)
+    if (r) return r;
     if (kernel_ms) *kernel_ms = total;
-    if (launches) *launches = h->prof_events.size();
+    if (launches) *launches = count;
     if (kernel_name) *kernel_name = (h->xlat || h->xlat2) ? "k_decim_mfma (one launch per channel, summed)" : h->single ? "k_resamp" : (h->opt_legacy_pfb == 0 && h->M == 64) ? "k_pfb_stream64" : "k_pfb_chan";
-    h->prof_events.clear();
-    for (auto* v : {&h->prof_tail, &h->prof_ss}) { for (auto& e : *v) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } v->clear(); }
     return QRL_OK;
 }
 int qrl_chan_profile_read_kernels(qrl_chan* h, double ms[3], uint64_t launches[3])
 {
     if (!h || !ms || !launches) return QRL_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->mid) HIPCHK(hipStreamSynchronize(h->mid));
-    if (h->tail) HIPCHK(hipStreamSynchronize(h->tail));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>>* sets[3] = {&h->prof_events, &h->prof_tail, &h->prof_ss};
-    for (int k = 0; k < 3; ++k) {
-        double total = 0;
-        for (auto& e : *sets[k]) {
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, e.first, e.second));
-            total += t;
-            (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
-        }
-        ms[k] = total; launches[k] = sets[k]->size();
-        sets[k]->clear();
-    }
+    QRLCHK(h->sync_all());
+    ProfSpans* sets[3] = {&h->prof, &h->prof_tail, &h->prof_ss};
+    for (int k = 0; k < 3; ++k) QRLCHK(sets[k]->read(ms[k], launches[k]));
     return QRL_OK;
 }
 int qrl_chan_sync(qrl_chan* h)
 {
     if (!h) return QRL_ERR_ARG;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->mid) HIPCHK(hipStreamSynchronize(h->mid));
-    if (h->tail) HIPCHK(hipStreamSynchronize(h->tail));
-    return QRL_OK;
+    return h->sync_all();
 }
 
 }  // extern "C"

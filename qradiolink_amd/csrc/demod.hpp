@@ -111,16 +111,18 @@ using namespace qrl;   // for the three receiver files, which are all that inclu
 struct qrl_demod {
     qrl_ctx* ctx = nullptr;
     qrl_demod_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // Streams in front of the events and fences: the events are destroyed first.
+    HandleStream stream;   // the caller's, or the handle's own
     // the serial tail (symbol sync + Viterbi: a handful of waves) runs on its own stream so that it overlaps the
     // HBM-facing kernels of the NEXT call instead of idling 250 CUs
-    hipStream_t tail = nullptr;
+    HandleStream tail;
     // QPSK / BPSK / 4FSK-discriminator families: the recursive chain (k_qpsk_*: latency bound, 64 streams per workgroup) runs on
     // `tail`, the Viterbi decoder on `fecs`: call k's decoder, call k + 1's recursion and call k + 2's front end run side by side.
     // The rings between them hold two calls; ev_q / ev_fec guard their reuse two calls later.
-    hipStream_t fecs = nullptr;
-    hipEvent_t ev_q[2] = {nullptr, nullptr}, ev_fec[2] = {nullptr, nullptr}; bool q_valid[2] = {false, false};
+    HandleStream fecs;
+    HandleStream pre;   // HELPER STREAM of the front end, below
+    // STICKY fences (host_common.hpp), one per ring slot: the recursion and the decoder of the call in slot k & 1
+    Fence ev_q[2], ev_fec[2];
     // GROUPED ORDER (gr_demod_qpsk chain whose recursion kernel has a workgroup for at least every second CU): k_qpsk_pipe4 is a serial
     // walk, one workgroup of 6 waves and 137 KB of LDS per 64 streams.  Left to the three streams, the front end of call k + 1 (tens of
     // thousands of small workgroups) and the decoder of call k - 1 (a wave per two trellises, for its whole run) take every LDS byte
@@ -131,17 +133,16 @@ struct qrl_demod {
     // (qrl_demod_sync, qrl_demod_stream_wait, reset, destroy), so a caller never sees the difference.
     bool grouped = false, grouped_capable = false, fec_deferred = false; FecParams fec_pending{}; int fec_pending_slot = 0;
     DevBuf<uint64_t> qp_snap;   // [2][B] symbols produced up to the end of call k (slot k & 1): what that call's decoder may read
-    hipEvent_t ev_ff = nullptr, ev_tail = nullptr;
+    Event ev_ff; Fence ev_tail;   // ev_tail: ONE-SHOT, taken by the next call's stage that rewrites ring r3 (serial order only)
     // HELPER STREAM of the front end (round 6): k_hist (the rotated tail of this call's IQ, kept for the next call) and k_pl_edge_stage (the
     // next call's edge scratch: that history + the head of the next buffer) read the caller's buffers only, yet they sat between two front-end
     // launches on the handle's stream -- 0.2 - 0.29 ms of C1's 8 ms step (profiles/r06_c1_helper_stream.log).  On `pre` they run BESIDE the
     // front end: edge(k) behind hist(k - 1); hist(k) behind the front end of call k - 1 (the last reader of the history buffer it overwrites);
     // the front end of call k waits for ev_pre.  The history and the edge scratch are double buffers.
     // Only with QRL_OPT_INPUT_RESIDENT: the helpers then read a call's IQ WITHOUT waiting for what the caller queued on the handle's stream before the call.
-    hipStream_t pre = nullptr; hipEvent_t ev_pre = nullptr, ev_fe[2] = {nullptr, nullptr}; bool fe_valid[2] = {false, false}; bool pre_pending = false;
+    Fence ev_pre, ev_fe[2];   // ev_pre: ONE-SHOT (also recorded by the launchers, DecimParams::pre_event: created with the stream); ev_fe: STICKY
     bool input_resident = false;
-    hipEvent_t ev_user[4] = {nullptr, nullptr, nullptr, nullptr};   // qrl_demod_stream_wait
-    bool tail_pending = false;
+    Event ev_user[4];   // qrl_demod_stream_wait
     // overlapped mode (2FSK / GMSK / 4FSK families): everything behind the first decimated ring runs on the tail stream while
     // the front end of the NEXT call already runs on the main stream; ring s2 holds two calls, ev_tail2 guards its reuse
     bool qpsk_fll = false, fsk4_disc = false;
@@ -149,7 +150,7 @@ struct qrl_demod {
     DevBuf<float2> s2g, disc4_taps; DevBuf<float> sym4_taps; int disc4_nt = 0, sym4_nt = 0;   // 4FSK non-FM branch
     bool fll_slim = false;   // QRL_OPT_FLL_SLIM: single-wave FLL workgroups (3 KB of LDS) that fit beside four front-end workgroups
     bool d2f_capable = false, d2f = false; DevBuf<float> d2f_taps;   // 1:2 decimator + shaping filter in one kernel (k_dec2_fir)
-    bool overlap = false, overlap_capable = false; hipEvent_t ev_tail2[2] = {nullptr, nullptr}; bool tail2_valid[2] = {false, false}; uint64_t call_no = 0;
+    bool overlap = false, overlap_capable = false; Fence ev_tail2[2]; uint64_t call_no = 0;   // ev_tail2: STICKY
     enum Family { F_2FSK, F_GMSK, F_QPSK, F_DMR, F_4FSK, F_BPSK, F_DSSS, F_ANALOG } fam = F_2FSK;
     int branches = 2;
 
@@ -192,23 +193,7 @@ struct qrl_demod {
     DsssChain ds;     // fam == F_DSSS
     uint64_t n_in = 0, n1 = 0, n2 = 0;  // items so far: device rate, 1 Msps, target rate
     bool profiling = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-
-    ~qrl_demod() {
-        for (auto& e : prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        if (ev_ff) (void)hipEventDestroy(ev_ff);
-        if (ev_tail) (void)hipEventDestroy(ev_tail);
-        for (auto e : ev_user) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_tail2) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_q) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_fec) if (e) (void)hipEventDestroy(e);
-        if (ev_pre) (void)hipEventDestroy(ev_pre);
-        for (auto e : ev_fe) if (e) (void)hipEventDestroy(e);
-        if (pre) (void)hipStreamDestroy(pre);
-        if (fecs) (void)hipStreamDestroy(fecs);
-        if (tail) (void)hipStreamDestroy(tail);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
+    ProfSpans prof;   // the HBM-facing kernel of each profiled call
 
     int flush_fec(bool behind_front_end);   // engine.cpp: launches the decoder call the grouped order holds back, if any
     int sync_all() {

@@ -22,13 +22,13 @@ int qrl_demod::flush_fec(bool behind_front_end)
 {
     if (!fec_deferred) return QRL_OK;
     fec_deferred = false;
-    HIPCHK(hipStreamWaitEvent(fecs, ev_q[fec_pending_slot], 0));
+    QRLCHK(ev_q[fec_pending_slot].wait(fecs));   // (armed: the call that deferred the decoder recorded it)
     if (behind_front_end) {   // starts with the recursion of the next call, not beside its front end -- and a moment AFTER it (k_fec_gate)
-        HIPCHK(hipStreamWaitEvent(fecs, ev_ff, 0));
+        QRLCHK(ev_ff.wait(fecs));
         launch_fec_gate(QRL_FEC_GATE_US, fecs);
     }
     launch_fec(fec_pending, cfg.batch, fecs);
-    HIPCHK(hipEventRecord(ev_fec[fec_pending_slot], fecs));
+    QRLCHK(ev_fec[fec_pending_slot].record(fecs));
     return QRL_OK;
 }
 
@@ -51,8 +51,8 @@ int qrl_demod::init_state()
     if ((r = ss_st.fill(cfg.batch, ss)) || (r = fec_st.fill((size_t)cfg.batch * 2, fs))) return r;
     if (qp_snap.p && (r = qp_snap.zero())) return r;
     if ((fam == F_DSSS && (r = ds.init_state(*this))) || (fam == F_ANALOG && (r = an.init_state(*this)))) return r;
-    q_valid[0] = q_valid[1] = false; tail2_valid[0] = tail2_valid[1] = false; tail_pending = false; call_no = 0;
-    fe_valid[0] = fe_valid[1] = false; pre_pending = false;
+    for (Fence* f : {&ev_q[0], &ev_q[1], &ev_fec[0], &ev_fec[1], &ev_tail2[0], &ev_tail2[1], &ev_fe[0], &ev_fe[1], &ev_tail, &ev_pre}) f->disarm();
+    call_no = 0;
     fec_deferred = false;
     n_in = n1 = n2 = 0;
     hist_flip = false;
@@ -344,14 +344,14 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     const int slot = (int)(call_no & 1);
     if (overlap) {
         // ring s2 is about to be overwritten two calls behind: the tail of call k - 2 must be through
-        if (tail2_valid[slot]) HIPCHK(hipStreamWaitEvent(stream, ev_tail2[slot], 0));
+        QRLCHK(ev_tail2[slot].wait(stream));
     } else {
         HIPCHK(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(uint32_t), stream));
     }
     // loops families: the rings the recursion reads hold two calls; call k - 2's recursion must be through before they are rewritten
-    if (loops_family() && q_valid[slot]) HIPCHK(hipStreamWaitEvent(stream, ev_q[slot], 0));
-    if (grouped && q_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(stream, ev_q[slot ^ 1], 0));   // grouped order: this front end behind the recursion of the call before
-    if (pre_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_pre, 0)); pre_pending = false; }   // k_hist of the call before (helper stream)
+    if (loops_family()) QRLCHK(ev_q[slot].wait(stream));
+    if (grouped) QRLCHK(ev_q[slot ^ 1].wait(stream));   // grouped order: this front end behind the recursion of the call before
+    QRLCHK(ev_pre.wait_once(stream));   // k_hist of the call before (helper stream)
     const bool use_pre = pre && input_resident;
     const float2* in = reinterpret_cast<const float2*>(iq);   // (IN_SC16, IN_SC8, IN_CU8: integer pairs behind it; only the kernels that read the caller's buffer know: the front end or, without one, what input_source feeds, and k_hist)
     const float2* hist_old = hist_flip ? hist_b.p : hist_a.p;
@@ -364,11 +364,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
     RingF r2d{s2d.p, s2_mask}, r3{s3.p, s2_mask};
 
     // the HBM-facing kernel is the first launch that reads the caller's IQ
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (profiling) {
-        HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
-        HIPCHK(hipEventRecord(ev0, stream));
-    }
+    if (profiling) QRLCHK(prof.begin(stream));
     // ---- stage A: gr_demod_base front end
     if (fe.used) {
         n1_1 = decim_count(n_in1, 1, fe_decim);
@@ -382,7 +378,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         if (use_pre) { p.pre_stream = pre; p.pre_event = ev_pre; }
         if (fe.launch(p, B, stream, use_pre ? slot : 0)) return qrl_set_error(QRL_ERR_HIP, "front-end launch: hipFuncSetAttribute failed");
     }
-    if (profiling && fe.used) { HIPCHK(hipEventRecord(ev1, stream)); prof_events.emplace_back(ev0, ev1); }
+    if (profiling && fe.used) QRLCHK(prof.end(stream));
     // ---- stage B: per-mode resampler
     const uint64_t src0 = fe.used ? n1_0 : n_in0, src1 = fe.used ? n1_1 : n_in1;
     const uint64_t n2_0 = n2, n2_1 = decim_count(src1, interp, decim);
@@ -410,7 +406,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         }
         launch_resamp(p, B, stream);
     }
-    if (profiling && !fe.used) { HIPCHK(hipEventRecord(ev1, stream)); prof_events.emplace_back(ev0, ev1); }
+    if (profiling && !fe.used) QRLCHK(prof.end(stream));
     // ---- time-domain scope tap: the 1 Msps signal behind the front end (the caller's rotated IQ when the device runs at 1 Msps) -> 1:10
     if (scope_out) {
         const uint64_t ns_1 = decim_count(src1, 1, scope_D);
@@ -429,18 +425,16 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         h.hist_old = hist_old; h.hist_new = hist_new; h.hist_len = hist_len;
         h.rot_enable = 1; rot.fill(h);
         in_format_fill(h, in_format(fmt));
-        if (pre) { HIPCHK(hipEventRecord(ev_fe[slot], stream)); fe_valid[slot] = true; }   // everything of this call that reads the history on the handle's stream has been launched
+        if (pre) QRLCHK(ev_fe[slot].record(stream));   // everything of this call that reads the history on the handle's stream has been launched
         if (use_pre) {
-            if (fe_valid[slot ^ 1]) HIPCHK(hipStreamWaitEvent(pre, ev_fe[slot ^ 1], 0));   // hist_new was the history of the call before
+            QRLCHK(ev_fe[slot ^ 1].wait(pre));   // hist_new was the history of the call before
             launch_hist_save(h, B, pre);
-            HIPCHK(hipEventRecord(ev_pre, pre));
-            pre_pending = true;
+            QRLCHK(ev_pre.record(pre));
         } else launch_hist_save(h, B, stream);
         hist_flip = !hist_flip;
     }
     if (overlap) {
-        HIPCHK(hipEventRecord(ev_ff, stream));
-        HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0));
+        QRLCHK(ev_ff.relay(stream, tail));
         HIPCHK(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(uint32_t), tail));
     }
     // ---- stage C: decimated-rate feed-forward (+ FLL for 2FSK)
@@ -478,12 +472,12 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         }
         QuadDemodParams q{}; q.in = dem_in; q.out = r2d; q.q0 = n2_0; q.count = c2; q.gain = demod_gain; q.atan_tab = atan_tab.p;
         launch_quad_demod(q, B, cs);
-        if (!overlap && tail_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_tail, 0)); tail_pending = false; }
+        if (!overlap) QRLCHK(ev_tail.wait_once(stream));
         FirFffParams f{}; f.in = r2d; f.out = r3; f.q0 = n2_0; f.count = c2; f.taps = symf_taps.p; f.nt = symf_nt;
         launch_fir_fff(f, B, cs);
-        if (!overlap) { HIPCHK(hipEventRecord(ev_ff, stream)); HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0)); }
+        if (!overlap) QRLCHK(ev_ff.relay(stream, tail));
     } else if (fused_2fsk) {
-        if (!overlap && tail_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_tail, 0)); tail_pending = false; }
+        if (!overlap) QRLCHK(ev_tail.wait_once(stream));
         Fsk2FfParams f{};
         f.in = filt_in; f.out = r3; f.q0 = n2_0; f.count = c2;
         f.tf = ff_tf.p; f.nf = fsk2_ff_padded(filt_nt); f.up = ff_up.p; f.lo = ff_lo.p; f.nb = fsk2_ff_padded(disc_nt);
@@ -493,7 +487,7 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
             Fsk2TailParams t{}; t.fll = fllp; t.ff = f;
             if (!(QRL_DEV_SKIP & 3)) launch_2fsk_tail(t, B, cs);
         } else if (!(QRL_DEV_SKIP & 2)) launch_2fsk_ff(f, B, cs);
-        if (!overlap) { HIPCHK(hipEventRecord(ev_ff, stream)); HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0)); }
+        if (!overlap) QRLCHK(ev_ff.relay(stream, tail));
     } else {
         if (!d2f) {
             FirCcfParams f{};
@@ -520,10 +514,10 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
             // the tail reads r2f (written by k_fir_ccf above): it runs on the handle's own stream for these families
         } else {
             // r3 is what the previous call's tail (other stream) may still be reading
-            if (!overlap && tail_pending) { HIPCHK(hipStreamWaitEvent(stream, ev_tail, 0)); tail_pending = false; }
+            if (!overlap) QRLCHK(ev_tail.wait_once(stream));
             FirFffParams f{}; f.in = r2d; f.out = r3; f.q0 = n2_0; f.count = c2; f.taps = symf_taps.p; f.nt = symf_nt;
             launch_fir_fff(f, B, cs);
-            if (!overlap) { HIPCHK(hipEventRecord(ev_ff, stream)); HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0)); }
+            if (!overlap) QRLCHK(ev_ff.relay(stream, tail));
         }
     }
     // ---- stage D: symbol sync + FEC
@@ -544,13 +538,12 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         q.port = cport.p; q.port_cap = cport.cap; q.counts = counts;
         q.oo_snap = qp_snap.p + (size_t)slot * B;
         // recursion on `tail` behind this call's feed-forward kernels, decoder on `fecs` behind the recursion
-        HIPCHK(hipEventRecord(ev_ff, stream));
-        HIPCHK(hipStreamWaitEvent(tail, ev_ff, 0));
-        if (q_valid[slot]) HIPCHK(hipStreamWaitEvent(tail, ev_fec[slot], 0));   // the soft ring holds two calls: decoder of call k - 2 done
+        QRLCHK(ev_ff.relay(stream, tail));
+        QRLCHK(ev_fec[slot].wait(tail));   // the soft ring holds two calls: decoder of call k - 2 done (grouped order: launched, and this recorded, by the call between)
         launch_qpsk_loops(q, B, tail);
-        HIPCHK(hipEventRecord(ev_q[slot], tail));
-        if (int rf = flush_fec(true)) return rf;                    // grouped order: the decoder of the call before goes with this recursion
-        if (!grouped) HIPCHK(hipStreamWaitEvent(fecs, ev_q[slot], 0));
+        QRLCHK(ev_q[slot].record(tail));
+        QRLCHK(flush_fec(true));                                    // grouped order: the decoder of the call before goes with this recursion
+        if (!grouped) QRLCHK(ev_q[slot].wait(fecs));
         FecParams f{};
         f.soft = RingB{soft.p, soft_mask};
         f.avail = q.oo_snap; f.avail_stride = sizeof(uint64_t); f.avail_mul = fam == F_BPSK ? 1 : 2;
@@ -560,9 +553,8 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
         if (grouped) { fec_pending = f; fec_pending_slot = slot; fec_deferred = true; }
         else {
             launch_fec(f, B, fecs);
-            HIPCHK(hipEventRecord(ev_fec[slot], fecs));
+            QRLCHK(ev_fec[slot].record(fecs));
         }
-        q_valid[slot] = true;
     } else {
         SymSyncParams s{};
         s.in = r3; s.avail = n2_1; s.soft = RingB{soft.p, soft_mask}; s.st = ss_st.p; s.mmse = mmse_tab.p;
@@ -582,17 +574,16 @@ int qrl_demod::process(const void* iq, size_t stride, size_t n, const qrl_demod_
             dp.out = dmo_out; dp.cap = dmo_cap; dp.counts = dmo_counts;
             launch_dmo_sink(dp, B, tail);
         }
-        if (fam == F_DMR) { HIPCHK(hipEventRecord(ev_tail, tail)); tail_pending = true; }
+        if (fam == F_DMR) QRLCHK(ev_tail.record(tail));
         FecParams f{};
         f.soft = RingB{soft.p, soft_mask}; f.avail = &ss_st.p[0].oo; f.avail_stride = sizeof(SymSyncState); f.avail_mul = fam == F_4FSK ? 2 : 1; f.st = fec_st.p;
         f.bits_a = out ? out->bits_a : nullptr; f.bits_b = out ? out->bits_b : nullptr; f.bits_cap = out ? out->bits_cap : 0;
         f.counts = counts; f.branches = branches;
         if (fam != F_DMR) {
             if (!(QRL_DEV_SKIP & 8)) launch_fec(f, B, tail);
-            HIPCHK(hipEventRecord(ev_tail, tail));
-            tail_pending = true;
+            QRLCHK(ev_tail.record(tail));
         }
-        if (overlap) { HIPCHK(hipEventRecord(ev_tail2[slot], tail)); tail2_valid[slot] = true; }
+        if (overlap) QRLCHK(ev_tail2[slot].record(tail));
     }
     HIPCHK(hipGetLastError());
     if (take_launch_error()) return QRL_ERR_HIP;   // (message already recorded by dyn_lds_limit)
@@ -678,18 +669,7 @@ int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp
     // Streams.  The tail stream has the highest priority and its kernels are small enough to take over the slot of ONE
     // retiring front-end workgroup.  (Reserving CUs for it with a CU mask was measured: it costs the front end ~18 %.)
     {
-        if (c.hip_stream) d->stream = static_cast<hipStream_t>(c.hip_stream);
-        else {
-            int r0;
-            if (std::getenv("QRL_CU_MAIN")) { if ((r0 = create_role_stream(&d->stream, 0, "MAIN"))) return r0; }
-            else if (std::getenv("QRL_MAIN_PRIO_LOW")) {   // experiment: a CU-masked stream has no priority argument (it is a NORMAL stream), so the masked tail only outranks the
-                int plo = 0, phi = 0;                      // front end when the front end's stream is created BELOW normal
-                (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-                HIPCHK(hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, plo));
-            }
-            else HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-            d->own_stream = true;
-        }
+        QRLCHK(d->stream.open(c.hip_stream, "MAIN", "QRL_MAIN_PRIO_LOW"));   // (the experiment: the masked tail only outranks the front end when the front end's stream is BELOW normal)
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         // THREE DIFFERENT PRIORITIES, and not for the scheduling: the runtime multiplexes the streams of one priority onto a few hardware
@@ -697,18 +677,11 @@ int qrl_demod_create(qrl_ctx* ctx, const qrl_demod_config* cfg, qrl_demod** outp
         // the overlapped and grouped orders then silently degrade to the serial one (seen as C4 4.5 instead of 3.05 ms and C2 2.2 instead
         // of 1.78 ms per step in the sub-lines of a long bench process, depending on how many streams the process had created and
         // destroyed before: tools/experiments/r04_subline_order*.py).  Queues of different priorities are never shared.
-        int r1;
-        if ((r1 = create_role_stream(&d->tail, hi, "TAIL")) || (r1 = create_role_stream(&d->fecs, lo, "FEC"))) return r1;
+        QRLCHK(d->tail.open_internal(hi, "TAIL"));
+        QRLCHK(d->fecs.open_internal(lo, "FEC"));
         // the front end's helper stream: the handle's own stream only (a caller's stream may share its hardware queue with anything), normal priority
-        if (d->own_stream && !std::getenv("QRL_NO_PRE")) { if ((r1 = create_role_stream(&d->pre, 0, "PRE"))) return r1; }
+        if (d->stream.owned() && !std::getenv("QRL_NO_PRE")) { QRLCHK(d->pre.open_internal(0, "PRE")); QRLCHK(d->ev_pre.create()); }
     }
-    HIPCHK(hipEventCreateWithFlags(&d->ev_ff, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&d->ev_pre, hipEventDisableTiming));
-    for (auto& e : d->ev_fe) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&d->ev_tail, hipEventDisableTiming));
-    for (auto& e : d->ev_tail2) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : d->ev_q) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : d->ev_fec) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int r = d->build();
     if (r) return r;
     *outp = d.release();
@@ -742,12 +715,9 @@ int qrl_demod_stream_wait(qrl_demod* d, void* hip_stream)
     if (!d) return QRL_ERR_ARG;
     if (int rf = d->flush_fec(false)) return rf;
     hipStream_t user = static_cast<hipStream_t>(hip_stream);
-    if (!d->ev_user[0]) for (auto& e : d->ev_user) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(d->ev_user[0], d->stream));
-    HIPCHK(hipEventRecord(d->ev_user[1], d->tail));
-    HIPCHK(hipEventRecord(d->ev_user[2], d->fecs));
-    HIPCHK(hipEventRecord(d->ev_user[3], d->pre ? d->pre : d->stream));   // k_hist reads the caller's IQ on the helper stream
-    for (auto e : d->ev_user) HIPCHK(hipStreamWaitEvent(user, e, 0));
+    const hipStream_t from[4] = {d->stream, d->tail, d->fecs, d->pre ? d->pre : d->stream};   // ([3]: k_hist reads the caller's IQ on the helper stream)
+    for (int k = 0; k < 4; ++k) QRLCHK(d->ev_user[k].record(from[k]));
+    for (auto& e : d->ev_user) QRLCHK(e.wait(user));
     return QRL_OK;
 }
 int qrl_demod_set_dmo_output(qrl_demod* d, uint8_t* frames, size_t cap_frames, uint32_t* counts)
@@ -776,7 +746,7 @@ int qrl_demod_set_option(qrl_demod* d, int option, int value)
         if (value != 0 && !d->overlap_capable) return qrl_set_error(QRL_ERR_ARG, "overlapped mode exists for the 2FSK family only");
         if (int rs = d->sync_all()) return rs;
         d->overlap = value != 0;
-        d->tail2_valid[0] = d->tail2_valid[1] = false;
+        d->ev_tail2[0].disarm(); d->ev_tail2[1].disarm();
         return QRL_OK;
     case QRL_OPT_FLL_SLIM:
         if (int rs = d->sync_all()) return rs;
@@ -916,21 +886,15 @@ int qrl_demod_profile_read(qrl_demod* d, double* kernel_ms, uint64_t* launches, 
 {
     if (!d) return QRL_ERR_ARG;
     if (int rs = d->sync_all()) return rs;
-    double total = 0;
-    for (auto& e : d->prof_events) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e.first, e.second));
-        total += ms;
-        (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
-    }
+    double total = 0; uint64_t count = 0;
+    QRLCHK(d->prof.read(total, count));
     if (kernel_ms) *kernel_ms = total;
-    if (launches) *launches = d->prof_events.size();
+    if (launches) *launches = count;
     if (kernel_name) {
         const DecimStage& st = d->fe.used ? d->fe : d->first;
         *kernel_name = (!d->fe.used && d->d2f) ? "k_dec2_fir"
                      : (d->fe.used || d->interp == 1) ? st.kernel_name() : "k_resamp";
     }
-    d->prof_events.clear();
     return QRL_OK;
 }
 

@@ -45,13 +45,60 @@ int create_role_stream(hipStream_t* s, int priority, const char* role)
     return QRL_OK;
 }
 
-int HandleStream::open(void* user_stream, const char* role)
+int HandleStream::open(void* user_stream, const char* role, const char* low_prio_env)
 {
     if (user_stream) { s = static_cast<hipStream_t>(user_stream); return QRL_OK; }
-    if (role && std::getenv((std::string("QRL_CU_") + role).c_str())) { if (int r = create_role_stream(&s, 0, role)) return r; }
+    if (role && std::getenv((std::string("QRL_CU_") + role).c_str())) return open_internal(0, role);
+    if (low_prio_env && std::getenv(low_prio_env)) {   // experiment: a CU-masked stream has no priority argument (it is a NORMAL stream), so a masked
+        int plo = 0, phi = 0;                          // internal stream only outranks this one when this one is created BELOW normal
+        (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
+        HIPCHK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, plo));
+    }
     else HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     own = true;
     return QRL_OK;
+}
+
+int ProfSpans::begin(hipStream_t s)
+{
+    drop_open();
+    HIPCHK(hipEventCreate(&b0)); HIPCHK(hipEventCreate(&b1));
+    HIPCHK(hipEventRecord(b0, s));
+    return QRL_OK;
+}
+int ProfSpans::end(hipStream_t s)
+{
+    HIPCHK(hipEventRecord(b1, s));
+    spans.emplace_back(b0, b1);
+    b0 = b1 = nullptr;
+    return QRL_OK;
+}
+int ProfSpans::read(double& ms, uint64_t& count)
+{
+    hipError_t err = hipSuccess;
+    double total = 0;
+    for (auto& e : spans) {
+        float t = 0;
+        if (err == hipSuccess) err = hipEventElapsedTime(&t, e.first, e.second);
+        total += t;
+    }
+    count = spans.size();
+    clear();
+    if (err != hipSuccess) return qrl_set_error(QRL_ERR_HIP, std::string("hipEventElapsedTime: ") + hipGetErrorString(err));
+    ms = total;
+    return QRL_OK;
+}
+void ProfSpans::clear()
+{
+    for (auto& e : spans) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    spans.clear();
+    drop_open();
+}
+void ProfSpans::drop_open()
+{
+    if (b0) (void)hipEventDestroy(b0);
+    if (b1) (void)hipEventDestroy(b1);
+    b0 = b1 = nullptr;
 }
 bool sc16_scale_ok(const char* who, float scale)
 {

@@ -1,5 +1,5 @@
 // host_common.hpp — what every host translation unit of libqrl_hip.so shares: the context, error reporting, the owning device
-// buffer, the stream and the carrier NCO of a handle, the checks of an sc16 input.  Host only: no .hip file includes it.
+// buffer, the streams, events, fences and profile spans of a handle, its carrier NCO, the checks of an sc16 input.  Host only: no .hip file includes it.
 #pragma once
 #include "../../include/qrl_hip.h"
 #include "engine.hpp"
@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 struct qrl_ctx { int device; };
@@ -57,17 +58,65 @@ template <class T> struct DevBuf {
     }
 };
 
-// The stream of a single-stream handle: the caller's, or one of the handle's own (hipStreamNonBlocking; with a role, the QRL_CU_<ROLE> stream
-// of create_role_stream when that variable is set).  Destroys only what it made.
+// A stream of a handle.  open(): the caller's, or one of the handle's own (hipStreamNonBlocking; with a role, the QRL_CU_<ROLE> stream of
+// create_role_stream when that variable is set; else, when the variable `low_prio_env` names is set, a stream of the lowest priority).
+// open_internal(): an internal stream of the handle, create_role_stream(priority, role).  Null until opened; destroys only what it made.
 struct HandleStream {
     HandleStream() = default;
     HandleStream(const HandleStream&) = delete; HandleStream& operator=(const HandleStream&) = delete;
     ~HandleStream() { if (own && s) (void)hipStreamDestroy(s); }
-    int open(void* user_stream, const char* role = nullptr);
+    int open(void* user_stream, const char* role = nullptr, const char* low_prio_env = nullptr);
+    int open_internal(int priority, const char* role) { if (int r = create_role_stream(&s, priority, role)) return r; own = true; return QRL_OK; }
     operator hipStream_t() const { return s; }
     bool owned() const { return own; }
 private:
     hipStream_t s = nullptr; bool own = false;
+};
+
+#define QRLCHK(expr) do { if (int r_ = (expr)) return r_; } while (0)   // for the int-status members below
+
+// Owning event, made on first record() or by create() (before its raw handle is given to a launcher); hipEventDisableTiming.
+struct Event {
+    Event() = default;
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int create() { if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return QRL_OK; }
+    int record(hipStream_t s) { QRLCHK(create()); HIPCHK(hipEventRecord(e, s)); return QRL_OK; }
+    int wait(hipStream_t s) const { HIPCHK(hipStreamWaitEvent(s, e, 0)); return QRL_OK; }
+    int relay(hipStream_t from, hipStream_t to) { QRLCHK(record(from)); return wait(to); }   // `to` goes on behind what `from` holds now
+    operator hipEvent_t() const { return e; }
+private:
+    hipEvent_t e = nullptr;
+};
+
+// An event that orders a later call behind an earlier one, and whether it has been recorded since the last disarm().  Two rules:
+// STICKY (wait): every call waits again -- the guard of a ring slot that is reused every second or third call;
+// ONE-SHOT (wait_once): the first waiter takes it -- "the call before has left this buffer", needed once per record.
+struct Fence {
+    int create() { return ev.create(); }
+    int record(hipStream_t s) { QRLCHK(ev.record(s)); armed = true; return QRL_OK; }
+    int wait(hipStream_t s) const { return armed ? ev.wait(s) : QRL_OK; }
+    int wait_once(hipStream_t s) { if (!armed) return QRL_OK; armed = false; return ev.wait(s); }
+    void disarm() { armed = false; }
+    operator hipEvent_t() const { return ev; }
+private:
+    Event ev; bool armed = false;
+};
+
+// The timing-event pairs around one kernel set of the profiled calls (default flags, a new pair per call).  A span begun and not
+// ended (an error return in between) is freed by the next begin(), by read() or with the set.
+struct ProfSpans {
+    ProfSpans() = default;
+    ProfSpans(const ProfSpans&) = delete; ProfSpans& operator=(const ProfSpans&) = delete;
+    ~ProfSpans() { clear(); }
+    int begin(hipStream_t s);
+    int end(hipStream_t s);
+    bool open() const { return b0 != nullptr; }       // begun, not yet ended
+    int read(double& ms, uint64_t& count);             // sum and number of the ended spans; empties the set, on an error return too
+    void clear();
+private:
+    void drop_open();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans; hipEvent_t b0 = nullptr, b1 = nullptr;
 };
 
 // ---- sc16 input (qrl_*_process_sc16 of the receivers and the spectrum tap): false = refused, with the error text set ----

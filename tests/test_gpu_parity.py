@@ -799,7 +799,7 @@ def test_pipelined_calls_without_sync(qrl_ctx, mode_name, modem):
         dem = q.Demod(qrl_ctx, modem, batch=B, max_chunk=chunk)
         if mode_name.startswith("2fsk"):
             # QRL_OPT_OVERLAP is the library default for this family since round 3: the synced reference run takes the SERIAL order
-            # (cs = stream, ev_tail / tail_pending waits), the unsynced run the overlapped one -- both paths are checked against each
+            # (cs = stream, the one-shot ev_tail waits), the unsynced run the overlapped one -- both paths are checked against each
             # other and against the oracle
             dem.set_option(q.OPT_OVERLAP, 0 if sync_each else 1)
         if mode_name == "qpsk250k":
